@@ -1,14 +1,18 @@
 """Benchmark of the AGCN hot path: skeleton-clips/sec, forward+backward(+clip+SGD step), NTU (N,3,300,25,2).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One process per GPU; per-GPU batch fixed at 64 (BASELINE.json configs[1]/[2], weak scaling); gradients are summed by
 two RCCL all-reduces of slices of the flat gradient buffer per step (the tail of the model overlapped with the
 backward); with more than one rank BatchNorm statistics are synchronised like the reference's DDP path.  Rank 0 prints one JSON line.  Inputs are synthetic and
-resident in HBM before the timed region.  The roofline object is measured live (HIP events on the launch stream)
-for the dominant kernel; the cpu_baseline object times the CPU oracle (a port of the reference, never the product
-path) on a bounded sample on this box's host cores.
+resident in HBM before the timed region.
+
+A plain run sets up, warms up, times the K steps and prints the line; --dump-outputs DIR also writes what the last
+timed step computed (see dump_outputs).  --full adds the measurements the headline does not need: the roofline
+objects, measured live (HIP events on the launch stream) for the dominant kernel, the chain and every unit_gcn layer
+shape; the exact-f32 context value; the one-rank multi-GPU rehearsal; and the cpu_baseline object, which times the CPU
+oracle (a port of the reference, never the product path) on a bounded sample on this box's host cores.
 """
 import argparse
 import json
@@ -397,6 +401,38 @@ def dp_rehearsal(args, device, wl, plain_ms):
                     "the previous stage's output, so they cannot be merged further) and 2 gradient buckets"}
 
 
+DUMP_BUDGET_BYTES = 60 * 10 ** 6      # --dump-outputs stays under 64 MB in all
+
+
+def dump_outputs(out_dir, engine, loss):
+    """What the last timed step handed back to its caller, as out_dir/<name>.npy (float32): the loss it returned, the
+    gradient norm of the clip, the parameters after the update and the gradients of the step (both in parameter order,
+    concatenated) and the BatchNorm running statistics.  Inputs and initial weights are seeded, so two builds run with
+    the same arguments can be compared file by file.  Above the budget every large array is cut to a fixed, seeded
+    sample of its elements."""
+    import numpy as np
+    fp = engine.fp
+    arrays = {
+        'loss': loss.detach().reshape(1),
+        'grad_norm': engine.norm[:1],
+        'params': torch.cat([p.detach().reshape(-1) for p in fp.params]),
+        'grads': torch.cat([fp.grad[o:o + p.numel()] for p, o in zip(fp.params, fp.offsets)]),
+        'bn_running_stats': torch.cat([b.reshape(-1) for n, b in engine.model.named_buffers()
+                                       if n.endswith(('running_mean', 'running_var'))]),
+    }
+    arrays = {k: v.float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        rng = np.random.default_rng(0)
+        for k, a in arrays.items():
+            if a.size > 1024:
+                idx = rng.choice(a.size, int(a.size * DUMP_BUDGET_BYTES / total), replace=False)
+                arrays[k] = a[np.sort(idx)]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -416,6 +452,12 @@ def main():
                          'time they add to the step (dp_rehearsal)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also measure the roofline objects, the exact-f32 context value, the '
+                         'one-rank multi-GPU rehearsal and the CPU baseline (minus what --no-roofline / '
+                         '--no-cpu-baseline drop); a plain run only times the step')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (dump_outputs)')
     args = ap.parse_args()
     if args.workload.endswith('_bf16'):
         os.environ['AGCN_GEMM'] = 'bf16'          # fixed per process, read by the library on first use
@@ -474,6 +516,8 @@ def main():
     final_loss = float(loss.detach())
     if rank == 0:
         print(f"[bench] timed {args.steps} steps in {dt:.3f}s", file=sys.stderr, flush=True)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, engine, loss)
 
     if rank == 0:
         from agcn_amd import lib as _lib
@@ -507,7 +551,7 @@ def main():
                                                        "bar; diagnostic mode only)")},
             "final_loss": round(final_loss, 5),
         }
-        if world == 1 and not args.no_roofline and args.workload in ('ntu_agcn', 'ntu_aagcn', 'ntu_aagcn_bf16'):
+        if args.full and world == 1 and not args.no_roofline and args.workload in ('ntu_agcn', 'ntu_aagcn', 'ntu_aagcn_bf16'):
             out["roofline"] = dominant_kernel_roofline(device)
             out["roofline"]["top_profiled_kernel"] = top_profiled_kernel()
             out["chain_kernel"] = chain_kernel_roofline(device)
@@ -515,9 +559,9 @@ def main():
             if gemm_mode == 'bf16x6' and args.workload == 'ntu_agcn':
                 out["exact_f32_value"] = exact_f32_value(args)     # same step, every contraction on exact-f32 MFMA
             print("[bench] roofline done", file=sys.stderr, flush=True)
-        if world == 1 and (args.rehearse_dp or (not args.no_roofline and args.workload == 'ntu_agcn')):
+        if world == 1 and (args.rehearse_dp or (args.full and not args.no_roofline and args.workload == 'ntu_agcn')):
             out["dp_rehearsal"] = dp_rehearsal(args, device, wl, dt / args.steps * 1e3)
-        if world == 1 and not args.no_cpu_baseline and args.workload == 'ntu_agcn':
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == 'ntu_agcn':
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -73,6 +73,15 @@ def pack_grads(out, named_params, prefix='g.', full_limit=40000):
 
 
 
+def save_logits64(name, **arrays):
+    """fp64 logits of a model fixture, kept (rounded to fp32) in the small side file model_logits64.npz under
+    '<name>.<key>' so that the large fixture files stay as they are; tests/golden_util.py::load merges them in."""
+    path = os.path.join(HERE, 'model_logits64.npz')
+    side = dict(np.load(path)) if os.path.exists(path) else {}
+    side.update({f'{name}.{k}': np.asarray(a).astype(np.float32) for k, a in arrays.items()})
+    np.savez_compressed(path, **side)
+
+
 def add_unit_sens(out, unit64, xn, rn, seed):
     """Per-tensor conditioning band for a unit fixture: how far the fp64 reference gradient moves when the input is
     perturbed by 1e-6 relative (ReLU-kink flips, cancelling sums); see make_model."""
@@ -226,6 +235,18 @@ def make_model(ref, name, n, v, num_class, graph, seed, stress, t):
             sens[k] = max(sens[k], d)
     for k, v_ in sens.items():
         out['sens.' + k] = np.float32(v_)
+    # eval-mode logits of the reference in fp64, on a fresh instance: the fp32 ones carry the reference's own rounding
+    # (an fp32 run in another summation order lands up to ~1e-5 of max|logit| away), so tests that must not depend on
+    # the host's summation order compare an fp64 evaluation against these
+    eval64 = ref.Model(num_class=num_class, num_point=v, num_person=2, graph=graph,
+                       graph_args=dict(labeling_mode='spatial')).double()
+    eval64.load_state_dict({k: v_.double() if v_.is_floating_point() else v_ for k, v_ in sd.items()})
+    for m_ in eval64.modules():
+        if hasattr(m_, 'A') and isinstance(getattr(m_, 'A'), torch.Tensor) and not isinstance(m_.A, torch.nn.Parameter):
+            m_.A = m_.A.double()
+    eval64.eval()
+    with torch.no_grad():
+        save_logits64(name, logits_eval64=eval64(torch.from_numpy(xn).double()).numpy())
     out['meta'] = np.array([n, v, num_class, seed, t], dtype=np.int64)
     out['meta.stress'] = np.float32(stress)
     np.savez_compressed(os.path.join(HERE, name + '.npz'), **out)
@@ -421,6 +442,7 @@ def make_aagcn_model(ref, name='am_ntu_b1_t64', n=1, v=25, num_class=60, seed=50
     model64.train()
     l64, _ = model64(torch.from_numpy(xn).double())
     torch.nn.functional.cross_entropy(l64, torch.from_numpy(lab)).backward()
+    save_logits64(name, logits64=l64.detach().numpy())
     pack_grads(out, model64.named_parameters(), prefix='g64.', full_limit=2000)
     g64 = {k: p.grad.detach().clone() for k, p in model64.named_parameters()}
     sens = {k: 0.0 for k in g64}
@@ -434,6 +456,11 @@ def make_aagcn_model(ref, name='am_ntu_b1_t64', n=1, v=25, num_class=60, seed=50
             sens[k] = max(sens[k], float((p.grad - g64[k]).abs().max() / max(1e-300, float(g64[k].abs().max()))))
     for k, v_ in sens.items():
         out['sens.' + k] = np.float32(v_)
+    eval64 = ref.Model(**mk).double()          # fp64 eval-mode logits on a fresh instance (see make_model)
+    eval64.load_state_dict({k: v_.double() if v_.is_floating_point() else v_ for k, v_ in sd.items()})
+    eval64.eval()
+    with torch.no_grad():
+        save_logits64(name, logits_eval64=eval64(torch.from_numpy(xn).double())[0].numpy())
     out['meta'] = np.array([n, v, num_class, seed, t], dtype=np.int64)
     out['meta.stress'] = np.float32(stress)
     out['meta.layers'] = np.int64(model_layers)

@@ -11,8 +11,14 @@ UNIT_NAMES = ['u_3_64_s1_v25', 'u_64_64_s1_v25', 'u_64_64_s1_v25_stress', 'u_64_
 MODEL_NAMES = ['m_ntu_b1', 'm_ntu_b2', 'm_kin_b2_t64', 'm_kin_b2']
 
 
+LOGITS64 = os.path.join(GOLDEN, 'model_logits64.npz')   # '<fixture>.<key>': fp64 logits of the model fixtures
+
+
 def load(name):
-    return dict(np.load(os.path.join(GOLDEN, name + '.npz')))
+    gold = dict(np.load(os.path.join(GOLDEN, name + '.npz')))
+    with np.load(LOGITS64) as side:
+        gold.update({k[len(name) + 1:]: side[k] for k in side.files if k.startswith(name + '.')})
+    return gold
 
 
 def unit_inputs(cin, cout, stride, t, v, seed, n=2):
@@ -43,15 +49,20 @@ def rel_err(a, ref):
     return float(np.abs(a - ref).max() / max(1.0, np.abs(ref).max()))
 
 
-def grad_err(g, gold, name):
+def grad_err(g, gold, name, prefix='g.'):
     """Gradient parity: normalised by the per-tensor max|g_ref| (floor 1e-6: structurally-zero
-    gradients, SURVEY F9, are compared absolutely)."""
+    gradients, SURVEY F9, are compared absolutely).  prefix 'g.' = the reference's fp32 run, 'g64.' = its fp64 run."""
     g = np.asarray(g, dtype=np.float64)
-    scale = max(float(gold['g.' + name + '.absmax']), 1e-6)
-    if ('g.' + name) in gold:
-        return float(np.abs(g - gold['g.' + name]).max() / scale) if scale > 1e-6 else float(np.abs(g).max())
-    idx = gold['g.' + name + '.idx']
-    return float(np.abs(g.reshape(-1)[idx] - gold['g.' + name + '.samples']).max() / scale)
+    scale = max(float(gold[prefix + name + '.absmax']), 1e-6)
+    if (prefix + name) in gold:
+        return float(np.abs(g - gold[prefix + name]).max() / scale) if scale > 1e-6 else float(np.abs(g).max())
+    idx = gold[prefix + name + '.idx']
+    return float(np.abs(g.reshape(-1)[idx] - gold[prefix + name + '.samples']).max() / scale)
+
+
+def to_fp64(sd):
+    """A fp32 state dict in fp64: the values the reference's fp64 run of a fixture was loaded with."""
+    return {k: v.double() if v.is_floating_point() else v for k, v in sd.items()}
 
 
 ZERO_GRAD_BIAS = ('conv_d.0.bias', 'conv_d.1.bias', 'conv_d.2.bias', 'down.0.bias', 'tcn1.conv.bias',

@@ -6,11 +6,11 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 O=gpurun_out/final
 rm -rf $O && mkdir -p $O
-python3 bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
-python3 bench.py --workload ntu_aagcn --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_ntu_aagcn.json 2> /dev/null
-python3 bench.py --workload ntu_aagcn_bf16 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_ntu_aagcn_bf16.json 2> /dev/null
-python3 bench.py --workload kinetics_agcn --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_kinetics_agcn.json 2> /dev/null
-AGCN_GEMM=f32 python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_f32mfma.json 2> /dev/null
+python3 bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
+python3 bench.py --full --workload ntu_aagcn --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_ntu_aagcn.json 2> /dev/null
+python3 bench.py --full --workload ntu_aagcn_bf16 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_ntu_aagcn_bf16.json 2> /dev/null
+python3 bench.py --full --workload kinetics_agcn --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_kinetics_agcn.json 2> /dev/null
+AGCN_GEMM=f32 python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_f32mfma.json 2> /dev/null
 AGCN_SIDE_STREAM=0 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-roofline > $O/prof.log 2>&1
 python3 tools/prof_summary.py $O/prof 8 70 > $O/kernel_stats.txt
 cp $(ls $O/prof/*/*kernel_stats.csv | head -1) $O/kernel_stats.csv
