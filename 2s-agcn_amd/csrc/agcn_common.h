@@ -72,6 +72,17 @@ int agcn_bf16_conv9_bwd_data(const float* dy, const float* w, float* dx, int acc
                              int N, int Cin, int Cout, int T, int V, int stride, int npl, hipStream_t s,
                              const float* dy_absmax = nullptr);
 
+// stride-1 3/5/7-tap temporal convolutions with explicit padding on the same kernels (agcn_tconv_*)
+bool agcn_bf16_tconv_supported(int taps, int stride);
+int agcn_bf16_tconv_tile_frames(int taps, int M, int V, int T_out, int npl);
+int agcn_bf16_tconv_fwd(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* ws,
+                        size_t ws_bytes, int N, int Cin, int Cout, int T, int V, int taps, int pad, int npl,
+                        hipStream_t s, const float* x_absmax);
+int agcn_bf16_tconv_bwd_data(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
+                             const float* mask1, const float* add2, const float* mask2, void* ws, size_t ws_bytes,
+                             int N, int Cin, int Cout, int T, int V, int taps, int pad, int npl, hipStream_t s,
+                             const float* dy_absmax);
+
 size_t agcn_bf16_conv1_workspace(int Cin, int Cout, int T, int V, int stride);
 int agcn_bf16_conv1_fwd(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* ws,
                         size_t ws_bytes, int N, int Cin, int Cout, int T, int V, int stride, int npl, hipStream_t s,
@@ -111,6 +122,12 @@ bool agcn_wgrad9_bf16_supported(int M, int C, int V, int stride);
 size_t agcn_wgrad9_bf16_workspace(int N, int M, int C, int V, int T, int stride);
 int agcn_wgrad9_bf16(const float* dy, const float* x, void* ws, size_t ws_bytes, int* nslabs, int N, int M, int C, int V,
                      int T, int stride, hipStream_t s, const float* dy_absmax = nullptr, const float* x_absmax = nullptr);
+
+// the same f16x3 kernel for stride-1 3/5/7-tap gradients with taps - pad <= 5 (agcn_tconv_bwd_weight): slabs [taps][M][C]
+bool agcn_wgrad_tconv_f16_supported(int M, int C, int V, int taps, int stride, int pad);
+size_t agcn_wgrad_tconv_f16_workspace(int N, int M, int C, int V, int T, int taps, int pad);
+int agcn_wgrad_tconv_f16(const float* dy, const float* x, void* ws, size_t ws_bytes, int* nslabs, int N, int M, int C,
+                         int V, int T, int taps, int pad, hipStream_t s, const float* dy_absmax, const float* x_absmax);
 
 // GEMM arithmetic of the channel contractions: 3 = bf16x6 (default: fp32-equivalent accuracy, measured), 0 = f32 MFMA,
 // 2 = bf16x3 (~5e-6 per GEMM; does NOT hold the 1e-4 parity bar end to end), 1 = bf16 (plain bf16 MFMA operands, ONE

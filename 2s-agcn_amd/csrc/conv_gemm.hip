@@ -463,11 +463,12 @@ struct Geometry {
 
 // host-side tile geometry shared by the launcher and the workspace queries
 template <int TAPS, int AGG, int WM, int WN, int TM, int TN, int CK, int EPI>
-Geometry make_geometry(int V, int T_out, int src_stride, int M, int Kinner) {
+Geometry make_geometry(int V, int T_out, int src_stride, int M, int Kinner, int tt_cap = 0) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32, NSUB = AGG ? 3 : 1, NW = WM * WN;
   Geometry g;
   g.tt = BN / V;
   if (g.tt > T_out) g.tt = T_out;
+  if (tt_cap > 0 && g.tt > tt_cap) g.tt = tt_cap;     // long strided windows (agcn_tconv_*): fewer frames per tile
   if (g.tt < 1) g.tt = 1;
   g.ttv = g.tt * V;
   g.ntiles = (T_out + g.tt - 1) / g.tt;
@@ -497,13 +498,14 @@ struct Problem {          // what differs between the entry points
   int tap_mul, tap_add, tap_flip_from;
   void* ws;
   size_t ws_bytes;
+  int tt_cap;             // 0: frames per tile as the tile width gives them
 };
 
 template <int TAPS, int AGG, int WM, int WN, int TM, int TN, int CK, int WB, int EPI>
 int launch_cfg(Problem& p, hipStream_t stream) {
   constexpr int BM = WM * TM * 32, NSUB = AGG ? 3 : 1;
   ConvGemmArgs a = p.a;
-  const Geometry g = make_geometry<TAPS, AGG, WM, WN, TM, TN, CK, EPI>(a.V, a.T_out, a.src_stride, a.M, a.Kinner);
+  const Geometry g = make_geometry<TAPS, AGG, WM, WN, TM, TN, CK, EPI>(a.V, a.T_out, a.src_stride, a.M, a.Kinner, p.tt_cap);
   if (g.smem_bytes > 160 * 1024) return AGCN_ERR_UNSUPPORTED;
   if (g.FW * a.V > WB * 64) return AGCN_ERR_UNSUPPORTED;
   if (g.pack_floats * 4 > p.ws_bytes) return AGCN_ERR_WORKSPACE;
@@ -542,6 +544,58 @@ size_t pack_bytes(int V, int T_out, int src_stride, int M, int Kinner) {
                     : pack_bytes<TAPS, AGG, 1, 4, 2, 2, CK64, 0>(V, T, ss, M, K))
 
 constexpr int CK9 = 8, CK1 = 16, CKA = 8, CKD = 64;
+
+// ---- temporal convolution with any taps (1..9), stride (1..9) and padding (0..(taps-1)/2): agcn_tconv_* ----
+constexpr int WBT = 12;                 // window bound of the exact-f32 kernel (768 floats per staged row)
+
+inline int tconv_out_frames(int T, int taps, int stride, int pad) { return (T + 2 * pad - taps) / stride + 1; }
+
+// AGCN_ERR_UNSUPPORTED outside the supported domain (the caller's shapes), 0 otherwise
+inline int tconv_domain(int T, int taps, int stride, int pad) {
+  if (taps < 1 || taps > 9 || stride < 1 || stride > 9 || pad < 0 || pad > (taps - 1) / 2) return AGCN_ERR_UNSUPPORTED;
+  if (T + 2 * pad < taps) return AGCN_ERR_UNSUPPORTED;       // not one whole window
+  return 0;
+}
+
+// the shapes the agcn_conv_* entry points cover: routed there unchanged (same kernels, same bits)
+inline bool tconv_legacy(int taps, int stride, int pad) {
+  return pad == (taps - 1) / 2 && (taps == 1 || taps == 9) && (stride == 1 || stride == 2);
+}
+
+// the split-bf16 / f16x3 kernels of conv_gemm_bf16.hip (stride 1, 3/5/7 taps) in the split-bf16 modes
+inline bool tconv_fast(int taps, int stride) { return agcn_gemm_precision() != 0 && agcn_bf16_tconv_supported(taps, stride); }
+
+// frames per tile of the exact-f32 kernel: a staged window row of (tt-1)*stride + taps frames must fit WBT*64 floats
+inline int tconv_f32_tt(int V, int T_out, int taps, int stride) {
+  int tt = 256 / V;
+  if (tt > T_out) tt = T_out;
+  while (tt > 1 && ((tt - 1) * stride + taps) * V > WBT * 64) --tt;
+  return tt < 1 ? 1 : tt;
+}
+
+template <int TAPS>
+int tconv_f32_launch(Problem& p, hipStream_t s) {
+  constexpr int CK = TAPS == 1 ? CK1 : CK9;
+  p.tt_cap = tconv_f32_tt(p.a.V, p.a.T_out, TAPS, p.a.src_stride);
+  return DISPATCH_BM(TAPS, 0, CK, CK, WBT, p, s);
+}
+
+int tconv_f32_dispatch(int taps, Problem& p, hipStream_t s) {
+  switch (taps) {
+    case 1: return tconv_f32_launch<1>(p, s);
+    case 2: return tconv_f32_launch<2>(p, s);
+    case 3: return tconv_f32_launch<3>(p, s);
+    case 4: return tconv_f32_launch<4>(p, s);
+    case 5: return tconv_f32_launch<5>(p, s);
+    case 6: return tconv_f32_launch<6>(p, s);
+    case 7: return tconv_f32_launch<7>(p, s);
+    case 8: return tconv_f32_launch<8>(p, s);
+    case 9: return tconv_f32_launch<9>(p, s);
+    default: return AGCN_ERR_UNSUPPORTED;
+  }
+}
+
+inline size_t round_up(size_t v, size_t m) { return (v + m - 1) / m * m; }
 
 
 }  // namespace
@@ -895,6 +949,92 @@ int agcn_gcn_dadj_ex(const float* dy, const float* wcat, const float* x, float* 
   p.w = wcat; p.sa_m = 1; p.sa_i = 0; p.sa_c = 3L * C; p.tap_flip_from = -1;
   p.ws = workspace; p.ws_bytes = workspace_bytes;
   return launch_cfg<1, 0, 1, 4, 2, 1, CKD, 2, 1>(p, (hipStream_t)stream);
+}
+
+
+// ---- temporal convolution with explicit padding (reference aagcn.py:184-207 TCNUnit(kernel_size, stride, pad),
+// agcn.py:36-50 unit_tcn(kernel_size, stride)): taps 1..9, stride 1..9, pad 0..(taps-1)/2 ----
+size_t agcn_tconv_workspace(int Cin, int Cout, int T, int V, int taps, int stride, int pad) {
+  if (tconv_domain(T, taps, stride, pad)) return 256;
+  if (tconv_legacy(taps, stride, pad)) return agcn_conv_workspace(Cin, Cout, T, V, taps, stride);
+  // upper bound of every packed weight image the paths below build: rows rounded to 128, K to 16, 6 bytes per element
+  // (three bf16 planes; the f32 image takes 4)
+  const size_t a = round_up(Cout, 128) * round_up(Cin, 16), b = round_up(Cin, 128) * round_up(Cout, 16);
+  return (a > b ? a : b) * (size_t)taps * 6 + 256;
+}
+
+int agcn_tconv_stats_tiles(int Cin, int Cout, int T_out, int V, int taps, int stride, int pad) {
+  if (T_out <= 0 || V <= 0) return 0;
+  if (tconv_legacy(taps, stride, pad)) return agcn_conv_stats_tiles(Cin, Cout, T_out, V, taps, stride);
+  const int tt = tconv_fast(taps, stride) ? agcn_bf16_tconv_tile_frames(taps, Cout, V, T_out, agcn_gemm_precision())
+                                          : tconv_f32_tt(V, T_out, taps, stride);
+  return (T_out + tt - 1) / tt;
+}
+
+// y[n][o][t,v] = bias[o] + sum_{c,k} w[o][c][k] x[n][c][t*stride + k - pad, v],  T_out = (T + 2 pad - taps)/stride + 1
+int agcn_tconv_fwd(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* workspace,
+                   size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride, int pad,
+                   const float* x_absmax, void* stream) {
+  if (!x || !w || !y || !workspace || N <= 0 || Cin <= 0 || Cout <= 0 || T <= 0 || V <= 0 || V > 32)
+    return AGCN_ERR_ARG;
+  if (int rc = tconv_domain(T, taps, stride, pad)) return rc;
+  if (tconv_legacy(taps, stride, pad))
+    return agcn_conv_fwd_ex(x, w, bias, y, stats_part, workspace, workspace_bytes, N, Cin, Cout, T, V, taps, stride,
+                            x_absmax, stream);
+  hipStream_t s = (hipStream_t)stream;
+  if (tconv_fast(taps, stride))
+    return agcn_bf16_tconv_fwd(x, w, bias, y, stats_part, workspace, workspace_bytes, N, Cin, Cout, T, V, taps, pad,
+                               agcn_gemm_precision(), s, x_absmax);
+  Problem p = {};
+  ConvGemmArgs& a = p.a;
+  a.in = x; a.bias = bias; a.out = y; a.stats = stats_part;
+  a.N = N; a.M = Cout; a.Kinner = Cin; a.in_rows = Cin; a.V = V;
+  a.T_src = T; a.T_out = tconv_out_frames(T, taps, stride, pad); a.T_full = a.T_out;
+  a.src_stride = stride; a.f_off = -pad; a.out_fs = 1; a.out_fo = 0;
+  p.w = w; p.sa_m = (long)Cin * taps; p.sa_i = 0; p.sa_c = taps; p.tap_flip_from = -1;
+  p.ws = workspace; p.ws_bytes = workspace_bytes;
+  return tconv_f32_dispatch(taps, p, s);
+}
+
+// dx[n][c][t,v] (+)= sum_{o,k: (t + pad - k) = stride*tau} w[o][c][k] dy[n][o][tau, v]  (+ masked addends); frames no
+// window reaches get 0 (+ addends)
+int agcn_tconv_bwd_data(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
+                        const float* mask1, const float* add2, const float* mask2, void* workspace,
+                        size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride, int pad,
+                        const float* dy_absmax, void* stream) {
+  if (!dy || !w || !dx || !workspace || N <= 0 || Cin <= 0 || Cout <= 0 || T <= 0 || V <= 0 || V > 32)
+    return AGCN_ERR_ARG;
+  if (int rc = tconv_domain(T, taps, stride, pad)) return rc;
+  if (tconv_legacy(taps, stride, pad))
+    return agcn_conv_bwd_data_ex(dy, w, dx, accumulate, add1, mask1, add2, mask2, workspace, workspace_bytes, N, Cin,
+                                 Cout, T, V, taps, stride, dy_absmax, stream);
+  hipStream_t s = (hipStream_t)stream;
+  if (tconv_fast(taps, stride))
+    return agcn_bf16_tconv_bwd_data(dy, w, dx, accumulate, add1, mask1, add2, mask2, workspace, workspace_bytes, N, Cin,
+                                    Cout, T, V, taps, pad, agcn_gemm_precision(), s, dy_absmax);
+  // output frames t = stride*tau + r of one residue r form a stride-1 problem over tau: only the taps
+  // k = k0 + stride*i (k0 = (r + pad) mod stride) reach them,  dx[stride*tau + r] = sum_j W[k0 + stride*(J-1-j)]
+  // dy[tau + (r + pad - k0)/stride - (J-1) + j],  J = number of such taps (0: the residue receives no signal)
+  Problem p = {};
+  ConvGemmArgs& a = p.a;
+  a.in = dy; a.out = dx; a.accumulate = accumulate;
+  a.add1 = add1; a.mask1 = mask1; a.add2 = add2; a.mask2 = mask2;
+  a.N = N; a.M = Cin; a.in_rows = Cout; a.V = V;
+  a.T_src = tconv_out_frames(T, taps, stride, pad); a.T_full = T; a.src_stride = 1; a.out_fs = stride;
+  p.w = w; p.sa_m = taps; p.sa_i = 0; p.sa_c = (long)Cin * taps;
+  p.ws = workspace; p.ws_bytes = workspace_bytes;
+  for (int r = 0; r < stride && r < T; ++r) {
+    const int k0 = (r + pad) % stride;
+    const int J = k0 < taps ? (taps - k0 + stride - 1) / stride : 0;
+    a.T_out = (T - r + stride - 1) / stride;
+    a.out_fo = r;
+    a.Kinner = J > 0 ? Cout : 0;          // no K chunks: the epilogue writes 0 (+accumulate/addends)
+    a.f_off = J > 0 ? (r + pad - k0) / stride - (J - 1) : 0;
+    p.tap_mul = stride; p.tap_add = 0; p.tap_flip_from = k0 + stride * (J > 0 ? J - 1 : 0);
+    const int rc = tconv_f32_dispatch(J > 0 ? J : 1, p, s);
+    if (rc) return rc;
+  }
+  return 0;
 }
 
 }  // extern "C"

@@ -625,6 +625,7 @@ struct BfProblem {
   int tap_mul, tap_add, tap_flip_from;
   void* ws;
   size_t ws_bytes;
+  int stats_tiles;             // > 0: tiles per sample the caller sized the stats partials for (agcn_tconv_stats_tiles)
 };
 
 template <int TAPS, int NPL, int WQ, int TM, int TN = 1, bool F16 = false>
@@ -635,6 +636,7 @@ int launch_bf(BfProblem& p, hipStream_t stream) {
   if (g.smem_bytes > 160 * 1024) return AGCN_ERR_UNSUPPORTED;
   if ((g.FW * a.V + 3) / 4 > WQ * 64) return AGCN_ERR_UNSUPPORTED;
   if (g.pack_bytes > p.ws_bytes) return AGCN_ERR_WORKSPACE;
+  if (a.stats && p.stats_tiles > 0 && g.ntiles != p.stats_tiles) return AGCN_ERR_ARG;   // (never write past the partials)
   a.tt = g.tt; a.ntiles = g.ntiles; a.FW = g.FW; a.WLR = g.WLR; a.nchunks = g.nchunks; a.nmb = g.nmb;
   a.off_b = g.off_b; a.off_bias = g.off_bias;
   a.wp = (const unsigned short*)p.ws;
@@ -698,6 +700,7 @@ int launch_pc(BfProblem& p, hipStream_t stream) {
   const BfGeom g = bf_geometry_pc<TAPS, NPL, R>(a.V, a.T_out, a.M, a.Kinner);
   if (g.smem_bytes > 160 * 1024) return AGCN_ERR_UNSUPPORTED;
   if (g.pack_bytes > p.ws_bytes) return AGCN_ERR_WORKSPACE;
+  if (a.stats && p.stats_tiles > 0 && g.ntiles != p.stats_tiles) return AGCN_ERR_ARG;   // (never write past the partials)
   a.tt = g.tt; a.ntiles = g.ntiles; a.FW = g.FW; a.WLR = g.WLR; a.nchunks = g.nchunks; a.nmb = g.nmb;
   a.off_b = g.off_b; a.off_bias = g.off_bias;
   a.wp = (const unsigned short*)p.ws;
@@ -783,70 +786,105 @@ size_t agcn_bf16_conv_workspace(int Cin, int Cout, int T, int V, int stride) {
   return b + 256;
 }
 
-int agcn_bf16_conv9_fwd(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* ws,
-                        size_t ws_bytes, int N, int Cin, int Cout, int T, int V, int stride, int npl,
-                        hipStream_t s, const float* add, int relu, const float* x_absmax) {
+namespace {
+
+// f16x3 range scale of the streamed operand: the maximum its producer left behind, or a streaming pass of our own whose
+// result sits in the last 16 bytes of the workspace (its size carries 256 bytes of slack); shrinks ws_bytes accordingly
+int bf16_in_absmax(BfProblem& p, const float* given, const float* in, long n, hipStream_t s) {
+  if (given) {
+    p.a.in_absmax = given;
+    return 0;
+  }
+  if (p.ws_bytes < 64) return AGCN_ERR_WORKSPACE;
+  unsigned* amax = reinterpret_cast<unsigned*>(static_cast<char*>(p.ws) + ((p.ws_bytes - 16) & ~(size_t)15));
+  if (hipMemsetAsync(amax, 0, 4, s) != hipSuccess) return AGCN_ERR_ARG;
+  hipLaunchKernelGGL(absmax_kernel, dim3(2048), dim3(256), 0, s, in, n, amax);
+  if (int rc = agcn_check_launch()) return rc;
+  p.a.in_absmax = reinterpret_cast<const float*>(amax);
+  p.ws_bytes = (p.ws_bytes - 16) & ~(size_t)15;
+  return 0;
+}
+
+int bf16_fwd_f16x3(int npl) {   // AGCN_CONV_F16X3=0 keeps the temporal convolutions on bf16x6
+  static const int f16x3 = getenv("AGCN_CONV_F16X3") ? atoi(getenv("AGCN_CONV_F16X3")) : 1;
+  return f16x3 && npl == 3;
+}
+
+// y = bias + conv_TAPS(x; stride, pad) [+ add] (reference agcn.py:40-41,49; aagcn.py:194-201)
+template <int TAPS, int WQ>
+int bf16_tconv_fwd(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* ws,
+                   size_t ws_bytes, int N, int Cin, int Cout, int T, int V, int stride, int pad, int npl, hipStream_t s,
+                   const float* add, int relu, const float* x_absmax) {
   BfProblem p = {};
   BfArgs& a = p.a;
   a.in = x; a.bias = bias; a.out = y; a.stats = stats_part; a.add1 = add; a.relu = relu;
-  {   // AGCN_CONV_F16X3=0 keeps the forward on bf16x6
-    static const int f16x3 = getenv("AGCN_CONV_F16X3") ? atoi(getenv("AGCN_CONV_F16X3")) : 1;
-    p.fwd_f16 = f16x3 && npl == 3;
-  }
-  if (p.fwd_f16 && x_absmax) {
-    a.in_absmax = x_absmax;                    // left behind by the kernel that produced x (agcn_bn_act_fwd_ex)
-  } else if (p.fwd_f16) {
-    // max |x| for the range scale: the last 16 bytes of the workspace (its size carries 256 bytes of slack)
-    if (ws_bytes < 64) return AGCN_ERR_WORKSPACE;
-    unsigned* amax = reinterpret_cast<unsigned*>(static_cast<char*>(ws) + ((ws_bytes - 16) & ~(size_t)15));
-    if (hipMemsetAsync(amax, 0, 4, s) != hipSuccess) return AGCN_ERR_ARG;
-    hipLaunchKernelGGL(absmax_kernel, dim3(2048), dim3(256), 0, s, x, (long)N * Cin * T * V, amax);
-    if (int rc = agcn_check_launch()) return rc;
-    a.in_absmax = reinterpret_cast<const float*>(amax);
-    ws_bytes = (ws_bytes - 16) & ~(size_t)15;
-  }
-  a.N = N; a.M = Cout; a.Kinner = Cin; a.in_rows = Cin; a.V = V;
-  a.T_src = T; a.T_out = (T + 8 - 9) / stride + 1; a.T_full = a.T_out;
-  a.src_stride = stride; a.f_off = -4; a.out_fs = 1; a.out_fo = 0;
-  p.w = w; p.sa_m = (long)Cin * 9; p.sa_c = 9; p.tap_flip_from = -1;
+  p.fwd_f16 = bf16_fwd_f16x3(npl);
   p.ws = ws; p.ws_bytes = ws_bytes;
-  if (stride == 1) return launch_npl<9, 2>(p, npl, s);
-  return launch_npl<9, 3>(p, npl, s);
+  if (p.fwd_f16)
+    if (int rc = bf16_in_absmax(p, x_absmax, x, (long)N * Cin * T * V, s)) return rc;
+  a.N = N; a.M = Cout; a.Kinner = Cin; a.in_rows = Cin; a.V = V;
+  a.T_src = T; a.T_out = (T + 2 * pad - TAPS) / stride + 1; a.T_full = a.T_out;
+  a.src_stride = stride; a.f_off = -pad; a.out_fs = 1; a.out_fo = 0;
+  p.w = w; p.sa_m = (long)Cin * TAPS; p.sa_c = TAPS; p.tap_flip_from = -1;
+  if (TAPS != 9 && stats_part) {     // the caller sized the partials by agcn_bf16_tconv_tile_frames: the launch checks it
+    const int tt = agcn_bf16_tconv_tile_frames(TAPS, Cout, V, a.T_out, npl);
+    p.stats_tiles = (a.T_out + tt - 1) / tt;
+  }
+  return launch_npl<TAPS, WQ>(p, npl, s);
+}
+
+// stride-1 backward-data: dx[t] = sum_j W[TAPS-1-j] dy[t + j - (TAPS-1-pad)]   (+ masked addends)
+template <int TAPS>
+int bf16_tconv_bwd_data_s1(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
+                           const float* mask1, const float* add2, const float* mask2, void* ws, size_t ws_bytes, int N,
+                           int Cin, int Cout, int T, int V, int pad, int npl, hipStream_t s, const float* dy_absmax) {
+  BfProblem p = {};
+  BfArgs& a = p.a;
+  p.fwd_f16 = bf16_fwd_f16x3(npl);     // f16x3 with the gradient normalised by its maximum
+  p.ws = ws; p.ws_bytes = ws_bytes;
+  const int To = T + 2 * pad - TAPS + 1;
+  if (p.fwd_f16)
+    if (int rc = bf16_in_absmax(p, dy_absmax, dy, (long)N * Cout * To * V, s)) return rc;
+  a.in = dy; a.out = dx; a.accumulate = accumulate;
+  a.add1 = add1; a.mask1 = mask1; a.add2 = add2; a.mask2 = mask2;
+  a.N = N; a.M = Cin; a.Kinner = Cout; a.in_rows = Cout; a.V = V;
+  a.T_src = To; a.T_full = T; a.src_stride = 1;
+  a.T_out = T; a.out_fs = 1; a.out_fo = 0; a.f_off = pad - (TAPS - 1);
+  p.w = w; p.sa_m = TAPS; p.sa_c = (long)Cin * TAPS;
+  p.tap_mul = 1; p.tap_add = 0; p.tap_flip_from = TAPS - 1;
+  return launch_npl<TAPS, 2>(p, npl, s);
+}
+
+}  // namespace
+
+int agcn_bf16_conv9_fwd(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* ws,
+                        size_t ws_bytes, int N, int Cin, int Cout, int T, int V, int stride, int npl,
+                        hipStream_t s, const float* add, int relu, const float* x_absmax) {
+  if (stride == 1)
+    return bf16_tconv_fwd<9, 2>(x, w, bias, y, stats_part, ws, ws_bytes, N, Cin, Cout, T, V, 1, 4, npl, s, add, relu,
+                                x_absmax);
+  return bf16_tconv_fwd<9, 3>(x, w, bias, y, stats_part, ws, ws_bytes, N, Cin, Cout, T, V, stride, 4, npl, s, add, relu,
+                              x_absmax);
 }
 
 int agcn_bf16_conv9_bwd_data(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
                              const float* mask1, const float* add2, const float* mask2, void* ws, size_t ws_bytes,
                              int N, int Cin, int Cout, int T, int V, int stride, int npl, hipStream_t s,
                              const float* dy_absmax) {
+  if (stride == 1)
+    return bf16_tconv_bwd_data_s1<9>(dy, w, dx, accumulate, add1, mask1, add2, mask2, ws, ws_bytes, N, Cin, Cout, T, V,
+                                     4, npl, s, dy_absmax);
   BfProblem p = {};
   BfArgs& a = p.a;
-  {   // f16x3 with the gradient normalised by its maximum (AGCN_CONV_F16X3=0: bf16x6)
-    static const int f16x3 = getenv("AGCN_CONV_F16X3") ? atoi(getenv("AGCN_CONV_F16X3")) : 1;
-    p.fwd_f16 = f16x3 && npl == 3;
-  }
-  if (p.fwd_f16 && dy_absmax) {
-    a.in_absmax = dy_absmax;                   // left behind by agcn_bn_bwd_apply_ex
-  } else if (p.fwd_f16) {
-    if (ws_bytes < 64) return AGCN_ERR_WORKSPACE;
-    unsigned* amax = reinterpret_cast<unsigned*>(static_cast<char*>(ws) + ((ws_bytes - 16) & ~(size_t)15));
-    if (hipMemsetAsync(amax, 0, 4, s) != hipSuccess) return AGCN_ERR_ARG;
-    const int To = (T + 8 - 9) / stride + 1;
-    hipLaunchKernelGGL(absmax_kernel, dim3(2048), dim3(256), 0, s, dy, (long)N * Cout * To * V, amax);
-    if (int rc = agcn_check_launch()) return rc;
-    a.in_absmax = reinterpret_cast<const float*>(amax);
-    ws_bytes = (ws_bytes - 16) & ~(size_t)15;
-  }
+  p.fwd_f16 = bf16_fwd_f16x3(npl);
+  p.ws = ws; p.ws_bytes = ws_bytes;
+  if (p.fwd_f16)
+    if (int rc = bf16_in_absmax(p, dy_absmax, dy, (long)N * Cout * ((T + 8 - 9) / stride + 1) * V, s)) return rc;
   a.in = dy; a.out = dx; a.accumulate = accumulate;
   a.add1 = add1; a.mask1 = mask1; a.add2 = add2; a.mask2 = mask2;
   a.N = N; a.M = Cin; a.Kinner = Cout; a.in_rows = Cout; a.V = V;
   a.T_src = (T + 8 - 9) / stride + 1; a.T_full = T; a.src_stride = 1;
   p.w = w; p.sa_m = 9; p.sa_c = (long)Cin * 9;
-  p.ws = ws; p.ws_bytes = ws_bytes;
-  if (stride == 1) {
-    a.T_out = T; a.out_fs = 1; a.out_fo = 0; a.f_off = -4;
-    p.tap_mul = 1; p.tap_add = 0; p.tap_flip_from = 8;
-    return launch_npl<9, 2>(p, npl, s);
-  }
   a.T_out = (T + 1) / 2; a.out_fs = 2; a.out_fo = 0; a.f_off = -2;
   p.tap_mul = 2; p.tap_add = 0; p.tap_flip_from = 8;
   int rc = launch_npl<5, 2>(p, npl, s);
@@ -855,6 +893,59 @@ int agcn_bf16_conv9_bwd_data(const float* dy, const float* w, float* dx, int acc
   p.tap_add = 1;
   if (a.T_out > 0) rc = launch_npl<4, 2>(p, npl, s);
   return rc;
+}
+
+// stride-1 temporal convolutions with 3, 5 or 7 taps and any padding on the same kernels (conv_pc_kernel where the
+// 9-tap layer takes it); AGCN_ERR_UNSUPPORTED for other shapes (the caller runs the exact-f32 kernel then)
+bool agcn_bf16_tconv_supported(int taps, int stride) { return stride == 1 && (taps == 3 || taps == 5 || taps == 7); }
+
+int agcn_bf16_tconv_fwd(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* ws,
+                        size_t ws_bytes, int N, int Cin, int Cout, int T, int V, int taps, int pad, int npl,
+                        hipStream_t s, const float* x_absmax) {
+  switch (taps) {
+    case 3: return bf16_tconv_fwd<3, 2>(x, w, bias, y, stats_part, ws, ws_bytes, N, Cin, Cout, T, V, 1, pad, npl, s,
+                                        nullptr, 0, x_absmax);
+    case 5: return bf16_tconv_fwd<5, 2>(x, w, bias, y, stats_part, ws, ws_bytes, N, Cin, Cout, T, V, 1, pad, npl, s,
+                                        nullptr, 0, x_absmax);
+    case 7: return bf16_tconv_fwd<7, 2>(x, w, bias, y, stats_part, ws, ws_bytes, N, Cin, Cout, T, V, 1, pad, npl, s,
+                                        nullptr, 0, x_absmax);
+    default: return AGCN_ERR_UNSUPPORTED;
+  }
+}
+
+int agcn_bf16_tconv_bwd_data(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
+                             const float* mask1, const float* add2, const float* mask2, void* ws, size_t ws_bytes,
+                             int N, int Cin, int Cout, int T, int V, int taps, int pad, int npl, hipStream_t s,
+                             const float* dy_absmax) {
+  switch (taps) {
+    case 3: return bf16_tconv_bwd_data_s1<3>(dy, w, dx, accumulate, add1, mask1, add2, mask2, ws, ws_bytes, N, Cin, Cout,
+                                             T, V, pad, npl, s, dy_absmax);
+    case 5: return bf16_tconv_bwd_data_s1<5>(dy, w, dx, accumulate, add1, mask1, add2, mask2, ws, ws_bytes, N, Cin, Cout,
+                                             T, V, pad, npl, s, dy_absmax);
+    case 7: return bf16_tconv_bwd_data_s1<7>(dy, w, dx, accumulate, add1, mask1, add2, mask2, ws, ws_bytes, N, Cin, Cout,
+                                             T, V, pad, npl, s, dy_absmax);
+    default: return AGCN_ERR_UNSUPPORTED;
+  }
+}
+
+// frames per stats tile of agcn_bf16_tconv_fwd (the wide 64-row tile covers 512 positions, every other one 256)
+int agcn_bf16_tconv_tile_frames(int taps, int M, int V, int T_out, int npl) {
+  int tt = 256 / V;
+  if (M <= 64 && agcn_bf16_conv_wide(taps, M) && (npl == 3 || npl == 1)) {
+    bool ok = false;
+    switch (taps) {
+      case 3: ok = bf_geometry<3, 64, 2>(V, T_out, 1, M, 16).smem_bytes <= 160 * 1024; break;
+      case 5: ok = bf_geometry<5, 64, 2>(V, T_out, 1, M, 16).smem_bytes <= 160 * 1024; break;
+      case 7: ok = bf_geometry<7, 64, 2>(V, T_out, 1, M, 16).smem_bytes <= 160 * 1024; break;
+      default: break;
+    }
+    int tw = 512 / V;
+    if (tw > T_out) tw = T_out;
+    if (ok && ((tw - 1) + taps) * V <= 3 * 64 * 4) tt = 512 / V;     // (launch_bf's WQ = 3 window bound)
+  }
+  if (tt > T_out) tt = T_out;
+  if (tt < 1) tt = 1;
+  return tt;
 }
 
 // 1x1 convolutions (conv_a/conv_b/down/residual; reference agcn.py:66-75,122-125) on the same kernel, TAPS = 1

@@ -19,6 +19,7 @@ struct WgradArgs {
   const float* adj;
   float* part;
   int N, M, C, V, T_src, T_out, stride;
+  int pad;                     // plain: first source frame of output frame t is t*stride - pad
   int tt, ntiles, FW, WLP, DAP, GP;
   long so_m, so_t, so_c;
   long wsize;
@@ -26,7 +27,7 @@ struct WgradArgs {
   int off_bx, off_bg, off_adj, off_qoff;
 };
 
-// TAPS: 1 or 9 taps (plain) ; AGG: B = x . adj_i with the 3 subsets playing the role of taps.
+// TAPS: 1..9 taps (plain) ; AGG: B = x . adj_i with the 3 subsets playing the role of taps.
 // 8 waves = MW (m tiles) x CW (c tiles) x TH ; TH=2 splits the taps (KSPLIT=false) or the positions (KSPLIT=true).
 // WBX = 64-float column blocks of a window row (bound of the prefetch registers).
 template <int TAPS, int AGG, int MW, int CW, int TH, bool KSPLIT, int WBX>
@@ -35,7 +36,6 @@ __global__ void __launch_bounds__(512) conv_wgrad_kernel(const WgradArgs a) {
   static_assert(MW * CW * TH == NW, "8 waves");
   constexpr int BM = MW * 32, CB = CW * 32;
   constexpr int NSUB = AGG ? 3 : 1;
-  constexpr int PAD = (TAPS - 1) / 2;
   constexpr bool TSPLIT = (TH == 2) && !KSPLIT;
   constexpr int NTW = TSPLIT ? (TAPS + 1) / 2 : TAPS;     // taps per wave
   constexpr int NACC = NSUB * NTW;
@@ -88,7 +88,7 @@ __global__ void __launch_bounds__(512) conv_wgrad_kernel(const WgradArgs a) {
     const int tile = p - n * a.ntiles;
     t0 = tile * tt;
     nvalid = min(tt, a.T_out - t0) * V;
-    g0 = (AGG ? t0 : (t0 * a.stride - PAD)) * V;
+    g0 = (AGG ? t0 : (t0 * a.stride - a.pad)) * V;
   };
   // raw loads into registers (predicates are re-evaluated at commit time, so nothing waits on them early)
   auto issue_loads = [&](int p) __attribute__((always_inline)) {
@@ -306,11 +306,12 @@ struct WGeom {
 };
 
 template <int TAPS, int AGG, int MW, int CW, int TH, bool KSPLIT>
-WGeom wgeom(int N, int M, int C, int V, int T_out, int stride) {
+WGeom wgeom(int N, int M, int C, int V, int T_out, int stride, int tt_cap = 0) {
   constexpr int BM = MW * 32, CB = CW * 32;
   WGeom g;
   g.tt = 128 / V;
   if (g.tt > T_out) g.tt = T_out;
+  if (tt_cap > 0 && g.tt > tt_cap) g.tt = tt_cap;     // long strided windows (agcn_tconv_bwd_weight)
   const int ttv = g.tt * V;
   g.ntiles = (T_out + g.tt - 1) / g.tt;
   g.FW = AGG ? g.tt : ((g.tt - 1) * stride + TAPS);
@@ -342,8 +343,8 @@ WGeom wgeom(int N, int M, int C, int V, int T_out, int stride) {
 }
 
 template <int TAPS, int AGG, int MW, int CW, int TH, bool KSPLIT, int WBX>
-int launch_wgrad(WgradArgs a, float* dw, void* ws, size_t ws_bytes, hipStream_t stream) {
-  const WGeom g = wgeom<TAPS, AGG, MW, CW, TH, KSPLIT>(a.N, a.M, a.C, a.V, a.T_out, a.stride);
+int launch_wgrad(WgradArgs a, float* dw, void* ws, size_t ws_bytes, hipStream_t stream, int tt_cap = 0) {
+  const WGeom g = wgeom<TAPS, AGG, MW, CW, TH, KSPLIT>(a.N, a.M, a.C, a.V, a.T_out, a.stride, tt_cap);
   if (g.smem_bytes > 160 * 1024) return AGCN_ERR_UNSUPPORTED;
   if (g.WLP > WBX * 64 || g.tt * a.V > 128) return AGCN_ERR_UNSUPPORTED;
   if ((size_t)g.nslabs * a.wsize * 4 > ws_bytes) return AGCN_ERR_WORKSPACE;
@@ -361,8 +362,8 @@ int launch_wgrad(WgradArgs a, float* dw, void* ws, size_t ws_bytes, hipStream_t 
 }
 
 template <int TAPS, int AGG, int MW, int CW, int TH, bool KSPLIT>
-size_t ws_wgrad(int N, int M, int C, int V, int T_out, int stride, long wsize) {
-  const WGeom g = wgeom<TAPS, AGG, MW, CW, TH, KSPLIT>(N, M, C, V, T_out, stride);
+size_t ws_wgrad(int N, int M, int C, int V, int T_out, int stride, long wsize, int tt_cap = 0) {
+  const WGeom g = wgeom<TAPS, AGG, MW, CW, TH, KSPLIT>(N, M, C, V, T_out, stride, tt_cap);
   return (size_t)g.nslabs * wsize * 4;
 }
 
@@ -384,6 +385,58 @@ inline bool wgrad9_bf16_enabled() {
     v = (e && atoi(e) == 0) ? 0 : 1;
   }
   return v == 1;
+}
+
+// ---- agcn_tconv_bwd_weight: any taps (1..9), stride (1..9), padding (0..(taps-1)/2) on the exact-f32 kernel ----
+constexpr int WBXT = 8;                  // window bound: 512 floats per staged row
+
+inline int tconv_w_tt(int V, int T_out, int taps, int stride) {
+  int tt = 128 / V;
+  if (tt > T_out) tt = T_out;
+  while (tt > 1 && ((tt - 1) * stride + taps) * V + 2 > WBXT * 64) --tt;
+  return tt < 1 ? 1 : tt;
+}
+
+// the 8 waves split the taps (TAPS >= 2) or the positions (1 tap) in two, as the 9- and 1-tap gradients do
+template <int TAPS>
+int tconv_wgrad(WgradArgs a, float* dw, void* ws, size_t ws_bytes, hipStream_t s, size_t* ws_need) {
+  const int cap = tconv_w_tt(a.V, a.T_out, TAPS, a.stride);
+  if (!ws_need) AGCN_NOTE_KERNEL("conv_wgrad_kernel<%d, 0>", TAPS);
+  if (TAPS == 1) {
+    if (a.M % 128 == 0) {
+      if (ws_need) { *ws_need = ws_wgrad<1, 0, 4, 2, 1, false>(a.N, a.M, a.C, a.V, a.T_out, a.stride, a.wsize, cap); return 0; }
+      return launch_wgrad<1, 0, 4, 2, 1, false, WBXT>(a, dw, ws, ws_bytes, s, cap);
+    }
+    if (ws_need) { *ws_need = ws_wgrad<1, 0, 2, 2, 2, true>(a.N, a.M, a.C, a.V, a.T_out, a.stride, a.wsize, cap); return 0; }
+    return launch_wgrad<1, 0, 2, 2, 2, true, WBXT>(a, dw, ws, ws_bytes, s, cap);
+  }
+  if (a.M % 128 == 0) {
+    if (ws_need) { *ws_need = ws_wgrad<TAPS, 0, 4, 1, 2, false>(a.N, a.M, a.C, a.V, a.T_out, a.stride, a.wsize, cap); return 0; }
+    return launch_wgrad<TAPS, 0, 4, 1, 2, false, WBXT>(a, dw, ws, ws_bytes, s, cap);
+  }
+  if (ws_need) { *ws_need = ws_wgrad<TAPS, 0, 2, 2, 2, false>(a.N, a.M, a.C, a.V, a.T_out, a.stride, a.wsize, cap); return 0; }
+  return launch_wgrad<TAPS, 0, 2, 2, 2, false, WBXT>(a, dw, ws, ws_bytes, s, cap);
+}
+
+// ws_need non-null: only report the workspace bytes
+int tconv_wgrad_dispatch(int taps, const WgradArgs& a, float* dw, void* ws, size_t ws_bytes, hipStream_t s,
+                         size_t* ws_need) {
+  switch (taps) {
+    case 1: return tconv_wgrad<1>(a, dw, ws, ws_bytes, s, ws_need);
+    case 2: return tconv_wgrad<2>(a, dw, ws, ws_bytes, s, ws_need);
+    case 3: return tconv_wgrad<3>(a, dw, ws, ws_bytes, s, ws_need);
+    case 4: return tconv_wgrad<4>(a, dw, ws, ws_bytes, s, ws_need);
+    case 5: return tconv_wgrad<5>(a, dw, ws, ws_bytes, s, ws_need);
+    case 6: return tconv_wgrad<6>(a, dw, ws, ws_bytes, s, ws_need);
+    case 7: return tconv_wgrad<7>(a, dw, ws, ws_bytes, s, ws_need);
+    case 8: return tconv_wgrad<8>(a, dw, ws, ws_bytes, s, ws_need);
+    case 9: return tconv_wgrad<9>(a, dw, ws, ws_bytes, s, ws_need);
+    default: return AGCN_ERR_UNSUPPORTED;
+  }
+}
+
+inline bool tconv_w_domain(int T, int taps, int stride, int pad) {
+  return taps >= 1 && taps <= 9 && stride >= 1 && stride <= 9 && pad >= 0 && pad <= (taps - 1) / 2 && T + 2 * pad >= taps;
 }
 
 inline bool chain_wgrad_enabled() {
@@ -442,7 +495,7 @@ int agcn_conv_bwd_weight_ex(const float* dy, const float* x, float* dw, void* wo
   const int pad = (taps - 1) / 2;
   WgradArgs a = {};
   a.dy = dy; a.in = x; a.N = N; a.M = Cout; a.C = Cin; a.V = V; a.T_src = T;
-  a.T_out = (T + 2 * pad - taps) / stride + 1; a.stride = stride;
+  a.T_out = (T + 2 * pad - taps) / stride + 1; a.stride = stride; a.pad = pad;
   a.so_m = (long)Cin * taps; a.so_t = 1; a.so_c = taps; a.wsize = (long)Cout * Cin * taps;
   hipStream_t s = (hipStream_t)stream;
   if (taps == 9) {
@@ -499,6 +552,49 @@ int agcn_gcn_project_bwd_weight_ex(const float* dy, const float* x, const float*
     return chain_wgrad_and_reduce(1, a, dwcat, workspace, workspace_bytes, s, dy_absmax, x_absmax);
   if (Cout % 128 == 0) return launch_wgrad<1, 1, 4, 2, 1, false, 2>(a, dwcat, workspace, workspace_bytes, s);
   return launch_wgrad<1, 1, 2, 2, 2, true, 2>(a, dwcat, workspace, workspace_bytes, s);
+}
+
+
+// ---- weight gradient of the temporal convolution with explicit padding (reference aagcn.py:184-207) ----
+size_t agcn_tconv_bwd_weight_workspace(int N, int Cin, int Cout, int T, int V, int taps, int stride, int pad) {
+  if (N <= 0 || Cin <= 0 || Cout <= 0 || T <= 0 || V <= 0 || !tconv_w_domain(T, taps, stride, pad)) return 0;
+  if (pad == (taps - 1) / 2 && (taps == 1 || taps == 9) && (stride == 1 || stride == 2))
+    return agcn_conv_bwd_weight_workspace(N, Cin, Cout, T, V, taps, stride);
+  WgradArgs a = {};
+  a.N = N; a.M = Cout; a.C = Cin; a.V = V; a.T_src = T; a.T_out = (T + 2 * pad - taps) / stride + 1; a.stride = stride;
+  a.pad = pad; a.wsize = (long)Cout * Cin * taps;
+  size_t need = 0;
+  tconv_wgrad_dispatch(taps, a, nullptr, nullptr, 0, nullptr, &need);
+  if (agcn_wgrad_tconv_f16_supported(Cout, Cin, V, taps, stride, pad)) {
+    const size_t t = agcn_wgrad_tconv_f16_workspace(N, Cout, Cin, V, T, taps, pad);
+    if (t > need) need = t;
+  }
+  return need;
+}
+
+// dw[o][c][k] = sum_{n,t,v} dy[n][o][t,v] * x[n][c][t*stride + k - pad, v]   (fixed-order slab reduction)
+int agcn_tconv_bwd_weight(const float* dy, const float* x, float* dw, void* workspace, size_t workspace_bytes, int N,
+                          int Cin, int Cout, int T, int V, int taps, int stride, int pad, const float* dy_absmax,
+                          const float* x_absmax, void* stream) {
+  if (!dy || !x || !dw || !workspace || N <= 0 || Cin <= 0 || Cout <= 0 || T <= 0 || V <= 0 || V > 32)
+    return AGCN_ERR_ARG;
+  if (!tconv_w_domain(T, taps, stride, pad)) return AGCN_ERR_UNSUPPORTED;
+  if (pad == (taps - 1) / 2 && (taps == 1 || taps == 9) && (stride == 1 || stride == 2))
+    return agcn_conv_bwd_weight_ex(dy, x, dw, workspace, workspace_bytes, N, Cin, Cout, T, V, taps, stride, dy_absmax,
+                                   x_absmax, stream);
+  WgradArgs a = {};
+  a.dy = dy; a.in = x; a.N = N; a.M = Cout; a.C = Cin; a.V = V; a.T_src = T;
+  a.T_out = (T + 2 * pad - taps) / stride + 1; a.stride = stride; a.pad = pad;
+  a.so_m = (long)Cin * taps; a.so_t = 1; a.so_c = taps; a.wsize = (long)Cout * Cin * taps;
+  hipStream_t s = (hipStream_t)stream;
+  if (agcn_wgrad_tconv_f16_supported(Cout, Cin, V, taps, stride, pad)) {     // stride 1, 3/5/7 taps: f16x3
+    int nslabs = 0;
+    const int rc = agcn_wgrad_tconv_f16(dy, x, workspace, workspace_bytes, &nslabs, N, Cout, Cin, V, T, taps, pad, s,
+                                        dy_absmax, x_absmax);
+    if (rc) return rc;
+    return launch_reduce((const float*)workspace, dw, a.wsize, nslabs, a.M, a.C, a.so_m, a.so_t, a.so_c, s);
+  }
+  return tconv_wgrad_dispatch(taps, a, dw, workspace, workspace_bytes, s, nullptr);
 }
 
 }  // extern "C"

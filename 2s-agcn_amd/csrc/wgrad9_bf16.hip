@@ -334,8 +334,12 @@ __device__ __forceinline__ f32x16 tap_mfma_f16(f16x8 ah, f16x8 al, const unsigne
   return c;
 }
 
-template <int RT, int CT, int STRIDE>
+// TAPS / SH0 (stride 1 only): tap k of a TAPS-tap convolution with padding 4 - SH0 reads the window shifted by SH0 + k
+// (the window starts 4 frames before the chunk); the 9-tap layer is TAPS = 9, SH0 = 0.  Slabs are [TAPS][M][C].
+template <int RT, int CT, int STRIDE, int TAPS = 9, int SH0 = 0>
 __global__ void __launch_bounds__(256, 2) wgrad9_f16_kernel(const W9Args a) {
+  static_assert(STRIDE == 1 || (TAPS == 9 && SH0 == 0), "other tap counts at stride 1 only");
+  static_assert(SH0 >= 0 && SH0 + TAPS - 1 <= 8, "every tap's 8 frames lie inside the 16-frame window");
   constexpr int NT = 256, BM = RT * 32, CBW = CT * 32, SETS = STRIDE;
   static_assert(RT * CT == 4, "four waves");
   constexpr int ND = BM * (TC / 4) / NT;                 // 4-frame groups of the dy tile per thread and plane (exact)
@@ -450,16 +454,16 @@ __global__ void __launch_bounds__(256, 2) wgrad9_f16_kernel(const W9Args a) {
         o0[i] = bw[SETS - 1][0][i >> 2][i & 3];
         o1[i] = bw[SETS - 1][1][i >> 2][i & 3];
       }
-      if (STRIDE == 1) {                           // tap k = window shift k
-        acc[0] = tap_mfma_f16<0>(ah, al, p0, p1, acc[0]);
-        acc[1] = tap_mfma_f16<1>(ah, al, p0, p1, acc[1]);
-        acc[2] = tap_mfma_f16<2>(ah, al, p0, p1, acc[2]);
-        acc[3] = tap_mfma_f16<3>(ah, al, p0, p1, acc[3]);
-        acc[4] = tap_mfma_f16<4>(ah, al, p0, p1, acc[4]);
-        acc[5] = tap_mfma_f16<5>(ah, al, p0, p1, acc[5]);
-        acc[6] = tap_mfma_f16<6>(ah, al, p0, p1, acc[6]);
-        acc[7] = tap_mfma_f16<7>(ah, al, p0, p1, acc[7]);
-        acc[8] = tap_mfma_f16<8>(ah, al, p0, p1, acc[8]);
+      if constexpr (STRIDE == 1) {                 // tap k = window shift SH0 + k
+        acc[0] = tap_mfma_f16<SH0 + 0>(ah, al, p0, p1, acc[0]);
+        if constexpr (TAPS > 1) acc[1] = tap_mfma_f16<SH0 + 1>(ah, al, p0, p1, acc[1]);
+        if constexpr (TAPS > 2) acc[2] = tap_mfma_f16<SH0 + 2>(ah, al, p0, p1, acc[2]);
+        if constexpr (TAPS > 3) acc[3] = tap_mfma_f16<SH0 + 3>(ah, al, p0, p1, acc[3]);
+        if constexpr (TAPS > 4) acc[4] = tap_mfma_f16<SH0 + 4>(ah, al, p0, p1, acc[4]);
+        if constexpr (TAPS > 5) acc[5] = tap_mfma_f16<SH0 + 5>(ah, al, p0, p1, acc[5]);
+        if constexpr (TAPS > 6) acc[6] = tap_mfma_f16<SH0 + 6>(ah, al, p0, p1, acc[6]);
+        if constexpr (TAPS > 7) acc[7] = tap_mfma_f16<SH0 + 7>(ah, al, p0, p1, acc[7]);
+        if constexpr (TAPS > 8) acc[8] = tap_mfma_f16<SH0 + 8>(ah, al, p0, p1, acc[8]);
       } else {                                     // even taps: xE shifted by 4 + (k-4)/2 ; odd taps: xO by 4 + (k-5)/2
         acc[0] = tap_mfma_f16<2>(ah, al, p0, p1, acc[0]);
         acc[1] = tap_mfma_f16<2>(ah, al, o0, o1, acc[1]);
@@ -478,9 +482,9 @@ __global__ void __launch_bounds__(256, 2) wgrad9_f16_kernel(const W9Args a) {
   f16_range_scale(a.dy_absmax, s_dy, inv_dy);
   f16_range_scale(a.x_absmax, s_x, inv_x);
   const float inv = inv_dy * inv_x;
-  float* dst = a.part + (long)split * 9 * a.M * a.C;
+  float* dst = a.part + (long)split * TAPS * a.M * a.C;
 #pragma unroll
-  for (int z = 0; z < 9; ++z)
+  for (int z = 0; z < TAPS; ++z)
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
       const int m = m0 + rt * 32 + mfma_row(j, h);
@@ -494,11 +498,13 @@ struct W9Geom {
   size_t slab_bytes, dyT_bytes, xT_bytes, smem_bytes, smem_f16;
 };
 
-inline W9Geom w9_geometry(int N, int M, int C, int V, int T, int stride) {      // T = OUTPUT frames
+// T = OUTPUT frames; Tx > T: frames of x (an unpadded convolution's input is longer than its output: both copies then
+// hold Tx frames, dy's zero beyond T)
+inline W9Geom w9_geometry(int N, int M, int C, int V, int T, int stride, int taps = 9, int Tx = 0) {
   W9Geom g;
   g.rt = (M % 128 == 0) ? 4 : 2;
   const int BM = g.rt * 32, CBW = (4 / g.rt) * 32;
-  g.Tp = (T + 7) & ~7;                               // (the fp16 transposer writes 8 frames per lane)
+  g.Tp = ((Tx > T ? Tx : T) + 7) & ~7;               // (the fp16 transposer writes 8 frames per lane)
   g.nchunk = (T + TC - 1) / TC;
   g.units = N * V * g.nchunk;
   g.nmb = (M + BM - 1) / BM;
@@ -509,7 +515,7 @@ inline W9Geom w9_geometry(int N, int M, int C, int V, int T, int stride) {      
   if (want > g.units) want = g.units;
   g.units_per_split = (g.units + want - 1) / want;
   g.nsplit = (g.units + g.units_per_split - 1) / g.units_per_split;
-  g.slab_bytes = (size_t)g.nsplit * 9 * M * C * 4;
+  g.slab_bytes = (size_t)g.nsplit * taps * M * C * 4;
   g.dyT_bytes = (size_t)N * V * M * g.Tp * 4;
   g.xT_bytes = (size_t)N * V * C * stride * g.Tp * 4;
   g.smem_bytes = (size_t)BM * DP * 4 + (size_t)3 * stride * CBW * XPB * 2;
@@ -544,12 +550,13 @@ int w9_transpose(const float* in, float* out, int N, int R, int T, int V, int Tp
   return agcn_check_launch();
 }
 
-template <int RT, int CT, int STRIDE>
+template <int RT, int CT, int STRIDE, int TAPS = 9, int SH0 = 0>
 int w9_launch_f16(const W9Args& a, const W9Geom& g, hipStream_t s) {
-  constexpr auto kern = wgrad9_f16_kernel<RT, CT, STRIDE>;
+  constexpr auto kern = wgrad9_f16_kernel<RT, CT, STRIDE, TAPS, SH0>;
   int rc = agcn_allow_big_lds<kern>();
   if (rc) return rc;
-  AGCN_NOTE_KERNEL("wgrad9_f16_kernel<%d, %d, %d>", RT, CT, STRIDE);
+  if (TAPS == 9) AGCN_NOTE_KERNEL("wgrad9_f16_kernel<%d, %d, %d>", RT, CT, STRIDE);
+  else AGCN_NOTE_KERNEL("wgrad9_f16_kernel<%d, %d, %d, %d, %d>", RT, CT, STRIDE, TAPS, SH0);
   hipLaunchKernelGGL(kern, dim3((unsigned)(g.nmb * g.ncb), (unsigned)g.nsplit), dim3(256), g.smem_f16, s, a);
   return agcn_check_launch();
 }
@@ -630,4 +637,77 @@ int agcn_wgrad9_bf16(const float* dy, const float* x, void* ws, size_t ws_bytes,
   }
   if (stride == 2) return w9_launch<4, 1, 2>(a, g, s);
   return g.rt == 4 ? w9_launch<4, 1, 1>(a, g, s) : w9_launch<2, 2, 1>(a, g, s);
+}
+
+// ---- stride-1 3/5/7-tap weight gradients (agcn_tconv_bwd_weight) on the same f16x3 kernel: tap k reads the window
+// shifted by 4 - pad + k, so every tap's frames lie in the 16-frame window while taps - pad <= 5 ("same" padding, and
+// pad 0 up to 5 taps).  Only in the default split mode (the f16x3 arithmetic); the caller runs the exact-f32 kernel
+// otherwise. ----
+bool agcn_wgrad_tconv_f16_supported(int M, int C, int V, int taps, int stride, int pad) {
+  if (stride != 1 || (taps != 3 && taps != 5 && taps != 7) || pad < 0 || pad > (taps - 1) / 2 || taps - pad > 5)
+    return false;
+  return agcn_gemm_precision() == 3 && w9_f16x3() && M % 64 == 0 && C % 64 == 0 && V >= 1 && V <= 32;
+}
+
+// T = frames of x
+size_t agcn_wgrad_tconv_f16_workspace(int N, int M, int C, int V, int T, int taps, int pad) {
+  const int To = T + 2 * pad - taps + 1;
+  const W9Geom g = w9_geometry(N, M, C, V, To, 1, taps, T);
+  return g.slab_bytes + g.dyT_bytes + g.xT_bytes + 512;
+}
+
+namespace {
+template <int TAPS, int SH0>
+int w9_launch_taps(const W9Args& a, const W9Geom& g, hipStream_t s) {
+  return g.rt == 4 ? w9_launch_f16<4, 1, 1, TAPS, SH0>(a, g, s) : w9_launch_f16<2, 2, 1, TAPS, SH0>(a, g, s);
+}
+}  // namespace
+
+// writes *nslabs slabs [taps][M][C] at the start of ws (summed by the caller's slab reduction); the maxima as for 9 taps
+int agcn_wgrad_tconv_f16(const float* dy, const float* x, void* ws, size_t ws_bytes, int* nslabs, int N, int M, int C,
+                         int V, int T, int taps, int pad, hipStream_t s, const float* dy_absmax, const float* x_absmax) {
+  if (!agcn_wgrad_tconv_f16_supported(M, C, V, taps, 1, pad)) return AGCN_ERR_UNSUPPORTED;
+  const int To = T + 2 * pad - taps + 1;
+  if (To < 1) return AGCN_ERR_UNSUPPORTED;
+  const W9Geom g = w9_geometry(N, M, C, V, To, 1, taps, T);
+  if (g.slab_bytes + g.dyT_bytes + g.xT_bytes + 512 > ws_bytes) return AGCN_ERR_WORKSPACE;
+  unsigned char* base = (unsigned char*)ws;
+  float* dyT = (float*)(base + ((g.slab_bytes + 255) & ~(size_t)255));
+  float* xT = (float*)((unsigned char*)dyT + g.dyT_bytes);
+  if ((size_t)((unsigned char*)xT - base) + g.xT_bytes + 8 > ws_bytes) return AGCN_ERR_WORKSPACE;
+  unsigned* scr = reinterpret_cast<unsigned*>((unsigned char*)xT + g.xT_bytes);     // two scalars behind the copies
+  if (!dy_absmax) {
+    if (int rc = agcn_launch_absmax(dy, (long)N * M * To * V, scr, s)) return rc;
+    dy_absmax = reinterpret_cast<const float*>(scr);
+  }
+  if (!x_absmax) {
+    if (int rc = agcn_launch_absmax(x, (long)N * C * T * V, scr + 1, s)) return rc;
+    x_absmax = reinterpret_cast<const float*>(scr + 1);
+  }
+  int rc = w9_transpose(dy, dyT, N, M, To, V, g.Tp, 1, s, dy_absmax);
+  if (rc) return rc;
+  rc = w9_transpose(x, xT, N, C, T, V, g.Tp, 1, s, x_absmax);
+  if (rc) return rc;
+  W9Args a = {};
+  a.dyT = dyT; a.xT = xT; a.part = (float*)ws;
+  a.N = N; a.M = M; a.C = C; a.V = V; a.T = To; a.Tp = g.Tp;
+  a.nchunk = g.nchunk; a.units = g.units; a.units_per_split = g.units_per_split; a.ncb = g.ncb;
+  a.npl = 3;
+  a.dyH = reinterpret_cast<const unsigned short*>(dyT);
+  a.xH = reinterpret_cast<const unsigned short*>(xT);
+  a.dy_plane = (long)N * V * M * g.Tp;
+  a.x_plane = (long)N * V * C * g.Tp;
+  a.dy_absmax = dy_absmax; a.x_absmax = x_absmax;
+  *nslabs = g.nsplit;
+  const int sh0 = 4 - pad;
+  switch (taps * 16 + sh0) {
+    case 3 * 16 + 3: return w9_launch_taps<3, 3>(a, g, s);      // pad 1
+    case 3 * 16 + 4: return w9_launch_taps<3, 4>(a, g, s);      // pad 0
+    case 5 * 16 + 2: return w9_launch_taps<5, 2>(a, g, s);      // pad 2
+    case 5 * 16 + 3: return w9_launch_taps<5, 3>(a, g, s);      // pad 1
+    case 5 * 16 + 4: return w9_launch_taps<5, 4>(a, g, s);      // pad 0
+    case 7 * 16 + 1: return w9_launch_taps<7, 1>(a, g, s);      // pad 3
+    case 7 * 16 + 2: return w9_launch_taps<7, 2>(a, g, s);      // pad 2
+    default: return AGCN_ERR_UNSUPPORTED;
+  }
 }

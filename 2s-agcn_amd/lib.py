@@ -46,6 +46,12 @@ SIGNATURES = {
     "agcn_conv_bwd_weight_ex": (_I, [_P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "agcn_gcn_project_bwd_weight_ex": (_I, [_P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _P, _P, _P]),
     "agcn_absmax": (_I, [_P, ctypes.c_long, _P, _P]),
+    "agcn_tconv_workspace": (_Z, [_I] * 7),
+    "agcn_tconv_stats_tiles": (_I, [_I] * 7),
+    "agcn_tconv_fwd": (_I, [_P] * 6 + [_Z] + [_I] * 8 + [_P, _P]),
+    "agcn_tconv_bwd_data": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _Z] + [_I] * 8 + [_P, _P]),
+    "agcn_tconv_bwd_weight_workspace": (_Z, [_I] * 8),
+    "agcn_tconv_bwd_weight": (_I, [_P] * 4 + [_Z] + [_I] * 8 + [_P] * 3),
     "agcn_bn_act_fwd_ex": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "agcn_bn_bwd_apply_ex": (_I, [_P, _I, _D, _F, _P, _P, _I] + [_P] * 16 + [_I, _I, _I, _P]),
     "agcn_conv_fwd_ex": (_I, [_P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _I, _I, _P, _P]),

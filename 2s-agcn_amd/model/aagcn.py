@@ -135,20 +135,21 @@ class AdaptiveGCN(nn.Module):
 class TCNUnit(nn.Module):
     def __init__(self, in_channels, out_channels, kernel_size=9, stride=1, pad=True, gbn_split=None):
         super().__init__()
-        if kernel_size not in (1, 9) or not pad:
-            raise NotImplementedError("agcn_amd.aagcn.TCNUnit: kernel_size in {1, 9} with padding only")
-        padding = (kernel_size - 1) // 2
+        if not 1 <= kernel_size <= 9:
+            raise NotImplementedError(f"agcn_amd.aagcn.TCNUnit: kernel_size {kernel_size} is outside 1..9, the "
+                                      f"temporal kernel sizes the HIP convolution kernels are built for")
+        padding = (kernel_size - 1) // 2 if pad else 0           # reference aagcn.py:193
         self.conv = nn.Conv2d(in_channels, out_channels, kernel_size=(kernel_size, 1), padding=(padding, 0),
                               stride=(stride, 1))
         self.bn = batch_norm_2d(out_channels, gbn_split)
-        self.stride = stride
+        self.stride, self.pad = stride, padding
         conv_init(self.conv)
         bn_init(self.bn, 1)
 
     def forward(self, x):
         _require_gpu(x, 'aagcn.TCNUnit')
         y = ops.UnitTCNFunction.apply(x, self.conv.weight, self.conv.bias, *_bn_args(self.bn), self.stride,
-                                      self.training, ops.sync_of(self.bn))
+                                      self.training, ops.sync_of(self.bn), self.pad)
         _bn_tick(self.bn, self.training)
         return y
 
@@ -255,7 +256,7 @@ class TCNGCNUnit(nn.Module):
             rargs = (None,) * 6
         out = ops.TCNResidualFunction.apply(y, x if self.res_mode else None, t.conv.weight, t.conv.bias,
                                             *_bn_args(t.bn), self.res_mode, *rargs, self.stride, self.training,
-                                            ops.sync_of(t.bn))
+                                            ops.sync_of(t.bn), t.pad)
         _bn_tick(t.bn, self.training)
         if self.res_mode == 2:
             _bn_tick(self.residual.bn, self.training)
@@ -290,7 +291,8 @@ class BaseModel(nn.Module):
             setattr(self, f'l{k}', lambda x: x)
 
     def init_model_backbone(self, model_layers, tcngcn_unit, output_channel=None):
-        """Layer subsets of reference aagcn.py:403-474 (3, 6, 7, 10 and the 101-103 one-width stacks)."""
+        """Layer subsets of reference aagcn.py:403-474 (3, 6, 7, 10, the 101-103 one-width stacks and the 1002/1003
+        stacks whose first layers ask the unit factory for padding=True)."""
         self.init_empty_model_backbone()
         full = {1: (3, 64, 1, False), 2: (64, 64, 1, True), 3: (64, 64, 1, True), 4: (64, 64, 1, True),
                 5: (64, 128, 2, True), 6: (128, 128, 1, True), 7: (128, 128, 1, True), 8: (128, 256, 2, True),
@@ -305,6 +307,15 @@ class BaseModel(nn.Module):
             self.l1 = tcngcn_unit(3, c, residual=False)
             for k in range(2, model_layers - 100 + 1):
                 setattr(self, f'l{k}', tcngcn_unit(c, c))
+        elif model_layers == 1002:
+            c = output_channel if output_channel is not None else 64
+            self.l1 = tcngcn_unit(3, c, stride=1, padding=True, residual=False)
+            self.l2 = tcngcn_unit(c, c)
+        elif model_layers == 1003:
+            c = output_channel if output_channel is not None else 64
+            self.l1 = tcngcn_unit(3, c, stride=1, padding=True, residual=False)
+            self.l2 = tcngcn_unit(c, c, stride=1, padding=True)
+            self.l3 = tcngcn_unit(c, c)
         else:
             raise ValueError(f"Model with {model_layers} layers is not supported.")
 

@@ -81,21 +81,22 @@ def data_bn_forward(bn, x):
 class unit_tcn(nn.Module):
     def __init__(self, in_channels, out_channels, kernel_size=9, stride=1):
         super().__init__()
-        if kernel_size not in (1, 9):
-            raise ValueError("agcn_amd.unit_tcn: kernel_size must be 1 or 9")
+        if not 1 <= kernel_size <= 9:
+            raise NotImplementedError(f"agcn_amd.unit_tcn: kernel_size {kernel_size} is outside 1..9, the temporal "
+                                      f"kernel sizes the HIP convolution kernels are built for")
         pad = int((kernel_size - 1) / 2)
         self.conv = nn.Conv2d(in_channels, out_channels, kernel_size=(kernel_size, 1), padding=(pad, 0),
                               stride=(stride, 1))
         self.bn = nn.BatchNorm2d(out_channels)
         self.relu = nn.ReLU()
-        self.stride = stride
+        self.stride, self.pad = stride, pad
         conv_init(self.conv)
         bn_init(self.bn, 1)
 
     def forward(self, x):
         _require_gpu(x, 'unit_tcn')
         y = ops.UnitTCNFunction.apply(x, self.conv.weight, self.conv.bias, *_bn_args(self.bn), self.stride,
-                                      self.training, ops.sync_of(self.bn))
+                                      self.training, ops.sync_of(self.bn), self.pad)
         _bn_tick(self.bn, self.training)
         return y
 

@@ -30,8 +30,9 @@ def _ws(nbytes, like):
     return torch.empty((int(nbytes) + 3) // 4, dtype=torch.float32, device=like.device)
 
 
-def _conv_ws(Cin, Cout, T, V, taps, stride, like):
-    n = _L().agcn_conv_workspace(Cin, Cout, T, V, taps, stride)
+def _conv_ws(Cin, Cout, T, V, taps, stride, like, pad=None):
+    pad = (taps - 1) // 2 if pad is None else pad
+    n = _L().agcn_tconv_workspace(Cin, Cout, T, V, taps, stride, pad)
     return _ws(n, like), n
 
 
@@ -119,55 +120,63 @@ def _take_out_amax(t):
     return e[2] if hit else None
 
 
-def conv_out_frames(T, taps, stride):
-    pad = (taps - 1) // 2
+def conv_out_frames(T, taps, stride, pad=None):
+    """Output frames of the (taps x 1) temporal convolution; pad None = (taps-1)//2 (reference unit_tcn / TCNUnit
+    with pad=True), 0 for TCNUnit(pad=False) (aagcn.py:194)."""
+    pad = (taps - 1) // 2 if pad is None else pad
     return (T + 2 * pad - taps) // stride + 1
 
 
-def conv_fwd(x, w, b, stride=1, want_stats=False, x_amax=None):
-    """y = conv2d(x, w(k,1), b, stride=(s,1), padding=((k-1)/2,0)); optional per-channel (sum,sumsq) partials."""
+def conv_fwd(x, w, b, stride=1, want_stats=False, x_amax=None, pad=None):
+    """y = conv2d(x, w(k,1), b, stride=(s,1), padding=(pad,0)), pad None = (k-1)//2; optional per-channel (sum,sumsq)
+    partials.  Every kernel size 1..9, stride 1..9 and padding 0..(k-1)//2 (agcn_tconv_fwd)."""
     N, Cin, T, V = x.shape
     Cout, Cin2, taps, one = w.shape
     assert Cin2 == Cin and one == 1
-    To = conv_out_frames(T, taps, stride)
+    pad = (taps - 1) // 2 if pad is None else pad
+    To = conv_out_frames(T, taps, stride, pad)
+    if To < 1:
+        raise ValueError(f"agcn_amd: a {taps}-frame kernel with padding {pad} does not fit {T} frames")
     y = _empty((N, Cout, To, V), x)
     stats = None
     if want_stats:
-        nt = _L().agcn_conv_stats_tiles(Cin, Cout, To, V, taps, stride)
+        nt = _L().agcn_tconv_stats_tiles(Cin, Cout, To, V, taps, stride, pad)
         stats = _empty((N * nt, 2, Cout), x)
-    ws, nb = _conv_ws(Cin, Cout, T, V, taps, stride, x)
+    ws, nb = _conv_ws(Cin, Cout, T, V, taps, stride, x, pad)
     # x_amax: 1-element tensor with max |x| left by bn_act_fwd(..., want_amax=True): the split-fp16 temporal convolution
     # then skips its own pass over x
-    _lib.check(_L().agcn_conv_fwd_ex(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(y), _lib.ptr(stats), ws.data_ptr(),
-                                     nb, N, Cin, Cout, T, V, taps, stride, _lib.ptr(x_amax), _lib.stream()),
-               "agcn_conv_fwd")
+    _lib.check(_L().agcn_tconv_fwd(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(y), _lib.ptr(stats), ws.data_ptr(),
+                                   nb, N, Cin, Cout, T, V, taps, stride, pad, _lib.ptr(x_amax), _lib.stream()),
+               "agcn_tconv_fwd")
     return y, stats
 
 
 def conv_bwd_data(dy, w, x_shape, stride=1, out=None, accumulate=False, add1=None, mask1=None, add2=None,
-                  mask2=None, dy_amax=None):
+                  mask2=None, dy_amax=None, pad=None):
     N, Cin, T, V = x_shape
     Cout, _, taps, _ = w.shape
+    pad = (taps - 1) // 2 if pad is None else pad
     dx = out if out is not None else _empty(x_shape, dy)
-    ws, nb = _conv_ws(Cin, Cout, T, V, taps, stride, dy)
-    _lib.check(_L().agcn_conv_bwd_data_ex(_lib.ptr(dy), _lib.ptr(w), _lib.ptr(dx), int(accumulate), _lib.ptr(add1),
-                                          _lib.ptr(mask1), _lib.ptr(add2), _lib.ptr(mask2), ws.data_ptr(), nb, N, Cin,
-                                          Cout, T, V, taps, stride, _lib.ptr(dy_amax), _lib.stream()),
-               "agcn_conv_bwd_data")
+    ws, nb = _conv_ws(Cin, Cout, T, V, taps, stride, dy, pad)
+    _lib.check(_L().agcn_tconv_bwd_data(_lib.ptr(dy), _lib.ptr(w), _lib.ptr(dx), int(accumulate), _lib.ptr(add1),
+                                        _lib.ptr(mask1), _lib.ptr(add2), _lib.ptr(mask2), ws.data_ptr(), nb, N, Cin,
+                                        Cout, T, V, taps, stride, pad, _lib.ptr(dy_amax), _lib.stream()),
+               "agcn_tconv_bwd_data")
     return dx
 
 
-def conv_bwd_weight(dy, x, w_shape, stride=1, dy_amax=None, x_amax=None):
+def conv_bwd_weight(dy, x, w_shape, stride=1, dy_amax=None, x_amax=None, pad=None):
     """dy_amax / x_amax: device scalars max |dy| / max |x| left behind by their producers; with both, the tap-free
     gradients run on f16x3 (agcn_conv_bwd_weight_ex)."""
     N, Cin, T, V = x.shape
     Cout, _, taps, _ = w_shape
-    nbytes = _L().agcn_conv_bwd_weight_workspace(N, Cin, Cout, T, V, taps, stride)
+    pad = (taps - 1) // 2 if pad is None else pad
+    nbytes = _L().agcn_tconv_bwd_weight_workspace(N, Cin, Cout, T, V, taps, stride, pad)
     ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x.device)
     dw = _empty(tuple(w_shape), x)
-    _lib.check(_L().agcn_conv_bwd_weight_ex(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(dw), _lib.ptr(ws), nbytes, N, Cin, Cout,
-                                            T, V, taps, stride, _lib.ptr(dy_amax), _lib.ptr(x_amax), _lib.stream()),
-               "agcn_conv_bwd_weight")
+    _lib.check(_L().agcn_tconv_bwd_weight(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(dw), _lib.ptr(ws), nbytes, N, Cin, Cout,
+                                          T, V, taps, stride, pad, _lib.ptr(dy_amax), _lib.ptr(x_amax), _lib.stream()),
+               "agcn_tconv_bwd_weight")
     return dw
 
 
@@ -876,15 +885,23 @@ def gcn_backward(c, dout, extra_add=None, extra_mask=None):
     return dx, dPA, dwab, dbab, dwd, dg1, db1, dwdown, dg2, db2
 
 
-def tcn_forward(c, g, w, b, bn, stride, res_x, res, relu, training, sync=None):
+def tcn_forward(c, g, w, b, bn, stride, res_x, res, relu, training, sync=None, pad=None):
     """unit_tcn.forward (reference agcn.py:48-50) optionally fused with the TCN_GCN_unit tail
     relu(tcn(g) + residual(x)) (agcn.py:127-129).  res = None (no residual) | 'identity' |
-    (w, b, bn_w, bn_b, bn_rm, bn_rv) for the unit_tcn(kernel_size=1, stride) residual."""
+    (w, b, bn_w, bn_b, bn_rm, bn_rv) for the unit_tcn(kernel_size=1, stride) residual.  pad: temporal padding of the
+    convolution (None = (k-1)//2; TCNUnit(pad=False): 0)."""
     N, C, T, V = g.shape
+    if res is not None:
+        To = conv_out_frames(T, w.shape[2], stride, pad)
+        Tr = res_x.shape[2] if isinstance(res, str) else conv_out_frames(res_x.shape[2], 1, stride, 0)
+        if Tr != To:
+            raise RuntimeError(f"agcn_amd: the residual has {Tr} frames but the temporal convolution ({w.shape[2]} taps, "
+                               f"stride {stride}, padding {(w.shape[2] - 1) // 2 if pad is None else pad}) gives {To} "
+                               f"for {T} input frames; they must agree (the reference fails here too)")
     g_amax = getattr(c, 'g_amax', None) if getattr(c, 'g_out', None) is g else None   # only for the tensor it describes
     if g_amax is None and getattr(c, 'g_out', None) is None:
         g_amax = _take_out_amax(g)       # stand-alone unit_tcn (AAGCN): the producer of g (attention gates / unit_gcn) noted it
-    zpre, st = conv_fwd(g, w, b, stride, want_stats=training, x_amax=g_amax)
+    zpre, st = conv_fwd(g, w, b, stride, want_stats=training, x_amax=g_amax, pad=pad)
     To = zpre.shape[2]
     count = N * To * V
     rpre = bn2 = None
@@ -905,7 +922,7 @@ def tcn_forward(c, g, w, b, bn, stride, res_x, res, relu, training, sync=None):
     c.t_g_amax = g_amax
     c.t_resx, c.t_res_identity = res_x, isinstance(res, str)
     c.t_params = (w, bn[0], res[0] if isinstance(res, tuple) else None, res[2] if isinstance(res, tuple) else None)
-    c.t_stride, c.t_relu = stride, relu
+    c.t_stride, c.t_relu, c.t_pad = stride, relu, pad
     return out
 
 
@@ -916,12 +933,12 @@ def tcn_backward(c, dout, join=True):
     dz_amax = _empty((1,), dout) if fused_amax_enabled() else None   # max |dzpre| for the backward-data convolution
     dzpre, dg1, db1, drpre, dg2, db2 = bn_bwd(dout, mask, c.t_zpre, gamma1, c.t_bn1, c.t_rpre, gamma2, c.t_bn2,
                                               sync=c.t_sync, gcount=c.t_count, amax_out=dz_amax)
-    t_g, t_stride = c.t_g, c.t_stride
+    t_g, t_stride, t_pad = c.t_g, c.t_stride, getattr(c, 't_pad', None)
     t_g_amax = getattr(c, 't_g_amax', None)
     # (the device scalars are inputs of the side-stream kernels too: dz_amax dies with this frame, possibly before the join)
-    dw = _side_run(lambda: conv_bwd_weight(dzpre, t_g, w.shape, t_stride, dz_amax, t_g_amax),
+    dw = _side_run(lambda: conv_bwd_weight(dzpre, t_g, w.shape, t_stride, dz_amax, t_g_amax, pad=t_pad),
                    (dzpre, t_g, dz_amax, t_g_amax))
-    dg = conv_bwd_data(dzpre, w, c.t_g.shape, c.t_stride, dy_amax=dz_amax)
+    dg = conv_bwd_data(dzpre, w, c.t_g.shape, c.t_stride, dy_amax=dz_amax, pad=t_pad)
     dwres = None
     if drpre is not None:
         t_resx = c.t_resx
@@ -1000,7 +1017,7 @@ def unit_infer(x, A, PA, wab, bab, wd, bd, gbn, down, tw, tb, tbn, res_mode, res
     x = x.contiguous()
     N, C, T, V = x.shape
     Cout = wd.shape[0]
-    if C < 32:
+    if C < 32 or tw.shape[2] != 9:       # (the folded temporal kernel is the 9-tap one)
         return None
     srcs = [wd, bd, *gbn, tw, tb, *tbn] + (list(down) if down is not None else []) + \
            (list(res) if isinstance(res, tuple) else [])
@@ -1087,13 +1104,13 @@ class UnitGCNFunction(torch.autograd.Function):
 
 
 class UnitTCNFunction(torch.autograd.Function):
-    """unit_tcn (no residual, no ReLU): args (x, w, b, bn_w, bn_b, bn_rm, bn_rv, stride, training)"""
+    """unit_tcn (no residual, no ReLU): args (x, w, b, bn_w, bn_b, bn_rm, bn_rv, stride, training, sync, pad)"""
 
     @staticmethod
-    def forward(ctx, x, w, b, bn_w, bn_b, bn_rm, bn_rv, stride, training, sync=None):
+    def forward(ctx, x, w, b, bn_w, bn_b, bn_rm, bn_rv, stride, training, sync=None, pad=None):
         c = _Ctx()
         out = tcn_forward(c, x.contiguous(), w, b, (bn_w, bn_b, bn_rm, bn_rv), stride, None, None, False, training,
-                          sync)
+                          sync, pad)
         ctx.c, ctx.training = c, training
         return out
 
@@ -1103,21 +1120,22 @@ class UnitTCNFunction(torch.autograd.Function):
         dg, dw, dg1, db1, _, _, _, _ = tcn_backward(ctx.c, dout.contiguous())
         dbias = torch.zeros(dw.shape[0], dtype=torch.float32, device=dout.device)
         ctx.c = None
-        return dg, dw, dbias, dg1, db1, None, None, None, None, None
+        return dg, dw, dbias, dg1, db1, None, None, None, None, None, None
 
 
 class TCNResidualFunction(torch.autograd.Function):
     """relu(bn(conv9(g)) + residual(x)) as its own autograd node (AAGCN: the attention ops sit between the GCN core and
     this).  args: g, x, w, b, bn_w, bn_b, bn_rm, bn_rv, res_mode (0 none, 1 identity, 2 conv), rw, rb, rbn_w, rbn_b,
-    rbn_rm, rbn_rv, stride, training"""
+    rbn_rm, rbn_rv, stride, training, sync, pad (of the temporal convolution; None = (k-1)//2)"""
 
     @staticmethod
     def forward(ctx, g, x, w, b, bn_w, bn_b, bn_rm, bn_rv, res_mode, rw, rb, rbn_w, rbn_b, rbn_rm, rbn_rv, stride,
-                training, sync=None):
+                training, sync=None, pad=None):
         c = _Ctx()
         res = None if res_mode == 0 else ('identity' if res_mode == 1 else (rw, rb, rbn_w, rbn_b, rbn_rm, rbn_rv))
         x = x.contiguous() if x is not None else None
-        out = tcn_forward(c, g.contiguous(), w, b, (bn_w, bn_b, bn_rm, bn_rv), stride, x, res, True, training, sync)
+        out = tcn_forward(c, g.contiguous(), w, b, (bn_w, bn_b, bn_rm, bn_rv), stride, x, res, True, training, sync,
+                          pad)
         ctx.c, ctx.training, ctx.res_mode, ctx.stride = c, training, res_mode, stride
         ctx.x_shape = tuple(x.shape) if x is not None else None
         return out
@@ -1137,7 +1155,7 @@ class TCNResidualFunction(torch.autograd.Function):
             dx = conv_bwd_data(drpre, c.t_params[2], ctx.x_shape, ctx.stride)
         ctx.c = None
         return (dg, dx, dw, zb(dw.shape[0]), dg1, db1, None, None, None,
-                dwres, zb(dwres.shape[0]) if ctx.res_mode == 2 else None, dg2, db2, None, None, None, None, None)
+                dwres, zb(dwres.shape[0]) if ctx.res_mode == 2 else None, dg2, db2, None, None, None, None, None, None)
 
 
 class TCNGCNUnitFunction(torch.autograd.Function):

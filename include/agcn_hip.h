@@ -132,6 +132,31 @@ int agcn_conv_bwd_data_ex(const float* dy, const float* w, float* dx, int accumu
                           size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride,
                           const float* dy_absmax, void* stream);
 
+/* ---- temporal convolution with any kernel size, stride and padding ----------------------------------------------------
+ * replaces the convolution of TCNUnit(kernel_size, stride, pad) (reference aagcn.py:184-207: padding = (kernel_size-1)//2
+ * if pad else 0) and of unit_tcn(kernel_size, stride) (agcn.py:36-50) for the configurations agcn_conv_* rejects (the
+ * aagcn_vNN backbones: kernel_size 3, stride 3, pad False, aagcn_v17.py:202-204; kernel_size 3 stride 1 in v37).
+ * Domain: 1 <= taps <= 9, 1 <= stride <= 9, 0 <= pad <= (taps-1)/2, T + 2 pad >= taps; T_out = (T + 2 pad - taps)/stride + 1.
+ * Outside it: AGCN_ERR_UNSUPPORTED (bad pointers / sizes: AGCN_ERR_ARG), checked on the host before any launch.
+ * Shapes agcn_conv_* covers (taps 1 or 9, pad (taps-1)/2, stride 1 or 2) run there unchanged; stride-1 3/5/7-tap
+ * convolutions run on the split-bf16 / f16x3 kernels in those AGCN_GEMM modes; everything else (and AGCN_GEMM=f32) on the
+ * exact-f32 kernels.  Frames of x that no window reaches receive a zero gradient.  The *_absmax arguments are those of
+ * the _ex forms (NULL: a pass of its own where the f16x3 kernels need it).  Workspaces: agcn_tconv_workspace (forward,
+ * backward-data), agcn_tconv_bwd_weight_workspace; stats_part: N * agcn_tconv_stats_tiles slots. */
+size_t agcn_tconv_workspace(int Cin, int Cout, int T, int V, int taps, int stride, int pad);
+int agcn_tconv_stats_tiles(int Cin, int Cout, int T_out, int V, int taps, int stride, int pad);
+int agcn_tconv_fwd(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* workspace,
+                   size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride, int pad,
+                   const float* x_absmax, void* stream);
+int agcn_tconv_bwd_data(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
+                        const float* mask1, const float* add2, const float* mask2, void* workspace,
+                        size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride, int pad,
+                        const float* dy_absmax, void* stream);
+size_t agcn_tconv_bwd_weight_workspace(int N, int Cin, int Cout, int T, int V, int taps, int stride, int pad);
+int agcn_tconv_bwd_weight(const float* dy, const float* x, float* dw, void* workspace, size_t workspace_bytes, int N,
+                          int Cin, int Cout, int T, int V, int taps, int stride, int pad, const float* dy_absmax,
+                          const float* x_absmax, void* stream);
+
 /* ---- unit_gcn forward of the first layer (1..4 input channels) ----------------------------------------------------------
  * replaces agcn.py:103-105 AND the `down` convolution (agcn.py:74-77, 108) for in_channels = 3 in one pass over x:
  * ypre = bias + sum_i Wd_i (x . adj_i), dpre = bdown + Wdown x (wdown (Cout, C) row-major or NULL), and the per-tile
