@@ -83,6 +83,13 @@ int agcn_bf16_tconv_bwd_data(const float* dy, const float* w, float* dx, int acc
                              int N, int Cin, int Cout, int T, int V, int taps, int pad, int npl, hipStream_t s,
                              const float* dy_absmax);
 
+// BN-folded inference on the same kernels, the attention gates of gate.h applied while the operand is staged
+struct GateArgs;
+bool agcn_bf16_tconv_infer_supported(int taps, int stride, int pad);
+int agcn_bf16_tconv_infer(const float* x, const float* w, const float* bias, float* y, void* ws, size_t ws_bytes, int N,
+                          int Cin, int Cout, int T, int V, int taps, int stride, int pad, int npl, hipStream_t s,
+                          const float* add, int relu, const float* x_absmax, const GateArgs* gate);
+
 size_t agcn_bf16_conv1_workspace(int Cin, int Cout, int T, int V, int stride);
 int agcn_bf16_conv1_fwd(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* ws,
                         size_t ws_bytes, int N, int Cin, int Cout, int T, int V, int stride, int npl, hipStream_t s,

@@ -20,6 +20,8 @@
 //   chunk k and committed to LDS after it, so HBM/L2 latency hides under the MFMAs; operand fragments are read one
 //   step ahead of the MFMAs that use them.
 #include "agcn_common.h"
+#include "epilogue.h"
+#include "gate.h"
 #include "split_f16.h"
 
 namespace {
@@ -48,6 +50,17 @@ struct ConvGemmArgs {
   int nchunks, nmb;
   int off_bx, off_bg, off_adj;       // LDS offsets (floats)
 };
+
+// EPI == 2 (agcn_tconv_infer) only -- a kernel argument type of its own, so that every other instantiation keeps the
+// argument block it was tuned with: attention factors applied to `in` while it is staged (gate.h), the folded-BatchNorm
+// store epilogue of epilogue.h (bias, residual `add1`, ReLU)
+struct InferGemmArgs : ConvGemmArgs {
+  GateArgs gate;
+  int gated, relu;
+  int off_bias, off_gate;            // LDS offsets (floats) of the bias row and the gate image, behind the epilogue tile
+};
+template <int EPI> struct GemmArgsOf { typedef ConvGemmArgs type; };
+template <> struct GemmArgsOf<2> { typedef InferGemmArgs type; };
 
 struct PackArgs {
   const float* w;
@@ -94,8 +107,9 @@ __device__ __forceinline__ f32x16 agg_chain(const float* bxrow, const float* adj
 }
 
 // WB = max number of 64-float column blocks of a staged window row (compile-time bound of the prefetch registers)
+// EPI: 0 = plain store with BatchNorm partials, 1 = adjacency gradient, 2 = folded inference (gates on load, epilogue.h)
 template <int TAPS, int AGG, int WM, int WN, int TM, int TN, int CK, int WB, int EPI>
-__global__ void __launch_bounds__(WM* WN * 64, (TAPS == 1 && EPI == 0 && (AGG == 0 || WM * WN == 8) && (WB < 8 || WM * WN == 8)) ? 4 : 2) conv_gemm_kernel(const ConvGemmArgs a) {
+__global__ void __launch_bounds__(WM* WN * 64, (TAPS == 1 && EPI == 0 && (AGG == 0 || WM * WN == 8) && (WB < 8 || WM * WN == 8)) ? 4 : 2) conv_gemm_kernel(const typename GemmArgsOf<EPI>::type a) {
   constexpr int NW = WM * WN, NT = NW * 64;
   constexpr int BM = WM * TM * 32;
   constexpr int NSUB = AGG ? 3 : 1;
@@ -166,6 +180,23 @@ __global__ void __launch_bounds__(WM* WN * 64, (TAPS == 1 && EPI == 0 && (AGG ==
   // ---- prefetch registers ----
   f32x4 ra[EA];
   float rb[RPW][WB];
+  // EPI == 2: bias row and gate vectors in LDS; a lane stages the same window positions in every K chunk, so their
+  // (joint, frame) factor is taken once
+  const int KPG = a.nchunks * CK;
+  const float* gl = smem;
+  bool gated = false;
+  float gpos[WB];
+  if constexpr (EPI == 2) {
+    gl = smem + a.off_gate;
+    gated = a.gated != 0;
+    for (int e = tid; e < BM; e += NT) smem[a.off_bias + e] = (a.bias && m0 + e < a.M) ? a.bias[m0 + e] : 0.f;
+    if (gated) {
+      gate_stage<NT>(smem + a.off_gate, a.gate, n, V, a.T_src, a.Kinner, f0, a.FW, KPG);
+      __syncthreads();
+#pragma unroll
+      for (int u = 0; u < WB; ++u) gpos[u] = gate_pos(gl, KPG, lane + 64 * u, V, WL);
+    }
+  }
   const f32x4* wp4 = reinterpret_cast<const f32x4*>(a.wp) + (long)mbk * a.nchunks * N4;
   const int g0 = f0 * V;
 
@@ -204,7 +235,13 @@ __global__ void __launch_bounds__(WM* WN * 64, (TAPS == 1 && EPI == 0 && (AGG ==
         const int r = lane + 64 * u;
         const int gp = g0 + r;
         const bool ok = rok && gp >= 0 && gp < Psrc;
-        if (kcl < CK && r < WL) Bx[kcl * WLP + r] = ok ? rb[j][u] : 0.f;
+        if constexpr (EPI == 2) {
+          float xv = ok ? rb[j][u] : 0.f;
+          if (gated) xv = xv * gpos[u] * gl[min(kc0 + kcl, KPG - 1)];   // (the channel factor is a wave-uniform LDS read)
+          if (kcl < CK && r < WL) Bx[kcl * WLP + r] = xv;
+        } else {
+          if (kcl < CK && r < WL) Bx[kcl * WLP + r] = ok ? rb[j][u] : 0.f;
+        }
       }
     }
   };
@@ -301,7 +338,36 @@ __global__ void __launch_bounds__(WM* WN * 64, (TAPS == 1 && EPI == 0 && (AGG ==
     }
   }
 
-  if (EPI == 0) {
+  if constexpr (EPI == 2) {
+    // ---- folded inference: tile -> LDS -> epilogue.h (bias, residual, ReLU; coalesced row stores) ----
+    constexpr int TP = WN * TN * 32 + 1;
+    float* otile = smem;                // [BM][TP]; the bias row and the gate image lie behind it
+    float* red = otile + BM * TP;
+    __syncthreads();                   // every wave is done with the A/B images
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+      for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+          otile[((wm * TM + tm) * 32 + mfma_row(j, h)) * TP + (wn * TN + tn) * 32 + lr] = acc[tm][tn][j];
+    __syncthreads();
+    constexpr int XB = WN * TN * 32 / 64;
+    int poff[XB];
+#pragma unroll
+    for (int u = 0; u < XB; ++u) {
+      const int q2 = lane + 64 * u;
+      const int tl2 = q2 / V;
+      poff[u] = tl2 * a.out_fs * V + (q2 - tl2 * V);
+    }
+    EpiPtrs ep;
+    ep.out = a.out; ep.add1 = a.add1; ep.mask1 = nullptr; ep.add2 = nullptr; ep.mask2 = nullptr; ep.stats = nullptr;
+    ep.accumulate = 0; ep.relu = a.relu;
+    const long Pfull = (long)a.T_full * V;
+    const long rows0 = (long)n * a.M * Pfull + ((long)t0 * a.out_fs + a.out_fo) * V;
+    epilogue_rows<BM, NW, XB>(ep, otile, TP, smem + a.off_bias, red, a.M, m0, rows0, Pfull, nvalid, poff,
+                              (long)n * a.ntiles + tile);
+  } else if (EPI == 0) {
     // ---- store (+bias, +accumulate, +masked addends) and per-channel (sum, sumsq) partials ----
     float* red = smem;   // aliases Aw: [WN][2][BM]
     const long Pfull = (long)a.T_full * V;
@@ -459,6 +525,7 @@ struct Geometry {
   int tt, ntiles, FW, WLP, ttv, nchunks, nmb;
   size_t smem_bytes, pack_floats;
   int off_bx, off_bg, off_adj;
+  int off_bias, off_gate;            // EPI == 2
 };
 
 // host-side tile geometry shared by the launcher and the workspace queries
@@ -486,13 +553,22 @@ Geometry make_geometry(int V, int T_out, int src_stride, int M, int Kinner, int 
   const int adjsz = AGG ? 3 * VP * 32 : 0;
   size_t main_f = (size_t)g.off_adj + adjsz;
   size_t epi_f = (EPI == 0) ? (size_t)WN * 2 * BM : (size_t)2 * BM * g.ttv + (size_t)NW * V * V;
+  if (EPI == 2) epi_f = (size_t)BM * (WN * TN * 32 + 1) + (size_t)NW * 64 * 2;   // epilogue.h: tile + scratch
   g.smem_bytes = 4 * (main_f > epi_f ? main_f : epi_f);
+  g.off_bias = g.off_gate = 0;
+  if (EPI == 2) {                     // bias row and gate image (gate.h) behind everything the epilogue overwrites
+    g.off_bias = (int)((g.smem_bytes / 4 + 3) & ~(size_t)3);
+    g.off_gate = g.off_bias + BM;
+    g.smem_bytes = 4 * ((size_t)g.off_gate + gate_lds_floats(g.FW, g.nchunks * CK));
+  }
   g.pack_floats = (size_t)g.nmb * g.nchunks * aw;
   return g;
 }
 
 struct Problem {          // what differs between the entry points
   ConvGemmArgs a;
+  GateArgs gate;          // EPI == 2: see InferGemmArgs
+  int gated, relu;
   const float* w;
   long sa_m, sa_i, sa_c;
   int tap_mul, tap_add, tap_flip_from;
@@ -504,13 +580,18 @@ struct Problem {          // what differs between the entry points
 template <int TAPS, int AGG, int WM, int WN, int TM, int TN, int CK, int WB, int EPI>
 int launch_cfg(Problem& p, hipStream_t stream) {
   constexpr int BM = WM * TM * 32, NSUB = AGG ? 3 : 1;
-  ConvGemmArgs a = p.a;
+  typename GemmArgsOf<EPI>::type a;
+  static_cast<ConvGemmArgs&>(a) = p.a;
   const Geometry g = make_geometry<TAPS, AGG, WM, WN, TM, TN, CK, EPI>(a.V, a.T_out, a.src_stride, a.M, a.Kinner, p.tt_cap);
   if (g.smem_bytes > 160 * 1024) return AGCN_ERR_UNSUPPORTED;
   if (g.FW * a.V > WB * 64) return AGCN_ERR_UNSUPPORTED;
   if (g.pack_floats * 4 > p.ws_bytes) return AGCN_ERR_WORKSPACE;
   a.tt = g.tt; a.ntiles = g.ntiles; a.FW = g.FW; a.WLP = g.WLP; a.nchunks = g.nchunks; a.nmb = g.nmb;
   a.off_bx = g.off_bx; a.off_bg = g.off_bg; a.off_adj = g.off_adj;
+  if constexpr (EPI == 2) {
+    a.gate = p.gate; a.gated = p.gated; a.relu = p.relu;
+    a.off_bias = g.off_bias; a.off_gate = g.off_gate;
+  }
   a.wp = (const float*)p.ws;
   if (g.nchunks > 0) {
     PackArgs pk;
@@ -525,7 +606,10 @@ int launch_cfg(Problem& p, hipStream_t stream) {
   static unsigned char lds_ok[AGCN_MAX_DEVICES] = {};   // per (kernel instantiation, device): the attribute is per device
   if (int e = agcn_allow_big_lds_rt(reinterpret_cast<const void*>(kern), lds_ok)) return e;
   dim3 grid((unsigned)(a.N * g.ntiles * g.nmb));
-  AGCN_NOTE_KERNEL("conv_gemm_kernel<%d, %d, %d, %d, %d, %d, %d, %d, %d>", TAPS, AGG, WM, WN, TM, TN, CK, WB, EPI);
+  if (EPI == 2 && p.gated)
+    AGCN_NOTE_KERNEL("conv_gemm_kernel<%d, %d, %d, %d, %d, %d, %d, %d, %d> [gates on load]", TAPS, AGG, WM, WN, TM, TN, CK, WB, EPI);
+  else
+    AGCN_NOTE_KERNEL("conv_gemm_kernel<%d, %d, %d, %d, %d, %d, %d, %d, %d>", TAPS, AGG, WM, WN, TM, TN, CK, WB, EPI);
   hipLaunchKernelGGL(kern, grid, dim3(WM * WN * 64), g.smem_bytes, stream, a);
   return agcn_check_launch();
 }
@@ -591,6 +675,29 @@ int tconv_f32_dispatch(int taps, Problem& p, hipStream_t s) {
     case 7: return tconv_f32_launch<7>(p, s);
     case 8: return tconv_f32_launch<8>(p, s);
     case 9: return tconv_f32_launch<9>(p, s);
+    default: return AGCN_ERR_UNSUPPORTED;
+  }
+}
+
+// folded inference on the exact-f32 kernel: 64-row blocks (the epilogue tile of epilogue.h is 64 x 257 floats of LDS)
+template <int TAPS>
+int tconv_f32_infer_launch(Problem& p, hipStream_t s) {
+  constexpr int CK = TAPS == 1 ? CK1 : CK9;
+  p.tt_cap = tconv_f32_tt(p.a.V, p.a.T_out, TAPS, p.a.src_stride);
+  return launch_cfg<TAPS, 0, 1, 4, 2, 2, CK, WBT, 2>(p, s);
+}
+
+int tconv_f32_infer_dispatch(int taps, Problem& p, hipStream_t s) {
+  switch (taps) {
+    case 1: return tconv_f32_infer_launch<1>(p, s);
+    case 2: return tconv_f32_infer_launch<2>(p, s);
+    case 3: return tconv_f32_infer_launch<3>(p, s);
+    case 4: return tconv_f32_infer_launch<4>(p, s);
+    case 5: return tconv_f32_infer_launch<5>(p, s);
+    case 6: return tconv_f32_infer_launch<6>(p, s);
+    case 7: return tconv_f32_infer_launch<7>(p, s);
+    case 8: return tconv_f32_infer_launch<8>(p, s);
+    case 9: return tconv_f32_infer_launch<9>(p, s);
     default: return AGCN_ERR_UNSUPPORTED;
   }
 }
@@ -994,6 +1101,41 @@ int agcn_tconv_fwd(const float* x, const float* w, const float* bias, float* y, 
   p.w = w; p.sa_m = (long)Cin * taps; p.sa_i = 0; p.sa_c = taps; p.tap_flip_from = -1;
   p.ws = workspace; p.ws_bytes = workspace_bytes;
   return tconv_f32_dispatch(taps, p, s);
+}
+
+// BN-folded inference form (eval mode; reference aagcn.py:264-271 gates, :194-201 TCNUnit, :316-321 unit tail):
+//   y = act( bias + tconv(x * gate ; w, stride, pad) [+ res] ),   gate[n,c,t,v] = a_s[n,v] * a_t[n,t] * a_c[n,c]
+// The caller has folded the BatchNorm into w and bias.  a_s (N,V), a_t (N,T), a_c (N,Cin): each optional, null = ones;
+// they multiply x where its tile is staged for the matrix cores (gate.h), so the gated tensor is never stored.  res
+// (N, Cout, T_out, V) or null; x_absmax: optional device scalar max |x| (of the UNGATED x) for the f16x3 range scale.
+// Same domain and workspace as agcn_tconv_fwd.  9 taps / pad 4 / stride 1-2 and stride-1 3/5/7 taps run on the
+// split-bf16 / f16x3 kernels, everything else (and AGCN_GEMM=f32) on the exact-f32 kernel; one epilogue (epilogue.h).
+int agcn_tconv_infer(const float* x, const float* w, const float* bias, const float* a_s, const float* a_t,
+                     const float* a_c, const float* res, int relu, float* y, void* workspace, size_t workspace_bytes,
+                     int N, int Cin, int Cout, int T, int V, int taps, int stride, int pad, const float* x_absmax,
+                     void* stream) {
+  if (!x || !w || !y || !workspace || N <= 0 || Cin <= 0 || Cout <= 0 || T <= 0 || V <= 0 || V > 32)
+    return AGCN_ERR_ARG;
+  if (int rc = tconv_domain(T, taps, stride, pad)) return rc;
+  if (workspace_bytes < agcn_tconv_workspace(Cin, Cout, T, V, taps, stride, pad)) return AGCN_ERR_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  GateArgs gate = {a_s, a_t, a_c};
+  if (agcn_gemm_precision() != 0 && agcn_bf16_tconv_infer_supported(taps, stride, pad)) {
+    const int rc = agcn_bf16_tconv_infer(x, w, bias, y, workspace, workspace_bytes, N, Cin, Cout, T, V, taps, stride, pad,
+                                         agcn_gemm_precision(), s, res, relu, x_absmax, &gate);
+    // (a window too long for their LDS is refused before anything is launched there: the exact kernel below)
+    if (rc != AGCN_ERR_UNSUPPORTED) return rc;
+  }
+  Problem p = {};
+  ConvGemmArgs& a = p.a;
+  a.in = x; a.bias = bias; a.out = y; a.add1 = res;
+  p.gate = gate; p.gated = (a_s || a_t || a_c) ? 1 : 0; p.relu = relu;
+  a.N = N; a.M = Cout; a.Kinner = Cin; a.in_rows = Cin; a.V = V;
+  a.T_src = T; a.T_out = tconv_out_frames(T, taps, stride, pad); a.T_full = a.T_out;
+  a.src_stride = stride; a.f_off = -pad; a.out_fs = 1; a.out_fo = 0;
+  p.w = w; p.sa_m = (long)Cin * taps; p.sa_i = 0; p.sa_c = taps; p.tap_flip_from = -1;
+  p.ws = workspace; p.ws_bytes = workspace_bytes;
+  return tconv_f32_infer_dispatch(taps, p, s);
 }
 
 // dx[n][c][t,v] (+)= sum_{o,k: (t + pad - k) = stride*tau} w[o][c][k] dy[n][o][tau, v]  (+ masked addends); frames no

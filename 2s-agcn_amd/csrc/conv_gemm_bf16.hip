@@ -13,6 +13,7 @@
 // fragment (8 consecutive k for one row/column) is one conflict-free ds_read_b128, and a temporal tap is a row offset.
 #include "agcn_common.h"
 #include "epilogue.h"
+#include "gate.h"
 #include "split_f16.h"
 
 namespace {
@@ -48,6 +49,15 @@ struct BfArgs {
   int relu;                    // epilogue: out = max(., 0) (BN-folded inference)
   const float* in_absmax;      // f16x3: max |in| (device scalar written by absmax_kernel): range scaling of the activations
 };
+
+// GATE kernels (agcn_tconv_infer) only -- an argument type of their own, so that every other instantiation keeps the
+// argument block it was tuned with: attention factors applied to `in` while it is staged, and where they live in LDS
+struct GateBfArgs : BfArgs {
+  GateArgs gate;
+  int off_gate;                // byte offset of the gate vectors' LDS image (gate.h)
+};
+template <bool GATE> struct BfArgsOf { typedef BfArgs type; };
+template <> struct BfArgsOf<true> { typedef GateBfArgs type; };
 
 struct BfPackArgs {
   const float* w;
@@ -115,8 +125,9 @@ __global__ void __launch_bounds__(256) pack_weights_bf16_kernel(const BfPackArgs
 // NPL = 3: bf16x6 (fp32-equivalent) ; NPL = 2: bf16x3.  WQ = 64-row blocks per staging quarter (2: windows <= 512 rows)
 // TN = 32-position tiles per wave (2: 64-row blocks cover 512 positions, so every weight fragment feeds two MFMAs and
 // the 8-frame halo of the window is amortised over 20 frames instead of 10)
-template <int TAPS, int NPL, int WQ, int TM, int TN = 1, bool F16 = false>
-__global__ void __launch_bounds__(NT, (TAPS == 1 && TM == 2 && TN == 1) ? 4 : 2) conv_gemm_bf16_kernel(const BfArgs a) {
+// GATE: the window is multiplied by the attention factors of gate.h between the global load and the plane split
+template <int TAPS, int NPL, int WQ, int TM, int TN = 1, bool F16 = false, bool GATE = false>
+__global__ void __launch_bounds__(NT, (TAPS == 1 && TM == 2 && TN == 1) ? 4 : 2) conv_gemm_bf16_kernel(const typename BfArgsOf<GATE>::type a) {
   constexpr int BM = TM * 32;
   constexpr int A_PLANE = TAPS * 2 * BM * 16;          // bytes per plane of the A image
   constexpr int A4 = NPL * A_PLANE / 16;               // 16-byte units of the A image that are used
@@ -168,6 +179,31 @@ __global__ void __launch_bounds__(NT, (TAPS == 1 && TM == 2 && TN == 1) ? 4 : 2)
   const int qlen = (WL + 3) >> 2;          // rows per quarter
   u32x4 ra[EA];
   float rb[WQ][8];
+  // GATE: a lane stages the same window rows in every K chunk, so their (joint, frame) factor is taken once
+  const int KP = a.nchunks * CK;
+  const float* gl = nullptr;
+  float gpos[WQ];
+  if constexpr (GATE) {
+    gl = reinterpret_cast<const float*>(smem + a.off_gate);
+    gate_stage<NT>(reinterpret_cast<float*>(smem + a.off_gate), a.gate, n, V, a.T_src, a.Kinner, f0, a.FW, KP);
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < WQ; ++u) {
+      const int rr = lane + 64 * u;
+      gpos[u] = rr < qlen ? gate_pos(gl, KP, wq * qlen + rr, V, WL) : 0.f;
+    }
+    if constexpr (F16) {
+      // Range scale of the GATED operand without a pass over it: max |in| (of the ungated tensor) times the maxima of
+      // this sample's channel and joint factors and of the window's frame factors.  It is an upper bound of the true
+      // maximum, loose by at most the spread of the factors (AAGCN's 1 + sigmoid lie in (1, 2): < 2^3), and a loose
+      // bound only raises the fp16 subnormal floor by as many bits: from 2^-40 to 2^-37 of the bound, still far
+      // below fp32's own 2^-24.  The scale is per workgroup; it is undone on this workgroup's accumulators.
+      if (a.in_absmax) {
+        f16_range_scale_of<14>(*a.in_absmax * gate_bound(gl, KP, a.FW, lane), rs_s, rs_inv);
+        rs_inv *= F16_W_INV;
+      }
+    }
+  }
   const u32x4* wp4 = reinterpret_cast<const u32x4*>(a.wp) + (long)mbk * a.nchunks * (3 * A_PLANE / 16);
 
   auto issue_loads = [&](int ch) __attribute__((always_inline)) {
@@ -202,8 +238,12 @@ __global__ void __launch_bounds__(NT, (TAPS == 1 && TM == 2 && TN == 1) ? 4 : 2)
       u32x4 ph, pm, pl;
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        const float x0 = (okp && (kc0 + 2 * c) < a.Kinner) ? rb[u][2 * c] : 0.f;
-        const float x1 = (okp && (kc0 + 2 * c + 1) < a.Kinner) ? rb[u][2 * c + 1] : 0.f;
+        float x0 = (okp && (kc0 + 2 * c) < a.Kinner) ? rb[u][2 * c] : 0.f;
+        float x1 = (okp && (kc0 + 2 * c + 1) < a.Kinner) ? rb[u][2 * c + 1] : 0.f;
+        if constexpr (GATE) {                // (the channel factors are wave-uniform LDS reads)
+          x0 = x0 * gpos[u] * gl[kc0 + 2 * c];
+          x1 = x1 * gpos[u] * gl[kc0 + 2 * c + 1];
+        }
         unsigned a0, a1, a2 = 0;
         if constexpr (F16) split_pair_f16(x0 * rs_s, x1 * rs_s, a0, a1);
         else split_pair(x0, x1, a0, a1, a2);
@@ -325,8 +365,8 @@ __global__ void __launch_bounds__(NT, (TAPS == 1 && TM == 2 && TN == 1) ? 4 : 2)
 // Only the producers have vector-memory operations in flight, so the consumers' LDS reads never wait on a vmcnt.
 // One barrier per step.  The ring slot of step g is (g mod R).
 // F16: the planes are fp16 pieces (NPL = 2, three products): forward convolution only
-template <int TAPS, int NPL, int R, int NWP = 4, bool F16 = false>
-__global__ void __launch_bounds__((8 + NWP) * 64, 3) conv_pc_kernel(const BfArgs a) {
+template <int TAPS, int NPL, int R, int NWP = 4, bool F16 = false, bool GATE = false>
+__global__ void __launch_bounds__((8 + NWP) * 64, 3) conv_pc_kernel(const typename BfArgsOf<GATE>::type a) {
   constexpr int TM = 4, BM = 128, NWC = 8, NTALL = (NWC + NWP) * 64, NTP = NWP * 64;
   constexpr int SLOT = NPL * 2 * BM * 16;               // bytes of one step's weight image [plane][h][m][8]
   constexpr int PIECES = SLOT / 1024;                   // 1 KB LDS-DMA pieces per slot
@@ -358,6 +398,19 @@ __global__ void __launch_bounds__((8 + NWP) * 64, 3) conv_pc_kernel(const BfArgs
 
   float* bias_s = reinterpret_cast<float*>(smem + a.off_bias);
   for (int e = threadIdx.x; e < BM; e += NTALL) bias_s[e] = (a.bias && m0 + e < a.M) ? a.bias[m0 + e] : 0.f;
+  const int KP = nchunks * CK;
+  const float* gl = nullptr;
+  if constexpr (GATE) {                                  // before the roles part: the gate vectors (gate.h)
+    gl = reinterpret_cast<const float*>(smem + a.off_gate);
+    gate_stage<NTALL>(reinterpret_cast<float*>(smem + a.off_gate), a.gate, n, V, a.T_src, a.Kinner, t0 + a.f_off, a.FW, KP);
+    __syncthreads();
+    if constexpr (F16) {                                 // range scale of the gated operand: see conv_gemm_bf16_kernel
+      if (a.in_absmax) {
+        f16_range_scale_of<14>(*a.in_absmax * gate_bound(gl, KP, a.FW, lane), rs_s, rs_inv);
+        rs_inv *= F16_W_INV;
+      }
+    }
+  }
 
   auto step_barrier = [&]() __attribute__((always_inline)) {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -409,21 +462,44 @@ __global__ void __launch_bounds__((8 + NWP) * 64, 3) conv_pc_kernel(const BfArgs
         }
       }
     };
-    auto commit_B = [&](unsigned char* Bb) __attribute__((always_inline)) {
+    // GATE: a task's four window rows are the same in every chunk: their (joint, frame) factors are taken once
+    float gpos[TK][4];
+    if constexpr (GATE) {
+#pragma unroll
+      for (int k = 0; k < TK; ++k) {
+        int task = ptid + k * NTP;
+        if (task >= ntask) task = ntask - 1;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) gpos[k][e] = (k * NTP < ntask) ? gate_pos(gl, KP, (task >> 1) * 4 + e, V, WL) : 0.f;
+      }
+    }
+    auto commit_B = [&](unsigned char* Bb, int ch) __attribute__((always_inline)) {
 #pragma unroll
       for (int k = 0; k < TK; ++k) {
         if (k * NTP >= ntask) continue;
         int task = ptid + k * NTP;
         if (task >= ntask) task = ntask - 1;
         const int hb = task & 1, r0 = (task >> 1) * 4;
+        float gch[8];
+        if constexpr (GATE) {
+          const f32x4 g0v = *reinterpret_cast<const f32x4*>(gl + ch * CK + hb * 8);
+          const f32x4 g1v = *reinterpret_cast<const f32x4*>(gl + ch * CK + hb * 8 + 4);
+#pragma unroll
+          for (int c = 0; c < 4; ++c) { gch[c] = g0v[c]; gch[4 + c] = g1v[c]; }
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           u32x4 ph, pm, pl;
 #pragma unroll
           for (int c = 0; c < 4; ++c) {
             unsigned q0, q1, q2 = 0;
-            if constexpr (F16) split_pair_f16(rb[k][2 * c][e] * rs_s, rb[k][2 * c + 1][e] * rs_s, q0, q1);
-            else split_pair(rb[k][2 * c][e], rb[k][2 * c + 1][e], q0, q1, q2);
+            float x0 = rb[k][2 * c][e], x1 = rb[k][2 * c + 1][e];
+            if constexpr (GATE) {
+              x0 = x0 * gpos[k][e] * gch[2 * c];
+              x1 = x1 * gpos[k][e] * gch[2 * c + 1];
+            }
+            if constexpr (F16) split_pair_f16(x0 * rs_s, x1 * rs_s, q0, q1);
+            else split_pair(x0, x1, q0, q1, q2);
             ph[c] = q0; pm[c] = q1; pl[c] = q2;
           }
           const int r = r0 + e;
@@ -440,7 +516,7 @@ __global__ void __launch_bounds__((8 + NWP) * 64, 3) conv_pc_kernel(const BfArgs
     for (int g = 0; g < R - 1; ++g)
       if (g < G) dma_slot(g);
     issue_B(0);
-    commit_B(Bbase);
+    commit_B(Bbase, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     step_barrier();
     int g = 0;
@@ -452,9 +528,9 @@ __global__ void __launch_bounds__((8 + NWP) * 64, 3) conv_pc_kernel(const BfArgs
         if (TAPS >= 3) {
           if (tap == 0 && ch + 1 < nchunks && !(a.dbg & 4)) issue_B(ch + 1);
           if (tap == (TAPS >= 6 ? TAPS - 3 : TAPS - 2) && ch + 1 < nchunks && !(a.dbg & 4))
-            commit_B(Bbase + ((ch + 1) & 1) * B_BYTES);  // loads had TAPS-3 steps to land; readers start at tap TAPS-1
+            commit_B(Bbase + ((ch + 1) & 1) * B_BYTES, ch + 1);  // loads had TAPS-3 steps to land; readers start at tap TAPS-1
         } else {
-          if (tap == 0 && ch + 1 < nchunks) { issue_B(ch + 1); commit_B(Bbase + ((ch + 1) & 1) * B_BYTES); }
+          if (tap == 0 && ch + 1 < nchunks) { issue_B(ch + 1); commit_B(Bbase + ((ch + 1) & 1) * B_BYTES, ch + 1); }
         }
         // the slot of step g+2 is read from the next barrier on: at most the R-3 NEWER slots may still be in flight.
         // (vector-memory operations complete in order, so "at most PPW*(R-3) outstanding" implies slot g+2 has landed
@@ -619,6 +695,7 @@ BfGeom bf_geometry(int V, int T_out, int src_stride, int M, int Kinner) {
 
 struct BfProblem {
   BfArgs a;
+  GateArgs gate;               // GATE launches: see GateBfArgs
   int fwd_f16;                 // use the f16x3 arithmetic (a.in_absmax holds the streamed operand's max)
   const float* w;
   long sa_m, sa_c;
@@ -628,11 +705,20 @@ struct BfProblem {
   int stats_tiles;             // > 0: tiles per sample the caller sized the stats partials for (agcn_tconv_stats_tiles)
 };
 
-template <int TAPS, int NPL, int WQ, int TM, int TN = 1, bool F16 = false>
+// bytes of the gate vectors' LDS image behind the bias row (gate.h)
+inline size_t gate_bytes(const BfGeom& g) { return 4 * (size_t)gate_lds_floats(g.FW, g.nchunks * CK); }
+
+template <int TAPS, int NPL, int WQ, int TM, int TN = 1, bool F16 = false, bool GATE = false>
 int launch_bf(BfProblem& p, hipStream_t stream) {
   constexpr int BM = TM * 32;
-  BfArgs a = p.a;
-  const BfGeom g = bf_geometry<TAPS, BM, TN>(a.V, a.T_out, a.src_stride, a.M, a.Kinner);
+  typename BfArgsOf<GATE>::type a;
+  static_cast<BfArgs&>(a) = p.a;
+  BfGeom g = bf_geometry<TAPS, BM, TN>(a.V, a.T_out, a.src_stride, a.M, a.Kinner);
+  if constexpr (GATE) {
+    a.gate = p.gate;
+    a.off_gate = (int)g.smem_bytes;
+    g.smem_bytes += gate_bytes(g);
+  }
   if (g.smem_bytes > 160 * 1024) return AGCN_ERR_UNSUPPORTED;
   if ((g.FW * a.V + 3) / 4 > WQ * 64) return AGCN_ERR_UNSUPPORTED;
   if (g.pack_bytes > p.ws_bytes) return AGCN_ERR_WORKSPACE;
@@ -651,10 +737,11 @@ int launch_bf(BfProblem& p, hipStream_t stream) {
     int rc = agcn_check_launch();
     if (rc) return rc;
   }
-  auto kern = conv_gemm_bf16_kernel<TAPS, NPL, WQ, TM, TN, F16>;
+  auto kern = conv_gemm_bf16_kernel<TAPS, NPL, WQ, TM, TN, F16, GATE>;
   static unsigned char lds_ok[AGCN_MAX_DEVICES] = {};   // per (kernel instantiation, device): the attribute is per device
   if (int e = agcn_allow_big_lds_rt(reinterpret_cast<const void*>(kern), lds_ok)) return e;
-  AGCN_NOTE_KERNEL("conv_gemm_bf16_kernel<%d, %d, %d, %d, %d, %s>", TAPS, NPL, WQ, TM, TN, F16 ? "true" : "false");
+  if (GATE) AGCN_NOTE_KERNEL("conv_gemm_bf16_kernel<%d, %d, %d, %d, %d, %s, true> [gates on load]", TAPS, NPL, WQ, TM, TN, F16 ? "true" : "false");
+  else AGCN_NOTE_KERNEL("conv_gemm_bf16_kernel<%d, %d, %d, %d, %d, %s>", TAPS, NPL, WQ, TM, TN, F16 ? "true" : "false");
   hipLaunchKernelGGL(kern, dim3((unsigned)(a.N * g.ntiles * g.nmb)), dim3(NT), g.smem_bytes, stream, a);
   return agcn_check_launch();
 }
@@ -693,11 +780,17 @@ static inline bool conv_pc_enabled() {
   return v == 1;
 }
 
-template <int TAPS, int NPL, int R = 5, int NWP = 4, bool F16 = false>
+template <int TAPS, int NPL, int R = 5, int NWP = 4, bool F16 = false, bool GATE = false>
 int launch_pc(BfProblem& p, hipStream_t stream) {
   constexpr int BM = 128;
-  BfArgs a = p.a;
-  const BfGeom g = bf_geometry_pc<TAPS, NPL, R>(a.V, a.T_out, a.M, a.Kinner);
+  typename BfArgsOf<GATE>::type a;
+  static_cast<BfArgs&>(a) = p.a;
+  BfGeom g = bf_geometry_pc<TAPS, NPL, R>(a.V, a.T_out, a.M, a.Kinner);
+  if constexpr (GATE) {
+    a.gate = p.gate;
+    a.off_gate = (int)g.smem_bytes;
+    g.smem_bytes += gate_bytes(g);
+  }
   if (g.smem_bytes > 160 * 1024) return AGCN_ERR_UNSUPPORTED;
   if (g.pack_bytes > p.ws_bytes) return AGCN_ERR_WORKSPACE;
   if (a.stats && p.stats_tiles > 0 && g.ntiles != p.stats_tiles) return AGCN_ERR_ARG;   // (never write past the partials)
@@ -711,57 +804,58 @@ int launch_pc(BfProblem& p, hipStream_t stream) {
   hipLaunchKernelGGL((pack_weights_slots_kernel<TAPS, BM, NPL, F16>), dim3(g.nmb * g.nchunks * TAPS), dim3(256), 0, stream, pk);
   int rc = agcn_check_launch();
   if (rc) return rc;
-  auto kern = conv_pc_kernel<TAPS, NPL, R, NWP, F16>;
+  auto kern = conv_pc_kernel<TAPS, NPL, R, NWP, F16, GATE>;
   static unsigned char lds_ok[AGCN_MAX_DEVICES] = {};
   if (int e = agcn_allow_big_lds_rt(reinterpret_cast<const void*>(kern), lds_ok)) return e;
   static const int dbg = getenv("AGCN_CB_DBG") ? atoi(getenv("AGCN_CB_DBG")) : 0;
   a.dbg = dbg;
-  AGCN_NOTE_KERNEL("conv_pc_kernel<%d, %d, %d, %d, %s>", TAPS, NPL, R, NWP, F16 ? "true" : "false");   // (as rocprofv3 prints it)
+  if (GATE) AGCN_NOTE_KERNEL("conv_pc_kernel<%d, %d, %d, %d, %s, true> [gates on load]", TAPS, NPL, R, NWP, F16 ? "true" : "false");
+  else AGCN_NOTE_KERNEL("conv_pc_kernel<%d, %d, %d, %d, %s>", TAPS, NPL, R, NWP, F16 ? "true" : "false");   // (as rocprofv3 prints it)
   hipLaunchKernelGGL(kern, dim3((unsigned)(a.N * g.ntiles * g.nmb)), dim3((8 + NWP) * 64), g.smem_bytes, stream, a);
   return agcn_check_launch();
 }
 
 template <int TAPS>
-bool pc_applies(const BfProblem& p, int npl) {
+bool pc_applies(const BfProblem& p, int npl, bool gate = false) {
   if (!conv_pc_enabled() || TAPS < 3 || npl != 3) return false;
   if (p.a.M % 128 != 0 || p.a.Kinner % CK != 0 || p.a.src_stride != 1 || p.a.V > 32) return false;
   const BfGeom g = bf_geometry_pc<TAPS, 3, 5>(p.a.V, p.a.T_out, p.a.M, p.a.Kinner);
-  return g.smem_bytes <= 160 * 1024 && g.FW * p.a.V <= 512;
+  return g.smem_bytes + (gate ? gate_bytes(g) : 0) <= 160 * 1024 && g.FW * p.a.V <= 512;
 }
 
 // 128-row blocks (4 m-tiles per wave) when M allows it: the staged+split window is reused by twice the MFMAs
-template <int TAPS, int WQ>
+template <int TAPS, int WQ, bool GATE = false>
 int launch_npl(BfProblem& p, int npl, hipStream_t s) {
-  const bool fits128 = bf_geometry<TAPS, 128>(p.a.V, p.a.T_out, p.a.src_stride, p.a.M, p.a.Kinner).smem_bytes <=
-                       160 * 1024;
+  const BfGeom g128 = bf_geometry<TAPS, 128>(p.a.V, p.a.T_out, p.a.src_stride, p.a.M, p.a.Kinner);
+  const bool fits128 = g128.smem_bytes + (GATE ? gate_bytes(g128) : 0) <= 160 * 1024;
   if constexpr (TAPS >= 3) {
-    if (pc_applies<TAPS>(p, npl)) {
+    if (pc_applies<TAPS>(p, npl, GATE)) {
       static const int nwp2 = getenv("AGCN_CONV_NWP2") ? atoi(getenv("AGCN_CONV_NWP2")) : 0;
-      if (nwp2) return launch_pc<TAPS, 3, 5, 2>(p, s);
-      if (p.fwd_f16) return launch_pc<TAPS, 2, 5, 4, true>(p, s);
-      return launch_pc<TAPS, 3>(p, s);
+      if (nwp2 && !GATE) return launch_pc<TAPS, 3, 5, 2>(p, s);
+      if (p.fwd_f16) return launch_pc<TAPS, 2, 5, 4, true, GATE>(p, s);
+      return launch_pc<TAPS, 3, 5, 4, false, GATE>(p, s);
     }
   }
   if constexpr (TAPS >= 3) {
     if (p.fwd_f16) {      // f16x3 (three fp16 products), same tiles
-      if (p.a.M % 128 == 0 && fits128) return launch_bf<TAPS, 2, WQ, 4, 1, true>(p, s);
+      if (p.a.M % 128 == 0 && fits128) return launch_bf<TAPS, 2, WQ, 4, 1, true, GATE>(p, s);
       if (agcn_bf16_conv_wide(TAPS, p.a.M)) {
-        const int rc = launch_bf<TAPS, 2, 3, 2, 2, true>(p, s);
+        const int rc = launch_bf<TAPS, 2, 3, 2, 2, true, GATE>(p, s);
         if (rc != AGCN_ERR_UNSUPPORTED) return rc;
       }
-      return launch_bf<TAPS, 2, WQ, 2, 1, true>(p, s);
+      return launch_bf<TAPS, 2, WQ, 2, 1, true, GATE>(p, s);
     }
   }
   if (p.a.M % 128 == 0 && fits128) {
-    if (npl == 1) return launch_bf<TAPS, 1, WQ, 4>(p, s);
-    return npl == 2 ? launch_bf<TAPS, 2, WQ, 4>(p, s) : launch_bf<TAPS, 3, WQ, 4>(p, s);
+    if (npl == 1) return launch_bf<TAPS, 1, WQ, 4, 1, false, GATE>(p, s);
+    return npl == 2 ? launch_bf<TAPS, 2, WQ, 4, 1, false, GATE>(p, s) : launch_bf<TAPS, 3, WQ, 4, 1, false, GATE>(p, s);
   }
   if (agcn_bf16_conv_wide(TAPS, p.a.M) && (npl == 3 || npl == 1)) {   // (a window too long for the wide tile: narrow one)
-    const int rc = npl == 3 ? launch_bf<TAPS, 3, 3, 2, 2>(p, s) : launch_bf<TAPS, 1, 3, 2, 2>(p, s);
+    const int rc = npl == 3 ? launch_bf<TAPS, 3, 3, 2, 2, false, GATE>(p, s) : launch_bf<TAPS, 1, 3, 2, 2, false, GATE>(p, s);
     if (rc != AGCN_ERR_UNSUPPORTED) return rc;
   }
-  if (npl == 1) return launch_bf<TAPS, 1, WQ, 2>(p, s);
-  return npl == 2 ? launch_bf<TAPS, 2, WQ, 2>(p, s) : launch_bf<TAPS, 3, WQ, 2>(p, s);
+  if (npl == 1) return launch_bf<TAPS, 1, WQ, 2, 1, false, GATE>(p, s);
+  return npl == 2 ? launch_bf<TAPS, 2, WQ, 2, 1, false, GATE>(p, s) : launch_bf<TAPS, 3, WQ, 2, 1, false, GATE>(p, s);
 }
 
 }  // namespace
@@ -811,13 +905,14 @@ int bf16_fwd_f16x3(int npl) {   // AGCN_CONV_F16X3=0 keeps the temporal convolut
 }
 
 // y = bias + conv_TAPS(x; stride, pad) [+ add] (reference agcn.py:40-41,49; aagcn.py:194-201)
-template <int TAPS, int WQ>
+template <int TAPS, int WQ, bool GATE = false>
 int bf16_tconv_fwd(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* ws,
                    size_t ws_bytes, int N, int Cin, int Cout, int T, int V, int stride, int pad, int npl, hipStream_t s,
-                   const float* add, int relu, const float* x_absmax) {
+                   const float* add, int relu, const float* x_absmax, const GateArgs* gate = nullptr) {
   BfProblem p = {};
   BfArgs& a = p.a;
   a.in = x; a.bias = bias; a.out = y; a.stats = stats_part; a.add1 = add; a.relu = relu;
+  if (GATE) p.gate = *gate;
   p.fwd_f16 = bf16_fwd_f16x3(npl);
   p.ws = ws; p.ws_bytes = ws_bytes;
   if (p.fwd_f16)
@@ -830,7 +925,7 @@ int bf16_tconv_fwd(const float* x, const float* w, const float* bias, float* y, 
     const int tt = agcn_bf16_tconv_tile_frames(TAPS, Cout, V, a.T_out, npl);
     p.stats_tiles = (a.T_out + tt - 1) / tt;
   }
-  return launch_npl<TAPS, WQ>(p, npl, s);
+  return launch_npl<TAPS, WQ, GATE>(p, npl, s);
 }
 
 // stride-1 backward-data: dx[t] = sum_j W[TAPS-1-j] dy[t + j - (TAPS-1-pad)]   (+ masked addends)
@@ -926,6 +1021,50 @@ int agcn_bf16_tconv_bwd_data(const float* dy, const float* w, float* dx, int acc
                                              T, V, pad, npl, s, dy_absmax);
     default: return AGCN_ERR_UNSUPPORTED;
   }
+}
+
+// BN-folded inference form of the same forward kernels (agcn_tconv_infer): y = act(bias + conv(x * gate) [+ add]) for
+// the shapes they are tuned for -- 9 taps with padding 4 at stride 1 or 2, and stride-1 3/5/7 taps with any padding.
+// gate null (or all three factors null): the ungated kernels (the very instantiations agcn_conv9_infer launches).
+template <int TAPS, int WQ>
+static int bf16_tconv_infer_t(const float* x, const float* w, const float* bias, float* y, void* ws, size_t ws_bytes, int N,
+                              int Cin, int Cout, int T, int V, int stride, int pad, int npl, hipStream_t s,
+                              const float* add, int relu, const float* x_absmax, const GateArgs* gate) {
+  // the narrowest tile these kernels fall back to must hold the window (launch_bf's own checks): decided here, before
+  // the f16x3 maximum is taken, so that a shape handed on to the exact kernel has launched nothing
+  const bool gated = gate && (gate->gs || gate->gt || gate->gc);
+  {
+    const int To = (T + 2 * pad - TAPS) / stride + 1;
+    const BfGeom g = bf_geometry<TAPS, 64>(V, To, stride, Cout, Cin);
+    if (g.smem_bytes + (gated ? gate_bytes(g) : 0) > 160 * 1024 || (g.FW * V + 3) / 4 > WQ * 64) return AGCN_ERR_UNSUPPORTED;
+  }
+  if (gated)
+    return bf16_tconv_fwd<TAPS, WQ, true>(x, w, bias, y, nullptr, ws, ws_bytes, N, Cin, Cout, T, V, stride, pad, npl, s, add,
+                                          relu, x_absmax, gate);
+  return bf16_tconv_fwd<TAPS, WQ>(x, w, bias, y, nullptr, ws, ws_bytes, N, Cin, Cout, T, V, stride, pad, npl, s, add, relu,
+                                  x_absmax);
+}
+
+bool agcn_bf16_tconv_infer_supported(int taps, int stride, int pad) {
+  if (taps == 9) return pad == 4 && (stride == 1 || stride == 2);
+  return agcn_bf16_tconv_supported(taps, stride);
+}
+
+int agcn_bf16_tconv_infer(const float* x, const float* w, const float* bias, float* y, void* ws, size_t ws_bytes, int N,
+                          int Cin, int Cout, int T, int V, int taps, int stride, int pad, int npl, hipStream_t s,
+                          const float* add, int relu, const float* x_absmax, const GateArgs* gate) {
+  if (!agcn_bf16_tconv_infer_supported(taps, stride, pad)) return AGCN_ERR_UNSUPPORTED;
+#define AGCN_INFER_CASE(TAPS, WQ) \
+  return bf16_tconv_infer_t<TAPS, WQ>(x, w, bias, y, ws, ws_bytes, N, Cin, Cout, T, V, stride, pad, npl, s, add, relu, x_absmax, gate)
+  switch (taps) {
+    case 3: AGCN_INFER_CASE(3, 2);
+    case 5: AGCN_INFER_CASE(5, 2);
+    case 7: AGCN_INFER_CASE(7, 2);
+    default: break;
+  }
+  if (stride == 1) AGCN_INFER_CASE(9, 2);
+  AGCN_INFER_CASE(9, 3);
+#undef AGCN_INFER_CASE
 }
 
 // frames per stats tile of agcn_bf16_tconv_fwd (the wide 64-row tile covers 512 positions, every other one 256)

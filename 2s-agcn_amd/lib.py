@@ -62,6 +62,7 @@ SIGNATURES = {
     "agcn_gcn_unit_infer_workspace": (_Z, [_I, _I, _I, _I, _I]),
     "agcn_gcn_unit_infer": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _Z, _I, _I, _I, _I, _I, _P]),
     "agcn_conv9_infer": (_I, [_P, _P, _P, _P, _I, _P, _P, _Z, _I, _I, _I, _I, _I, _I, _P]),
+    "agcn_tconv_infer": (_I, [_P] * 7 + [_I, _P, _P, _Z] + [_I] * 8 + [_P, _P]),
     "agcn_gcn_aggregate_project_bwd_data": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _Z, _I, _I, _I, _I, _I, _P]),
     "agcn_gcn_bwd_data_fused_supported": (_I, [_I, _I, _I]),
     "agcn_gcn_aggregate_project_bwd_data_fused": (_I, [_P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _Z, _I, _I, _I, _I, _I, _P]),

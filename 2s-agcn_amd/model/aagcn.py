@@ -13,6 +13,9 @@ gates between them (bandwidth-bound mean -> tiny conv/fc -> sigmoid -> ``y*s + y
 node (``ops.STCAttentionFunction``): every pass over the (N,C,T,V) activation is a HIP kernel (``csrc/attention.hip``:
 3 reads + 1 write forward, 4 reads + 1 write backward); only the few-KB gate networks (Conv1d C->1, two Linears on
 (N,C,V)/(N,C,T)/(N,C) tensors) are tensor code.
+Inference (``model.eval()`` under ``torch.no_grad()``): every BatchNorm is folded into the contraction in front of it
+and the gates multiply the temporal convolution's operand on load (``ops.aagcn_unit_infer``: 2 reads of the unit_gcn
+output for the gate statistics, no gated copy of it); ``AGCN_INFER_FOLD=0`` keeps the passes above.
 GhostBatchNorm (``gbn_split >= 2``) runs on the same HIP BatchNorm stages (``ghostbatchnorm.py``).  Not supported:
 ``data_norm='ln'``.
 """
@@ -146,8 +149,18 @@ class TCNUnit(nn.Module):
         conv_init(self.conv)
         bn_init(self.bn, 1)
 
+    def train(self, mode=True):
+        # folded inference weights are derived from parameters the training path rewrites in place
+        self.__dict__.pop('_infer_cache', None)
+        return super().train(mode)
+
     def forward(self, x):
         _require_gpu(x, 'aagcn.TCNUnit')
+        if not self.training and not torch.is_grad_enabled() and ops.infer_fold_enabled():
+            y = ops.tcn_infer(x, self.conv.weight, self.conv.bias, _bn_args(self.bn), self.stride, self.pad,
+                              cache=self.__dict__.setdefault('_infer_cache', {}))
+            if y is not None:
+                return y
         y = ops.UnitTCNFunction.apply(x, self.conv.weight, self.conv.bias, *_bn_args(self.bn), self.stride,
                                       self.training, ops.sync_of(self.bn), self.pad)
         _bn_tick(self.bn, self.training)
@@ -245,8 +258,47 @@ class TCNGCNUnit(nn.Module):
             self.res_mode = 2
         self.relu = nn.ReLU(inplace=True)
 
+    def train(self, mode=True):
+        # folded inference weights are derived from parameters the training path rewrites in place
+        self.__dict__.pop('_infer_cache', None)
+        return super().train(mode)
+
+    def infer_params(self):
+        """The unit's raw parameters in the form ``ops.aagcn_unit_infer`` folds them from."""
+        g, t = self.gcn1, self.tcn1
+        adaptive = isinstance(g.agcn, AdaptiveGCN)
+        attn = None
+        if g.attn_s is not None and g.attn_t is not None and g.attn_c is not None:
+            s_, t_, c_ = g.attn_s.conv_sa, g.attn_t.conv_ta, g.attn_c
+            attn = (s_.weight, s_.bias, t_.weight, t_.bias, c_.fc1c.weight, c_.fc1c.bias, c_.fc2c.weight,
+                    c_.fc2c.bias)
+        elif not (g.attn_s is None and g.attn_t is None and g.attn_c is None):
+            return None                                   # a partial set of gates: the module path
+        down = None
+        if isinstance(g.down, nn.Sequential):
+            down = (g.down[0].weight, g.down[0].bias) + _bn_args(g.down[1])
+        res = None
+        if self.res_mode == 2:
+            res = (self.residual.conv.weight, self.residual.conv.bias) + _bn_args(self.residual.bn)
+        return dict(
+            conv_d=[(c.weight, c.bias) for c in g.conv_d],
+            ab=[(g.agcn.conv_a[i].weight, g.agcn.conv_a[i].bias, g.agcn.conv_b[i].weight, g.agcn.conv_b[i].bias)
+                for i in range(3)] if adaptive else None,
+            A=None if adaptive else g.agcn.A, PA=g.agcn.PA if adaptive else None,
+            alpha=g.agcn.alpha if adaptive else None, gbn=_bn_args(g.bn), down=down, attn=attn,
+            tw=t.conv.weight, tb=t.conv.bias, tbn=_bn_args(t.bn), res_mode=self.res_mode, res=res,
+            stride=self.stride, pad=t.pad)
+
     def forward(self, x):
         _require_gpu(x, 'aagcn.TCNGCNUnit')
+        if not self.training and not torch.is_grad_enabled() and ops.infer_fold_enabled():
+            # inference: BatchNorms folded into the contractions, the attention gates applied inside the temporal
+            # convolution, residual + ReLU in the epilogues
+            p = self.infer_params()
+            if p is not None:
+                y = ops.aagcn_unit_infer(x, p, cache=self.__dict__.setdefault('_infer_cache', {}))
+                if y is not None:
+                    return y
         y = self.gcn1(x)
         t = self.tcn1
         if self.res_mode == 2:

@@ -535,6 +535,7 @@ class STCAttentionFunction(torch.autograd.Function):
         out = torch.empty_like(y)
         # the gated tensor feeds the f16x3 temporal convolution (and its weight gradient): leave its maximum behind
         o_amax = _empty((1,), y) if fused_amax_enabled() else None
+        INFER_STATS['stc_apply'] += 1
         _lib.check(_L().agcn_stc_apply_ex(_lib.ptr(y), _lib.ptr(a_s), _lib.ptr(a_t), _lib.ptr(a_c), _lib.ptr(out),
                                           _lib.ptr(o_amax), N, C, T, V, _lib.stream()), "agcn_stc_apply")
         _note_out_amax(out, o_amax)
@@ -967,11 +968,25 @@ def infer_fold_enabled():
     return os.environ.get('AGCN_INFER_FOLD', '1') != '0'
 
 
+# diagnostic counters of the eval-mode routes (never read by a compute path): units that ran folded end to end, folded
+# temporal convolutions, and launches of the stand-alone gate pass agcn_stc_apply that the folded AAGCN unit replaces
+INFER_STATS = {'aagcn_unit_fused': 0, 'tconv_infer': 0, 'stc_apply': 0}
+
+
 def _fold(bn):
-    """(scale, shift) of an eval-mode BatchNorm: y = scale * x + shift  (reference nn.BatchNorm2d in eval mode)."""
+    """(scale, shift) of an eval-mode BatchNorm: y = scale * x + shift  (reference nn.BatchNorm2d in eval mode).
+    GhostBatchNorm keeps S*C running statistics and evaluates with the first C of them (ghostbatchnorm.py; .eval() has
+    collated them over the S sub-batches): the same entries ``_bn_coeffs`` reads."""
     w, b, rm, rv = bn
-    s = w / torch.sqrt(rv + BN_EPS)
-    return s, b - rm * s
+    C = w.numel()
+    s = w / torch.sqrt(rv[:C] + BN_EPS)
+    return s, b - rm[:C] * s
+
+
+def _fold_conv(w, b, bn):
+    """Weights and bias of ``bn(conv(x; w, b))`` in eval mode as one convolution; w (Cout, Cin, k, 1)."""
+    s, sh = _fold(bn)
+    return (w * s[:, None, None, None]).contiguous(), (b * s + sh).contiguous()
 
 
 def gcn_unit_infer(x, adj, wcat, bias, res=None, x2=None, w2=None, relu=True):
@@ -1006,6 +1021,123 @@ def conv9_infer(x, w, b, res=None, relu=True, stride=1):
     return y
 
 
+def tconv_infer(x, w, b, a_s=None, a_t=None, a_c=None, res=None, relu=True, stride=1, pad=None, x_amax=None):
+    """y = act(b + tconv(x * a_s[n,v] * a_t[n,t] * a_c[n,c]; w (k,1), stride, pad) [+ res]) with the BatchNorm already
+    folded into w, b (agcn_tconv_infer): every kernel size / stride / padding of ``conv_fwd``; the gates (each optional)
+    multiply x on load, the gated tensor is never stored.  None where the library reports the shape unsupported."""
+    N, Cin, T, V = x.shape
+    Cout, Cin2, taps, one = w.shape
+    assert Cin2 == Cin and one == 1
+    pad = (taps - 1) // 2 if pad is None else pad
+    To = conv_out_frames(T, taps, stride, pad)
+    if To < 1:
+        raise ValueError(f"agcn_amd: a {taps}-frame kernel with padding {pad} does not fit {T} frames")
+    ws, nbytes = _conv_ws(Cin, Cout, T, V, taps, stride, x, pad)
+    y = _empty((N, Cout, To, V), x)
+    rc = _L().agcn_tconv_infer(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(a_s), _lib.ptr(a_t), _lib.ptr(a_c),
+                               _lib.ptr(res), 1 if relu else 0, _lib.ptr(y), ws.data_ptr(), nbytes, N, Cin, Cout, T, V,
+                               taps, stride, pad, _lib.ptr(x_amax), _lib.stream())
+    if rc == ERR_UNSUPPORTED:
+        return None
+    _lib.check(rc, "agcn_tconv_infer")
+    INFER_STATS['tconv_infer'] += 1
+    return y
+
+
+def _cache_key(srcs):
+    return (_PARAM_EPOCH[0],) + tuple((t.data_ptr(), t._version) for t in srcs if t is not None)
+
+
+def tcn_infer(x, w, b, bn, stride, pad, cache=None):
+    """Eval-mode stand-alone TCNUnit / unit_tcn (reference aagcn.py:194-207): bn(conv(x)) as one folded convolution."""
+    key = _cache_key([w, b, *bn])
+    f = cache.get('folded') if cache is not None else None
+    if f is None or f[0] != key:
+        f = (key,) + _fold_conv(w, b, bn)
+        if cache is not None:
+            cache['folded'] = f
+    return tconv_infer(x.contiguous(), f[1], f[2], relu=False, stride=stride, pad=pad)
+
+
+def aagcn_unit_infer(x, p, cache=None):
+    """Eval-mode AAGCN TCNGCNUnit (reference aagcn.py:164-177, 264-271, 194-207, 316-321) with every BatchNorm folded
+    into the contraction in front of it and the three attention gates applied inside the temporal convolution:
+    adjacency, one aggregate+project kernel (unit BN and `down` folded; residual / ReLU in its epilogue), the two
+    reduction passes and the few-KB gate networks of ``STCAttentionFunction.forward`` (no ``agcn_stc_apply``: the gated
+    tensor is never written), [the folded 1x1 stride residual conv], one ``agcn_tconv_infer`` (gates on load, residual
+    add + ReLU in its epilogue).
+    p: the unit's raw parameters -- conv_d [(w, b)]*3, ab [(wa, ba, wb, bb)]*3 | None (NonAdaptiveGCN), A (fixed graph)
+    | None, PA, alpha, gbn / tbn (weight, bias, running_mean, running_var), down / res None | (w, b, *bn), attn None |
+    (sa_w, sa_b, ta_w, ta_b, fc1_w, fc1_b, fc2_w, fc2_b), tw, tb, res_mode, stride, pad.
+    Returns None where the fused kernels do not apply (3-channel first layer, C < 32, whatever agcn_gcn_unit_infer
+    rejects): the caller runs the unfused eval passes.  ``cache`` (a dict owned by the module) keeps the folded and
+    packed weights between calls, keyed on the parameter epoch and every source tensor's (data_ptr, version)."""
+    x = x.contiguous()
+    N, C, T, V = x.shape
+    # decided before anything is folded or launched: agcn_gcn_unit_infer exists on the chained split kernels only
+    # (AGCN_GEMM=bf16x6 / bf16) and from 32 channels on.  (A shape it still rejects below has run the adjacency once
+    # more than needed: the caller's unfused passes compute it again.)
+    if C < 32 or _L().agcn_gemm_mode() not in (b'bf16x6', b'bf16'):
+        return None
+    srcs = [t for wb in p['conv_d'] for t in wb] + [t for q in (p['ab'] or []) for t in q]
+    srcs += [*p['gbn'], p['tw'], p['tb'], *p['tbn']] + list(p['down'] or []) + list(p['res'] or [])
+    key = _cache_key(srcs)
+    f = cache.get('folded') if cache is not None else None
+    if f is None or f[0] != key:
+        Cout = p['conv_d'][0][0].shape[0]
+        wd = torch.cat([w.view(Cout, C) for w, _ in p['conv_d']], dim=1)
+        bd = p['conv_d'][0][1] + p['conv_d'][1][1] + p['conv_d'][2][1]
+        s1, sh1 = _fold(p['gbn'])
+        wdf = (wd * s1[:, None]).contiguous()
+        bias = bd * s1 + sh1
+        w2 = None
+        if p['down'] is not None:
+            dw, db = _fold_conv(p['down'][0], p['down'][1], p['down'][2:])
+            w2 = dw.reshape(Cout, C)
+            bias = bias + db
+        twf, tbf = _fold_conv(p['tw'], p['tb'], p['tbn'])
+        rwf = rbf = None
+        if p['res'] is not None:
+            rwf, rbf = _fold_conv(p['res'][0], p['res'][1], p['res'][2:])
+        wab = bab = None
+        if p['ab'] is not None:      # theta/phi weights stacked row-wise [a0|b0|a1|b1|a2|b2]
+            wab = torch.cat([t for wa, _, wb_, _ in p['ab'] for t in (wa, wb_)], 0).contiguous()
+            bab = torch.cat([t for _, ba, _, bb in p['ab'] for t in (ba, bb)], 0).contiguous()
+        f = (key, wdf, bias.contiguous(), w2, twf, tbf, rwf, rbf, wab, bab)
+        if cache is not None:
+            cache['folded'] = f
+    _, wdf, bias, w2, twf, tbf, rwf, rbf, wab, bab = f
+    if wab is not None and adjacency_fused_supported(C, wab.shape[0] // 6, T, V):
+        _, adj = adjacency_fused_fwd(x, wab, bab, None, p['PA'], p['alpha'])
+    elif wab is not None:
+        tp, _ = conv_fwd(x, wab, bab)
+        _, adj = adjacency_fwd(tp, None, p['PA'], p['alpha'])
+    else:
+        adj = p['A'].unsqueeze(0).expand(N, 3, V, V).contiguous()
+    if w2 is None:
+        g = gcn_unit_infer(x, adj, wdf, bias, res=x)
+    else:
+        g = gcn_unit_infer(x, adj, wdf, bias, x2=x, w2=w2)
+    if g is None:
+        return None
+    a_s = a_t = a_c = None
+    if p['attn'] is not None:        # exactly STCAttentionFunction.forward up to (and without) its apply pass
+        _, m_s = stc_row_reduce(g, want_v=True, scale_v=1.0 / T)                         # mean_t g
+        a_s = STCAttentionFunction._gates(m_s, None, *p['attn'])[0]
+        mv1, _ = stc_row_reduce(g, wv=a_s, want_t=True, scale_t=1.0 / V)                 # mean_v g*(1+se_s)
+        _, a_t, a_c, _, _ = STCAttentionFunction._gates(m_s, mv1, *p['attn'], a_s=a_s)
+    if p['res_mode'] == 0:
+        r = None
+    elif p['res_mode'] == 1:
+        r = x
+    else:
+        r, _ = conv_fwd(x, rwf, rbf, p['stride'])
+    y = tconv_infer(g, twf, tbf, a_s, a_t, a_c, res=r, relu=True, stride=p['stride'], pad=p['pad'])
+    if y is not None:
+        INFER_STATS['aagcn_unit_fused'] += 1
+    return y
+
+
 def unit_infer(x, A, PA, wab, bab, wd, bd, gbn, down, tw, tb, tbn, res_mode, res, stride, alpha=None, adaptive=True,
                cache=None):
     """Eval-mode TCN_GCN_unit (reference agcn.py:92-109, 48-50, 127-129) with every BatchNorm folded into the contraction
@@ -1017,7 +1149,7 @@ def unit_infer(x, A, PA, wab, bab, wd, bd, gbn, down, tw, tb, tbn, res_mode, res
     x = x.contiguous()
     N, C, T, V = x.shape
     Cout = wd.shape[0]
-    if C < 32 or tw.shape[2] != 9:       # (the folded temporal kernel is the 9-tap one)
+    if C < 32:
         return None
     srcs = [wd, bd, *gbn, tw, tb, *tbn] + (list(down) if down is not None else []) + \
            (list(res) if isinstance(res, tuple) else [])
@@ -1063,7 +1195,9 @@ def unit_infer(x, A, PA, wab, bab, wd, bd, gbn, down, tw, tb, tbn, res_mode, res
         r = x
     else:
         r, _ = conv_fwd(x, rwf, rbf, stride)
-    return conv9_infer(g, twf, tbf, r, relu=True, stride=stride)
+    if tw.shape[2] == 9:
+        return conv9_infer(g, twf, tbf, r, relu=True, stride=stride)
+    return tconv_infer(g, twf, tbf, res=r, relu=True, stride=stride)     # unit_tcn(kernel_size != 9): same fold
 
 
 def _need_train(training):

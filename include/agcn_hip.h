@@ -185,6 +185,20 @@ int agcn_conv9_infer(const float* x, const float* w, const float* bias, const fl
                      void* workspace, size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int stride,
                      void* stream);
 
+/* agcn_tconv_infer: the same fold for every temporal kernel of agcn_tconv_fwd, with AAGCN's three attention gates applied
+ * to the operand on load.  Replaces, for model.eval() under no_grad, `y = x * se + x` three times (aagcn.py:264-271, with
+ * a = 1 + se of SpatialAttention / TemporalAttention / ChannelAttention :59-116), TCNUnit.forward (:194-207) and the
+ * TCNGCNUnit tail relu(tcn(gcn(x)) + residual(x)) (:316-321):
+ *     y = act( bias + tconv(x * gate ; w (Cout,Cin,taps,1), stride, pad) [+ res] ),  gate[n,c,t,v] = a_s[n,v] a_t[n,t] a_c[n,c]
+ * a_s (N,V), a_t (N,T), a_c (N,Cin): each optional, NULL = ones; res (N,Cout,T_out,V) or NULL; x_absmax: optional device
+ * scalar max |x| of the ungated x (NULL: taken by a pass inside where the f16x3 kernels need it).  The gated tensor is
+ * never written: the factors multiply the operand tile between its global load and the LDS image the matrix cores read.
+ * Domain and workspace (agcn_tconv_workspace) of agcn_tconv_fwd; AGCN_ERR_UNSUPPORTED outside it, nothing is launched. */
+int agcn_tconv_infer(const float* x, const float* w, const float* bias, const float* a_s, const float* a_t,
+                     const float* a_c, const float* res, int relu, float* y, void* workspace, size_t workspace_bytes,
+                     int N, int Cin, int Cout, int T, int V, int taps, int stride, int pad, const float* x_absmax,
+                     void* stream);
+
 /* mask_bits = 1: mask1/mask2 are sign bit masks of agcn_bn_act_fwd (cast to const float*), 0: fp32 tensors (> 0 passes) */
 int agcn_gcn_aggregate_project_bwd_data(const float* dy, const float* adj, const float* wcat, float* dx,
                                         int accumulate, const float* add1, const float* mask1, const float* add2,

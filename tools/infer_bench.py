@@ -1,24 +1,86 @@
-"""Eval-mode (inference) throughput of the AGCN joint model, NTU shape, batch 64, synthetic input resident in HBM:
-the BN-folded chain (adjacency + two kernels per unit; AGCN_INFER_FOLD=1, default) against the unfused eval passes.
-    python tools/infer_bench.py [reps]"""
-import os, sys, time
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch
-import bench
+"""Eval-mode (inference) throughput at the NTU shape, batch 64, synthetic input resident in HBM: the BN-folded path
+(AGCN_INFER_FOLD=1, default) against the unfused eval passes, for either architecture.
+    python tools/infer_bench.py [reps] [--model agcn|aagcn] [--layers 10] [--gbn-split S] [--kernel K --kstride S]
+                                [--batch 64] [--frames 300] [--repeats 5] [--folds 1,0]
+--model agcn: the 2s-AGCN joint model (adjacency + two kernels per unit).  --model aagcn: model.aagcn.Model with
+``model_layers`` / ``gbn_split`` (adjacency, aggregate+project, two gate reductions, one gated temporal convolution per
+unit).  --layers 101|102|103 builds the one-width backbone from TCNGCNUnit(kernel_size=K, stride=S) as the reference's
+aagcn_vNN variants do.  Each figure is the median of --repeats timed runs of ``reps`` forwards after a warm-up, with
+the min..max spread of the runs."""
+import argparse
+import os
+import statistics
+import sys
+import time
 
-reps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
-dev = torch.device('cuda:0')
-model = bench.build_model('ntu_agcn').to(dev).eval()
-x = torch.randn(64, 3, 300, 25, 2, device=dev)
-for fold in ('1', '0'):
-    os.environ['AGCN_INFER_FOLD'] = fold
-    with torch.no_grad():
-        for _ in range(3):
-            model(x)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(reps):
-            model(x)
-        torch.cuda.synchronize()
-        dt = (time.perf_counter() - t0) / reps
-    print('AGCN_INFER_FOLD=%s: %.2f ms per batch of 64, %.0f clips/s' % (fold, dt * 1e3, 64 / dt), flush=True)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+import bench  # noqa: E402
+
+
+def build(args):
+    if args.model == 'agcn':
+        return bench.build_model('ntu_agcn')
+    import agcn_amd  # noqa: F401
+    from agcn_amd.model import aagcn
+    graph = dict(graph='graph.ntu_rgb_d.Graph', graph_args=dict(labeling_mode='spatial'))
+    if args.layers in (101, 102, 103):
+        class Backbone(aagcn.BaseModel):
+            def __init__(self):
+                super().__init__(num_class=60, num_point=25, num_person=2, in_channels=3, gbn_split=args.gbn_split)
+                self.init_graph(graph['graph'], graph['graph_args'])
+                A = self.graph.A
+
+                def unit(_in, _out, stride=1, residual=True):
+                    return aagcn.TCNGCNUnit(_in, _out, A, kernel_size=args.kernel, stride=args.kstride,
+                                            pad=args.kstride == 1, residual=residual, gbn_split=args.gbn_split)
+                self.init_model_backbone(model_layers=args.layers, tcngcn_unit=unit, output_channel=64)
+                self.init_fc(64, 60)
+        return Backbone()
+    return aagcn.Model(num_class=60, num_point=25, num_person=2, model_layers=args.layers, gbn_split=args.gbn_split,
+                       **graph)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('reps', nargs='?', type=int, default=10)
+    ap.add_argument('--model', choices=('agcn', 'aagcn'), default='agcn')
+    ap.add_argument('--layers', type=int, default=10)
+    ap.add_argument('--gbn-split', type=int, default=None)
+    ap.add_argument('--kernel', type=int, default=3)
+    ap.add_argument('--kstride', type=int, default=1)
+    ap.add_argument('--batch', type=int, default=64)
+    ap.add_argument('--frames', type=int, default=300)
+    ap.add_argument('--repeats', type=int, default=5)
+    ap.add_argument('--folds', default='1,0')
+    args = ap.parse_args()
+    dev = torch.device('cuda:0')
+    model = build(args)
+    bench.randomize_like_training(model, 0)
+    model = model.to(dev).eval()
+    x = torch.randn(args.batch, 3, args.frames, 25, 2, device=dev)
+    what = args.model + (f' layers={args.layers}' if args.model == 'aagcn' else '')
+    if args.model == 'aagcn' and args.layers in (101, 102, 103):
+        what += f' k={args.kernel} s={args.kstride}'
+    for fold in args.folds.split(','):
+        os.environ['AGCN_INFER_FOLD'] = fold
+        runs = []
+        with torch.no_grad():
+            for _ in range(3):
+                model(x)
+            torch.cuda.synchronize()
+            for _ in range(args.repeats):
+                t0 = time.perf_counter()
+                for _ in range(args.reps):
+                    model(x)
+                torch.cuda.synchronize()
+                runs.append((time.perf_counter() - t0) / args.reps)
+        med = statistics.median(runs)
+        print('%s AGCN_INFER_FOLD=%s: %.2f ms per batch of %d (min %.2f, max %.2f over %d runs), %.0f clips/s'
+              % (what, fold, med * 1e3, args.batch, min(runs) * 1e3, max(runs) * 1e3, len(runs), args.batch / med),
+              flush=True)
+
+
+if __name__ == '__main__':
+    main()
