@@ -85,6 +85,9 @@ SIGNATURES = {
     "agcn_bn_bwd": (_I, [_P, _P, _I] + [_P] * 16 + [_I, _I, _I, _P]),
     "agcn_bn_bwd_reduce": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
     "agcn_bn_bwd_apply": (_I, [_P, _I, _D, _F, _P, _P, _I] + [_P] * 15 + [_I, _I, _I, _P]),
+    "agcn_bn_eval_coeff_ex": (_I, [_P, _P, _P, _P, _F, _I, _P, _P, _P, _P, _P]),
+    "agcn_bn_bwd_eval": (_I, [_P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "agcn_bn_bwd_eval_finalize": (_I, [_P, _I, _I] + [_P] * 13),
     "agcn_stc_row_reduce": (_I, [_P, _P, _P, _P, _I, _P, _P, _F, _F, _I, _I, _I, _I, _P]),
     "agcn_stc_apply": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "agcn_stc_apply_ex": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),

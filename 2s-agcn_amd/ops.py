@@ -436,13 +436,31 @@ class DataBNFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        _need_train(ctx.training)
         x, w = ctx.saved_tensors
         st, sync = ctx.st, ctx.sync
         dy = dy.contiguous()
         N, C, T, V, M = x.shape
         CH = C * V * M
         L = _L()
+        if not ctx.training:
+            # frozen statistics: dx = gamma*invstd_run*dy is agcn_data_bn_bwd_apply with the two sums at zero (exactly:
+            # its correction terms are products with 0), dgamma / dbeta are the sums of the reduce stage at the running
+            # mean / invstd
+            dx = dgamma = dbeta = None
+            if ctx.needs_input_grad[0]:
+                dx = torch.empty_like(x)
+                zero = torch.zeros(2 * CH, dtype=torch.float32, device=x.device)
+                _lib.check(L.agcn_data_bn_bwd_apply(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(w), _lib.ptr(st.mean),
+                                                    _lib.ptr(st.invstd), _lib.ptr(zero), float(ctx.gcount), _lib.ptr(dx),
+                                                    N, C, T, V, M, _lib.stream()), "agcn_data_bn_bwd_apply")
+            if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+                part = _empty((N, 2, CH), x)
+                _lib.check(L.agcn_data_bn_bwd_reduce(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(st.mean), _lib.ptr(st.invstd),
+                                                     _lib.ptr(part), N, C, T, V, M, _lib.stream()),
+                           "agcn_data_bn_bwd_reduce")
+                sums = _colsum(part, N, 2 * CH)
+                dbeta, dgamma = sums[:CH], sums[CH:]
+            return dx, dgamma, dbeta, None, None, None, None
         part = _empty((N, 2, CH), x)
         _lib.check(L.agcn_data_bn_bwd_reduce(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(st.mean), _lib.ptr(st.invstd),
                                              _lib.ptr(part), N, C, T, V, M, _lib.stream()), "agcn_data_bn_bwd_reduce")
@@ -579,11 +597,14 @@ class BNState:
     model/layers/module/ghostbatchnorm.py:77-120) -- the statistics are per virtual sub-batch s = n % S, which is an
     ordinary BatchNorm over (N/S, S*C, T, V): the HIP stages are simply called with that shape (channel index of a row
     = (n*C + c) % (S*C) = (n % S)*C + c), the coefficient vectors hold S*C entries and the shared weight/bias are
-    repeated S times; nothing in the kernels changes."""
-    __slots__ = ("mean", "invstd", "scale", "shift", "S")
+    repeated S times; nothing in the kernels changes.  ``eval``: the stage ran on the frozen running statistics; ``mean``
+    / ``invstd`` are then copies of the running mean and 1/sqrt(running_var + eps) and ``bn_bwd`` takes the one-pass
+    eval-mode backward (always plain BatchNorm: S = 1)."""
+    __slots__ = ("mean", "invstd", "scale", "shift", "S", "eval")
 
     def __init__(self):
         self.S = 1
+        self.eval = False
 
 
 class SyncBN:
@@ -665,11 +686,13 @@ def bn_train_coeffs(stats_part, count, gamma, beta, running_mean, running_var, m
 def bn_eval_coeffs(gamma, beta, running_mean, running_var, eps=BN_EPS):
     C = gamma.numel()
     st = BNState()
-    st.mean = st.invstd = None
+    st.eval = True
     st.scale, st.shift = _empty((C,), gamma), _empty((C,), gamma)
-    _lib.check(_L().agcn_bn_eval_coeff(_lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(running_mean),
-                                       _lib.ptr(running_var), float(eps), C, _lib.ptr(st.scale), _lib.ptr(st.shift),
-                                       _lib.stream()), "agcn_bn_eval_coeff")
+    st.mean, st.invstd = _empty((C,), gamma), _empty((C,), gamma)     # frozen statistics, for the eval-mode backward
+    _lib.check(_L().agcn_bn_eval_coeff_ex(_lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(running_mean),
+                                          _lib.ptr(running_var), float(eps), C, _lib.ptr(st.scale), _lib.ptr(st.shift),
+                                          _lib.ptr(st.mean), _lib.ptr(st.invstd), _lib.stream()),
+               "agcn_bn_eval_coeff_ex")
     return st
 
 
@@ -691,10 +714,57 @@ def bn_act_fwd(y1, st1, r=None, st2=None, relu=True, want_bits=False, amax_out=N
     return (out, bits) if want_bits else out
 
 
-def bn_bwd(dout, mask, y1, gamma1, st1, y2=None, gamma2=None, st2=None, sync=None, gcount=None, amax_out=None):
-    """Backward through out = relu(bn1(y1) [+ bn2(y2)] [+ identity]) in train mode.  ``mask``: the fp32 output tensor
-    (positive elements pass) or the int32 sign bit mask of ``bn_act_fwd(..., want_bits=True)``; None = no ReLU.
-    Returns dy1, dgamma1, dbeta1, dy2, dgamma2, dbeta2 (branch-2 entries None without y2)."""
+EVAL_BWD_STATS = {'sums': 0, 'nosums': 0}     # diagnostic: agcn_bn_bwd_eval launches with / without the row partials
+
+
+def bn_bwd_eval(dout, mask, y1, st1, y2=None, st2=None, want_sums=True, amax_out=None):
+    """Backward through out = act(bn1(y1) [+ bn2(y2)] [+ identity]) with FROZEN statistics (``bn_eval_coeffs`` states):
+    dy = scale[c] * dout * mask in one streaming pass (agcn_bn_bwd_eval), the parameter gradients from its row partials
+    (agcn_bn_bwd_eval_finalize).  No sync collective, no GhostBatchNorm regrouping: eval is plain per-channel BN.
+    Returns dy1, dgamma1, dbeta1, dbias1, dy2, dgamma2, dbeta2, dbias2: dbias = scale * sum dz is the gradient of the
+    bias of the convolution in front of the BN (not zero here: only a batch mean would cancel it).  want_sums=False:
+    y1 / y2 are not read and every parameter gradient is None."""
+    N, C, T, V = dout.shape
+    two = st2 is not None
+    dy1 = torch.empty_like(dout)
+    dy2 = torch.empty_like(dout) if two else None
+    part = _empty((N * C * 3,), dout) if want_sums else None
+    mbits = int(mask is not None and mask.dtype == torch.int32)
+    mptr = _lib.ptr_bits(mask) if mbits else _lib.ptr(mask)
+    EVAL_BWD_STATS['sums' if want_sums else 'nosums'] += 1
+    _lib.check(_L().agcn_bn_bwd_eval(_lib.ptr(dout), mptr, mbits, _lib.ptr(y1) if want_sums else None,
+                                     _lib.ptr(st1.scale), _lib.ptr(y2) if (want_sums and two) else None,
+                                     _lib.ptr(st2.scale) if two else None, int(want_sums), _lib.ptr(part),
+                                     _lib.ptr(dy1), _lib.ptr(dy2), _lib.ptr(amax_out), N, C, T * V, _lib.stream()),
+               "agcn_bn_bwd_eval")
+    if not want_sums:
+        return dy1, None, None, None, dy2, None, None, None
+    dg1, db1, dc1 = _empty((C,), dout), _empty((C,), dout), _empty((C,), dout)
+    dg2 = db2 = dc2 = None
+    if two:
+        dg2, db2, dc2 = _empty((C,), dout), _empty((C,), dout), _empty((C,), dout)
+    _lib.check(_L().agcn_bn_bwd_eval_finalize(
+        _lib.ptr(part), N, C, _lib.ptr(st1.scale), _lib.ptr(st1.mean), _lib.ptr(st1.invstd),
+        _lib.ptr(st2.scale) if two else None, _lib.ptr(st2.mean) if two else None,
+        _lib.ptr(st2.invstd) if two else None, _lib.ptr(dg1), _lib.ptr(db1), _lib.ptr(dc1), _lib.ptr(dg2),
+        _lib.ptr(db2), _lib.ptr(dc2), _lib.stream()), "agcn_bn_bwd_eval_finalize")
+    return dy1, dg1, db1, dc1, dy2, dg2, db2, dc2
+
+
+def bn_bwd(dout, mask, y1, gamma1, st1, y2=None, gamma2=None, st2=None, sync=None, gcount=None, amax_out=None,
+           want_sums=True, bias_out=None):
+    """Backward through out = relu(bn1(y1) [+ bn2(y2)] [+ identity]).  ``mask``: the fp32 output tensor (positive
+    elements pass) or the int32 sign bit mask of ``bn_act_fwd(..., want_bits=True)``; None = no ReLU.
+    Returns dy1, dgamma1, dbeta1, dy2, dgamma2, dbeta2 (branch-2 entries None without y2).
+    Eval-mode states (frozen statistics) go to ``bn_bwd_eval``: ``want_sums=False`` skips the parameter gradients there,
+    and ``bias_out`` (a list) receives the gradients of the two convolution biases in front of the BatchNorms, which
+    train mode does not have (they are exactly zero)."""
+    if st1.eval:
+        dy1, dg1, db1, dc1, dy2, dg2, db2, dc2 = bn_bwd_eval(dout, mask, y1, st1, y2, st2 if y2 is not None else None,
+                                                             want_sums, amax_out)
+        if bias_out is not None:
+            bias_out[:] = [dc1, dc2]
+        return dy1, dg1, db1, dy2, dg2, db2
     N, C, T, V = y1.shape
     S = st1.S
     if S > 1:                          # GhostBatchNorm: see BNState; gamma repeated S times, dgamma/dbeta folded below
@@ -803,7 +873,7 @@ def gcn_forward(c, x, A, PA, wab, bab, wd, bd, bn, down, training, alpha=None, a
     if adaptive and adjacency_fused_supported(C, wab.shape[0] // 6, T, V):
         # theta/phi are formed and reduced on chip.  A training forward either keeps nothing (the backward recomputes
         # them, adjacency_bwd with tp = None) or lets the kernel drop a copy for the backward to re-read.
-        keep = training and need_bwd and not adjacency_recompute()
+        keep = need_bwd and not adjacency_recompute()     # (train or eval: a backward will follow)
         amax_here = None
         if x_amax is None and not first and fused_amax_enabled():
             amax_here = _empty((1,), x)    # this pass reads all of x: it takes the maximum along the way
@@ -856,8 +926,10 @@ def gcn_backward(c, dout, extra_add=None, extra_mask=None):
     wab, wd, gamma1, wdown, gamma2 = c.g_params
     Cout = wd.shape[0]
     dy_amax = _empty((1,), dout) if fused_amax_enabled() else None   # max |dypre| for the f16x3 backward-data chain
+    c.g_dbias = []            # eval mode: gradients of the conv_d / down biases (train mode: exactly zero, left empty)
     dypre, dg1, db1, ddpre, dg2, db2 = bn_bwd(dout, c.g_bits, ypre, gamma1, c.g_bn1, dpre, gamma2, c.g_bn2,
-                                              sync=c.g_sync, gcount=c.g_count, amax_out=dy_amax)
+                                              sync=c.g_sync, gcount=c.g_count, amax_out=dy_amax,
+                                              want_sums=getattr(c, 'g_want_sums', True), bias_out=c.g_dbias)
     x_amax = getattr(c, 'g_x_amax', None)
     dwd = _side_run(lambda: project_bwd_weight(dypre, x, adj, Cout, dy_amax, x_amax), (dypre, x, adj, dy_amax, x_amax))
     dPA = dwab = dbab = dalpha = dtp = dtp_amax = None
@@ -932,8 +1004,10 @@ def tcn_backward(c, dout, join=True):
     w, gamma1, wres, gamma2 = c.t_params
     mask = c.t_bits if c.t_relu else None
     dz_amax = _empty((1,), dout) if fused_amax_enabled() else None   # max |dzpre| for the backward-data convolution
+    c.t_dbias = []            # eval mode: gradients of the temporal / residual conv biases
     dzpre, dg1, db1, drpre, dg2, db2 = bn_bwd(dout, mask, c.t_zpre, gamma1, c.t_bn1, c.t_rpre, gamma2, c.t_bn2,
-                                              sync=c.t_sync, gcount=c.t_count, amax_out=dz_amax)
+                                              sync=c.t_sync, gcount=c.t_count, amax_out=dz_amax,
+                                              want_sums=getattr(c, 't_want_sums', True), bias_out=c.t_dbias)
     t_g, t_stride, t_pad = c.t_g, c.t_stride, getattr(c, 't_pad', None)
     t_g_amax = getattr(c, 't_g_amax', None)
     # (the device scalars are inputs of the side-stream kernels too: dz_amax dies with this frame, possibly before the join)
@@ -1200,10 +1274,14 @@ def unit_infer(x, A, PA, wab, bab, wd, bd, gbn, down, tw, tb, tbn, res_mode, res
     return tconv_infer(g, twf, tbf, res=r, relu=True, stride=stride)     # unit_tcn(kernel_size != 9): same fold
 
 
-def _need_train(training):
-    if not training:
-        raise NotImplementedError("agcn_amd: backward through eval-mode BatchNorm is not implemented; call "
-                                  "model.train() for training or torch.no_grad() for inference")
+def _bias_grad(slot, k, n, like, needed=True):
+    """Gradient of a convolution bias in front of a BatchNorm: ``slot[k]`` in eval mode (bn_bwd's ``bias_out``), exact
+    zeros in train mode where the batch mean cancels the bias; None where the eval backward skipped the sums."""
+    if slot and slot[k] is not None:
+        return slot[k]
+    if slot:                   # eval mode with want_sums=False: nobody asked for it
+        return None
+    return torch.zeros(n, dtype=torch.float32, device=like.device) if needed else None
 
 
 class UnitGCNFunction(torch.autograd.Function):
@@ -1224,11 +1302,12 @@ class UnitGCNFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        _need_train(ctx.training)
+        # eval mode: the BatchNorm partial sums only where a BN parameter or a conv bias in front of it wants a gradient
+        ng = ctx.needs_input_grad
+        ctx.c.g_want_sums = any(ng[i] for i in (6, 7, 8, 12, 13, 14))
         dx, dPA, dwab, dbab, dwd, dg1, db1, dwdown, dg2, db2 = gcn_backward(ctx.c, dout.contiguous())
-        zb = lambda t: torch.zeros(t.shape[0], dtype=torch.float32, device=dout.device)  # noqa: E731
-        dbd = zb(dwd)
-        dbdown = zb(dwdown) if ctx.has_down else None
+        dbd = _bias_grad(ctx.c.g_dbias, 0, dwd.shape[0], dout)
+        dbdown = _bias_grad(ctx.c.g_dbias, 1, dwd.shape[0], dout, ctx.has_down)
         dalpha = ctx.c.g_dalpha
         if dalpha is not None:
             dalpha = dalpha.reshape(1)
@@ -1250,9 +1329,9 @@ class UnitTCNFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        _need_train(ctx.training)
+        ctx.c.t_want_sums = any(ctx.needs_input_grad[i] for i in (2, 3, 4))
         dg, dw, dg1, db1, _, _, _, _ = tcn_backward(ctx.c, dout.contiguous())
-        dbias = torch.zeros(dw.shape[0], dtype=torch.float32, device=dout.device)
+        dbias = _bias_grad(ctx.c.t_dbias, 0, dw.shape[0], dout)
         ctx.c = None
         return dg, dw, dbias, dg1, db1, None, None, None, None, None, None
 
@@ -1276,20 +1355,20 @@ class TCNResidualFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        _need_train(ctx.training)
         c = ctx.c
         dout = dout.contiguous()
+        c.t_want_sums = any(ctx.needs_input_grad[i] for i in (3, 4, 5, 10, 11, 12))
         dg, dw, dg1, db1, drpre, dwres, dg2, db2 = tcn_backward(c, dout)
-        dev = dout.device
-        zb = lambda n: torch.zeros(n, dtype=torch.float32, device=dev)  # noqa: E731
+        dtb = _bias_grad(c.t_dbias, 0, dw.shape[0], dout)
+        drb = _bias_grad(c.t_dbias, 1, dw.shape[0], dout, ctx.res_mode == 2)
         dx = None
         if ctx.res_mode == 1:
             dx = torch.where(c.t_out > 0, dout, torch.zeros_like(dout))
         elif ctx.res_mode == 2:
             dx = conv_bwd_data(drpre, c.t_params[2], ctx.x_shape, ctx.stride)
         ctx.c = None
-        return (dg, dx, dw, zb(dw.shape[0]), dg1, db1, None, None, None,
-                dwres, zb(dwres.shape[0]) if ctx.res_mode == 2 else None, dg2, db2, None, None, None, None, None, None)
+        return (dg, dx, dw, dtb, dg1, db1, None, None, None,
+                dwres, drb, dg2, db2, None, None, None, None, None, None)
 
 
 class TCNGCNUnitFunction(torch.autograd.Function):
@@ -1316,9 +1395,11 @@ class TCNGCNUnitFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        _need_train(ctx.training)
         c = ctx.c
         dout = dout.contiguous()
+        ng = ctx.needs_input_grad
+        c.g_want_sums = any(ng[i] for i in (6, 7, 8, 12, 13, 14))
+        c.t_want_sums = any(ng[i] for i in (18, 19, 20, 25, 26, 27))
         _SIDE_SCOPE[0] += 1
         try:
             dg, dtw, dtg, dtb, drpre, drw, drg, drb = tcn_backward(c, dout, join=False)   # (gcn_backward joins)
@@ -1331,10 +1412,13 @@ class TCNGCNUnitFunction(torch.autograd.Function):
         dx, dPA, dwab, dbab, dwd, dg1, db1, dwdown, dg2, db2 = gres
         if ctx.res_mode == 2:
             conv_bwd_data(drpre, c.t_params[2], c.g_x.shape, ctx.stride, out=dx, accumulate=True)
-        dev = dout.device
-        zb = lambda n: torch.zeros(n, dtype=torch.float32, device=dev)  # noqa: E731
+        Cout = dwd.shape[0]
+        dbd = _bias_grad(c.g_dbias, 0, Cout, dout)
+        dbdown = _bias_grad(c.g_dbias, 1, Cout, dout, ctx.has_down)
+        dtbias = _bias_grad(c.t_dbias, 0, Cout, dout)
+        drbias = _bias_grad(c.t_dbias, 1, Cout, dout, ctx.res_mode == 2)
         ctx.c = None
-        return (dx, None, dPA, dwab, dbab, dwd, zb(dwd.shape[0]), dg1, db1, None, None,
-                dwdown, zb(dwdown.shape[0]) if ctx.has_down else None, dg2, db2, None, None,
-                dtw, zb(dtw.shape[0]), dtg, dtb, None, None, None,
-                drw, zb(drw.shape[0]) if ctx.res_mode == 2 else None, drg, drb, None, None, None, None, None)
+        return (dx, None, dPA, dwab, dbab, dwd, dbd, dg1, db1, None, None,
+                dwdown, dbdown, dg2, db2, None, None,
+                dtw, dtbias, dtg, dtb, None, None, None,
+                drw, drbias, drg, drb, None, None, None, None, None)

@@ -295,6 +295,25 @@ int agcn_bn_bwd(const float* dout, const void* mask, int mask_bits, const float*
                 const float* mean1, const float* invstd1, const float* y2, const float* gamma2, const float* mean2, const float* invstd2,
                 float* part, float* coef, float* dy1, float* dgamma1, float* dbeta1, float* dy2, float* dgamma2,
                 float* dbeta2, int N, int C, int P, void* stream);
+/* eval-mode (frozen statistics) backward of the same stage, scale = gamma * rsqrt(running_var + eps): one streaming pass
+ *   dz = dout*mask ; dy1 = scale1[c]*dz ; dy2 = scale2[c]*dz (branch 2 exists iff scale2 != NULL) ; absmax1_out
+ *   (optional, 4 bytes) = max |dy1| ; want_sums = 1: part[(n*C + c)*3 + k] = per-row (sum dz, sum dz*y1, sum dz*y2).
+ * want_sums = 0 reads neither y1 nor y2 and does not touch part (all three may be NULL): the input-gradient-only case.
+ * Any N*C*P (rows of P % 4 != 0 included); mask as in agcn_bn_bwd_reduce.
+ * agcn_bn_bwd_eval_finalize sums the `nrows` rows of part per channel in double, in row order:
+ *   dbeta = S0 ; dgamma = invstd*(S1 - mean*S0) ; dbias (optional) = scale*S0, the gradient of the bias of the
+ *   convolution in front of the BatchNorm -- not zero in eval mode, unlike train mode where the batch mean cancels it.
+ * agcn_bn_eval_coeff_ex: agcn_bn_eval_coeff (same scale / shift bits) that also copies out the frozen mean and
+ *   invstd = 1/sqrt(running_var + eps) the finalize takes. */
+int agcn_bn_eval_coeff_ex(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                          float eps, int C, float* scale, float* shift, float* mean, float* invstd, void* stream);
+int agcn_bn_bwd_eval(const float* dout, const void* mask, int mask_bits, const float* y1, const float* scale1,
+                     const float* y2, const float* scale2, int want_sums, float* part /* N*C*3 floats */, float* dy1,
+                     float* dy2, float* absmax1_out, int N, int C, int P, void* stream);
+int agcn_bn_bwd_eval_finalize(const float* part, int nrows, int C, const float* scale1, const float* mean1,
+                              const float* invstd1, const float* scale2, const float* mean2, const float* invstd2,
+                              float* dgamma1, float* dbeta1, float* dbias1, float* dgamma2, float* dbeta2,
+                              float* dbias2, void* stream);
 
 /* ---- AAGCN attention gates (config 4) ---------------------------------------------------------------------------------
  * replaces the full-tensor passes of aagcn.py:59-116, 268-270 (three "mean -> tiny net -> sigmoid -> y*s + y" gates):
