@@ -14,7 +14,7 @@ node (``ops.STCAttentionFunction``): every pass over the (N,C,T,V) activation is
 3 reads + 1 write forward, 4 reads + 1 write backward); only the few-KB gate networks (Conv1d C->1, two Linears on
 (N,C,V)/(N,C,T)/(N,C) tensors) are tensor code.
 Inference (``model.eval()`` under ``torch.no_grad()``): every BatchNorm is folded into the contraction in front of it
-and the gates multiply the temporal convolution's operand on load (``ops.aagcn_unit_infer``: 2 reads of the unit_gcn
+and the gates multiply the temporal convolution's operand on load (``ops.unit_infer``: 2 reads of the unit_gcn
 output for the gate statistics, no gated copy of it); ``AGCN_INFER_FOLD=0`` keeps the passes above.
 GhostBatchNorm (``gbn_split >= 2``) runs on the same HIP BatchNorm stages (``ghostbatchnorm.py``).  Not supported:
 ``data_norm='ln'``.
@@ -27,8 +27,8 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from .agcn import (_bn_args, _bn_tick, _require_gpu, bn_init, conv_branch_init, conv_init, data_bn_forward,
-                   import_class)
+from .agcn import (_bn_args, _bn_tick, _require_gpu, bn_init, conv_branch_init, conv_init, data_bn_forward, gcn_params,
+                   import_class, unit_params)
 from .ghostbatchnorm import GhostBatchNorm1d, GhostBatchNorm2d
 
 
@@ -203,35 +203,31 @@ class GCNUnit(nn.Module):
         for i in range(num_subset):
             conv_branch_init(self.conv_d[i], num_subset)
 
+    def params(self):
+        if isinstance(self.agcn, AdaptiveGCN):
+            return gcn_params(self, self.agcn, None, self.agcn.PA, self.agcn.alpha)
+        return gcn_params(self, None, self.agcn.A, None)
+
+    def attn_params(self):
+        """The parameters of the three gates where all three are present (they then run as one autograd node / inside
+        the folded temporal convolution), else None."""
+        if self.attn_s is None or self.attn_t is None or self.attn_c is None:
+            return None
+        s_, t_, c_ = self.attn_s.conv_sa, self.attn_t.conv_ta, self.attn_c
+        return (s_.weight, s_.bias, t_.weight, t_.bias, c_.fc1c.weight, c_.fc1c.bias, c_.fc2c.weight, c_.fc2c.bias)
+
     def forward(self, x):
         _require_gpu(x, 'aagcn.GCNUnit')
-        co, ci = self.out_c, self.in_c
-        wd = torch.cat([self.conv_d[i].weight.view(co, ci) for i in range(3)], dim=1)
-        bd = self.conv_d[0].bias + self.conv_d[1].bias + self.conv_d[2].bias
-        if isinstance(self.down, nn.Sequential):
-            dn = (self.down[0].weight, self.down[0].bias) + _bn_args(self.down[1])
-        else:
-            dn = (None,) * 6
-        if isinstance(self.agcn, AdaptiveGCN):
-            ws, bs = [], []
-            for i in range(3):
-                ws += [self.agcn.conv_a[i].weight, self.agcn.conv_b[i].weight]
-                bs += [self.agcn.conv_a[i].bias, self.agcn.conv_b[i].bias]
-            y = ops.UnitGCNFunction.apply(x, None, self.agcn.PA, torch.cat(ws, 0), torch.cat(bs, 0), wd, bd,
-                                          *_bn_args(self.bn), *dn, self.training, self.agcn.alpha, True,
-                                          ops.sync_of(self.bn))
-        else:
-            y = ops.UnitGCNFunction.apply(x, self.agcn.A, None, None, None, wd, bd, *_bn_args(self.bn), *dn,
-                                          self.training, None, False, ops.sync_of(self.bn))
+        p = self.params()
+        y = ops.UnitGCNFunction.apply(x, *ops.pack_gcn(p), self.training, p['alpha'], ops.sync_of(self.bn))
         _bn_tick(self.bn, self.training)
         if isinstance(self.down, nn.Sequential):
             _bn_tick(self.down[1], self.training)
-        if self.attn_s is not None and self.attn_t is not None and self.attn_c is not None:
+        attn = self.attn_params()
+        if attn is not None:
             # the three gates as one autograd node on the HIP reduction / apply passes (ops.STCAttentionFunction); the
             # attention modules only hold the parameters (their own forward is the stand-alone tensor-op version)
-            s_, t_, c_ = self.attn_s.conv_sa, self.attn_t.conv_ta, self.attn_c
-            return ops.STCAttentionFunction.apply(y, s_.weight, s_.bias, t_.weight, t_.bias, c_.fc1c.weight,
-                                                  c_.fc1c.bias, c_.fc2c.weight, c_.fc2c.bias)
+            return ops.STCAttentionFunction.apply(y, *attn)
         y = y if self.attn_s is None else self.attn_s(y)
         y = y if self.attn_t is None else self.attn_t(y)
         y = y if self.attn_c is None else self.attn_c(y)
@@ -263,51 +259,20 @@ class TCNGCNUnit(nn.Module):
         self.__dict__.pop('_infer_cache', None)
         return super().train(mode)
 
-    def infer_params(self):
-        """The unit's raw parameters in the form ``ops.aagcn_unit_infer`` folds them from."""
-        g, t = self.gcn1, self.tcn1
-        adaptive = isinstance(g.agcn, AdaptiveGCN)
-        attn = None
-        if g.attn_s is not None and g.attn_t is not None and g.attn_c is not None:
-            s_, t_, c_ = g.attn_s.conv_sa, g.attn_t.conv_ta, g.attn_c
-            attn = (s_.weight, s_.bias, t_.weight, t_.bias, c_.fc1c.weight, c_.fc1c.bias, c_.fc2c.weight,
-                    c_.fc2c.bias)
-        elif not (g.attn_s is None and g.attn_t is None and g.attn_c is None):
-            return None                                   # a partial set of gates: the module path
-        down = None
-        if isinstance(g.down, nn.Sequential):
-            down = (g.down[0].weight, g.down[0].bias) + _bn_args(g.down[1])
-        res = None
-        if self.res_mode == 2:
-            res = (self.residual.conv.weight, self.residual.conv.bias) + _bn_args(self.residual.bn)
-        return dict(
-            conv_d=[(c.weight, c.bias) for c in g.conv_d],
-            ab=[(g.agcn.conv_a[i].weight, g.agcn.conv_a[i].bias, g.agcn.conv_b[i].weight, g.agcn.conv_b[i].bias)
-                for i in range(3)] if adaptive else None,
-            A=None if adaptive else g.agcn.A, PA=g.agcn.PA if adaptive else None,
-            alpha=g.agcn.alpha if adaptive else None, gbn=_bn_args(g.bn), down=down, attn=attn,
-            tw=t.conv.weight, tb=t.conv.bias, tbn=_bn_args(t.bn), res_mode=self.res_mode, res=res,
-            stride=self.stride, pad=t.pad)
-
     def forward(self, x):
         _require_gpu(x, 'aagcn.TCNGCNUnit')
-        if not self.training and not torch.is_grad_enabled() and ops.infer_fold_enabled():
+        g, t = self.gcn1, self.tcn1
+        attn = g.attn_params()
+        p = unit_params(self, g.params(), attn)
+        if not self.training and not torch.is_grad_enabled() and ops.infer_fold_enabled() and \
+                (attn is not None or (g.attn_s is None and g.attn_t is None and g.attn_c is None)):     # (not a partial set)
             # inference: BatchNorms folded into the contractions, the attention gates applied inside the temporal
             # convolution, residual + ReLU in the epilogues
-            p = self.infer_params()
-            if p is not None:
-                y = ops.aagcn_unit_infer(x, p, cache=self.__dict__.setdefault('_infer_cache', {}))
-                if y is not None:
-                    return y
-        y = self.gcn1(x)
-        t = self.tcn1
-        if self.res_mode == 2:
-            r = self.residual
-            rargs = (r.conv.weight, r.conv.bias) + _bn_args(r.bn)
-        else:
-            rargs = (None,) * 6
-        out = ops.TCNResidualFunction.apply(y, x if self.res_mode else None, t.conv.weight, t.conv.bias,
-                                            *_bn_args(t.bn), self.res_mode, *rargs, self.stride, self.training,
+            y = ops.unit_infer(x, p, cache=self.__dict__.setdefault('_infer_cache', {}))
+            if y is not None:
+                return y
+        y = g(x)
+        out = ops.TCNResidualFunction.apply(y, x if self.res_mode else None, *ops.pack_tcn(p), self.training,
                                             ops.sync_of(t.bn), t.pad)
         _bn_tick(t.bn, self.training)
         if self.res_mode == 2:

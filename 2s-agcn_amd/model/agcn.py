@@ -63,6 +63,27 @@ def _bn_tick(bn, training):
         bn.num_batches_tracked.add_(1)
 
 
+def _conv_bn_args(conv, bn):
+    return (conv.weight, conv.bias) + _bn_args(bn)
+
+
+def gcn_params(g, ab, A, PA, alpha=None):
+    """The unit_gcn part of the parameter description ``ops.pack_gcn`` lays out for the kernels and ``ops.unit_infer``
+    folds (see ops.py): ``g`` holds conv_d / bn / down, ``ab`` conv_a / conv_b (None: no adaptive branch)."""
+    return dict(conv_d=[(c.weight, c.bias) for c in g.conv_d],
+                ab=None if ab is None else [(a.weight, a.bias, b.weight, b.bias) for a, b in zip(ab.conv_a, ab.conv_b)],
+                A=A, PA=PA, alpha=alpha, gbn=_bn_args(g.bn),
+                down=_conv_bn_args(*g.down) if isinstance(g.down, nn.Sequential) else None)
+
+
+def unit_params(unit, p, attn=None):
+    """``p`` (gcn_params of unit.gcn1) completed to the description of the whole TCN_GCN_unit / TCNGCNUnit."""
+    t, r = unit.tcn1, unit.residual
+    p.update(tw=t.conv.weight, tb=t.conv.bias, tbn=_bn_args(t.bn), res_mode=unit.res_mode,
+             res=_conv_bn_args(r.conv, r.bn) if unit.res_mode == 2 else None, stride=unit.stride, pad=t.pad, attn=attn)
+    return p
+
+
 def data_bn_forward(bn, x):
     """Model prologue: (N, C, T, V, M) -> BatchNorm1d over channels (m, v, c) -> (N*M, C, T, V) (reference
     agcn.py:163-165) on the deterministic HIP kernels; modules other than plain / synchronised BatchNorm1d (GhostBatchNorm1d)
@@ -137,23 +158,8 @@ class unit_gcn(nn.Module):
         for i in range(num_subset):
             conv_branch_init(self.conv_d[i], num_subset)
 
-    def packed_args(self):
-        """Parameters in the layout the kernels take: theta/phi weights stacked row-wise
-        [a0|b0|a1|b1|a2|b2], projection weights side by side [Wd0|Wd1|Wd2], conv_d biases summed."""
-        ws, bs = [], []
-        for i in range(3):
-            ws += [self.conv_a[i].weight, self.conv_b[i].weight]
-            bs += [self.conv_a[i].bias, self.conv_b[i].bias]
-        wab = torch.cat(ws, dim=0)
-        bab = torch.cat(bs, dim=0)
-        co, ci = self.out_channels, self.in_channels
-        wd = torch.cat([self.conv_d[i].weight.view(co, ci) for i in range(3)], dim=1)
-        bd = self.conv_d[0].bias + self.conv_d[1].bias + self.conv_d[2].bias
-        if isinstance(self.down, nn.Sequential):
-            dn = (self.down[0].weight, self.down[0].bias) + _bn_args(self.down[1])
-        else:
-            dn = (None,) * 6
-        return (self.A, self.PA, wab, bab, wd, bd) + _bn_args(self.bn) + dn
+    def params(self):
+        return gcn_params(self, self, self.A, self.PA)
 
     def tick(self):
         _bn_tick(self.bn, self.training)
@@ -162,7 +168,7 @@ class unit_gcn(nn.Module):
 
     def forward(self, x):
         _require_gpu(x, 'unit_gcn')
-        y = ops.UnitGCNFunction.apply(x, *self.packed_args(), self.training, None, True, ops.sync_of(self.bn))
+        y = ops.UnitGCNFunction.apply(x, *ops.pack_gcn(self.params()), self.training, None, ops.sync_of(self.bn))
         self.tick()
         return y
 
@@ -192,22 +198,13 @@ class TCN_GCN_unit(nn.Module):
     def forward(self, x):
         _require_gpu(x, 'TCN_GCN_unit')
         t = self.tcn1
-        if self.res_mode == 2:
-            r = self.residual
-            rargs = (r.conv.weight, r.conv.bias) + _bn_args(r.bn)
-        else:
-            rargs = (None,) * 6
+        p = unit_params(self, self.gcn1.params())
         if not self.training and not torch.is_grad_enabled() and ops.infer_fold_enabled():
             # inference: BatchNorms folded into the contractions, residual + ReLU in their epilogues
-            ga = self.gcn1.packed_args()
-            down = None if ga[10] is None else tuple(ga[10:16])
-            y = ops.unit_infer(x, *ga[:6], tuple(ga[6:10]), down, t.conv.weight, t.conv.bias, _bn_args(t.bn),
-                               self.res_mode, rargs if self.res_mode == 2 else None, self.stride,
-                               cache=self.__dict__.setdefault('_infer_cache', {}))
+            y = ops.unit_infer(x, p, cache=self.__dict__.setdefault('_infer_cache', {}))
             if y is not None:
                 return y
-        y = ops.TCNGCNUnitFunction.apply(x, *self.gcn1.packed_args(), t.conv.weight, t.conv.bias, *_bn_args(t.bn),
-                                         self.res_mode, *rargs, self.stride, self.training, ops.sync_of(t.bn))
+        y = ops.TCNGCNUnitFunction.apply(x, *ops.pack_gcn(p), *ops.pack_tcn(p), self.training, ops.sync_of(t.bn))
         self.gcn1.tick()
         _bn_tick(t.bn, self.training)
         if self.res_mode == 2:

@@ -167,7 +167,7 @@ def conv_bwd_data(dy, w, x_shape, stride=1, out=None, accumulate=False, add1=Non
 
 def conv_bwd_weight(dy, x, w_shape, stride=1, dy_amax=None, x_amax=None, pad=None):
     """dy_amax / x_amax: device scalars max |dy| / max |x| left behind by their producers; with both, the tap-free
-    gradients run on f16x3 (agcn_conv_bwd_weight_ex)."""
+    gradients run on f16x3 (agcn_tconv_bwd_weight)."""
     N, Cin, T, V = x.shape
     Cout, _, taps, _ = w_shape
     pad = (taps - 1) // 2 if pad is None else pad
@@ -201,7 +201,6 @@ def adjacency_recompute():
     """Backward policy of the adaptive branch: recompute theta/phi on chip from x (AGCN_ADJ_RECOMPUTE=1: nothing of
     size 6*Ci*T*V is kept per layer) or re-read the copy the fused forward leaves behind as a by-product (default:
     measured faster on MI355X)."""
-    import os
     return os.environ.get('AGCN_ADJ_RECOMPUTE', '0') == '1'
 
 
@@ -442,42 +441,31 @@ class DataBNFunction(torch.autograd.Function):
         N, C, T, V, M = x.shape
         CH = C * V * M
         L = _L()
-        if not ctx.training:
-            # frozen statistics: dx = gamma*invstd_run*dy is agcn_data_bn_bwd_apply with the two sums at zero (exactly:
-            # its correction terms are products with 0), dgamma / dbeta are the sums of the reduce stage at the running
-            # mean / invstd
-            dx = dgamma = dbeta = None
-            if ctx.needs_input_grad[0]:
-                dx = torch.empty_like(x)
-                zero = torch.zeros(2 * CH, dtype=torch.float32, device=x.device)
-                _lib.check(L.agcn_data_bn_bwd_apply(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(w), _lib.ptr(st.mean),
-                                                    _lib.ptr(st.invstd), _lib.ptr(zero), float(ctx.gcount), _lib.ptr(dx),
-                                                    N, C, T, V, M, _lib.stream()), "agcn_data_bn_bwd_apply")
-            if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-                part = _empty((N, 2, CH), x)
-                _lib.check(L.agcn_data_bn_bwd_reduce(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(st.mean), _lib.ptr(st.invstd),
-                                                     _lib.ptr(part), N, C, T, V, M, _lib.stream()),
-                           "agcn_data_bn_bwd_reduce")
-                sums = _colsum(part, N, 2 * CH)
-                dbeta, dgamma = sums[:CH], sums[CH:]
-            return dx, dgamma, dbeta, None, None, None, None
-        part = _empty((N, 2, CH), x)
-        _lib.check(L.agcn_data_bn_bwd_reduce(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(st.mean), _lib.ptr(st.invstd),
-                                             _lib.ptr(part), N, C, T, V, M, _lib.stream()), "agcn_data_bn_bwd_reduce")
-        sums = _colsum(part, N, 2 * CH)
+        # the reduce stage feeds the statistics' correction terms of dx (train) and dgamma / dbeta; with frozen statistics
+        # (eval) dx = gamma*invstd_run*dy is the apply stage with the two sums at zero (exactly: its correction terms are
+        # products with 0) and the sums, taken at the running mean / invstd, are needed for dgamma / dbeta only
+        ng = ctx.needs_input_grad
+        sums = None
+        if ctx.training or ng[1] or ng[2]:
+            part = _empty((N, 2, CH), x)
+            _lib.check(L.agcn_data_bn_bwd_reduce(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(st.mean), _lib.ptr(st.invstd),
+                                                 _lib.ptr(part), N, C, T, V, M, _lib.stream()), "agcn_data_bn_bwd_reduce")
+            sums = _colsum(part, N, 2 * CH)
         scale = 1.0
-        if sync is not None:
+        if ctx.training and sync is not None:
             sums = _allreduce_sum(sums, sync)
             scale = 1.0 / sync.world       # global sums, restored by the gradient average of the data-parallel step
-        dx = None
-        if ctx.needs_input_grad[0]:
+        dx = dgamma = dbeta = None
+        if ng[0]:
             dx = torch.empty_like(x)
+            corr = sums if ctx.training else torch.zeros(2 * CH, dtype=torch.float32, device=x.device)
             _lib.check(L.agcn_data_bn_bwd_apply(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(w), _lib.ptr(st.mean),
-                                                _lib.ptr(st.invstd), _lib.ptr(sums), float(ctx.gcount), _lib.ptr(dx), N, C,
+                                                _lib.ptr(st.invstd), _lib.ptr(corr), float(ctx.gcount), _lib.ptr(dx), N, C,
                                                 T, V, M, _lib.stream()), "agcn_data_bn_bwd_apply")
-        dbeta, dgamma = sums[:CH], sums[CH:]
-        if scale != 1.0:
-            dbeta, dgamma = dbeta * scale, dgamma * scale
+        if sums is not None:
+            dbeta, dgamma = sums[:CH], sums[CH:]
+            if scale != 1.0:
+                dbeta, dgamma = dbeta * scale, dgamma * scale
         return dx, dgamma, dbeta, None, None, None, None
 
 
@@ -751,6 +739,23 @@ def bn_bwd_eval(dout, mask, y1, st1, y2=None, st2=None, want_sums=True, amax_out
     return dy1, dg1, db1, dc1, dy2, dg2, db2, dc2
 
 
+def _bn_bwd_two_stage(grad, ins, outs, part, coef, amax_out, N, C, TV, sync, gcount):
+    """The train-mode BatchNorm backward as reduce + apply instead of the fused ``agcn_bn_bwd``: where the apply stage
+    also leaves max |dy1| behind (``amax_out``, for the split-fp16 kernels that read dy1 next) and / or the per-channel
+    sums are all-reduced in between (``sync``).  grad = (dout, mask, mask_bits), ins / outs: bn_bwd's pointer tuples."""
+    dout, mptr, mbits = grad
+    _lib.check(_L().agcn_bn_bwd_reduce(dout, mptr, mbits, ins[0], ins[4], _lib.ptr(part), N, C, TV, _lib.stream()),
+               "agcn_bn_bwd_reduce")
+    sums, nslots, total, scale = part, N, float(N) * float(TV), 1.0
+    if sync is not None:
+        # one collective for both branches; dgamma/dbeta come out as GLOBAL sums, scaled by 1/world so that the
+        # gradient average of the data-parallel step restores them (every rank holds the same value)
+        sums, nslots, scale = _allreduce_sum(_colsum(part, N, 3 * C), sync), 1, 1.0 / sync.world
+        total = float(gcount) if gcount is not None else total * sync.world
+    _lib.check(_L().agcn_bn_bwd_apply_ex(_lib.ptr(sums), nslots, total, scale, dout, mptr, mbits, *ins, _lib.ptr(coef),
+                                         *outs, _lib.ptr(amax_out), N, C, TV, _lib.stream()), "agcn_bn_bwd_apply")
+
+
 def bn_bwd(dout, mask, y1, gamma1, st1, y2=None, gamma2=None, st2=None, sync=None, gcount=None, amax_out=None,
            want_sums=True, bias_out=None):
     """Backward through out = relu(bn1(y1) [+ bn2(y2)] [+ identity]).  ``mask``: the fp32 output tensor (positive
@@ -780,36 +785,15 @@ def bn_bwd(dout, mask, y1, gamma1, st1, y2=None, gamma2=None, st2=None, sync=Non
         dy2 = torch.empty_like(y2)
         dg2, db2 = _empty((C,), y1), _empty((C,), y1)
     mbits = int(mask is not None and mask.dtype == torch.int32)
-    mptr = _lib.ptr_bits(mask) if mbits else _lib.ptr(mask)
-    if sync is None and amax_out is not None:
-        # (amax_out: 1-element tensor that receives max |dy1| for the split-fp16 kernels that read dy1 next)
-        _lib.check(_L().agcn_bn_bwd_reduce(_lib.ptr(dout), mptr, mbits, _lib.ptr(y1), _lib.ptr(y2),
-                                           _lib.ptr(part), N, C, T * V, _lib.stream()), "agcn_bn_bwd_reduce")
-        _lib.check(_L().agcn_bn_bwd_apply_ex(
-            _lib.ptr(part), N, float(N) * float(T * V), 1.0, _lib.ptr(dout), mptr, mbits, _lib.ptr(y1),
-            _lib.ptr(gamma1), _lib.ptr(st1.mean), _lib.ptr(st1.invstd), _lib.ptr(y2), _lib.ptr(gamma2),
-            _lib.ptr(st2.mean) if st2 else None, _lib.ptr(st2.invstd) if st2 else None, _lib.ptr(coef), _lib.ptr(dy1),
-            _lib.ptr(dg1), _lib.ptr(db1), _lib.ptr(dy2), _lib.ptr(dg2), _lib.ptr(db2), _lib.ptr(amax_out), N, C, T * V,
-            _lib.stream()), "agcn_bn_bwd_apply")
-    elif sync is None:
-        _lib.check(_L().agcn_bn_bwd(
-            _lib.ptr(dout), mptr, mbits, _lib.ptr(y1), _lib.ptr(gamma1), _lib.ptr(st1.mean), _lib.ptr(st1.invstd),
-            _lib.ptr(y2), _lib.ptr(gamma2), _lib.ptr(st2.mean) if st2 else None, _lib.ptr(st2.invstd) if st2 else None,
-            _lib.ptr(part), _lib.ptr(coef), _lib.ptr(dy1), _lib.ptr(dg1), _lib.ptr(db1), _lib.ptr(dy2), _lib.ptr(dg2),
-            _lib.ptr(db2), N, C, T * V, _lib.stream()), "agcn_bn_bwd")
+    grad = (_lib.ptr(dout), _lib.ptr_bits(mask) if mbits else _lib.ptr(mask), mbits)
+    ins = (_lib.ptr(y1), _lib.ptr(gamma1), _lib.ptr(st1.mean), _lib.ptr(st1.invstd), _lib.ptr(y2), _lib.ptr(gamma2),
+           _lib.ptr(st2.mean) if st2 else None, _lib.ptr(st2.invstd) if st2 else None)
+    outs = (_lib.ptr(dy1), _lib.ptr(dg1), _lib.ptr(db1), _lib.ptr(dy2), _lib.ptr(dg2), _lib.ptr(db2))
+    if sync is None and amax_out is None:
+        _lib.check(_L().agcn_bn_bwd(*grad, *ins, _lib.ptr(part), _lib.ptr(coef), *outs, N, C, T * V, _lib.stream()),
+                   "agcn_bn_bwd")
     else:
-        _lib.check(_L().agcn_bn_bwd_reduce(_lib.ptr(dout), mptr, mbits, _lib.ptr(y1), _lib.ptr(y2),
-                                           _lib.ptr(part), N, C, T * V, _lib.stream()), "agcn_bn_bwd_reduce")
-        # one collective for both branches; dgamma/dbeta come out as GLOBAL sums, scaled by 1/world so that the
-        # gradient average of the data-parallel step restores them (every rank holds the same value)
-        sums = _allreduce_sum(_colsum(part, N, 3 * C), sync)
-        total = float(gcount) if gcount is not None else float(N * T * V * sync.world)
-        _lib.check(_L().agcn_bn_bwd_apply_ex(
-            _lib.ptr(sums), 1, total, 1.0 / sync.world, _lib.ptr(dout), mptr, mbits, _lib.ptr(y1),
-            _lib.ptr(gamma1), _lib.ptr(st1.mean), _lib.ptr(st1.invstd), _lib.ptr(y2), _lib.ptr(gamma2),
-            _lib.ptr(st2.mean) if st2 else None, _lib.ptr(st2.invstd) if st2 else None, _lib.ptr(coef), _lib.ptr(dy1),
-            _lib.ptr(dg1), _lib.ptr(db1), _lib.ptr(dy2), _lib.ptr(dg2), _lib.ptr(db2), _lib.ptr(amax_out), N, C, T * V,
-            _lib.stream()), "agcn_bn_bwd_apply")
+        _bn_bwd_two_stage(grad, ins, outs, part, coef, amax_out, N, C, T * V, sync, gcount)
     if S > 1:                          # the weight / bias are shared by the S virtual sub-batches
         dg1, db1 = dg1.view(S, -1).sum(0), db1.view(S, -1).sum(0)
         if dg2 is not None:
@@ -818,11 +802,35 @@ def bn_bwd(dout, mask, y1, gamma1, st1, y2=None, gamma2=None, st2=None, sync=Non
 
 
 # ------------------------------------------------------------------------------------------------
-# unit_gcn / unit_tcn forward and backward as plain functions over a context object
+# unit_gcn / unit_tcn forward and backward as plain functions; each forward returns its output and the state object
+# its backward takes
 # ------------------------------------------------------------------------------------------------
 
-class _Ctx:
-    pass
+class _GCNState:
+    """What gcn_forward leaves for gcn_backward.  ``x_amax`` / ``g_amax``: device scalars max |x| / max |out| (None
+    where nobody took them); gamma1 / gamma2: the weights of the main and the `down` BatchNorm."""
+    __slots__ = ('x', 'tp', 'P', 'adj', 'ypre', 'dpre', 'bits', 'bn1', 'bn2', 'sync', 'count', 'x_amax', 'g_amax',
+                 'wab', 'bab', 'wd', 'gamma1', 'wdown', 'gamma2', 'alpha')
+
+    def __init__(self, x, tp, P, adj, ypre, dpre, bits, bn1, bn2, sync, count, x_amax, g_amax, wab, bab, wd, gamma1,
+                 wdown, gamma2, alpha):
+        self.x, self.tp, self.P, self.adj, self.ypre, self.dpre, self.bits = x, tp, P, adj, ypre, dpre, bits
+        self.bn1, self.bn2, self.sync, self.count, self.x_amax, self.g_amax = bn1, bn2, sync, count, x_amax, g_amax
+        self.wab, self.bab, self.wd, self.gamma1, self.wdown, self.gamma2 = wab, bab, wd, gamma1, wdown, gamma2
+        self.alpha = alpha
+
+
+class _TCNState:
+    """What tcn_forward leaves for tcn_backward.  ``g_amax``: device scalar max |g| or None; ``resx`` / ``rpre`` /
+    ``wres`` / ``gamma2``: input, pre-BatchNorm output and parameters of the convolutional residual (else None)."""
+    __slots__ = ('g', 'zpre', 'rpre', 'out', 'bits', 'bn1', 'bn2', 'sync', 'count', 'g_amax', 'resx', 'w', 'gamma1',
+                 'wres', 'gamma2', 'stride', 'relu', 'pad')
+
+    def __init__(self, g, zpre, rpre, out, bits, bn1, bn2, sync, count, g_amax, resx, w, gamma1, wres, gamma2, stride,
+                 relu, pad):
+        self.g, self.zpre, self.rpre, self.out, self.bits, self.bn1, self.bn2 = g, zpre, rpre, out, bits, bn1, bn2
+        self.sync, self.count, self.g_amax, self.resx, self.w, self.gamma1 = sync, count, g_amax, resx, w, gamma1
+        self.wres, self.gamma2, self.stride, self.relu, self.pad = wres, gamma2, stride, relu, pad
 
 
 def _bn_coeffs(training, stats, count, bns, sync=None, nsamples=None):
@@ -859,110 +867,116 @@ def _ghost_regroup(stats_part, S, nsamples):
     return stats_part.view(nsamples // S, S, nt, two, C).permute(0, 2, 3, 1, 4).reshape(nsamples // S * nt, two, S * C)
 
 
-def gcn_forward(c, x, A, PA, wab, bab, wd, bd, bn, down, training, alpha=None, adaptive=True, sync=None,
-                need_bwd=True):
+def _adjacency(x, wab, bab, A, PA, alpha, *, keep_tp, x_amax, want_amax):
+    """The mixing matrices adj (N,3,V,V) of one unit_gcn by the one route that applies: theta/phi formed and reduced on
+    chip (adjacency_fused_fwd), the theta/phi convolution followed by adjacency_fwd, or -- wab None (NonAdaptiveGCN) --
+    the fixed graph A expanded.  keep_tp: a backward will follow; the fused route then either keeps nothing (the
+    backward recomputes theta/phi, adjacency_bwd with tp = None) or lets the kernel drop a copy for the backward to
+    re-read (adjacency_recompute).  x_amax: max |x| where the producer of x left it behind; want_amax: the caller can
+    use it, so the fused route, which reads all of x anyway, takes it along the way where nobody has.
+    Returns (P, adj, tp, x_amax)."""
+    N, C, T, V = x.shape
+    if wab is None:
+        return None, A.unsqueeze(0).expand(N, 3, V, V).contiguous(), None, x_amax
+    if not adjacency_fused_supported(C, wab.shape[0] // 6, T, V):
+        tp, _ = conv_fwd(x, wab, bab)
+        P, adj = adjacency_fwd(tp, A, PA, alpha)
+        return P, adj, tp, x_amax
+    amax_here = _empty((1,), x) if want_amax and x_amax is None and fused_amax_enabled() else None
+    if keep_tp and not adjacency_recompute():
+        P, adj, tp = adjacency_fused_fwd(x, wab, bab, A, PA, alpha, keep_tp=True, x_amax_out=amax_here, x_amax=x_amax)
+    else:
+        tp = None
+        P, adj = adjacency_fused_fwd(x, wab, bab, A, PA, alpha, x_amax_out=amax_here, x_amax=x_amax)
+    return P, adj, tp, x_amax if amax_here is None else amax_here
+
+
+def gcn_forward(x, A, PA, wab, bab, wd, bd, bn, down, training, alpha=None, sync=None, need_bwd=True):
     """unit_gcn.forward (reference agcn.py:92-109) and AAGCN's GCNUnit core (aagcn.py:164-177, 264-266).
     wab: (6Ci, C, 1, 1) rows [a0|b0|a1|b1|a2|b2]; wd: (Cout, 3C); bd: summed conv_d biases;
     bn = (weight, bias, running_mean, running_var); down = None | (w, b, bn_w, bn_b, bn_rm, bn_rv).
-    AGCN: adj = P + A + PA.  AAGCN: A = None, adj = PA + alpha*P.  adaptive=False (NonAdaptiveGCN): adj = A."""
+    AGCN: adj = P + A + PA.  AAGCN: A = None, adj = PA + alpha*P.  wab = None (NonAdaptiveGCN): adj = A.
+    Returns (out, _GCNState)."""
     N, C, T, V = x.shape
     count = N * T * V
     first = down is not None and first_layer_enabled() and bool(_L().agcn_gcn_first_supported(C, wd.shape[0], V))
     # max |x| left behind by the pass that produced x (None: nobody did); the 3-channel first layer does not use it
     x_amax = None if first else _take_out_amax(x)
-    if adaptive and adjacency_fused_supported(C, wab.shape[0] // 6, T, V):
-        # theta/phi are formed and reduced on chip.  A training forward either keeps nothing (the backward recomputes
-        # them, adjacency_bwd with tp = None) or lets the kernel drop a copy for the backward to re-read.
-        keep = need_bwd and not adjacency_recompute()     # (train or eval: a backward will follow)
-        amax_here = None
-        if x_amax is None and not first and fused_amax_enabled():
-            amax_here = _empty((1,), x)    # this pass reads all of x: it takes the maximum along the way
-        if keep:
-            P, adj, tp = adjacency_fused_fwd(x, wab, bab, A, PA, alpha, keep_tp=True, x_amax_out=amax_here, x_amax=x_amax)
-        else:
-            tp = None
-            P, adj = adjacency_fused_fwd(x, wab, bab, A, PA, alpha, x_amax_out=amax_here, x_amax=x_amax)
-        if amax_here is not None:
-            x_amax = amax_here
-    elif adaptive:
-        tp, _ = conv_fwd(x, wab, bab)
-        P, adj = adjacency_fwd(tp, A, PA, alpha)
-    else:
-        tp = P = None
-        adj = A.unsqueeze(0).expand(N, 3, V, V).contiguous()
+    P, adj, tp, x_amax = _adjacency(x, wab, bab, A, PA, alpha, keep_tp=need_bwd, x_amax=x_amax, want_amax=not first)
     if first:
         # 3-channel first layer: aggregate+project and the `down` convolution in one pass over x (csrc/gcn_first.hip)
         ypre, st, dpre, st2 = gcn_first_fwd(x, adj, wd, bd, down[0], down[1], want_stats=training)
     else:
-        c.g_x_amax = x_amax                # kept for the weight gradients of the backward
-        ypre, st = aggregate_project_fwd(x, adj, wd, bd, want_stats=training, x_amax=c.g_x_amax)
-    bn2 = None
-    if not first:
-        dpre = None
+        ypre, st = aggregate_project_fwd(x, adj, wd, bd, want_stats=training, x_amax=x_amax)
+        dpre, st2 = conv_fwd(x, down[0], down[1], want_stats=training) if down is not None else (None, None)
     if down is not None:
-        if not first:
-            dpre, st2 = conv_fwd(x, down[0], down[1], want_stats=training)
         (bn1, bn2), gcount = _bn_coeffs(training, [st, st2], count, [bn, down[2:]], sync, N)
-        c.g_amax = _empty((1,), x) if fused_amax_enabled() else None   # max |g| for the temporal convolution that reads g
-        out, bits = bn_act_fwd(ypre, bn1, dpre, bn2, relu=True, want_bits=True, amax_out=c.g_amax)
+        r = dpre
     else:
         (bn1,), gcount = _bn_coeffs(training, [st], count, [bn], sync, N)
-        c.g_amax = _empty((1,), x) if fused_amax_enabled() else None
-        out, bits = bn_act_fwd(ypre, bn1, x, None, relu=True, want_bits=True, amax_out=c.g_amax)
-    c.g_sync, c.g_count = sync, gcount
-    c.g_bits = bits          # sign bit mask of `out` for the BatchNorm backward (32x less traffic than `out`)
-    c.g_x, c.g_tp, c.g_P, c.g_adj, c.g_ypre, c.g_dpre, c.g_out = x, tp, P, adj, ypre, dpre, out
-    c.g_bn1, c.g_bn2 = bn1, bn2
-    c.g_params = (wab, wd, bn[0], down[0] if down is not None else None, down[2] if down is not None else None)
-    c.g_bab = bab
-    c.g_alpha, c.g_adaptive = alpha, adaptive
-    return out
+        bn2, r = None, x
+    g_amax = _empty((1,), x) if fused_amax_enabled() else None   # max |out| for the temporal convolution that reads it
+    # (bits: sign bit mask of `out` for the BatchNorm backward, 32x less traffic than `out`)
+    out, bits = bn_act_fwd(ypre, bn1, r, bn2, relu=True, want_bits=True, amax_out=g_amax)
+    wdown, gamma2 = (down[0], down[2]) if down is not None else (None, None)
+    return out, _GCNState(x, tp, P, adj, ypre, dpre, bits, bn1, bn2, sync, gcount, x_amax, g_amax, wab, bab, wd, bn[0],
+                          wdown, gamma2, alpha)
 
 
-def gcn_backward(c, dout, extra_add=None, extra_mask=None):
+def _bias_grad(slot, k, n, like, needed=True):
+    """Gradient of a convolution bias in front of a BatchNorm: ``slot[k]`` in eval mode (bn_bwd's ``bias_out``), exact
+    zeros in train mode where the batch mean cancels the bias; None where the eval backward skipped the sums."""
+    if slot and slot[k] is not None:
+        return slot[k]
+    if slot:                   # eval mode with want_sums=False: nobody asked for it
+        return None
+    return torch.zeros(n, dtype=torch.float32, device=like.device) if needed else None
+
+
+def gcn_backward(s, dout, extra_add=None, extra_mask=None, want_sums=True):
     """Backward of gcn_forward.  ``extra_add`` (masked by ``extra_mask``) is an additional dx contribution folded
-    into the epilogue of the first dx kernel (the TCN_GCN_unit identity residual)."""
-    x, tp, P, adj, ypre, dpre, out = c.g_x, c.g_tp, c.g_P, c.g_adj, c.g_ypre, c.g_dpre, c.g_out
-    wab, wd, gamma1, wdown, gamma2 = c.g_params
+    into the epilogue of the first dx kernel (the TCN_GCN_unit identity residual).  want_sums=False (eval mode only): no
+    BatchNorm parameter or conv bias in front of one wants a gradient, the partial sums are skipped.
+    Returns dx, dPA, dwab, dbab, dwd, dbd, dgamma, dbeta, dwdown, dbdown, dgamma_down, dbeta_down, dalpha."""
+    x, tp, adj, ypre, dpre, wab, wd, wdown = s.x, s.tp, s.adj, s.ypre, s.dpre, s.wab, s.wd, s.wdown
     Cout = wd.shape[0]
     dy_amax = _empty((1,), dout) if fused_amax_enabled() else None   # max |dypre| for the f16x3 backward-data chain
-    c.g_dbias = []            # eval mode: gradients of the conv_d / down biases (train mode: exactly zero, left empty)
-    dypre, dg1, db1, ddpre, dg2, db2 = bn_bwd(dout, c.g_bits, ypre, gamma1, c.g_bn1, dpre, gamma2, c.g_bn2,
-                                              sync=c.g_sync, gcount=c.g_count, amax_out=dy_amax,
-                                              want_sums=getattr(c, 'g_want_sums', True), bias_out=c.g_dbias)
-    x_amax = getattr(c, 'g_x_amax', None)
+    dbias = []                # eval mode: gradients of the conv_d / down biases (train mode: exactly zero, left empty)
+    dypre, dg1, db1, ddpre, dg2, db2 = bn_bwd(dout, s.bits, ypre, s.gamma1, s.bn1, dpre, s.gamma2, s.bn2, sync=s.sync,
+                                              gcount=s.count, amax_out=dy_amax, want_sums=want_sums, bias_out=dbias)
+    x_amax = s.x_amax
     dwd = _side_run(lambda: project_bwd_weight(dypre, x, adj, Cout, dy_amax, x_amax), (dypre, x, adj, dy_amax, x_amax))
     dPA = dwab = dbab = dalpha = dtp = dtp_amax = None
-    if c.g_adaptive:      # adjacency branch first: its dtp rides along in the dx kernel where that is supported
-        dPA, dtp, dbab, dalpha, _, dtp_amax = adjacency_bwd(dypre, wd, x, tp, P, c.g_alpha, wab, c.g_bab,
+    if wab is not None:   # adjacency branch first: its dtp rides along in the dx kernel where that is supported
+        dPA, dtp, dbab, dalpha, _, dtp_amax = adjacency_bwd(dypre, wd, x, tp, s.P, s.alpha, wab, s.bab,
                                                             dy_amax=dy_amax, x_amax=x_amax)
         dwab = _side_run(lambda: conv_bwd_weight(dtp, x, wab.shape, 1, dtp_amax, x_amax), (dtp, x, dtp_amax, x_amax))
     fuse = dtp is not None and fused_bwd_data_supported(x.shape[1], Cout, x.shape[3])
-    ftp = dict(dtp=dtp, wab=wab) if fuse else {}
-    ftp['dy_amax'] = dy_amax
-    if fuse:
-        ftp['dtp_amax'] = dtp_amax
+    ftp = dict(dtp=dtp, wab=wab, dtp_amax=dtp_amax) if fuse else {}
     if dpre is None:      # identity `down`: dx += dout * (out > 0)
-        dx = aggregate_project_bwd_data(dypre, adj, wd, x.shape, add1=dout, mask1=c.g_bits, add2=extra_add,
-                                        mask2=extra_mask, **ftp)
+        dx = aggregate_project_bwd_data(dypre, adj, wd, x.shape, add1=dout, mask1=s.bits, add2=extra_add,
+                                        mask2=extra_mask, dy_amax=dy_amax, **ftp)
     else:
-        dx = aggregate_project_bwd_data(dypre, adj, wd, x.shape, add1=extra_add, mask1=extra_mask, **ftp)
+        dx = aggregate_project_bwd_data(dypre, adj, wd, x.shape, add1=extra_add, mask1=extra_mask, dy_amax=dy_amax,
+                                        **ftp)
     if dtp is not None and not fuse:
         conv_bwd_data(dtp, wab, x.shape, out=dx, accumulate=True)
-    c.g_dalpha = dalpha
     dwdown = None
     if dpre is not None:
         dwdown = _side_run(lambda: conv_bwd_weight(ddpre, x, wdown.shape), (ddpre, x))
         conv_bwd_data(ddpre, wdown, x.shape, out=dx, accumulate=True)
     _side_join()
-    return dx, dPA, dwab, dbab, dwd, dg1, db1, dwdown, dg2, db2
+    dbd = _bias_grad(dbias, 0, Cout, dout)
+    dbdown = _bias_grad(dbias, 1, Cout, dout, dpre is not None)
+    return dx, dPA, dwab, dbab, dwd, dbd, dg1, db1, dwdown, dbdown, dg2, db2, dalpha
 
 
-def tcn_forward(c, g, w, b, bn, stride, res_x, res, relu, training, sync=None, pad=None):
+def tcn_forward(g, w, b, bn, stride, res_x, res, relu, training, sync=None, pad=None, g_amax=None):
     """unit_tcn.forward (reference agcn.py:48-50) optionally fused with the TCN_GCN_unit tail
     relu(tcn(g) + residual(x)) (agcn.py:127-129).  res = None (no residual) | 'identity' |
     (w, b, bn_w, bn_b, bn_rm, bn_rv) for the unit_tcn(kernel_size=1, stride) residual.  pad: temporal padding of the
-    convolution (None = (k-1)//2; TCNUnit(pad=False): 0)."""
+    convolution (None = (k-1)//2; TCNUnit(pad=False): 0).  g_amax: device scalar max |g| where the producer of g left
+    it behind (the fused unit: the GCN state's; a stand-alone node: _take_out_amax(g)).  Returns (out, _TCNState)."""
     N, C, T, V = g.shape
     if res is not None:
         To = conv_out_frames(T, w.shape[2], stride, pad)
@@ -971,56 +985,46 @@ def tcn_forward(c, g, w, b, bn, stride, res_x, res, relu, training, sync=None, p
             raise RuntimeError(f"agcn_amd: the residual has {Tr} frames but the temporal convolution ({w.shape[2]} taps, "
                                f"stride {stride}, padding {(w.shape[2] - 1) // 2 if pad is None else pad}) gives {To} "
                                f"for {T} input frames; they must agree (the reference fails here too)")
-    g_amax = getattr(c, 'g_amax', None) if getattr(c, 'g_out', None) is g else None   # only for the tensor it describes
-    if g_amax is None and getattr(c, 'g_out', None) is None:
-        g_amax = _take_out_amax(g)       # stand-alone unit_tcn (AAGCN): the producer of g (attention gates / unit_gcn) noted it
     zpre, st = conv_fwd(g, w, b, stride, want_stats=training, x_amax=g_amax, pad=pad)
     To = zpre.shape[2]
     count = N * To * V
-    rpre = bn2 = None
+    rpre = bn2 = wres = gamma2 = None
     if res is None or isinstance(res, str):
         (bn1,), gcount = _bn_coeffs(training, [st], count, [bn], sync, N)
-        o_amax = _empty((1,), g) if fused_amax_enabled() else None   # max |out| for the next unit's f16x3 chain
-        out, bits = bn_act_fwd(zpre, bn1, None if res is None else res_x, None, relu=relu, want_bits=True,
-                               amax_out=o_amax)
+        r = None if res is None else res_x
     else:
-        rpre, st2 = conv_fwd(res_x, res[0], res[1], stride, want_stats=training)
+        r, st2 = conv_fwd(res_x, res[0], res[1], stride, want_stats=training)
         (bn1, bn2), gcount = _bn_coeffs(training, [st, st2], count, [bn, res[2:]], sync, N)
-        o_amax = _empty((1,), g) if fused_amax_enabled() else None
-        out, bits = bn_act_fwd(zpre, bn1, rpre, bn2, relu=relu, want_bits=True, amax_out=o_amax)
+        rpre, wres, gamma2 = r, res[0], res[2]
+    o_amax = _empty((1,), g) if fused_amax_enabled() else None   # max |out| for the next unit's f16x3 chain
+    out, bits = bn_act_fwd(zpre, bn1, r, bn2, relu=relu, want_bits=True, amax_out=o_amax)
     _note_out_amax(out, o_amax)
-    c.t_sync, c.t_count = sync, gcount
-    c.t_bits = bits
-    c.t_g, c.t_zpre, c.t_rpre, c.t_out, c.t_bn1, c.t_bn2 = g, zpre, rpre, out, bn1, bn2
-    c.t_g_amax = g_amax
-    c.t_resx, c.t_res_identity = res_x, isinstance(res, str)
-    c.t_params = (w, bn[0], res[0] if isinstance(res, tuple) else None, res[2] if isinstance(res, tuple) else None)
-    c.t_stride, c.t_relu, c.t_pad = stride, relu, pad
-    return out
+    return out, _TCNState(g, zpre, rpre, out, bits, bn1, bn2, sync, gcount, g_amax, res_x, w, bn[0], wres, gamma2,
+                          stride, relu, pad)
 
 
-def tcn_backward(c, dout, join=True):
-    """Returns dg, dw, dgamma, dbeta, (drpre, dw_res, dgamma_res, dbeta_res)."""
-    w, gamma1, wres, gamma2 = c.t_params
-    mask = c.t_bits if c.t_relu else None
+def tcn_backward(s, dout, join=True, want_sums=True):
+    """Backward of tcn_forward; want_sums as in gcn_backward.  Returns dg, dw, dbias, dgamma, dbeta and, of the
+    convolutional residual (else None), drpre, dw_res, dbias_res, dgamma_res, dbeta_res."""
+    w, wres, g, stride, pad, g_amax = s.w, s.wres, s.g, s.stride, s.pad, s.g_amax
+    mask = s.bits if s.relu else None
     dz_amax = _empty((1,), dout) if fused_amax_enabled() else None   # max |dzpre| for the backward-data convolution
-    c.t_dbias = []            # eval mode: gradients of the temporal / residual conv biases
-    dzpre, dg1, db1, drpre, dg2, db2 = bn_bwd(dout, mask, c.t_zpre, gamma1, c.t_bn1, c.t_rpre, gamma2, c.t_bn2,
-                                              sync=c.t_sync, gcount=c.t_count, amax_out=dz_amax,
-                                              want_sums=getattr(c, 't_want_sums', True), bias_out=c.t_dbias)
-    t_g, t_stride, t_pad = c.t_g, c.t_stride, getattr(c, 't_pad', None)
-    t_g_amax = getattr(c, 't_g_amax', None)
+    dbias = []                # eval mode: gradients of the temporal / residual conv biases
+    dzpre, dg1, db1, drpre, dg2, db2 = bn_bwd(dout, mask, s.zpre, s.gamma1, s.bn1, s.rpre, s.gamma2, s.bn2, sync=s.sync,
+                                              gcount=s.count, amax_out=dz_amax, want_sums=want_sums, bias_out=dbias)
     # (the device scalars are inputs of the side-stream kernels too: dz_amax dies with this frame, possibly before the join)
-    dw = _side_run(lambda: conv_bwd_weight(dzpre, t_g, w.shape, t_stride, dz_amax, t_g_amax, pad=t_pad),
-                   (dzpre, t_g, dz_amax, t_g_amax))
-    dg = conv_bwd_data(dzpre, w, c.t_g.shape, c.t_stride, dy_amax=dz_amax, pad=t_pad)
+    dw = _side_run(lambda: conv_bwd_weight(dzpre, g, w.shape, stride, dz_amax, g_amax, pad=pad),
+                   (dzpre, g, dz_amax, g_amax))
+    dg = conv_bwd_data(dzpre, w, g.shape, stride, dy_amax=dz_amax, pad=pad)
     dwres = None
     if drpre is not None:
-        t_resx = c.t_resx
-        dwres = _side_run(lambda: conv_bwd_weight(drpre, t_resx, wres.shape, t_stride), (drpre, t_resx))
+        resx = s.resx
+        dwres = _side_run(lambda: conv_bwd_weight(drpre, resx, wres.shape, stride), (drpre, resx))
     if join:
         _side_join()
-    return dg, dw, dg1, db1, drpre, dwres, dg2, db2
+    Cout = w.shape[0]
+    return (dg, dw, _bias_grad(dbias, 0, Cout, dout), dg1, db1,
+            drpre, dwres, _bias_grad(dbias, 1, Cout, dout, drpre is not None), dg2, db2)
 
 
 # ---- BN-folded inference (eval mode under no_grad): adjacency + two kernels per TCN_GCN_unit ----------------------
@@ -1042,8 +1046,9 @@ def infer_fold_enabled():
     return os.environ.get('AGCN_INFER_FOLD', '1') != '0'
 
 
-# diagnostic counters of the eval-mode routes (never read by a compute path): units that ran folded end to end, folded
-# temporal convolutions, and launches of the stand-alone gate pass agcn_stc_apply that the folded AAGCN unit replaces
+# diagnostic counters of the eval-mode routes (never read by a compute path).  'aagcn_unit_fused': units of EITHER model
+# (AGCN TCN_GCN_unit, AAGCN TCNGCNUnit) that ran folded end to end through unit_infer; 'tconv_infer': folded temporal
+# convolutions; 'stc_apply': launches of the stand-alone gate pass agcn_stc_apply that the folded AAGCN unit replaces
 INFER_STATS = {'aagcn_unit_fused': 0, 'tconv_infer': 0, 'stc_apply': 0}
 
 
@@ -1133,19 +1138,72 @@ def tcn_infer(x, w, b, bn, stride, pad, cache=None):
     return tconv_infer(x.contiguous(), f[1], f[2], relu=False, stride=stride, pad=pad)
 
 
-def aagcn_unit_infer(x, p, cache=None):
-    """Eval-mode AAGCN TCNGCNUnit (reference aagcn.py:164-177, 264-271, 194-207, 316-321) with every BatchNorm folded
-    into the contraction in front of it and the three attention gates applied inside the temporal convolution:
-    adjacency, one aggregate+project kernel (unit BN and `down` folded; residual / ReLU in its epilogue), the two
-    reduction passes and the few-KB gate networks of ``STCAttentionFunction.forward`` (no ``agcn_stc_apply``: the gated
-    tensor is never written), [the folded 1x1 stride residual conv], one ``agcn_tconv_infer`` (gates on load, residual
-    add + ReLU in its epilogue).
-    p: the unit's raw parameters -- conv_d [(w, b)]*3, ab [(wa, ba, wb, bb)]*3 | None (NonAdaptiveGCN), A (fixed graph)
-    | None, PA, alpha, gbn / tbn (weight, bias, running_mean, running_var), down / res None | (w, b, *bn), attn None |
-    (sa_w, sa_b, ta_w, ta_b, fc1_w, fc1_b, fc2_w, fc2_b), tw, tb, res_mode, stride, pad.
-    Returns None where the fused kernels do not apply (3-channel first layer, C < 32, whatever agcn_gcn_unit_infer
-    rejects): the caller runs the unfused eval passes.  ``cache`` (a dict owned by the module) keeps the folded and
-    packed weights between calls, keyed on the parameter epoch and every source tensor's (data_ptr, version)."""
+# ---- one description of a unit's parameters -----------------------------------------------------------------------------
+# The models describe a TCN_GCN_unit (AGCN) / TCNGCNUnit (AAGCN) as a dict ``p`` of its raw parameters:
+#   conv_d [(w, b)]*3, ab [(wa, ba, wb, bb)]*3 | None (NonAdaptiveGCN), A fixed graph | None, PA | None, alpha | None,
+#   gbn (weight, bias, running_mean, running_var), down None | (w, b, *bn)                       -- the unit_gcn part
+#   tw, tb, tbn, res_mode (0 none, 1 identity, 2 conv), res None | (w, b, *bn), stride, pad,
+#   attn None | (sa_w, sa_b, ta_w, ta_b, fc1_w, fc1_b, fc2_w, fc2_b)                             -- the rest of the unit
+# AGCN is the case A and PA both present, alpha = attn = None.  pack_gcn / pack_tcn lay it out as the autograd
+# Functions' arguments, _fold_unit as the folded inference weights.
+_NONE6 = (None,) * 6
+
+
+def _pack_wb(p):
+    """Parameters in the layout the kernels take: theta/phi weights and biases stacked row-wise [a0|b0|a1|b1|a2|b2]
+    (None without an adaptive branch), projection weights side by side [Wd0|Wd1|Wd2], conv_d biases summed.  Ordinary
+    differentiable tensor code: the gradients reach the individual conv_a / conv_b / conv_d parameters through it."""
+    wab = bab = None
+    if p['ab'] is not None:
+        wab = torch.cat([t for wa, _, wb, _ in p['ab'] for t in (wa, wb)], 0)
+        bab = torch.cat([t for _, ba, _, bb in p['ab'] for t in (ba, bb)], 0)
+    (w0, b0), (w1, b1), (w2, b2) = p['conv_d']
+    Cout, C = w0.shape[:2]
+    return wab, bab, torch.cat([w0.view(Cout, C), w1.view(Cout, C), w2.view(Cout, C)], dim=1), b0 + b1 + b2
+
+
+def pack_gcn(p):
+    """UnitGCNFunction's / TCNGCNUnitFunction's arguments 'A' .. 'dbn_rv' from the unit_gcn part of ``p``."""
+    return (p['A'], p['PA'], *_pack_wb(p), *p['gbn'], *(p['down'] or _NONE6))
+
+
+def pack_tcn(p):
+    """TCNResidualFunction's / TCNGCNUnitFunction's arguments 'tw' .. 'stride' from ``p``."""
+    return (p['tw'], p['tb'], *p['tbn'], p['res_mode'], *(p['res'] or _NONE6), p['stride'])
+
+
+def _fold_unit(p):
+    """Eval-mode weights of the unit ``p`` with every BatchNorm folded into the contraction in front of it; pure tensor
+    code on whatever device / float dtype the parameters have.  Returns (wdf, bias, w2, twf, tbf, rwf, rbf, wab, bab):
+    g = relu(bias + wdf . [x.adj_0; x.adj_1; x.adj_2] + (w2 . x | x)) is the unit_gcn with its BatchNorm and the conv
+    `down` (w2 None: identity) folded, (twf, tbf) / (rwf, rbf) the folded temporal / residual convolutions (the latter
+    None without a convolutional residual), wab / bab the packed theta/phi parameters."""
+    wab, bab, wd, bd = _pack_wb(p)
+    s1, sh1 = _fold(p['gbn'])
+    wdf = (wd * s1[:, None]).contiguous()
+    bias = bd * s1 + sh1
+    w2 = None
+    if p['down'] is not None:
+        dw, db = p['down'][:2]
+        s2, sh2 = _fold(p['down'][2:])
+        w2 = (dw.reshape(dw.shape[0], dw.shape[1]) * s2[:, None]).contiguous()
+        bias = bias + db * s2 + sh2
+    twf, tbf = _fold_conv(p['tw'], p['tb'], p['tbn'])
+    rwf, rbf = _fold_conv(*p['res'][:2], p['res'][2:]) if p['res'] is not None else (None, None)
+    return wdf, bias.contiguous(), w2, twf, tbf, rwf, rbf, wab, bab
+
+
+def unit_infer(x, p, cache=None):
+    """Eval-mode TCN_GCN_unit (reference agcn.py:92-109, 48-50, 127-129) / AAGCN TCNGCNUnit (aagcn.py:164-177, 264-271,
+    194-207, 316-321) from its description ``p`` (above) with every BatchNorm folded into the contraction in front of
+    it: adjacency, one aggregate+project kernel (unit BN and conv `down` folded; residual add / ReLU in its epilogue),
+    [AAGCN: the two reduction passes and the few-KB gate networks of ``STCAttentionFunction.forward`` -- no
+    ``agcn_stc_apply``: the gated tensor is never written], [the folded 1x1 stride residual conv], one
+    ``agcn_tconv_infer`` (gates on load, residual add + ReLU in its epilogue).
+    Returns None where the fused kernels do not apply (3-channel first layer, C < 32, AGCN_GEMM=f32, whatever
+    agcn_gcn_unit_infer rejects): the caller runs the unfused eval passes.  ``cache`` (a dict owned by the module) keeps
+    the folded and packed weights between calls, keyed on the parameter epoch and every source tensor's (data_ptr,
+    version)."""
     x = x.contiguous()
     N, C, T, V = x.shape
     # decided before anything is folded or launched: agcn_gcn_unit_infer exists on the chained split kernels only
@@ -1153,41 +1211,16 @@ def aagcn_unit_infer(x, p, cache=None):
     # more than needed: the caller's unfused passes compute it again.)
     if C < 32 or _L().agcn_gemm_mode() not in (b'bf16x6', b'bf16'):
         return None
-    srcs = [t for wb in p['conv_d'] for t in wb] + [t for q in (p['ab'] or []) for t in q]
-    srcs += [*p['gbn'], p['tw'], p['tb'], *p['tbn']] + list(p['down'] or []) + list(p['res'] or [])
+    srcs = [t for wb in p['conv_d'] for t in wb] + [t for q in (p['ab'] or ()) for t in q]
+    srcs += [*p['gbn'], p['tw'], p['tb'], *p['tbn'], *(p['down'] or ()), *(p['res'] or ())]
     key = _cache_key(srcs)
     f = cache.get('folded') if cache is not None else None
     if f is None or f[0] != key:
-        Cout = p['conv_d'][0][0].shape[0]
-        wd = torch.cat([w.view(Cout, C) for w, _ in p['conv_d']], dim=1)
-        bd = p['conv_d'][0][1] + p['conv_d'][1][1] + p['conv_d'][2][1]
-        s1, sh1 = _fold(p['gbn'])
-        wdf = (wd * s1[:, None]).contiguous()
-        bias = bd * s1 + sh1
-        w2 = None
-        if p['down'] is not None:
-            dw, db = _fold_conv(p['down'][0], p['down'][1], p['down'][2:])
-            w2 = dw.reshape(Cout, C)
-            bias = bias + db
-        twf, tbf = _fold_conv(p['tw'], p['tb'], p['tbn'])
-        rwf = rbf = None
-        if p['res'] is not None:
-            rwf, rbf = _fold_conv(p['res'][0], p['res'][1], p['res'][2:])
-        wab = bab = None
-        if p['ab'] is not None:      # theta/phi weights stacked row-wise [a0|b0|a1|b1|a2|b2]
-            wab = torch.cat([t for wa, _, wb_, _ in p['ab'] for t in (wa, wb_)], 0).contiguous()
-            bab = torch.cat([t for _, ba, _, bb in p['ab'] for t in (ba, bb)], 0).contiguous()
-        f = (key, wdf, bias.contiguous(), w2, twf, tbf, rwf, rbf, wab, bab)
+        f = (key,) + _fold_unit(p)
         if cache is not None:
             cache['folded'] = f
     _, wdf, bias, w2, twf, tbf, rwf, rbf, wab, bab = f
-    if wab is not None and adjacency_fused_supported(C, wab.shape[0] // 6, T, V):
-        _, adj = adjacency_fused_fwd(x, wab, bab, None, p['PA'], p['alpha'])
-    elif wab is not None:
-        tp, _ = conv_fwd(x, wab, bab)
-        _, adj = adjacency_fwd(tp, None, p['PA'], p['alpha'])
-    else:
-        adj = p['A'].unsqueeze(0).expand(N, 3, V, V).contiguous()
+    _, adj, _, _ = _adjacency(x, wab, bab, p['A'], p['PA'], p['alpha'], keep_tp=False, x_amax=None, want_amax=False)
     if w2 is None:
         g = gcn_unit_infer(x, adj, wdf, bias, res=x)
     else:
@@ -1212,213 +1245,169 @@ def aagcn_unit_infer(x, p, cache=None):
     return y
 
 
-def unit_infer(x, A, PA, wab, bab, wd, bd, gbn, down, tw, tb, tbn, res_mode, res, stride, alpha=None, adaptive=True,
-               cache=None):
-    """Eval-mode TCN_GCN_unit (reference agcn.py:92-109, 48-50, 127-129) with every BatchNorm folded into the contraction
-    in front of it: adjacency, one aggregate+project kernel (conv `down` as extra plain stages, residual add and ReLU
-    in its epilogue), [the 1x1 stride residual conv], one temporal-conv kernel (residual add + ReLU in its epilogue).
-    gbn / tbn = (weight, bias, running_mean, running_var); down / res = None | (w, b, bn_w, bn_b, bn_rm, bn_rv).
-    Returns None where the fused kernels do not apply (3-channel first layer, AGCN_GEMM=f32): the caller then runs the
-    unfused eval passes.  ``cache`` (a dict owned by the module) keeps the folded weights between calls."""
-    x = x.contiguous()
-    N, C, T, V = x.shape
-    Cout = wd.shape[0]
-    if C < 32:
-        return None
-    srcs = [wd, bd, *gbn, tw, tb, *tbn] + (list(down) if down is not None else []) + \
-           (list(res) if isinstance(res, tuple) else [])
-    key = (_PARAM_EPOCH[0],) + tuple((t.data_ptr(), t._version) for t in srcs)
-    f = cache.get('folded') if cache is not None else None
-    if f is None or f[0] != key:
-        s1, sh1 = _fold(gbn)
-        wdf = (wd * s1[:, None]).contiguous()
-        bias = bd * s1 + sh1
-        w2 = None
-        if down is not None:
-            s2, sh2 = _fold(down[2:])
-            w2 = (down[0].reshape(Cout, C) * s2[:, None]).contiguous()
-            bias = bias + down[1] * s2 + sh2
-        s3, sh3 = _fold(tbn)
-        twf = (tw * s3[:, None, None, None]).contiguous()
-        tbf = tb * s3 + sh3
-        rwf = rbf = None
-        if isinstance(res, tuple):
-            s4, sh4 = _fold(res[2:])
-            rwf = (res[0] * s4[:, None, None, None]).contiguous()
-            rbf = res[1] * s4 + sh4
-        f = (key, wdf, bias.contiguous(), w2, twf, tbf.contiguous(), rwf, rbf)
-        if cache is not None:
-            cache['folded'] = f
-    _, wdf, bias, w2, twf, tbf, rwf, rbf = f
-    if adaptive and adjacency_fused_supported(C, wab.shape[0] // 6, T, V):
-        _, adj = adjacency_fused_fwd(x, wab, bab, A, PA, alpha)
-    elif adaptive:
-        tp, _ = conv_fwd(x, wab, bab)
-        _, adj = adjacency_fwd(tp, A, PA, alpha)
-    else:
-        adj = A.unsqueeze(0).expand(N, 3, V, V).contiguous()
-    if down is None:
-        g = gcn_unit_infer(x, adj, wdf, bias, res=x)
-    else:
-        g = gcn_unit_infer(x, adj, wdf, bias, x2=x, w2=w2)
-    if g is None:
-        return None
-    if res_mode == 0:
-        r = None
-    elif res_mode == 1:
-        r = x
-    else:
-        r, _ = conv_fwd(x, rwf, rbf, stride)
-    if tw.shape[2] == 9:
-        return conv9_infer(g, twf, tbf, r, relu=True, stride=stride)
-    return tconv_infer(g, twf, tbf, res=r, relu=True, stride=stride)     # unit_tcn(kernel_size != 9): same fold
+# ---- the autograd nodes ---------------------------------------------------------------------------------------------------
+class _Args:
+    """The argument names of one autograd Function's forward, declared once next to it: the positions looked up in
+    ``needs_input_grad`` and the order of the gradients its backward returns are derived from the names, and a name
+    that is not an argument is a KeyError."""
+    __slots__ = ('names', 'index')
+
+    def __init__(self, *names):
+        self.names, self.index = names, {n: i for i, n in enumerate(names)}
+
+    def positions(self, *names):
+        return tuple(self.index[n] for n in names)
+
+    def grads(self, **by_name):
+        """The backward's return value: the given gradients at their arguments' positions, None everywhere else."""
+        out = [None] * len(self.names)
+        for n, g in by_name.items():
+            out[self.index[n]] = g
+        return tuple(out)
 
 
-def _bias_grad(slot, k, n, like, needed=True):
-    """Gradient of a convolution bias in front of a BatchNorm: ``slot[k]`` in eval mode (bn_bwd's ``bias_out``), exact
-    zeros in train mode where the batch mean cancels the bias; None where the eval backward skipped the sums."""
-    if slot and slot[k] is not None:
-        return slot[k]
-    if slot:                   # eval mode with want_sums=False: nobody asked for it
-        return None
-    return torch.zeros(n, dtype=torch.float32, device=like.device) if needed else None
+_GCN_ARGS = ('A', 'PA', 'wab', 'bab', 'wd', 'bd', 'bn_w', 'bn_b', 'bn_rm', 'bn_rv',
+             'down_w', 'down_b', 'dbn_w', 'dbn_b', 'dbn_rm', 'dbn_rv')                              # = pack_gcn(p)
+_TCN_ARGS = ('tw', 'tb', 'tbn_w', 'tbn_b', 'tbn_rm', 'tbn_rv',
+             'res_mode', 'rw', 'rb', 'rbn_w', 'rbn_b', 'rbn_rm', 'rbn_rv', 'stride')                # = pack_tcn(p)
+# eval mode: the BatchNorm partial sums only where a BN parameter or a conv bias in front of it wants a gradient
+_GCN_SUMS = ('bd', 'bn_w', 'bn_b', 'down_b', 'dbn_w', 'dbn_b')
+_TCN_SUMS = ('tb', 'tbn_w', 'tbn_b', 'rb', 'rbn_w', 'rbn_b')
+
+
+def _wants(ctx, positions):
+    ng = ctx.needs_input_grad
+    return any(ng[i] for i in positions)
+
+
+def _down(down_w, down_b, dbn_w, dbn_b, dbn_rm, dbn_rv):
+    return None if down_w is None else (down_w, down_b, dbn_w, dbn_b, dbn_rm, dbn_rv)
+
+
+def _residual(res_mode, rw, rb, rbn_w, rbn_b, rbn_rm, rbn_rv):
+    return None if res_mode == 0 else ('identity' if res_mode == 1 else (rw, rb, rbn_w, rbn_b, rbn_rm, rbn_rv))
 
 
 class UnitGCNFunction(torch.autograd.Function):
-    """unit_gcn: args (x, A, PA, wab, bab, wd, bd, bn_w, bn_b, bn_rm, bn_rv,
-                       down_w, down_b, dbn_w, dbn_b, dbn_rm, dbn_rv, training, alpha=None, adaptive=True)"""
+    """unit_gcn / GCNUnit core as its own autograd node."""
+    ARGS = _Args('x', *_GCN_ARGS, 'training', 'alpha', 'sync')
+    SUMS = ARGS.positions(*_GCN_SUMS)
 
     @staticmethod
     def forward(ctx, x, A, PA, wab, bab, wd, bd, bn_w, bn_b, bn_rm, bn_rv, down_w, down_b, dbn_w, dbn_b, dbn_rm,
-                dbn_rv, training, alpha=None, adaptive=True, sync=None):
-        c = _Ctx()
-        down = None if down_w is None else (down_w, down_b, dbn_w, dbn_b, dbn_rm, dbn_rv)
-        out = gcn_forward(c, x.contiguous(), A, PA, wab, bab, wd, bd, (bn_w, bn_b, bn_rm, bn_rv), down, training,
-                          alpha, adaptive, sync, need_bwd=any(ctx.needs_input_grad))
-        ctx.c, ctx.training = c, training
-        ctx.has_down = down is not None
-        _note_out_amax(out, getattr(c, 'g_amax', None))     # stand-alone node: a unit_tcn may read this tensor next
+                dbn_rv, training, alpha=None, sync=None):
+        out, ctx.gs = gcn_forward(x.contiguous(), A, PA, wab, bab, wd, bd, (bn_w, bn_b, bn_rm, bn_rv),
+                                  _down(down_w, down_b, dbn_w, dbn_b, dbn_rm, dbn_rv), training, alpha, sync,
+                                  need_bwd=any(ctx.needs_input_grad))
+        _note_out_amax(out, ctx.gs.g_amax)     # stand-alone node: a unit_tcn may read this tensor next
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        # eval mode: the BatchNorm partial sums only where a BN parameter or a conv bias in front of it wants a gradient
-        ng = ctx.needs_input_grad
-        ctx.c.g_want_sums = any(ng[i] for i in (6, 7, 8, 12, 13, 14))
-        dx, dPA, dwab, dbab, dwd, dg1, db1, dwdown, dg2, db2 = gcn_backward(ctx.c, dout.contiguous())
-        dbd = _bias_grad(ctx.c.g_dbias, 0, dwd.shape[0], dout)
-        dbdown = _bias_grad(ctx.c.g_dbias, 1, dwd.shape[0], dout, ctx.has_down)
-        dalpha = ctx.c.g_dalpha
+        dx, dPA, dwab, dbab, dwd, dbd, dg1, db1, dwdown, dbdown, dg2, db2, dalpha = gcn_backward(
+            ctx.gs, dout.contiguous(), want_sums=_wants(ctx, UnitGCNFunction.SUMS))
+        ctx.gs = None
         if dalpha is not None:
             dalpha = dalpha.reshape(1)
-        ctx.c = None
-        return (dx, None, dPA, dwab, dbab, dwd, dbd, dg1, db1, None, None, dwdown, dbdown, dg2, db2, None, None, None,
-                dalpha, None, None)
+        return UnitGCNFunction.ARGS.grads(x=dx, PA=dPA, wab=dwab, bab=dbab, wd=dwd, bd=dbd, bn_w=dg1, bn_b=db1,
+                                          down_w=dwdown, down_b=dbdown, dbn_w=dg2, dbn_b=db2, alpha=dalpha)
 
 
 class UnitTCNFunction(torch.autograd.Function):
-    """unit_tcn (no residual, no ReLU): args (x, w, b, bn_w, bn_b, bn_rm, bn_rv, stride, training, sync, pad)"""
+    """unit_tcn / TCNUnit (no residual, no ReLU) as its own autograd node."""
+    ARGS = _Args('x', 'tw', 'tb', 'tbn_w', 'tbn_b', 'tbn_rm', 'tbn_rv', 'stride', 'training', 'sync', 'pad')
+    SUMS = ARGS.positions('tb', 'tbn_w', 'tbn_b')
 
     @staticmethod
-    def forward(ctx, x, w, b, bn_w, bn_b, bn_rm, bn_rv, stride, training, sync=None, pad=None):
-        c = _Ctx()
-        out = tcn_forward(c, x.contiguous(), w, b, (bn_w, bn_b, bn_rm, bn_rv), stride, None, None, False, training,
-                          sync, pad)
-        ctx.c, ctx.training = c, training
+    def forward(ctx, x, tw, tb, tbn_w, tbn_b, tbn_rm, tbn_rv, stride, training, sync=None, pad=None):
+        x = x.contiguous()
+        out, ctx.ts = tcn_forward(x, tw, tb, (tbn_w, tbn_b, tbn_rm, tbn_rv), stride, None, None, False, training, sync,
+                                  pad, g_amax=_take_out_amax(x))
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        ctx.c.t_want_sums = any(ctx.needs_input_grad[i] for i in (2, 3, 4))
-        dg, dw, dg1, db1, _, _, _, _ = tcn_backward(ctx.c, dout.contiguous())
-        dbias = _bias_grad(ctx.c.t_dbias, 0, dw.shape[0], dout)
-        ctx.c = None
-        return dg, dw, dbias, dg1, db1, None, None, None, None, None, None
+        dg, dw, dbias, dg1, db1, _, _, _, _, _ = tcn_backward(ctx.ts, dout.contiguous(),
+                                                              want_sums=_wants(ctx, UnitTCNFunction.SUMS))
+        ctx.ts = None
+        return UnitTCNFunction.ARGS.grads(x=dg, tw=dw, tb=dbias, tbn_w=dg1, tbn_b=db1)
 
 
 class TCNResidualFunction(torch.autograd.Function):
-    """relu(bn(conv9(g)) + residual(x)) as its own autograd node (AAGCN: the attention ops sit between the GCN core and
-    this).  args: g, x, w, b, bn_w, bn_b, bn_rm, bn_rv, res_mode (0 none, 1 identity, 2 conv), rw, rb, rbn_w, rbn_b,
-    rbn_rm, rbn_rv, stride, training, sync, pad (of the temporal convolution; None = (k-1)//2)"""
+    """relu(bn(tconv(g)) + residual(x)) as its own autograd node (AAGCN: the attention gates sit between the GCN core
+    and this).  pad: of the temporal convolution (None = (k-1)//2)."""
+    ARGS = _Args('g', 'x', *_TCN_ARGS, 'training', 'sync', 'pad')
+    SUMS = ARGS.positions(*_TCN_SUMS)
 
     @staticmethod
-    def forward(ctx, g, x, w, b, bn_w, bn_b, bn_rm, bn_rv, res_mode, rw, rb, rbn_w, rbn_b, rbn_rm, rbn_rv, stride,
+    def forward(ctx, g, x, tw, tb, tbn_w, tbn_b, tbn_rm, tbn_rv, res_mode, rw, rb, rbn_w, rbn_b, rbn_rm, rbn_rv, stride,
                 training, sync=None, pad=None):
-        c = _Ctx()
-        res = None if res_mode == 0 else ('identity' if res_mode == 1 else (rw, rb, rbn_w, rbn_b, rbn_rm, rbn_rv))
+        g = g.contiguous()
         x = x.contiguous() if x is not None else None
-        out = tcn_forward(c, g.contiguous(), w, b, (bn_w, bn_b, bn_rm, bn_rv), stride, x, res, True, training, sync,
-                          pad)
-        ctx.c, ctx.training, ctx.res_mode, ctx.stride = c, training, res_mode, stride
-        ctx.x_shape = tuple(x.shape) if x is not None else None
+        out, ctx.ts = tcn_forward(g, tw, tb, (tbn_w, tbn_b, tbn_rm, tbn_rv), stride, x,
+                                  _residual(res_mode, rw, rb, rbn_w, rbn_b, rbn_rm, rbn_rv), True, training, sync, pad,
+                                  g_amax=_take_out_amax(g))     # (left by the attention gates / the unit_gcn node)
+        ctx.res_mode = res_mode
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        c = ctx.c
+        s = ctx.ts
         dout = dout.contiguous()
-        c.t_want_sums = any(ctx.needs_input_grad[i] for i in (3, 4, 5, 10, 11, 12))
-        dg, dw, dg1, db1, drpre, dwres, dg2, db2 = tcn_backward(c, dout)
-        dtb = _bias_grad(c.t_dbias, 0, dw.shape[0], dout)
-        drb = _bias_grad(c.t_dbias, 1, dw.shape[0], dout, ctx.res_mode == 2)
+        dg, dw, dtb, dg1, db1, drpre, dwres, drb, dg2, db2 = tcn_backward(
+            s, dout, want_sums=_wants(ctx, TCNResidualFunction.SUMS))
         dx = None
         if ctx.res_mode == 1:
-            dx = torch.where(c.t_out > 0, dout, torch.zeros_like(dout))
+            dx = torch.where(s.out > 0, dout, torch.zeros_like(dout))
         elif ctx.res_mode == 2:
-            dx = conv_bwd_data(drpre, c.t_params[2], ctx.x_shape, ctx.stride)
-        ctx.c = None
-        return (dg, dx, dw, dtb, dg1, db1, None, None, None,
-                dwres, drb, dg2, db2, None, None, None, None, None, None)
+            dx = conv_bwd_data(drpre, s.wres, s.resx.shape, s.stride)
+        ctx.ts = None
+        return TCNResidualFunction.ARGS.grads(g=dg, x=dx, tw=dw, tb=dtb, tbn_w=dg1, tbn_b=db1, rw=dwres, rb=drb,
+                                              rbn_w=dg2, rbn_b=db2)
 
 
 class TCNGCNUnitFunction(torch.autograd.Function):
     """TCN_GCN_unit = relu(tcn1(gcn1(x)) + residual(x)) as ONE autograd node, so that every dx contribution is
-    accumulated in a contraction epilogue instead of separate elementwise passes.
-
-    args: x, A, PA, wab, bab, wd, bd, gbn_w, gbn_b, gbn_rm, gbn_rv, down_w, down_b, dbn_w, dbn_b, dbn_rm, dbn_rv,
-          tw, tb, tbn_w, tbn_b, tbn_rm, tbn_rv, res_mode(0 none,1 identity,2 conv), rw, rb, rbn_w, rbn_b, rbn_rm,
-          rbn_rv, stride, training, sync (SyncBN policy or None)"""
+    accumulated in a contraction epilogue instead of separate elementwise passes."""
+    ARGS = _Args('x', *_GCN_ARGS, *_TCN_ARGS, 'training', 'sync')
+    GCN_SUMS, TCN_SUMS = ARGS.positions(*_GCN_SUMS), ARGS.positions(*_TCN_SUMS)
 
     @staticmethod
-    def forward(ctx, x, A, PA, wab, bab, wd, bd, gbn_w, gbn_b, gbn_rm, gbn_rv, down_w, down_b, dbn_w, dbn_b, dbn_rm,
+    def forward(ctx, x, A, PA, wab, bab, wd, bd, bn_w, bn_b, bn_rm, bn_rv, down_w, down_b, dbn_w, dbn_b, dbn_rm,
                 dbn_rv, tw, tb, tbn_w, tbn_b, tbn_rm, tbn_rv, res_mode, rw, rb, rbn_w, rbn_b, rbn_rm, rbn_rv, stride,
                 training, sync=None):
-        c = _Ctx()
         x = x.contiguous()
-        down = None if down_w is None else (down_w, down_b, dbn_w, dbn_b, dbn_rm, dbn_rv)
-        g = gcn_forward(c, x, A, PA, wab, bab, wd, bd, (gbn_w, gbn_b, gbn_rm, gbn_rv), down, training, sync=sync,
-                        need_bwd=any(ctx.needs_input_grad))
-        res = None if res_mode == 0 else ('identity' if res_mode == 1 else (rw, rb, rbn_w, rbn_b, rbn_rm, rbn_rv))
-        out = tcn_forward(c, g, tw, tb, (tbn_w, tbn_b, tbn_rm, tbn_rv), stride, x, res, True, training, sync)
-        ctx.c, ctx.training, ctx.has_down, ctx.res_mode, ctx.stride = c, training, down is not None, res_mode, stride
+        g, ctx.gs = gcn_forward(x, A, PA, wab, bab, wd, bd, (bn_w, bn_b, bn_rm, bn_rv),
+                                _down(down_w, down_b, dbn_w, dbn_b, dbn_rm, dbn_rv), training, sync=sync,
+                                need_bwd=any(ctx.needs_input_grad))
+        out, ctx.ts = tcn_forward(g, tw, tb, (tbn_w, tbn_b, tbn_rm, tbn_rv), stride, x,
+                                  _residual(res_mode, rw, rb, rbn_w, rbn_b, rbn_rm, rbn_rv), True, training, sync,
+                                  g_amax=ctx.gs.g_amax)
+        ctx.res_mode = res_mode
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        c = ctx.c
+        gs, ts = ctx.gs, ctx.ts
         dout = dout.contiguous()
-        ng = ctx.needs_input_grad
-        c.g_want_sums = any(ng[i] for i in (6, 7, 8, 12, 13, 14))
-        c.t_want_sums = any(ng[i] for i in (18, 19, 20, 25, 26, 27))
+        cls = TCNGCNUnitFunction
         _SIDE_SCOPE[0] += 1
         try:
-            dg, dtw, dtg, dtb, drpre, drw, drg, drb = tcn_backward(c, dout, join=False)   # (gcn_backward joins)
-            if ctx.res_mode == 1:
-                gres = gcn_backward(c, dg, extra_add=dout, extra_mask=c.t_bits)
-            else:
-                gres = gcn_backward(c, dg)
+            dg, dtw, dtbias, dtg, dtb, drpre, drw, drbias, drg, drb = tcn_backward(      # (gcn_backward joins)
+                ts, dout, join=False, want_sums=_wants(ctx, cls.TCN_SUMS))
+            extra = dict(extra_add=dout, extra_mask=ts.bits) if ctx.res_mode == 1 else {}
+            dx, dPA, dwab, dbab, dwd, dbd, dg1, db1, dwdown, dbdown, dg2, db2, _ = gcn_backward(
+                gs, dg, want_sums=_wants(ctx, cls.GCN_SUMS), **extra)
         finally:
             _SIDE_SCOPE[0] -= 1
-        dx, dPA, dwab, dbab, dwd, dg1, db1, dwdown, dg2, db2 = gres
         if ctx.res_mode == 2:
-            conv_bwd_data(drpre, c.t_params[2], c.g_x.shape, ctx.stride, out=dx, accumulate=True)
-        Cout = dwd.shape[0]
-        dbd = _bias_grad(c.g_dbias, 0, Cout, dout)
-        dbdown = _bias_grad(c.g_dbias, 1, Cout, dout, ctx.has_down)
-        dtbias = _bias_grad(c.t_dbias, 0, Cout, dout)
-        drbias = _bias_grad(c.t_dbias, 1, Cout, dout, ctx.res_mode == 2)
-        ctx.c = None
-        return (dx, None, dPA, dwab, dbab, dwd, dbd, dg1, db1, None, None,
-                dwdown, dbdown, dg2, db2, None, None,
-                dtw, dtbias, dtg, dtb, None, None, None,
-                drw, drbias, drg, drb, None, None, None, None, None)
+            conv_bwd_data(drpre, ts.wres, gs.x.shape, ts.stride, out=dx, accumulate=True)
+        ctx.gs = ctx.ts = None
+        return cls.ARGS.grads(x=dx, PA=dPA, wab=dwab, bab=dbab, wd=dwd, bd=dbd, bn_w=dg1, bn_b=db1, down_w=dwdown,
+                            down_b=dbdown, dbn_w=dg2, dbn_b=db2, tw=dtw, tb=dtbias, tbn_w=dtg, tbn_b=dtb, rw=drw,
+                            rb=drbias, rbn_w=drg, rbn_b=drb)
+
+
+# the names above are the forward signatures: an argument added to one and not to the other fails here, at import
+for _f in (UnitGCNFunction, UnitTCNFunction, TCNResidualFunction, TCNGCNUnitFunction):
+    assert _f.forward.__code__.co_varnames[1:_f.forward.__code__.co_argcount] == _f.ARGS.names, _f.__name__

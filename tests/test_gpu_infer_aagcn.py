@@ -382,6 +382,69 @@ def test_folded_weights_follow_the_parameters(name, monkeypatch):
     assert not torch.equal(y2, y1)
 
 
+# ---- the same driver under the AGCN unit -----------------------------------------------------------------------------------
+AGCN_UNIT = (64, 128, 2, 2, 24, 25, 7)           # cin, cout, stride, n, t, v, seed
+
+
+def _agcn_unit(dev):
+    from agcn_amd.model.agcn import TCN_GCN_unit
+    cin, cout, stride, n, t, v, seed = AGCN_UNIT
+    unit = TCN_GCN_unit(cin, cout, gu.graph_A(v).numpy(), stride=stride)
+    unit.load_state_dict(orc.randomized_state(orc.unit_param_shapes('', cin, cout, v, stride, True), seed, stress=4.0))
+    xn, _ = gu.unit_inputs(cin, cout, stride, t, v, seed, n=n)
+    return unit.to(dev).eval(), torch.from_numpy(xn).to(dev)
+
+
+_UNFUSED_CHILD = r'''
+import sys, numpy as np, torch
+sys.path.insert(0, %(root)r)
+import agcn_amd
+from tests.test_gpu_infer_aagcn import _agcn_unit
+from agcn_amd import ops
+unit, x = _agcn_unit(torch.device('cuda:0'))
+with torch.no_grad():
+    y = unit(x)
+torch.cuda.synchronize()
+assert ops.INFER_STATS['aagcn_unit_fused'] == 0 and ops.INFER_STATS['tconv_infer'] == 0, ops.INFER_STATS
+np.save(%(out)r, y.cpu().numpy())
+'''
+
+
+def test_agcn_unit_folded_route_cache_and_fold_off(tmp_path, monkeypatch):
+    """An AGCN TCN_GCN_unit(64, 128, stride 2) in eval under no_grad runs folded end to end through ``ops.unit_infer``
+    (9-tap temporal convolution on ``agcn_tconv_infer``), keeps its folded weights between calls, rebuilds them after
+    ``note_params_changed`` and equals the unfused eval passes of a process with AGCN_INFER_FOLD=0."""
+    from agcn_amd import ops
+    dev = _gpu()
+    monkeypatch.setenv('AGCN_INFER_FOLD', '1')
+    fus = int(_fusable(AGCN_UNIT[0]))
+    unit, x = _agcn_unit(dev)
+    before = _counters()
+    with torch.no_grad():
+        y = unit(x)
+    d = _delta(before)
+    assert d['aagcn_unit_fused'] == fus and d['tconv_infer'] == fus and d['stc_apply'] == 0, d
+    if fus:
+        entry = unit.__dict__['_infer_cache']['folded']
+        with torch.no_grad():
+            y_again = unit(x)
+        assert unit.__dict__['_infer_cache']['folded'] is entry           # served from the cache
+        ops.note_params_changed()
+        with torch.no_grad():
+            y_rebuilt = unit(x)
+        rebuilt = unit.__dict__['_infer_cache']['folded']
+        assert rebuilt is not entry and rebuilt[0] != entry[0]
+        assert all((a is None and b is None) or torch.equal(a, b) for a, b in zip(entry[1:], rebuilt[1:]))
+        assert torch.equal(y, y_again) and torch.equal(y, y_rebuilt)
+    out = str(tmp_path / 'y_unfused.npy')
+    r = subprocess.run([sys.executable, '-c', _UNFUSED_CHILD % dict(root=ROOT, out=out)], cwd=ROOT,
+                       env=dict(os.environ, AGCN_INFER_FOLD='0'), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    err = gu.rel_err(y.cpu().numpy(), np.load(out))
+    print(f'AGCN unit folded vs unfused: {err:.2e}')
+    assert err < TOL
+
+
 # ---- determinism ---------------------------------------------------------------------------------------------------------
 _CHILD = r'''
 import hashlib, sys, torch

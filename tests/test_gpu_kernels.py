@@ -541,6 +541,31 @@ def test_conv9_infer(case):
     assert rel(y, y_ref) < TOL
 
 
+@pytest.mark.parametrize('case', INFER_CONV_CASES)
+def test_tconv_infer_is_conv9_infer_at_9_taps(case):
+    """The folded units run their 9-tap temporal convolution through ``tconv_infer`` (no gates, pad 4): the same
+    instantiation as ``conv9_infer`` on the same inputs, hence the same bits."""
+    from agcn_amd import lib, ops
+    dev = _gpu()
+    L = lib.load()
+    N, Cin, Cout, T, V, stride, has_res, relu = case
+    g = torch.Generator().manual_seed(29 + Cin + T)
+    x = rnd(g, N, Cin, T, V).float().to(dev)
+    w = rnd(g, Cout, Cin, 9, 1, scale=1.0 / np.sqrt(9 * Cin)).float().to(dev)
+    b = rnd(g, Cout, scale=0.1).float().to(dev)
+    res = rnd(g, N, Cout, (T - 1) // stride + 1, V).float().to(dev) if has_res else None
+    y9 = ops.conv9_infer(x, w, b, res, relu=relu, stride=stride)
+    if y9 is None:
+        pytest.skip("fused inference kernels not available in this AGCN_GEMM mode")
+    torch.cuda.synchronize()
+    k9 = L.agcn_last_kernel().decode()
+    yt = ops.tconv_infer(x, w, b, res=res, relu=relu, stride=stride)
+    torch.cuda.synchronize()
+    kt = L.agcn_last_kernel().decode()
+    assert yt is not None and torch.equal(yt, y9)
+    assert kt == k9, (kt, k9)
+
+
 FIRST_CASES = [(8, 3, 64, 300, 25), (3, 3, 64, 23, 25), (2, 3, 64, 37, 18), (2, 2, 48, 11, 20)]
 
 
