@@ -104,6 +104,9 @@ SIGNATURES = {
     "agcn_gate_conv_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "agcn_sgd_step_workspace": (_Z, [ctypes.c_long]),
     "agcn_sgd_step": (_I, [_P, _P, _P, ctypes.c_long, _F, _F, _F, _I, _F, _F, _I, _P, _Z, _P, _P]),
+    "agcn_prenorm_max_frames": (_I, []),
+    "agcn_skel_append": (_I, [_P, _P] + [_I] * 6 + [_P]),
+    "agcn_prenorm": (_I, [_P] * 4 + [_I] * 16 + [_P]),
 }
 
 _lib = None

@@ -1245,6 +1245,56 @@ def unit_infer(x, p, cache=None):
     return y
 
 
+# ---- skeleton preprocessing on the device (csrc/prenorm.hip) -----------------------------------------------------------
+def _axis(pair):
+    if pair is None:
+        return -1, -1
+    j0, j1 = (int(j) for j in pair)
+    if j0 < 0 or j1 < 0:
+        raise ValueError(f"agcn_amd: joint indices are 0-based and non-negative, got {pair}")
+    return j0, j1
+
+
+def skel_append(ring, frame, slot, count, moving_avg=1):
+    """frame (Mmax, V, 3) into slot ``slot`` of the device ring (Mmax, Tmax, V, 3); ``count`` = frames present
+    including this one.  ``moving_avg`` k > 1: once count >= k the slot holds the mean of the last k slots
+    (agcn_skel_append).  The host owns slot and count; nothing is read back."""
+    Mmax, Tmax, V, C = ring.shape
+    if C != 3 or tuple(frame.shape) != (Mmax, V, 3):
+        raise ValueError(f"agcn_amd: skel_append takes a ({Mmax}, {V}, 3) frame for this ring, got {tuple(frame.shape)}")
+    rc = _L().agcn_skel_append(_lib.ptr(frame), _lib.ptr(ring), Mmax, Tmax, V, int(slot), int(count), int(moving_avg),
+                               _lib.stream())
+    _lib.check(rc, "agcn_skel_append")
+
+
+def prenorm(x, num_select=None, origin=0, frames=None, zaxis=(0, 1), zaxis2=None, xaxis=(8, 4), pad=True, center=True,
+            center_firstframe=False):
+    """Body selection + pre_normalization of raw skeletons x (N, M, Tmax, V, 3) -> (N, 3, T, V, K) (agcn_prenorm).
+    Logical frame t is slot (origin + t) mod Tmax; ``frames`` T defaults to Tmax.  ``num_select`` K: the K most active
+    of the M bodies, most active first; None keeps all M in their order.  Returns (out, selected (N, K) int32,
+    energy (N, M) or None), all on the device.
+
+    A frame (joint) counts as null iff ALL its values are zero.  The reference tests ``sum() == 0``; the two differ only
+    where a non-null frame or joint sums to exactly zero by cancellation."""
+    if (center or center_firstframe) and center == center_firstframe:
+        raise ValueError("agcn_amd: center and center_firstframe exclude each other")
+    if x.dim() != 5 or x.shape[-1] != 3:
+        raise ValueError(f"agcn_amd: prenorm takes (N, M, T, V, 3), got {tuple(x.shape)}")
+    N, M, Tmax, V, _ = x.shape
+    T = Tmax if frames is None else int(frames)
+    select = num_select is not None
+    K = int(num_select) if select else M
+    out = _empty((N, 3, T, V, K), x)
+    sel = torch.empty((N, K), dtype=torch.int32, device=x.device)
+    energy = _empty((N, M), x) if select else None
+    (z0, z1), (x0, x1), (zz0, zz1) = _axis(zaxis), _axis(xaxis), _axis(zaxis2)
+    rc = _L().agcn_prenorm(_lib.ptr(x), _lib.ptr(out), _lib.ptr_bits(sel), _lib.ptr(energy), N, M, K, T, Tmax, int(origin),
+                           V, 1 if select else 0, 1 if pad else 0, 1 if center else (2 if center_firstframe else 0),
+                           z0, z1, x0, x1, zz0, zz1, _lib.stream())
+    _lib.check(rc, "agcn_prenorm")
+    return out, sel, energy
+
+
 # ---- the autograd nodes ---------------------------------------------------------------------------------------------------
 class _Args:
     """The argument names of one autograd Function's forward, declared once next to it: the positions looked up in

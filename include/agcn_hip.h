@@ -378,6 +378,36 @@ int agcn_sgd_step(float* param, const float* grad, float* momentum_buf, long n, 
                   float weight_decay, int nesterov, float max_norm, float grad_scale, int first_step, void* workspace,
                   size_t workspace_bytes, float* norm_out, void* stream);
 
+/* ---- skeleton preprocessing on the device (online recognition, dataset generation) -------------------------------------
+ * replaces infer/data_preprocess.py (DataPreprocessor.append_data, select_skeletons) and data_gen/preprocess.py
+ * (pre_normalization).  A frame (joint) is null iff all its 3V (3) values are zero; the reference tests sum() == 0.
+ *
+ * skel_append: frame (Mmax, V, 3) -> slot `slot` of ring (Mmax, Tmax, V, 3).  `count` = frames present INCLUDING this
+ *   one (1..Tmax; while count < Tmax the slot must be count - 1: the ring fills from slot 0 upward).  k > 1: once
+ *   count >= k the slot holds the mean of the last k slots (sum oldest to newest in fp32, / k), the new frame included;
+ *   earlier slots already hold averaged frames.  1 <= k <= Tmax.
+ *
+ * prenorm: in = N blocks (M, Tmax, V, 3); logical frame t of a block is slot (origin + t) mod Tmax (a plain tensor:
+ *   origin 0, Tmax = T).  out (N, 3, T, V, K).  One workgroup per sample:
+ *   select != 0: the K bodies of largest energy (sum over channels of the population std over valid frames x joints,
+ *     fp64, fixed order), largest first, the higher index first among equals; else bodies 0..K-1.  sel (N, K) int32
+ *     receives the indices, energy (N, M) the energies (only written, and only required, with select).
+ *   pad != 0: a body whose frame 0 is null has its valid frames compacted to the front; frames after the last valid one
+ *     repeat the frames before them cyclically.
+ *   center: 0 none, 1 subtract the first selected body's joint 1 of the same (padded) frame, 2 that of its first
+ *     non-null frame; null joints stay zero.
+ *   (z0, z1): rotate the first body's frame-0 bone z1 - z0 onto z; (x0, x1): then x0 - x1 onto x; (zz0, zz1): then
+ *   zz1 - zz0 onto z again.  A pair of -1 skips that rotation.  Matrices in fp64 (reference data_gen/rotation.py), their
+ *   product applied once in fp32.
+ *   AGCN_ERR_ARG: null pointer, V < 2, V > 32, T < 1, T > agcn_prenorm_max_frames() (2048: the per-body source-frame
+ *   table lives in LDS), Tmax < T, origin outside [0, Tmax), M > 8, K < 1, K > M, an axis joint outside [0, V) or a
+ *   half-given pair.  Every gathered index is clamped in the kernel as well. */
+int agcn_prenorm_max_frames(void);
+int agcn_skel_append(const float* frame, float* ring, int Mmax, int Tmax, int V, int slot, int count, int k,
+                     void* stream);
+int agcn_prenorm(const float* in, float* out, int* sel, float* energy, int N, int M, int K, int T, int Tmax, int origin,
+                 int V, int select, int pad, int center, int z0, int z1, int x0, int x1, int zz0, int zz1, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
