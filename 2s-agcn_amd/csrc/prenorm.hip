@@ -7,8 +7,16 @@
 //     data_gen/preprocess.py pre_normalization (pad null frames, centre on the first body's joint 1, rotate one bone
 //     onto z and one onto x) of N samples, one workgroup per sample, written in the model's (N, 3, T, V, K) layout.
 //
+//   * agcn_prenorm_windows: the same kernel, second instantiation, with per-sample addressing read on the device: sample
+//     n is the window (block[n], start[n], len[n]) of a pool of (M, Tmax, V, 3) blocks.  The windows may be any
+//     positions of one long recording or the current windows of many rings.
+//   * agcn_skel_smooth: a whole recording (L, Mmax, V, 3) -> (Mmax, L, V, 3) with the moving average of agcn_skel_append
+//     run over all its frames, and agcn_skel_append_many: one frame into each of S rings in one launch.
+//
 // Logical frame t of a sample lives in slot (origin + t) mod Tmax of its (M, Tmax, V, 3) block: a ring passes its oldest
-// slot, a plain (N, M, T, V, 3) tensor passes origin 0 and Tmax = T.
+// slot, a plain (N, M, T, V, 3) tensor passes origin 0 and Tmax = T.  A window has len <= T frames; frames t >= len are
+// null: they read as zeros and no memory is touched (in a recording the slots behind a window hold future frames).
+// Every read of a frame goes through one helper (Frames::load3) that knows this.
 //
 // Null tests: a frame (joint) is null iff ALL its 3V (3) values are zero; the reference tests sum() == 0, which differs
 // only where a non-null frame or joint sums to exactly zero by cancellation.
@@ -23,13 +31,16 @@
 #define PRENORM_THREADS 1024
 #define PRENORM_WAVES (PRENORM_THREADS / 64)
 #define PRENORM_FLAG_WORDS (PRENORM_MAX_T / 32)
+#define SMOOTH_THREADS 64
+#define SMOOTH_CHIP 32            // earlier outputs agcn_skel_smooth keeps in LDS per value (k - 1 <= 32)
+#define SMOOTH_AHEAD 8            // raw frames loaded ahead of the serial recursion
 
 namespace {
 
-__global__ void __launch_bounds__(256) skel_append_kernel(const float* __restrict__ frame, float* __restrict__ ring,
-                                                          int Mmax, int Tmax, int V, int slot, int count, int k) {
+// one value e of one ring: the arithmetic of agcn_skel_append, shared by the one-ring and the many-ring kernel
+__device__ __forceinline__ void append_value(const float* __restrict__ frame, float* __restrict__ ring, int e, int Mmax,
+                                             int Tmax, int V, int slot, int count, int k) {
   const int row = V * 3;
-  const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= Mmax * row) return;
   const int m = e / row, j = e - m * row;
   float* body = ring + (long)m * Tmax * row;
@@ -49,10 +60,87 @@ __global__ void __launch_bounds__(256) skel_append_kernel(const float* __restric
   body[(long)slot * row + j] = val;
 }
 
+__global__ void __launch_bounds__(256) skel_append_kernel(const float* __restrict__ frame, float* __restrict__ ring,
+                                                          int Mmax, int Tmax, int V, int slot, int count, int k) {
+  append_value(frame, ring, blockIdx.x * 256 + threadIdx.x, Mmax, Tmax, V, slot, count, k);
+}
+
+// stream blockIdx.y: its frame into its ring at slot[s] (< 0: no frame this tick), with count[s] frames present
+__global__ void __launch_bounds__(256) skel_append_many_kernel(const float* __restrict__ frames, float* __restrict__ rings,
+                                                               const int* __restrict__ slot, const int* __restrict__ count,
+                                                               int Mmax, int Tmax, int V, int k) {
+  const int s = blockIdx.y;
+  const int sl = slot[s];
+  if (sl < 0) return;
+  const long per = (long)Mmax * V * 3;
+  append_value(frames + s * per, rings + s * per * Tmax, blockIdx.x * 256 + threadIdx.x, Mmax, Tmax, V,
+               min(sl, Tmax - 1), min(max(count[s], 1), Tmax), k);
+}
+
+// k = 1: raw (L, E) -> out (Mmax, L, row), E = Mmax * row
+__global__ void __launch_bounds__(256) skel_transpose_kernel(const float* __restrict__ raw, float* __restrict__ out,
+                                                             int Mmax, int L, int row) {
+  const long total = (long)L * Mmax * row;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int E = Mmax * row;
+  const int t = (int)(i / E), e = (int)(i - (long)t * E);
+  const int m = e / row, j = e - m * row;
+  out[((long)m * L + t) * row + j] = raw[i];
+}
+
+// k > 1: one thread per value, serial in t.  The k - 1 earlier outputs of the value are a circular history: in LDS
+// (CHIP) or, for k - 1 > SMOOTH_CHIP, the thread's own earlier stores to `out`, read back.  Summed oldest first, the raw
+// frame last, from 0.f, then / k: the expression of append_value.
+template <bool CHIP>
+__global__ void __launch_bounds__(SMOOTH_THREADS) skel_smooth_kernel(const float* __restrict__ raw, float* out, int Mmax,
+                                                                     int L, int row, int k) {
+  __shared__ float hist[CHIP ? SMOOTH_CHIP : 1][SMOOTH_THREADS];
+  const int E = Mmax * row, lane = threadIdx.x;
+  const int e = blockIdx.x * SMOOTH_THREADS + lane;
+  if (e >= E) return;                            // no barrier below: a thread reads only what it wrote itself
+  const int m = e / row, j = e - m * row;
+  float* mine = out + (long)m * L * row + j;     // mine[t * row]
+  const int H = k - 1;
+  int pos = 0;                                   // t mod H: the oldest entry of the history, overwritten by frame t
+  for (int t0 = 0; t0 < L; t0 += SMOOTH_AHEAD) {
+    float r[SMOOTH_AHEAD];
+#pragma unroll
+    for (int i = 0; i < SMOOTH_AHEAD; ++i) r[i] = t0 + i < L ? raw[(long)(t0 + i) * E + e] : 0.f;
+#pragma unroll
+    for (int i = 0; i < SMOOTH_AHEAD; ++i) {
+      const int t = t0 + i;
+      if (t >= L) break;
+      float val = r[i];
+      if (t >= H) {
+        float s = 0.f;
+        if (CHIP) {
+          int p = pos;
+          for (int q = 0; q < H; ++q) {
+            s += hist[p][lane];
+            if (++p == H) p = 0;
+          }
+        } else {
+          for (int q = t - H; q < t; ++q) s += mine[(long)q * row];
+        }
+        s += val;
+        val = s / (float)k;
+      }
+      mine[(long)t * row] = val;
+      if (CHIP) {
+        hist[pos][lane] = val;
+        if (++pos == H) pos = 0;
+      }
+    }
+  }
+}
+
 __device__ __forceinline__ double wave_sum(double v) {
   for (int k = 32; k >= 1; k >>= 1) v += __shfl_xor(v, k);
   return v;
 }
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 struct PrenormArgs {
   const float* in;
@@ -61,9 +149,46 @@ struct PrenormArgs {
   float* energy;
   int M, K, T, Tmax, origin, V, select, pad, center;
   int z0, z1, x0, x1, zz0, zz1;
+  const int* block;                 // windows only: (N) block of the pool, or NULL = block 0; (N) first slot; (N) frames
+  const int* start;
+  const int* len;
+  int nblocks;
 };
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+// The frames of one sample.  WINDOWS = false: block n of the input, origin and T from the host (agcn_prenorm).
+// WINDOWS = true: block, first slot and length from the device arrays, clamped into the pool; frames t >= len are null.
+template <bool WINDOWS>
+struct Frames {
+  const float* in;                  // the sample's (M, Tmax, V, 3) block
+  long body_stride;
+  int Tmax, row, origin, len;
+
+  __device__ Frames(const PrenormArgs& a, int n) : body_stride((long)a.Tmax * a.V * 3), Tmax(a.Tmax), row(a.V * 3) {
+    int blk = n;
+    origin = a.origin;
+    len = a.T;
+    if (WINDOWS) {
+      blk = a.block ? clampi(a.block[n], 0, a.nblocks - 1) : 0;
+      origin = clampi(a.start[n], 0, a.Tmax - 1);
+      len = clampi(a.len[n], 0, a.T);
+    }
+    in = a.in + (long)blk * a.M * body_stride;
+  }
+  __device__ __forceinline__ int slot_of(int t) const {      // ring slot of logical frame t, clamped into the block
+    int s = origin + t;
+    if (s >= Tmax) s -= Tmax;
+    return clampi(s, 0, Tmax - 1);
+  }
+  // joint j of logical frame t of body m: THE read of a frame (flags, energy, centre / rotation, gather)
+  __device__ __forceinline__ void load3(int m, int t, int j, float& x0, float& x1, float& x2) const {
+    if (WINDOWS && t >= len) {
+      x0 = x1 = x2 = 0.f;
+      return;
+    }
+    const float* q = in + m * body_stride + (long)slot_of(t) * row + j * 3;
+    x0 = q[0]; x1 = q[1]; x2 = q[2];
+  }
+};
 
 // reference data_gen/rotation.py angle_between + rotation_matrix for the rotation that takes v onto the unit axis e
 // (e = z: ez = 1, e = x: ez = 0), in fp64: R (row major)
@@ -96,6 +221,7 @@ __device__ void matmul3(const double A[9], const double B[9], double C[9]) {
     for (int j = 0; j < 3; ++j) C[i * 3 + j] = A[i * 3] * B[j] + A[i * 3 + 1] * B[3 + j] + A[i * 3 + 2] * B[6 + j];
 }
 
+template <bool WINDOWS>
 __global__ void __launch_bounds__(PRENORM_THREADS) prenorm_kernel(PrenormArgs a) {
   __shared__ unsigned flags[PRENORM_MAX_M][PRENORM_FLAG_WORDS];     // bit t of body m: frame t has a non-zero value
   __shared__ unsigned short src[PRENORM_MAX_M][PRENORM_MAX_T];      // source frame of output frame t, per selected body
@@ -107,15 +233,9 @@ __global__ void __launch_bounds__(PRENORM_THREADS) prenorm_kernel(PrenormArgs a)
   __shared__ float rot_s[9];
 
   const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int M = a.M, K = a.K, T = a.T, V = a.V, row = a.V * 3;
-  const long body_stride = (long)a.Tmax * row;
-  const float* in = a.in + (long)n * M * body_stride;
+  const int M = a.M, K = a.K, T = a.T, V = a.V;
+  const Frames<WINDOWS> fr(a, n);
   const int TV = T * V;
-  auto slot_of = [&](int t) {                    // ring slot of logical frame t, clamped into the block
-    int s = a.origin + t;
-    if (s >= a.Tmax) s -= a.Tmax;
-    return clampi(s, 0, a.Tmax - 1);
-  };
   auto valid = [&](int m, int t) { return (flags[m][t >> 5] >> (t & 31)) & 1u; };
 
   for (int i = tid; i < PRENORM_MAX_M * PRENORM_FLAG_WORDS; i += PRENORM_THREADS) (&flags[0][0])[i] = 0u;
@@ -123,11 +243,11 @@ __global__ void __launch_bounds__(PRENORM_THREADS) prenorm_kernel(PrenormArgs a)
 
   // ---- frame flags of every body ------------------------------------------------------------------------------------
   for (int m = 0; m < M; ++m) {
-    const float* body = in + m * body_stride;
     for (int p = tid; p < TV; p += PRENORM_THREADS) {
       const int t = p / V, v = p - t * V;
-      const float* q = body + (long)slot_of(t) * row + v * 3;
-      if (q[0] != 0.f || q[1] != 0.f || q[2] != 0.f) atomicOr(&flags[m][t >> 5], 1u << (t & 31));
+      float q0, q1, q2;
+      fr.load3(m, t, v, q0, q1, q2);
+      if (q0 != 0.f || q1 != 0.f || q2 != 0.f) atomicOr(&flags[m][t >> 5], 1u << (t & 31));
     }
   }
   __syncthreads();
@@ -136,14 +256,14 @@ __global__ void __launch_bounds__(PRENORM_THREADS) prenorm_kernel(PrenormArgs a)
   if (a.select) {
     for (int pass = 0; pass < 2; ++pass) {
       for (int m = 0; m < M; ++m) {
-        const float* body = in + m * body_stride;
         double s0 = 0.0, s1 = 0.0, s2 = 0.0;
         const double m0 = pass ? mean[m][0] : 0.0, m1 = pass ? mean[m][1] : 0.0, m2 = pass ? mean[m][2] : 0.0;
         for (int p = tid; p < TV; p += PRENORM_THREADS) {
           const int t = p / V, v = p - t * V;
           if (!valid(m, t)) continue;
-          const float* q = body + (long)slot_of(t) * row + v * 3;
-          const double d0 = (double)q[0] - m0, d1 = (double)q[1] - m1, d2 = (double)q[2] - m2;
+          float q0, q1, q2;
+          fr.load3(m, t, v, q0, q1, q2);
+          const double d0 = (double)q0 - m0, d1 = (double)q1 - m1, d2 = (double)q2 - m2;
           if (pass) { s0 += d0 * d0; s1 += d1 * d1; s2 += d2 * d2; }
           else { s0 += d0; s1 += d1; s2 += d2; }
         }
@@ -232,20 +352,19 @@ __global__ void __launch_bounds__(PRENORM_THREADS) prenorm_kernel(PrenormArgs a)
 
   // ---- centre of frame 0 and the rotations, one lane, fp64 -----------------------------------------------------------
   const int b0 = clampi(sel_s[0], 0, M - 1);
-  const float* body0 = in + b0 * body_stride;
+  // joint 1 of the first body's first non-null frame (center == 2)
+  auto first_centre = [&](float o[3]) {
+    fr.load3(b0, clampi((int)src[0][clampi(first_s, 0, T - 1)], 0, T - 1), 1, o[0], o[1], o[2]);
+  };
   if (tid == 0) {
     const int f0 = clampi((int)src[0][0], 0, T - 1);
-    const float* fr = body0 + (long)slot_of(f0) * row;
     float c0[3] = {0.f, 0.f, 0.f};
-    if (a.center == 1) {
-      for (int c = 0; c < 3; ++c) c0[c] = fr[3 + c];
-    } else if (a.center == 2 && first_s >= 0) {
-      const float* ff = body0 + (long)slot_of(clampi((int)src[0][clampi(first_s, 0, T - 1)], 0, T - 1)) * row;
-      for (int c = 0; c < 3; ++c) c0[c] = ff[3 + c];
-    }
+    if (a.center == 1) fr.load3(b0, f0, 1, c0[0], c0[1], c0[2]);
+    else if (a.center == 2 && first_s >= 0) first_centre(c0);
     // centred, masked joints of the first body's frame 0, as the reference holds them (fp32) when it builds a matrix
     auto joint = [&](int j, float o[3]) {
-      const float* q = fr + clampi(j, 0, V - 1) * 3;
+      float q[3];
+      fr.load3(b0, f0, clampi(j, 0, V - 1), q[0], q[1], q[2]);
       const bool nz = q[0] != 0.f || q[1] != 0.f || q[2] != 0.f;
       for (int c = 0; c < 3; ++c) o[c] = nz ? q[c] - c0[c] : 0.f;
     };
@@ -274,22 +393,16 @@ __global__ void __launch_bounds__(PRENORM_THREADS) prenorm_kernel(PrenormArgs a)
   float R[9];
   for (int i = 0; i < 9; ++i) R[i] = rot_s[i];
   float cf[3] = {0.f, 0.f, 0.f};
-  if (a.center == 2 && first_s >= 0) {
-    const float* ff = body0 + (long)slot_of(clampi((int)src[0][clampi(first_s, 0, T - 1)], 0, T - 1)) * row;
-    for (int c = 0; c < 3; ++c) cf[c] = ff[3 + c];
-  }
+  if (a.center == 2 && first_s >= 0) first_centre(cf);
   float* out = a.out + (long)n * 3 * TV * K;
   for (int p = tid; p < TV; p += PRENORM_THREADS) {
     const int t = p / V, v = p - t * V;
     float ctr[3] = {cf[0], cf[1], cf[2]};
-    if (a.center == 1) {
-      const float* q = body0 + (long)slot_of(clampi((int)src[0][t], 0, T - 1)) * row + 3;
-      for (int c = 0; c < 3; ++c) ctr[c] = q[c];
-    }
+    if (a.center == 1) fr.load3(b0, clampi((int)src[0][t], 0, T - 1), 1, ctr[0], ctr[1], ctr[2]);
     for (int k = 0; k < K; ++k) {
       const int m = clampi(sel_s[k], 0, M - 1);
-      const float* q = in + m * body_stride + (long)slot_of(clampi((int)src[k][t], 0, T - 1)) * row + v * 3;
-      const float x0 = q[0], x1 = q[1], x2 = q[2];
+      float x0, x1, x2;
+      fr.load3(m, clampi((int)src[k][t], 0, T - 1), v, x0, x1, x2);
       const bool nz = x0 != 0.f || x1 != 0.f || x2 != 0.f;
       const float d0 = nz ? x0 - ctr[0] : 0.f, d1 = nz ? x1 - ctr[1] : 0.f, d2 = nz ? x2 - ctr[2] : 0.f;
       for (int c = 0; c < 3; ++c)
@@ -328,6 +441,55 @@ extern "C" int agcn_prenorm(const float* in, float* out, int* sel, float* energy
   a.M = M; a.K = K; a.T = T; a.Tmax = Tmax; a.origin = origin; a.V = V;
   a.select = select ? 1 : 0; a.pad = pad ? 1 : 0; a.center = center;
   a.z0 = z0; a.z1 = z1; a.x0 = x0; a.x1 = x1; a.zz0 = zz0; a.zz1 = zz1;
-  prenorm_kernel<<<N, PRENORM_THREADS, 0, (hipStream_t)stream>>>(a);
+  a.block = a.start = a.len = nullptr;
+  a.nblocks = N;
+  prenorm_kernel<false><<<N, PRENORM_THREADS, 0, (hipStream_t)stream>>>(a);
+  return agcn_check_launch();
+}
+
+extern "C" int agcn_prenorm_windows(const float* in, float* out, int* sel, float* energy, const int* block,
+                                    const int* start, const int* len, int N, int nblocks, int M, int K, int T, int Tmax,
+                                    int V, int select, int pad, int center, int z0, int z1, int x0, int x1, int zz0,
+                                    int zz1, void* stream) {
+  if (!in || !out || !sel || (select && !energy) || !start || !len) return AGCN_ERR_ARG;
+  if (N < 1 || nblocks < 1 || M < 1 || M > PRENORM_MAX_M || K < 1 || K > M) return AGCN_ERR_ARG;
+  if (V < 2 || V > 32 || T < 1 || T > PRENORM_MAX_T || Tmax < T) return AGCN_ERR_ARG;
+  if (center < 0 || center > 2) return AGCN_ERR_ARG;
+  if (!axis_ok(z0, z1, V) || !axis_ok(x0, x1, V) || !axis_ok(zz0, zz1, V)) return AGCN_ERR_ARG;
+  PrenormArgs a;
+  a.in = in; a.out = out; a.sel = sel; a.energy = energy;
+  a.M = M; a.K = K; a.T = T; a.Tmax = Tmax; a.origin = 0; a.V = V;
+  a.select = select ? 1 : 0; a.pad = pad ? 1 : 0; a.center = center;
+  a.z0 = z0; a.z1 = z1; a.x0 = x0; a.x1 = x1; a.zz0 = zz0; a.zz1 = zz1;
+  a.block = block; a.start = start; a.len = len; a.nblocks = nblocks;
+  prenorm_kernel<true><<<N, PRENORM_THREADS, 0, (hipStream_t)stream>>>(a);
+  return agcn_check_launch();
+}
+
+extern "C" int agcn_skel_smooth(const float* raw, float* out, int Mmax, int L, int V, int k, void* stream) {
+  if (!raw || !out) return AGCN_ERR_ARG;
+  if (Mmax < 1 || L < 1 || V < 1 || V > 32 || k < 1 || k > L) return AGCN_ERR_ARG;
+  const int row = V * 3, E = Mmax * row;
+  if (k == 1) {
+    const long total = (long)L * E;
+    if ((total + 255) / 256 > 0x7fffffffL) return AGCN_ERR_ARG;
+    skel_transpose_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(raw, out, Mmax, L, row);
+  } else if (k - 1 <= SMOOTH_CHIP) {
+    skel_smooth_kernel<true><<<(E + SMOOTH_THREADS - 1) / SMOOTH_THREADS, SMOOTH_THREADS, 0, (hipStream_t)stream>>>(
+        raw, out, Mmax, L, row, k);
+  } else {
+    skel_smooth_kernel<false><<<(E + SMOOTH_THREADS - 1) / SMOOTH_THREADS, SMOOTH_THREADS, 0, (hipStream_t)stream>>>(
+        raw, out, Mmax, L, row, k);
+  }
+  return agcn_check_launch();
+}
+
+extern "C" int agcn_skel_append_many(const float* frames, float* rings, const int* slot, const int* count, int S,
+                                     int Mmax, int Tmax, int V, int k, void* stream) {
+  if (!frames || !rings || !slot || !count) return AGCN_ERR_ARG;
+  if (S < 1 || S > 65535 || Mmax < 1 || Tmax < 1 || V < 1 || V > 32 || k < 1 || k > Tmax) return AGCN_ERR_ARG;
+  const int total = Mmax * V * 3;
+  skel_append_many_kernel<<<dim3((total + 255) / 256, S), 256, 0, (hipStream_t)stream>>>(frames, rings, slot, count, Mmax,
+                                                                                       Tmax, V, k);
   return agcn_check_launch();
 }

@@ -107,6 +107,9 @@ SIGNATURES = {
     "agcn_prenorm_max_frames": (_I, []),
     "agcn_skel_append": (_I, [_P, _P] + [_I] * 6 + [_P]),
     "agcn_prenorm": (_I, [_P] * 4 + [_I] * 16 + [_P]),
+    "agcn_prenorm_windows": (_I, [_P] * 7 + [_I] * 16 + [_P]),
+    "agcn_skel_smooth": (_I, [_P, _P] + [_I] * 4 + [_P]),
+    "agcn_skel_append_many": (_I, [_P] * 4 + [_I] * 5 + [_P]),
 }
 
 _lib = None

@@ -7,6 +7,9 @@ Per frame: one host-to-device copy of the frame and one launch (``ops.skel_appen
 selection + normalisation (``ops.prenorm``), the folded eval forward, softmax/argmax, and one device-to-host copy of the
 scores and the label, which is the only synchronisation.
 
+``RecordingRecognition`` labels a whole recording and ``MultiStreamRecognition`` serves several streams: both normalise
+many windows in one launch (``ops.prenorm_windows``) and run them through the model as one batch.
+
 The frame handed to ``append_data`` always carries exactly ``max_num_skeleton`` bodies (absent ones as zeros), as the
 reference's main loop does; its ``M < max_person`` case, which leaves stale rows in the window, is not reproduced."""
 import numpy as np
@@ -27,7 +30,33 @@ def load_model(model, model_args=None, weights=None):
     return net
 
 
-class ActionRecognition:
+def window_plan(L, T, ends):
+    """The windows of a recording of ``L`` frames that a recogniser with a window of ``T`` frames holds after appending
+    frame ``ends[i]``: -> (start, len) int32 arrays, start = max(0, end - T + 1), len = end - start + 1 (below T while
+    the window fills).  Pure host arithmetic."""
+    ends = np.asarray(ends, dtype=np.int64).reshape(-1)
+    if L < 1 or T < 1:
+        raise ValueError("agcn_amd: window_plan needs L >= 1 and T >= 1")
+    if ends.size and (ends.min() < 0 or ends.max() >= L):
+        raise ValueError(f"agcn_amd: window_plan takes frame indices in [0, {L}), got {ends.min()}..{ends.max()}")
+    start = np.maximum(0, ends - T + 1)
+    return start.astype(np.int32), (ends - start + 1).astype(np.int32)
+
+
+def window_plan_device(L, T, device, interval=1, first=0):
+    """``window_plan`` for ends = first, first + interval, ... < L, built on the device: nothing is uploaded.
+    -> (start, len, ends) int32 tensors."""
+    if L < 1 or T < 1 or interval < 1 or not 0 <= first < L:
+        raise ValueError("agcn_amd: window_plan_device needs L >= 1, T >= 1, interval >= 1 and 0 <= first < L")
+    ends = torch.arange(first, L, interval, dtype=torch.int32, device=device)
+    start = torch.clamp(ends - (T - 1), min=0)
+    return start, ends - start + 1, ends
+
+
+class _Recogniser:
+    """What the recognisers share: the model in eval mode on the device, the window geometry and the normalisation
+    options."""
+
     def __init__(self, model, model_args=None, weights=None, max_frame=300, max_num_skeleton=4,
                  max_num_skeleton_true=2, num_joint=25, moving_avg=1, zaxis=(0, 1), xaxis=(8, 4), zaxis2=None,
                  device='cuda:0'):
@@ -42,11 +71,41 @@ class ActionRecognition:
         self.max_frame, self.max_person, self.num_select = int(max_frame), int(max_num_skeleton), int(max_num_skeleton_true)
         self.num_joint, self.moving_avg = int(num_joint), int(moving_avg)
         self.zaxis, self.xaxis, self.zaxis2 = zaxis, xaxis, zaxis2
+        # what the last prediction left on the device: the normalised windows (N, 3, T, V, K), the selected bodies
+        # (N, K) int32, the energies (N, Mmax) and the logits (N, num_class)
+        self.window = self.selected = self.energy = self.logits = None
+
+    def forward(self, window):
+        """The model in eval mode under no_grad (the folded path) -> (logits, scores, label) on the device; no sync."""
+        with torch.no_grad(), torch.cuda.device(self.device):
+            out = self.model(window)
+            self.logits = out[0] if isinstance(out, tuple) else out
+            scores = torch.softmax(self.logits, 1)
+            return self.logits, scores, torch.argmax(scores, 1)
+
+    def _frames(self, frames, lead, what):
+        """``frames`` (lead, max_num_skeleton, [1,] V, 3), numpy array or tensor, ``lead`` None for any length ->
+        contiguous fp32 (lead, max_num_skeleton, V, 3) on the device: the one upload."""
+        body = (self.max_person, self.num_joint, 3)
+        shape = tuple(frames.shape)
+        n = shape[0] if shape else 0
+        if n < 1 or (lead is not None and n != lead) or shape[1:] not in (body, body[:1] + (1,) + body[1:]):
+            first = 'L' if lead is None else lead
+            raise ValueError(f"agcn_amd: {what} takes frames of shape {(first, body[0], 1) + body[1:]} or "
+                             f"{(first,) + body} (absent bodies as zeros), got {shape}")
+        if isinstance(frames, np.ndarray):
+            frames = torch.from_numpy(np.ascontiguousarray(frames, dtype=np.float32))
+        return frames.to(device=self.device, dtype=torch.float32).reshape((n,) + body).contiguous()
+
+    def _options(self):
+        return dict(num_select=self.num_select, zaxis=self.zaxis, xaxis=self.xaxis, zaxis2=self.zaxis2)
+
+
+class ActionRecognition(_Recogniser):
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
         self.ring = torch.zeros((self.max_person, self.max_frame, self.num_joint, 3), dtype=torch.float32,
                                 device=self.device)
-        # what the last predict() left on the device: the normalised window (1, 3, T, V, K), the selected bodies (1, K)
-        # int32, the energies (1, Mmax) and the logits (1, num_class)
-        self.window = self.selected = self.energy = self.logits = None
         self.reset()
 
     def reset(self):
@@ -81,16 +140,146 @@ class ActionRecognition:
                 zaxis2=self.zaxis2)
         return self.window
 
-    def forward(self, window):
-        """The model in eval mode under no_grad (the folded path) -> (logits, scores, label) on the device; no sync."""
-        with torch.no_grad(), torch.cuda.device(self.device):
-            out = self.model(window)
-            self.logits = out[0] if isinstance(out, tuple) else out
-            scores = torch.softmax(self.logits, 1)
-            return self.logits, scores, torch.argmax(scores, 1)
-
     def predict(self):
         """-> (softmax scores of the current window as a list, label)."""
         _, scores, label = self.forward(self.normalize())
         both = torch.cat((scores[0], label.to(scores.dtype))).cpu()      # the one synchronising copy
         return both[:-1].tolist(), int(both[-1].item())
+
+
+def _fetch(scores, labels):
+    """(P, C) scores and (P,) labels on the device -> numpy (P, C) fp32 and (P,) int64 in one synchronising copy."""
+    both = torch.cat((scores, labels.to(scores.dtype).unsqueeze(1)), 1).cpu().numpy()
+    return both[:, :-1].copy(), both[:, -1].astype(np.int64)
+
+
+class RecordingRecognition(_Recogniser):
+    """Labels a whole recording: the window ``ActionRecognition`` holds after appending frame ``end``, for many ``end``
+    at once.  One upload of the recording, one ``ops.skel_smooth``, then per batch of at most ``batch`` windows one
+    ``ops.prenorm_windows`` and one eval forward; the scores of all batches come to the host in one copy."""
+
+    def __init__(self, *args, batch=64, **kwargs):
+        super().__init__(*args, **kwargs)
+        if batch < 1:
+            raise ValueError("agcn_amd: need batch >= 1")
+        self.batch = int(batch)
+        self.smoothed = None      # (max_num_skeleton, max(L, max_frame), V, 3): the recording as a ring would hold it
+
+    def prepare(self, frames):
+        """Upload + moving average -> the pool (1, Mmax, Lp, V, 3) the window kernel reads, Lp = max(L, max_frame): a
+        recording shorter than the window is followed by zero frames, which no window reaches (len <= end + 1)."""
+        raw = self._frames(frames, None, 'label')
+        L = raw.shape[0]
+        if self.moving_avg > L:
+            raise ValueError(f"agcn_amd: a recording of {L} frames is shorter than moving_avg = {self.moving_avg}")
+        if L < self.max_frame:
+            raw = torch.cat((raw, raw.new_zeros((self.max_frame - L,) + tuple(raw.shape[1:]))))
+        with torch.cuda.device(self.device):
+            self.smoothed = ops.skel_smooth(raw, self.moving_avg)
+        return self.smoothed.unsqueeze(0), L
+
+    def normalize(self, pool, start, length):
+        """Selection + normalisation of the windows (start, length) -> (N, 3, max_frame, V, K) on the device; no sync."""
+        with torch.cuda.device(self.device):
+            self.window, self.selected, self.energy = ops.prenorm_windows(pool, start, length, frames=self.max_frame,
+                                                                          **self._options())
+        return self.window
+
+    def label(self, frames, interval=1, first=0, ends=None):
+        """frames (L, max_num_skeleton, [1,] V, 3), numpy array or tensor.  Predicts after frames first, first + interval,
+        ... (or after the frames listed in ``ends``, in any order) -> (scores (P, num_class) fp32, labels (P,) int64,
+        ends (P,) int64) as numpy arrays.  The logits of all P windows stay on the device in ``self.logits``; window,
+        selected and energy are those of the last batch."""
+        pool, L = self.prepare(frames)
+        if ends is None:
+            start, length, _ = window_plan_device(L, self.max_frame, self.device, interval, first)
+            ends = np.arange(first, L, interval, dtype=np.int64)
+        else:
+            ends = np.asarray(ends, dtype=np.int64).reshape(-1)
+            plan = np.stack(window_plan(L, self.max_frame, ends))
+            start, length = torch.from_numpy(plan).to(self.device)         # one small upload for an explicit list
+        if not len(ends):
+            raise ValueError("agcn_amd: label needs at least one window")
+        logits, scores, labels = [], [], []
+        for b in range(0, len(ends), self.batch):
+            win = self.normalize(pool, start[b:b + self.batch], length[b:b + self.batch])
+            lg, sc, lb = self.forward(win)
+            logits.append(lg)
+            scores.append(sc)
+            labels.append(lb)
+        self.logits = torch.cat(logits)
+        scores, labels = _fetch(torch.cat(scores), torch.cat(labels))    # the one synchronising copy
+        return scores, labels, ends
+
+
+class MultiStreamRecognition(_Recogniser):
+    """``num_streams`` independent streams on one device: one ring each, one launch per tick for all of them
+    (``ops.skel_append_many``) and one batch per prediction (``ops.prenorm_windows`` over the rings, block = the stream,
+    start = its oldest slot, len = its frame count).  The host keeps (count, head) per stream."""
+
+    def __init__(self, model, num_streams, *args, **kwargs):
+        super().__init__(model, *args, **kwargs)
+        if num_streams < 1:
+            raise ValueError("agcn_amd: need num_streams >= 1")
+        self.num_streams = int(num_streams)
+        self.rings = torch.zeros((self.num_streams, self.max_person, self.max_frame, self.num_joint, 3),
+                                 dtype=torch.float32, device=self.device)
+        self.streams = []         # the streams of the last predict(), in the order of its rows
+        self.reset()
+
+    def reset(self):
+        self.rings.zero_()
+        self.counter = np.zeros(self.num_streams, dtype=np.int32)      # frames present, at most max_frame
+        self.head = np.zeros(self.num_streams, dtype=np.int32)         # oldest slot once a ring is full
+
+    def append_data(self, frames, present=None):
+        """frames (S, max_num_skeleton, [1,] V, 3), numpy array or tensor; ``present`` a host bool mask (S,), None =
+        every stream has a frame this tick.  One frame upload, one index upload, one launch."""
+        S = self.num_streams
+        frames = self._frames(frames, S, 'append_data')
+        present = np.ones(S, dtype=bool) if present is None else np.asarray(present, dtype=bool).reshape(-1)
+        if present.shape != (S,):
+            raise ValueError(f"agcn_amd: present is a mask of length {S}, got {present.shape}")
+        filling = present & (self.counter < self.max_frame)
+        full = present & ~filling
+        slot = np.where(filling, self.counter, np.where(full, self.head, -1)).astype(np.int32)
+        self.counter = self.counter + filling
+        self.head = np.where(full, (self.head + 1) % self.max_frame, self.head).astype(np.int32)
+        index = torch.from_numpy(np.stack((slot, self.counter.astype(np.int32)))).to(self.device)
+        with torch.cuda.device(self.device):
+            ops.skel_append_many(self.rings, frames, index[0], index[1], self.moving_avg)
+
+    def plan(self, streams=None):
+        """-> (streams that have frames, (3, N) int32 host plan: block, start, len)."""
+        ids = range(self.num_streams) if streams is None else [int(s) for s in streams]
+        if any(not 0 <= s < self.num_streams for s in ids):
+            raise ValueError(f"agcn_amd: streams are numbered 0..{self.num_streams - 1}")
+        ids = np.asarray([s for s in ids if self.counter[s] > 0], dtype=np.int32)
+        count = self.counter[ids]
+        start = np.where(count == self.max_frame, self.head[ids], 0)
+        return ids, np.stack((ids, start, count)).astype(np.int32)
+
+    def normalize(self, streams=None):
+        """Selection + normalisation of the streams' current windows -> (S', 3, max_frame, V, K) on the device, None if
+        no stream has a frame yet; no sync."""
+        ids, plan = self.plan(streams)
+        self.streams = ids.tolist()
+        if not len(ids):
+            self.window = self.selected = self.energy = None
+            return None
+        block, start, length = torch.from_numpy(plan).to(self.device)
+        with torch.cuda.device(self.device):
+            self.window, self.selected, self.energy = ops.prenorm_windows(self.rings, start, length, block=block,
+                                                                          **self._options())
+        return self.window
+
+    def predict(self, streams=None):
+        """-> (scores (S', num_class) fp32, labels (S',) int64, streams (S',)) for the streams (default: all) that have
+        received a frame, as numpy arrays."""
+        win = self.normalize(streams)
+        if win is None:
+            self.logits = None
+            return np.zeros((0, 0), dtype=np.float32), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+        _, scores, labels = self.forward(win)
+        scores, labels = _fetch(scores, labels)                          # the one synchronising copy
+        return scores, labels, np.asarray(self.streams, dtype=np.int64)

@@ -1295,6 +1295,83 @@ def prenorm(x, num_select=None, origin=0, frames=None, zaxis=(0, 1), zaxis2=None
     return out, sel, energy
 
 
+def _plan(t, n, what):
+    """An (n,) int32 index array of a plan (None passes through); the device is checked where its pointer is taken."""
+    if t is not None and (t.dim() != 1 or t.dtype != torch.int32 or (n is not None and t.numel() != n)):
+        raise ValueError(f"agcn_amd: {what} must be a 1-D int32 tensor" + (f" of length {n}" if n is not None else "")
+                         + f", got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def prenorm_windows(pool, start, length, block=None, frames=None, num_select=None, zaxis=(0, 1), zaxis2=None,
+                    xaxis=(8, 4), pad=True, center=True, center_firstframe=False):
+    """``prenorm`` of N windows of a pool (nblocks, M, Tmax, V, 3) in one launch (agcn_prenorm_windows): window n is
+    ``length[n]`` frames from slot ``start[n]`` (wrapping at Tmax) of block ``block[n]`` (None: block 0), the frames
+    after them null whatever the pool holds there.  start / length / block: int32 tensors (N,) on the device, clamped
+    into the pool by the kernel.  ``frames`` T (the window length of the output) defaults to Tmax.  Returns what
+    ``prenorm`` returns, with the same bits for the same logical window."""
+    if (center or center_firstframe) and center == center_firstframe:
+        raise ValueError("agcn_amd: center and center_firstframe exclude each other")
+    if pool.dim() != 5 or pool.shape[-1] != 3:
+        raise ValueError(f"agcn_amd: prenorm_windows takes a pool (nblocks, M, Tmax, V, 3), got {tuple(pool.shape)}")
+    nblocks, M, Tmax, V, _ = pool.shape
+    T = Tmax if frames is None else int(frames)
+    if not 1 <= T <= Tmax:
+        raise ValueError(f"agcn_amd: prenorm_windows needs 1 <= frames <= Tmax = {Tmax}, got {T}")
+    if start is None or length is None:
+        raise ValueError("agcn_amd: prenorm_windows needs start and length")
+    N = _plan(start, None, 'start').numel()
+    if N < 1:
+        raise ValueError("agcn_amd: prenorm_windows needs at least one window")
+    _plan(length, N, 'length')
+    _plan(block, N, 'block')
+    select = num_select is not None
+    K = int(num_select) if select else M
+    out = _empty((N, 3, T, V, K), pool)
+    sel = torch.empty((N, K), dtype=torch.int32, device=pool.device)
+    energy = _empty((N, M), pool) if select else None
+    (z0, z1), (x0, x1), (zz0, zz1) = _axis(zaxis), _axis(xaxis), _axis(zaxis2)
+    rc = _L().agcn_prenorm_windows(_lib.ptr(pool), _lib.ptr(out), _lib.ptr_bits(sel), _lib.ptr(energy),
+                                   _lib.ptr_bits(block), _lib.ptr_bits(start), _lib.ptr_bits(length), N, nblocks, M, K,
+                                   T, Tmax, V, 1 if select else 0, 1 if pad else 0,
+                                   1 if center else (2 if center_firstframe else 0), z0, z1, x0, x1, zz0, zz1,
+                                   _lib.stream())
+    _lib.check(rc, "agcn_prenorm_windows")
+    return out, sel, energy
+
+
+def skel_smooth(raw, moving_avg=1):
+    """A recording raw (L, Mmax, V, 3), time-major -> (Mmax, L, V, 3), body-major, with ``skel_append``'s recursive
+    moving average run over all its frames (agcn_skel_smooth): bit for bit what a ring holds after appending the frames
+    one by one.  ``moving_avg`` 1 is a transposing copy."""
+    if raw.dim() != 4 or raw.shape[-1] != 3:
+        raise ValueError(f"agcn_amd: skel_smooth takes a recording (L, Mmax, V, 3), got {tuple(raw.shape)}")
+    L, Mmax, V, _ = raw.shape
+    if not 1 <= int(moving_avg) <= L:
+        raise ValueError(f"agcn_amd: skel_smooth needs 1 <= moving_avg <= L = {L}, got {moving_avg}")
+    out = _empty((Mmax, L, V, 3), raw)
+    rc = _L().agcn_skel_smooth(_lib.ptr(raw), _lib.ptr(out), Mmax, L, V, int(moving_avg), _lib.stream())
+    _lib.check(rc, "agcn_skel_smooth")
+    return out
+
+
+def skel_append_many(rings, frames, slot, count, moving_avg=1):
+    """One frame into each of S rings in one launch (agcn_skel_append_many): rings (S, Mmax, Tmax, V, 3), frames
+    (S, Mmax, V, 3), slot / count int32 tensors (S,) on the device as ``skel_append`` takes them per ring; slot < 0
+    leaves that ring untouched."""
+    if rings.dim() != 5 or rings.shape[-1] != 3:
+        raise ValueError(f"agcn_amd: skel_append_many takes rings (S, Mmax, Tmax, V, 3), got {tuple(rings.shape)}")
+    S, Mmax, Tmax, V, _ = rings.shape
+    if tuple(frames.shape) != (S, Mmax, V, 3):
+        raise ValueError(f"agcn_amd: skel_append_many takes ({S}, {Mmax}, {V}, 3) frames for these rings, got "
+                         f"{tuple(frames.shape)}")
+    _plan(slot, S, 'slot')
+    _plan(count, S, 'count')
+    rc = _L().agcn_skel_append_many(_lib.ptr(frames), _lib.ptr(rings), _lib.ptr_bits(slot), _lib.ptr_bits(count), S, Mmax,
+                                    Tmax, V, int(moving_avg), _lib.stream())
+    _lib.check(rc, "agcn_skel_append_many")
+
+
 # ---- the autograd nodes ---------------------------------------------------------------------------------------------------
 class _Args:
     """The argument names of one autograd Function's forward, declared once next to it: the positions looked up in

@@ -401,12 +401,42 @@ int agcn_sgd_step(float* param, const float* grad, float* momentum_buf, long n, 
  *   product applied once in fp32.
  *   AGCN_ERR_ARG: null pointer, V < 2, V > 32, T < 1, T > agcn_prenorm_max_frames() (2048: the per-body source-frame
  *   table lives in LDS), Tmax < T, origin outside [0, Tmax), M > 8, K < 1, K > M, an axis joint outside [0, V) or a
- *   half-given pair.  Every gathered index is clamped in the kernel as well. */
+ *   half-given pair.  Every gathered index is clamped in the kernel as well.
+ *
+ * prenorm_windows: prenorm with per-sample addressing read on the device.  in = a pool of `nblocks` blocks
+ *   (M, Tmax, V, 3); block, start, len = device int32 arrays of length N (block NULL: block 0 for every sample).  For
+ *   t < len[n], logical frame t of sample n is slot (start[n] + t) mod Tmax of block block[n]; for t >= len[n] the frame
+ *   is null: it reads as zeros and no memory is touched, whatever the slot holds (in a recording: a future frame).  The
+ *   windows may overlap in any way: positions of one recording (nblocks 1, Tmax = its length), or the current windows of
+ *   many rings (block = the ring, start = its oldest slot, len = its frame count).  The kernel clamps block into
+ *   [0, nblocks), start into [0, Tmax) and len into [0, T], and every derived index as prenorm does: a wrong plan gives
+ *   a wrong number, never an out-of-range read.  Outputs, options, limits and error codes are prenorm's (start and len
+ *   may not be NULL); for the same logical window out, sel and energy are bit-identical to prenorm's.
+ *
+ * skel_smooth: a recording raw (L, Mmax, V, 3), time-major as frames arrive -> out (Mmax, L, V, 3), the layout the
+ *   window kernel reads.  k = 1: a transposing copy.  k > 1: skel_append's recursion over the whole recording:
+ *   out[t] = raw[t] while t + 1 < k, else (out[t-k+1] + ... + out[t-1] + raw[t]) / k, summed in that order in fp32:
+ *   bit-identical to appending the frames one by one to a ring of any size >= k.  Serial in t, one thread per value.
+ *   The k - 1 earlier outputs of a value are kept in LDS for k <= 33; beyond that the thread reads its own earlier
+ *   stores back from `out` (same sums, more latency per frame).  1 <= k <= L, V <= 32.
+ *
+ * skel_append_many: skel_append for S rings (S, Mmax, Tmax, V, 3) and frames (S, Mmax, V, 3) in one launch.  slot, count
+ *   = device int32 arrays of length S; slot[s] < 0: stream s has no frame this tick and its ring is untouched.  The
+ *   kernel clamps slot into [0, Tmax) and count into [1, Tmax]; arithmetic and bits per stream are skel_append's.
+ *   1 <= S <= 65535.
+ *
+ * None of these synchronises, allocates or copies to the host. */
 int agcn_prenorm_max_frames(void);
 int agcn_skel_append(const float* frame, float* ring, int Mmax, int Tmax, int V, int slot, int count, int k,
                      void* stream);
 int agcn_prenorm(const float* in, float* out, int* sel, float* energy, int N, int M, int K, int T, int Tmax, int origin,
                  int V, int select, int pad, int center, int z0, int z1, int x0, int x1, int zz0, int zz1, void* stream);
+int agcn_prenorm_windows(const float* in, float* out, int* sel, float* energy, const int* block, const int* start,
+                         const int* len, int N, int nblocks, int M, int K, int T, int Tmax, int V, int select, int pad,
+                         int center, int z0, int z1, int x0, int x1, int zz0, int zz1, void* stream);
+int agcn_skel_smooth(const float* raw, float* out, int Mmax, int L, int V, int k, void* stream);
+int agcn_skel_append_many(const float* frames, float* rings, const int* slot, const int* count, int S, int Mmax,
+                          int Tmax, int V, int k, void* stream);
 
 #ifdef __cplusplus
 }

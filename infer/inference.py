@@ -1,2 +1,3 @@
 import agcn_amd  # noqa: F401
-from agcn_amd.online import ActionRecognition, load_model  # noqa: F401
+from agcn_amd.online import (ActionRecognition, MultiStreamRecognition, RecordingRecognition,  # noqa: F401
+                             load_model, window_plan)
