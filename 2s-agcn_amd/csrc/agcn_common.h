@@ -61,68 +61,96 @@ int agcn_adj_ws_scores(const float* x, const float* wab, const float* bab, float
                        int* nslots_used, const float* x_absmax, void* ws, size_t ws_bytes, int N, int C, int Ci, int T, int V,
                        hipStream_t s);
 
+// A size query is a dry run of the launch: it builds the same problem with null pointers and walks the same ladder
+// with this record attached.  A leaf launcher that is handed one runs its geometry and feasibility checks as always,
+// notes what it WOULD write and returns before its first HIP call.  Host only: reached through the host-side problem
+// structs or a launcher parameter, never a member of a struct a kernel takes by value.
+struct AgcnDryRun {
+  long slab_slots;     // slots the launch writes to its partial slab (BatchNorm partials, adjacency-gradient partials)
+  size_t ws_bytes;     // workspace bytes it touches, the absmax scalars parked behind the weight images included
+};
+// an operation of several launches reports the largest workspace and the slot count of the slab it writes
+static inline int agcn_dry_note(AgcnDryRun* d, long slab_slots, size_t ws_bytes) {
+  if (slab_slots > d->slab_slots) d->slab_slots = slab_slots;
+  if (ws_bytes > d->ws_bytes) d->ws_bytes = ws_bytes;
+  return AGCN_OK;
+}
+
+// What a dry run passes for an operand whose PRESENCE steers the routing (the slab to account for, a fused second
+// source, the gate vectors, the operand maxima): non-null, and host code never dereferences a tensor pointer.  The route
+// functions of the entry points may therefore be handed placeholders instead of tensors.
+static inline float* agcn_dry_present() { static float placeholder; return &placeholder; }
+
+// the size arguments every contraction entry point and size query checks first
+static inline bool agcn_sizes_ok(int N, int a, int b, int T, int V) {
+  return N > 0 && a > 0 && b > 0 && T > 0 && V > 0 && V <= 32;
+}
+
+// temporal convolutions (agcn_tconv_*): the supported domain, and the shapes the agcn_conv_* entry points cover (routed
+// there unchanged: same kernels, same bits)
+static inline bool agcn_tconv_domain(int T, int taps, int stride, int pad) {
+  return taps >= 1 && taps <= 9 && stride >= 1 && stride <= 9 && pad >= 0 && pad <= (taps - 1) / 2 && T + 2 * pad >= taps;
+}
+static inline bool agcn_tconv_legacy(int taps, int stride, int pad) {
+  return pad == (taps - 1) / 2 && (taps == 1 || taps == 9) && (stride == 1 || stride == 2);
+}
+
 // split-bf16 temporal convolution (conv_gemm_bf16.hip); npl: 3 = bf16x6 (fp32-equivalent), 2 = bf16x3
-size_t agcn_bf16_conv_workspace(int Cin, int Cout, int T, int V, int stride);
 bool agcn_bf16_conv_wide(int taps, int M);
 int agcn_bf16_conv9_fwd(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* ws,
                         size_t ws_bytes, int N, int Cin, int Cout, int T, int V, int stride, int npl, hipStream_t s,
-                        const float* add = nullptr, int relu = 0, const float* x_absmax = nullptr);
+                        const float* add = nullptr, int relu = 0, const float* x_absmax = nullptr,
+                        AgcnDryRun* dry = nullptr);
 int agcn_bf16_conv9_bwd_data(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
                              const float* mask1, const float* add2, const float* mask2, void* ws, size_t ws_bytes,
                              int N, int Cin, int Cout, int T, int V, int stride, int npl, hipStream_t s,
-                             const float* dy_absmax = nullptr);
+                             const float* dy_absmax = nullptr, AgcnDryRun* dry = nullptr);
 
 // stride-1 3/5/7-tap temporal convolutions with explicit padding on the same kernels (agcn_tconv_*)
 bool agcn_bf16_tconv_supported(int taps, int stride);
-int agcn_bf16_tconv_tile_frames(int taps, int M, int V, int T_out, int npl);
 int agcn_bf16_tconv_fwd(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* ws,
                         size_t ws_bytes, int N, int Cin, int Cout, int T, int V, int taps, int pad, int npl,
-                        hipStream_t s, const float* x_absmax);
+                        hipStream_t s, const float* x_absmax, AgcnDryRun* dry = nullptr);
 int agcn_bf16_tconv_bwd_data(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
                              const float* mask1, const float* add2, const float* mask2, void* ws, size_t ws_bytes,
                              int N, int Cin, int Cout, int T, int V, int taps, int pad, int npl, hipStream_t s,
-                             const float* dy_absmax);
+                             const float* dy_absmax, AgcnDryRun* dry = nullptr);
 
 // BN-folded inference on the same kernels, the attention gates of gate.h applied while the operand is staged
 struct GateArgs;
 bool agcn_bf16_tconv_infer_supported(int taps, int stride, int pad);
 int agcn_bf16_tconv_infer(const float* x, const float* w, const float* bias, float* y, void* ws, size_t ws_bytes, int N,
                           int Cin, int Cout, int T, int V, int taps, int stride, int pad, int npl, hipStream_t s,
-                          const float* add, int relu, const float* x_absmax, const GateArgs* gate);
+                          const float* add, int relu, const float* x_absmax, const GateArgs* gate,
+                          AgcnDryRun* dry = nullptr);
 
-size_t agcn_bf16_conv1_workspace(int Cin, int Cout, int T, int V, int stride);
 int agcn_bf16_conv1_fwd(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* ws,
                         size_t ws_bytes, int N, int Cin, int Cout, int T, int V, int stride, int npl, hipStream_t s,
-                        const float* add = nullptr, int relu = 0);
+                        const float* add = nullptr, int relu = 0, AgcnDryRun* dry = nullptr);
 int agcn_bf16_conv1_bwd_data(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
                              const float* mask1, const float* add2, const float* mask2, void* ws, size_t ws_bytes,
-                             int N, int Cin, int Cout, int T, int V, int npl, hipStream_t s);
+                             int N, int Cin, int Cout, int T, int V, int npl, hipStream_t s, AgcnDryRun* dry = nullptr);
 
 // register-chained aggregate+project (gcn_chain.hip); mode 0 = forward, 1 = backward-data
 bool agcn_gcn_chain_supported(int M, int K, int V);
 int agcn_chain_f16x3();                       // 1: the chain runs on f16x3 (split_f16.h), 0: bf16x6 / AGCN_GEMM's mode
 int agcn_gcn_chain_tiles(int T);
-int agcn_gcn_chain_stats_slots(int N, int M, int K, int T, int V);
-size_t agcn_gcn_chain_workspace(int M, int K, int K2, int T, int V);
 int agcn_gcn_chain(int mode, const float* in, const float* adj, const float* wcat, const float* bias, float* out,
                    float* stats_part, int accumulate, const float* add1, const float* mask1, const float* add2,
                    const float* mask2, int mask_bits, const float* in2, const float* w2, int K2, void* ws, size_t ws_bytes,
                    int N, int C, int Cout, int T, int V, hipStream_t stream, int relu = 0, int w2_rows_are_outputs = 0,
-                   const float* in_absmax = nullptr, const float* in2_absmax = nullptr);
+                   const float* in_absmax = nullptr, const float* in2_absmax = nullptr, AgcnDryRun* dry = nullptr);
 
 bool agcn_gcn_dadj_chain_supported(int C, int V);
-int agcn_gcn_dadj_chain_slots(int C, int T);
-size_t agcn_gcn_dadj_chain_workspace(int C, int Cout);
 int agcn_gcn_dadj_chain(const float* dy, const float* wcat, const float* x, float* dadj_part, void* ws, size_t ws_bytes,
                         int N, int C, int Cout, int T, int V, hipStream_t stream, const float* dy_absmax = nullptr,
-                        const float* x_absmax = nullptr);
+                        const float* x_absmax = nullptr, AgcnDryRun* dry = nullptr);
 
 // split-bf16 weight gradients of the tap-free contractions (wgrad_chain.hip): partial slabs only, reduced by the caller
 bool agcn_wgrad_chain_supported(int M, int C, int V);
-size_t agcn_wgrad_chain_workspace(int agg, int N, int M, int C, int V, int T_out);
 int agcn_wgrad_chain(int agg, const float* dy, const float* x, const float* adj, void* ws, size_t ws_bytes, int* nslabs,
                      int N, int M, int C, int V, int T_src, int T_out, int stride, hipStream_t s,
-                     const float* dy_absmax = nullptr, const float* x_absmax = nullptr);
+                     const float* dy_absmax = nullptr, const float* x_absmax = nullptr, AgcnDryRun* dry = nullptr);
 
 // split-bf16 weight gradient of the 9-tap temporal convolution (wgrad9_bf16.hip): slabs [nslabs][9][M][C] at ws
 bool agcn_wgrad9_bf16_supported(int M, int C, int V, int stride);

@@ -575,6 +575,7 @@ struct Problem {          // what differs between the entry points
   void* ws;
   size_t ws_bytes;
   int tt_cap;             // 0: frames per tile as the tile width gives them
+  AgcnDryRun* dry;        // non-null: a size query (agcn_common.h), nothing is launched
 };
 
 template <int TAPS, int AGG, int WM, int WN, int TM, int TN, int CK, int WB, int EPI>
@@ -585,6 +586,10 @@ int launch_cfg(Problem& p, hipStream_t stream) {
   const Geometry g = make_geometry<TAPS, AGG, WM, WN, TM, TN, CK, EPI>(a.V, a.T_out, a.src_stride, a.M, a.Kinner, p.tt_cap);
   if (g.smem_bytes > 160 * 1024) return AGCN_ERR_UNSUPPORTED;
   if (g.FW * a.V > WB * 64) return AGCN_ERR_UNSUPPORTED;
+  if (p.dry) {            // BatchNorm partials: one slot per (sample, tile); adjacency partials: per (sample, subset, tile, row block)
+    const long slots = a.stats ? (long)a.N * g.ntiles : a.dadj ? 3L * a.N * g.ntiles * (a.C >= BM ? a.C / BM : 1) : 0;
+    return agcn_dry_note(p.dry, slots, g.pack_floats * 4);
+  }
   if (g.pack_floats * 4 > p.ws_bytes) return AGCN_ERR_WORKSPACE;
   a.tt = g.tt; a.ntiles = g.ntiles; a.FW = g.FW; a.WLP = g.WLP; a.nchunks = g.nchunks; a.nmb = g.nmb;
   a.off_bx = g.off_bx; a.off_bg = g.off_bg; a.off_adj = g.off_adj;
@@ -614,18 +619,10 @@ int launch_cfg(Problem& p, hipStream_t stream) {
   return agcn_check_launch();
 }
 
-template <int TAPS, int AGG, int WM, int WN, int TM, int TN, int CK, int EPI>
-size_t pack_bytes(int V, int T_out, int src_stride, int M, int Kinner) {
-  return 4 * make_geometry<TAPS, AGG, WM, WN, TM, TN, CK, EPI>(V, T_out, src_stride, M, Kinner).pack_floats;
-}
-
 // BM = 64 (4 waves) unless M is a multiple of 128 (8 waves, BM = 128)
 #define DISPATCH_BM(TAPS, AGG, CK64, CK128, WB, p, s)                                        \
   (((p).a.M % 128 == 0) ? launch_cfg<TAPS, AGG, 2, 4, 2, 2, CK128, WB, 0>((p), (s))          \
                         : launch_cfg<TAPS, AGG, 1, 4, 2, 2, CK64, WB, 0>((p), (s)))
-#define PACK_BYTES_BM(TAPS, AGG, CK64, CK128, V, T, ss, M, K)                                \
-  (((M) % 128 == 0) ? pack_bytes<TAPS, AGG, 2, 4, 2, 2, CK128, 0>(V, T, ss, M, K)            \
-                    : pack_bytes<TAPS, AGG, 1, 4, 2, 2, CK64, 0>(V, T, ss, M, K))
 
 constexpr int CK9 = 8, CK1 = 16, CKA = 8, CKD = 64;
 
@@ -633,18 +630,6 @@ constexpr int CK9 = 8, CK1 = 16, CKA = 8, CKD = 64;
 constexpr int WBT = 12;                 // window bound of the exact-f32 kernel (768 floats per staged row)
 
 inline int tconv_out_frames(int T, int taps, int stride, int pad) { return (T + 2 * pad - taps) / stride + 1; }
-
-// AGCN_ERR_UNSUPPORTED outside the supported domain (the caller's shapes), 0 otherwise
-inline int tconv_domain(int T, int taps, int stride, int pad) {
-  if (taps < 1 || taps > 9 || stride < 1 || stride > 9 || pad < 0 || pad > (taps - 1) / 2) return AGCN_ERR_UNSUPPORTED;
-  if (T + 2 * pad < taps) return AGCN_ERR_UNSUPPORTED;       // not one whole window
-  return 0;
-}
-
-// the shapes the agcn_conv_* entry points cover: routed there unchanged (same kernels, same bits)
-inline bool tconv_legacy(int taps, int stride, int pad) {
-  return pad == (taps - 1) / 2 && (taps == 1 || taps == 9) && (stride == 1 || stride == 2);
-}
 
 // the split-bf16 / f16x3 kernels of conv_gemm_bf16.hip (stride 1, 3/5/7 taps) in the split-bf16 modes
 inline bool tconv_fast(int taps, int stride) { return agcn_gemm_precision() != 0 && agcn_bf16_tconv_supported(taps, stride); }
@@ -702,122 +687,21 @@ int tconv_f32_infer_dispatch(int taps, Problem& p, hipStream_t s) {
   }
 }
 
-inline size_t round_up(size_t v, size_t m) { return (v + m - 1) / m * m; }
-
-
-}  // namespace
-
-extern "C" {
-
-// frames per tile / tiles per sample used by the stats-partial layout of the conv kernels
-int agcn_conv_tile_frames(int V, int T_out) {
-  int tt = 256 / V;
-  return tt > T_out ? T_out : tt;
-}
-// diagnostic: kernel instantiation the calling thread's last contraction launch used ("" if none)
-const char* agcn_last_kernel(void) { return agcn_last_kernel_buf; }
-// "bf16x6" | "f32" | "bf16x3": the arithmetic of the channel contractions, fixed per process by AGCN_GEMM
-const char* agcn_gemm_mode(void) {
-  const int m = agcn_gemm_precision();
-  return m == 3 ? "bf16x6" : (m == 0 ? "f32" : (m == 1 ? "bf16" : "bf16x3"));
-}
-// *out = max |x| over n floats: the streaming pass the f16x3 kernels run themselves when no producer supplied the maximum
-int agcn_absmax(const float* x, long n, float* out, void* stream) {
-  if (!x || !out || n <= 0) return AGCN_ERR_ARG;
-  return agcn_launch_absmax(x, n, reinterpret_cast<unsigned*>(out), (hipStream_t)stream);
-}
-// arithmetic of unit_gcn's aggregate+project chain (forward and backward-data): "f16x3" in the default fp32-equivalent
-// mode (AGCN_CHAIN_F16X3=0: "bf16x6"), else AGCN_GEMM's mode
-const char* agcn_chain_mode(void) { return agcn_chain_f16x3() ? "f16x3" : agcn_gemm_mode(); }
-int agcn_conv_num_tiles(int V, int T_out) {
-  int tt = agcn_conv_tile_frames(V, T_out);
-  return (T_out + tt - 1) / tt;
-}
-// slots per sample of the (sum, sumsq) partials agcn_conv_fwd writes for these sizes (depends on the kernel picked)
-int agcn_conv_stats_tiles(int Cin, int Cout, int T_out, int V, int taps, int stride) {
-  (void)Cin; (void)stride;
-  if (taps == 9 && agcn_chained() && Cout % 128 != 0 && agcn_bf16_conv_wide(taps, Cout)) {
-    int tt = 512 / V;
-    if (tt > T_out) tt = T_out;
-    return (T_out + tt - 1) / tt;
-  }
-  return agcn_conv_num_tiles(V, T_out);
-}
-int agcn_dadj_num_slots(int C, int V, int T) {
-  if (agcn_chained() && agcn_gcn_dadj_chain_supported(C, V)) return agcn_gcn_dadj_chain_slots(C, T);
-  int tt = 128 / V;
-  if (tt > T) tt = T;
-  int ntiles = (T + tt - 1) / tt;
-  int nmb = C >= 64 ? C / 64 : 1;
-  return ntiles * nmb;
-}
-
-// bytes of workspace (packed weight images) the contraction entry points need; an upper bound over
-// forward / backward-data of a conv with these sizes, and over the aggregate/dadj kernels with C=Cin
-size_t agcn_conv_workspace(int Cin, int Cout, int T, int V, int taps, int stride) {
-  const int pad = (taps - 1) / 2;
-  const int To = (T + 2 * pad - taps) / stride + 1;
-  size_t b = 0, t;
-  if (taps == 9) {
-    b = PACK_BYTES_BM(9, 0, CK9, CK9, V, To, stride, Cout, Cin);
-    t = PACK_BYTES_BM(9, 0, CK9, CK9, V, T, 1, Cin, Cout); if (t > b) b = t;
-    t = PACK_BYTES_BM(5, 0, CK9, CK9, V, (T + 1) / 2, 1, Cin, Cout); if (t > b) b = t;
-    t = agcn_bf16_conv_workspace(Cin, Cout, T, V, stride); if (t > b) b = t;
-  } else {
-    b = PACK_BYTES_BM(1, 0, CK1, CK1, V, To, stride, Cout, Cin);
-    t = PACK_BYTES_BM(1, 0, CK1, CK1, V, T, 1, Cin, Cout); if (t > b) b = t;
-    t = agcn_bf16_conv1_workspace(Cin, Cout, T, V, stride); if (t > b) b = t;
-  }
-  return b + 256;
-}
-size_t agcn_gcn_workspace(int C, int Cout, int T, int V) {
-  size_t b = PACK_BYTES_BM(1, 1, CKA, CKA, V, T, 1, Cout, C), t;
-  t = PACK_BYTES_BM(1, 2, CKA, CKA, V, T, 1, C, Cout); if (t > b) b = t;
-  t = pack_bytes<1, 0, 1, 4, 2, 1, CKD, 1>(V, T, 1, 3 * C, Cout); if (t > b) b = t;
-  if (agcn_gcn_chain_supported(Cout, C, V)) { t = agcn_gcn_chain_workspace(Cout, C, 0, T, V); if (t > b) b = t; }
-  // backward-data, with room for the fused theta/phi term (6*Cout/4 channels)
-  if (agcn_gcn_chain_supported(C, Cout, V)) { t = agcn_gcn_chain_workspace(C, Cout, 6 * (Cout / 4), T, V); if (t > b) b = t; }
-  if (agcn_gcn_dadj_chain_supported(C, V)) { t = agcn_gcn_dadj_chain_workspace(C, Cout); if (t > b) b = t; }
-  return b + 256;
-}
-
-// slots per sample of the (sum, sumsq) partials agcn_gcn_aggregate_project_fwd writes for these sizes
-int agcn_gcn_stats_tiles(int C, int Cout, int T, int V) {
-  if (agcn_chained() && C >= 32 && agcn_gcn_chain_supported(Cout, C, V)) return agcn_gcn_chain_tiles(T);
-  return agcn_conv_num_tiles(V, T);
-}
-
-// total slots (all samples) of the same partials: what the caller allocates (the persistent chain kernel writes one slot
-// per (sample, frame split), whose count depends on N)
-int agcn_gcn_stats_slots(int N, int C, int Cout, int T, int V) {
-  if (agcn_chained() && C >= 32 && agcn_gcn_chain_supported(Cout, C, V)) return agcn_gcn_chain_stats_slots(N, Cout, C, T, V);
-  return N * agcn_conv_num_tiles(V, T);
-}
+// ---- the routing of each entry point, after its argument checks.  The size queries walk the same functions with null
+// tensors and a dry-run record (agcn_common.h): there is one copy of every routing decision.  In a dry run an operand
+// whose presence steers the routing may be a placeholder (agcn_dry_present): no route function dereferences a tensor. ----
 
 // y[n][o][t,v] = bias[o] + sum_{c,k} w[o][c][k] x[n][c][(t*stride + k - pad), v]      (unit_tcn conv, 1x1 convs)
-int agcn_conv_fwd_ex(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* workspace,
-                     size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride,
-                     const float* x_absmax, void* stream);
-int agcn_conv_fwd(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* workspace,
-                  size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride,
-                  void* stream) {
-  return agcn_conv_fwd_ex(x, w, bias, y, stats_part, workspace, workspace_bytes, N, Cin, Cout, T, V, taps, stride, nullptr,
-                          stream);
-}
-
-// same; x_absmax (optional): device scalar max |x| left by agcn_bn_act_fwd_ex when it produced x -- saves the split-fp16
-// temporal convolution its own pass over x for the range scale
-int agcn_conv_fwd_ex(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* workspace,
-                     size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride,
-                     const float* x_absmax, void* stream) {
-  if (!x || !w || !y || !workspace || N <= 0 || Cin <= 0 || Cout <= 0 || T <= 0 || V <= 0 || V > 32)
-    return AGCN_ERR_ARG;
+int conv_fwd_route(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* workspace,
+                   size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride,
+                   const float* x_absmax, hipStream_t s, AgcnDryRun* dry) {
   if ((taps != 1 && taps != 9) || (stride != 1 && stride != 2)) return AGCN_ERR_UNSUPPORTED;
   const int pad = (taps - 1) / 2;
   if (taps == 9 && agcn_gemm_precision() != 0)
     return agcn_bf16_conv9_fwd(x, w, bias, y, stats_part, workspace, workspace_bytes, N, Cin, Cout, T, V, stride,
-                               agcn_gemm_precision(), (hipStream_t)stream, nullptr, 0, x_absmax);
+                               agcn_gemm_precision(), s, nullptr, 0, x_absmax, dry);
   Problem p = {};
+  p.dry = dry;
   ConvGemmArgs& a = p.a;
   a.in = x; a.bias = bias; a.out = y; a.stats = stats_part;
   a.N = N; a.M = Cout; a.Kinner = Cin; a.in_rows = Cin; a.V = V;
@@ -825,42 +709,27 @@ int agcn_conv_fwd_ex(const float* x, const float* w, const float* bias, float* y
   a.src_stride = stride; a.f_off = -pad; a.out_fs = 1; a.out_fo = 0;
   p.w = w; p.sa_m = (long)Cin * taps; p.sa_i = 0; p.sa_c = taps; p.tap_flip_from = -1;
   p.ws = workspace; p.ws_bytes = workspace_bytes;
-  hipStream_t s = (hipStream_t)stream;
   if (taps == 9) return DISPATCH_BM(9, 0, CK9, CK9, 11, p, s);
   if (stride == 1) return DISPATCH_BM(1, 0, CK1, CK1, 4, p, s);
   return DISPATCH_BM(1, 0, CK1, CK1, 8, p, s);
 }
 
 // dx[n][c][t,v] (+)= sum_{o,k} w[o][c][k] dy[n][o][(t + pad - k)/stride, v]  (+ masked addends)
-int agcn_conv_bwd_data_ex(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
-                          const float* mask1, const float* add2, const float* mask2, void* workspace,
-                          size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride,
-                          const float* dy_absmax, void* stream);
-int agcn_conv_bwd_data(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
-                       const float* mask1, const float* add2, const float* mask2, void* workspace,
-                       size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride,
-                       void* stream) {
-  return agcn_conv_bwd_data_ex(dy, w, dx, accumulate, add1, mask1, add2, mask2, workspace, workspace_bytes, N, Cin, Cout, T,
-                               V, taps, stride, nullptr, stream);
-}
-
-// same; dy_absmax (optional): device scalar max |dy| left by agcn_bn_bwd_apply_ex
-int agcn_conv_bwd_data_ex(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
-                          const float* mask1, const float* add2, const float* mask2, void* workspace,
-                          size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride,
-                          const float* dy_absmax, void* stream) {
-  if (!dy || !w || !dx || !workspace || N <= 0 || Cin <= 0 || Cout <= 0 || T <= 0 || V <= 0 || V > 32)
-    return AGCN_ERR_ARG;
+int conv_bwd_data_route(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
+                        const float* mask1, const float* add2, const float* mask2, void* workspace,
+                        size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride,
+                        const float* dy_absmax, hipStream_t s, AgcnDryRun* dry) {
   if ((taps != 1 && taps != 9) || (stride != 1 && stride != 2)) return AGCN_ERR_UNSUPPORTED;
   const int pad = (taps - 1) / 2;
   if (taps == 9 && agcn_gemm_precision() != 0)
     return agcn_bf16_conv9_bwd_data(dy, w, dx, accumulate, add1, mask1, add2, mask2, workspace, workspace_bytes, N, Cin,
-                                    Cout, T, V, stride, agcn_gemm_precision(), (hipStream_t)stream, dy_absmax);
+                                    Cout, T, V, stride, agcn_gemm_precision(), s, dy_absmax, dry);
   // 1x1 backward-data: measured 10-17% faster on the split-bf16 kernel; the 1x1 forward (store-bound) is not
   if (taps == 1 && stride == 1 && agcn_chained() && Cin >= 64 && Cout >= 32)
     return agcn_bf16_conv1_bwd_data(dy, w, dx, accumulate, add1, mask1, add2, mask2, workspace, workspace_bytes, N, Cin,
-                                    Cout, T, V, agcn_gemm_precision(), (hipStream_t)stream);
+                                    Cout, T, V, agcn_gemm_precision(), s, dry);
   Problem p = {};
+  p.dry = dry;
   ConvGemmArgs& a = p.a;
   a.in = dy; a.out = dx; a.accumulate = accumulate;
   a.add1 = add1; a.mask1 = mask1; a.add2 = add2; a.mask2 = mask2;
@@ -868,7 +737,6 @@ int agcn_conv_bwd_data_ex(const float* dy, const float* w, float* dx, int accumu
   a.T_src = (T + 2 * pad - taps) / stride + 1; a.T_full = T; a.src_stride = 1;
   p.w = w; p.sa_m = taps; p.sa_i = 0; p.sa_c = (long)Cin * taps;
   p.ws = workspace; p.ws_bytes = workspace_bytes;
-  hipStream_t s = (hipStream_t)stream;
   if (stride == 1) {
     // dx[t] = sum_j W[taps-1-j] dy[t + j - pad]
     a.T_out = T; a.out_fs = 1; a.out_fo = 0; a.f_off = -pad;
@@ -901,6 +769,320 @@ int agcn_conv_bwd_data_ex(const float* dy, const float* w, float* dx, int accumu
 }
 
 // y[n][o][t,v] = bias[o] + sum_i sum_c wcat[o][i*C+c] * sum_u x[n][c][t,u] adj[n][i][u][v]
+int gcn_fwd_route(const float* x, const float* adj, const float* wcat, const float* bias, float* y, float* stats_part,
+                  void* workspace, size_t workspace_bytes, int N, int C, int Cout, int T, int V, const float* x_absmax,
+                  hipStream_t s, AgcnDryRun* dry) {
+  // (the 3-channel first layer's forward stays on the f32 kernel: measured 193 us against 260 us chained)
+  if (agcn_chained() && C >= 32 && agcn_gcn_chain_supported(Cout, C, V))
+    return agcn_gcn_chain(0, x, adj, wcat, bias, y, stats_part, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
+                          0, workspace, workspace_bytes, N, C, Cout, T, V, s, 0, 0, x_absmax, nullptr, dry);
+  Problem p = {};
+  p.dry = dry;
+  ConvGemmArgs& a = p.a;
+  a.in = x; a.bias = bias; a.out = y; a.adj = adj; a.stats = stats_part;
+  a.N = N; a.M = Cout; a.Kinner = C; a.in_rows = C; a.V = V; a.T_src = T; a.T_out = T; a.T_full = T;
+  a.src_stride = 1; a.f_off = 0; a.out_fs = 1; a.out_fo = 0;
+  p.w = wcat; p.sa_m = 3L * C; p.sa_i = C; p.sa_c = 1; p.tap_flip_from = -1;
+  p.ws = workspace; p.ws_bytes = workspace_bytes;
+  return DISPATCH_BM(1, 1, CKA, CKA, 4, p, s);
+}
+
+// dx[n][c][t,u] (+)= sum_i sum_o wcat[o][i*C+c] * sum_v dy[n][o][t,v] adj[n][i][u][v]   (+ masked addends); dtp
+// non-null: plus the fused 1x1 term W2^T dtp (chained path only)
+int gcn_bwd_data_route(const float* dy, const float* adj, const float* wcat, const float* dtp, const float* w2, int K2,
+                       float* dx, int accumulate, const float* add1, const float* mask1, const float* add2,
+                       const float* mask2, int mask_bits, void* workspace, size_t workspace_bytes, int N, int C, int Cout,
+                       int T, int V, const float* dy_absmax, const float* dtp_absmax, hipStream_t s, AgcnDryRun* dry) {
+  const bool chain = agcn_chained() && agcn_gcn_chain_supported(C, Cout, V);
+  if (dtp && !chain) return AGCN_ERR_UNSUPPORTED;
+  if (chain)
+    return agcn_gcn_chain(1, dy, adj, wcat, nullptr, dx, nullptr, accumulate, add1, mask1, add2, mask2, mask_bits, dtp,
+                          dtp ? w2 : nullptr, dtp ? K2 : 0, workspace, workspace_bytes, N, C, Cout, T, V, s, 0, 0,
+                          dy_absmax, dtp ? dtp_absmax : nullptr, dry);
+  Problem p = {};
+  p.dry = dry;
+  ConvGemmArgs& a = p.a;
+  a.in = dy; a.out = dx; a.adj = adj; a.accumulate = accumulate;
+  a.add1 = add1; a.mask1 = mask1; a.add2 = add2; a.mask2 = mask2; a.mask_bits = mask_bits;
+  a.N = N; a.M = C; a.Kinner = Cout; a.in_rows = Cout; a.V = V; a.T_src = T; a.T_out = T; a.T_full = T;
+  a.src_stride = 1; a.f_off = 0; a.out_fs = 1; a.out_fo = 0;
+  p.w = wcat; p.sa_m = 1; p.sa_i = C; p.sa_c = 3L * C; p.tap_flip_from = -1;
+  p.ws = workspace; p.ws_bytes = workspace_bytes;
+  return DISPATCH_BM(1, 2, CKA, CKA, 4, p, s);
+}
+
+// dadj_part[n][i][slot][u][v] = sum over the slot's (c,t) of x[n][c][t,u] * (sum_o wcat[o][i*C+c] dy[n][o][t,v])
+int gcn_dadj_route(const float* dy, const float* wcat, const float* x, float* dadj_part, void* workspace,
+                   size_t workspace_bytes, int N, int C, int Cout, int T, int V, const float* dy_absmax,
+                   const float* x_absmax, hipStream_t s, AgcnDryRun* dry) {
+  if (agcn_chained() && agcn_gcn_dadj_chain_supported(C, V))
+    return agcn_gcn_dadj_chain(dy, wcat, x, dadj_part, workspace, workspace_bytes, N, C, Cout, T, V, s, dy_absmax,
+                               x_absmax, dry);
+  if (C >= 64 && C % 64 != 0) return AGCN_ERR_UNSUPPORTED;
+  Problem p = {};
+  p.dry = dry;
+  ConvGemmArgs& a = p.a;
+  a.in = dy; a.xin = x; a.dadj = dadj_part;
+  a.N = N; a.M = 3 * C; a.Kinner = Cout; a.in_rows = Cout; a.V = V; a.T_src = T; a.T_out = T; a.T_full = T;
+  a.src_stride = 1; a.f_off = 0; a.out_fs = 1; a.out_fo = 0; a.C = C;
+  p.w = wcat; p.sa_m = 1; p.sa_i = 0; p.sa_c = 3L * C; p.tap_flip_from = -1;
+  p.ws = workspace; p.ws_bytes = workspace_bytes;
+  return launch_cfg<1, 0, 1, 4, 2, 1, CKD, 2, 1>(p, s);
+}
+
+// y = act( bias + sum_i W_i (x . adj_i) [+ res] [+ W2 . x2] ): only on the chained split-bf16 path (C >= 32)
+int gcn_unit_infer_route(const float* x, const float* adj, const float* wcat, const float* bias, const float* res,
+                         const float* x2, const float* w2, int K2, int relu, float* y, void* workspace,
+                         size_t workspace_bytes, int N, int C, int Cout, int T, int V, hipStream_t s, AgcnDryRun* dry) {
+  if (!(agcn_chained() && C >= 32 && agcn_gcn_chain_supported(Cout, C, V))) return AGCN_ERR_UNSUPPORTED;
+  if (x2 && K2 % 32 != 0) return AGCN_ERR_UNSUPPORTED;
+  return agcn_gcn_chain(0, x, adj, wcat, bias, y, nullptr, 0, res, nullptr, nullptr, nullptr, 0, x2, w2, x2 ? K2 : 0,
+                        workspace, workspace_bytes, N, C, Cout, T, V, s, relu, 1, nullptr, nullptr, dry);
+}
+
+// y[n][o][t,v] = bias[o] + sum_{c,k} w[o][c][k] x[n][c][t*stride + k - pad, v],  T_out = (T + 2 pad - taps)/stride + 1
+int tconv_fwd_route(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* workspace,
+                    size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride, int pad,
+                    const float* x_absmax, hipStream_t s, AgcnDryRun* dry) {
+  if (!agcn_tconv_domain(T, taps, stride, pad)) return AGCN_ERR_UNSUPPORTED;
+  if (agcn_tconv_legacy(taps, stride, pad))
+    return conv_fwd_route(x, w, bias, y, stats_part, workspace, workspace_bytes, N, Cin, Cout, T, V, taps, stride, x_absmax,
+                          s, dry);
+  if (tconv_fast(taps, stride))
+    return agcn_bf16_tconv_fwd(x, w, bias, y, stats_part, workspace, workspace_bytes, N, Cin, Cout, T, V, taps, pad,
+                               agcn_gemm_precision(), s, x_absmax, dry);
+  Problem p = {};
+  p.dry = dry;
+  ConvGemmArgs& a = p.a;
+  a.in = x; a.bias = bias; a.out = y; a.stats = stats_part;
+  a.N = N; a.M = Cout; a.Kinner = Cin; a.in_rows = Cin; a.V = V;
+  a.T_src = T; a.T_out = tconv_out_frames(T, taps, stride, pad); a.T_full = a.T_out;
+  a.src_stride = stride; a.f_off = -pad; a.out_fs = 1; a.out_fo = 0;
+  p.w = w; p.sa_m = (long)Cin * taps; p.sa_i = 0; p.sa_c = taps; p.tap_flip_from = -1;
+  p.ws = workspace; p.ws_bytes = workspace_bytes;
+  return tconv_f32_dispatch(taps, p, s);
+}
+
+// 9 taps / pad 4 / stride 1-2 and stride-1 3/5/7 taps run on the split-bf16 / f16x3 kernels, everything else (and
+// AGCN_GEMM=f32) on the exact-f32 kernel; one epilogue (epilogue.h)
+int tconv_infer_route(const float* x, const float* w, const float* bias, const float* a_s, const float* a_t,
+                      const float* a_c, const float* res, int relu, float* y, void* workspace, size_t workspace_bytes,
+                      int N, int Cin, int Cout, int T, int V, int taps, int stride, int pad, const float* x_absmax,
+                      hipStream_t s, AgcnDryRun* dry) {
+  if (!agcn_tconv_domain(T, taps, stride, pad)) return AGCN_ERR_UNSUPPORTED;
+  GateArgs gate = {a_s, a_t, a_c};
+  if (agcn_gemm_precision() != 0 && agcn_bf16_tconv_infer_supported(taps, stride, pad)) {
+    const int rc = agcn_bf16_tconv_infer(x, w, bias, y, workspace, workspace_bytes, N, Cin, Cout, T, V, taps, stride, pad,
+                                         agcn_gemm_precision(), s, res, relu, x_absmax, &gate, dry);
+    // (a window too long for their LDS is refused before anything is launched there: the exact kernel below)
+    if (rc != AGCN_ERR_UNSUPPORTED) return rc;
+  }
+  Problem p = {};
+  p.dry = dry;
+  ConvGemmArgs& a = p.a;
+  a.in = x; a.bias = bias; a.out = y; a.add1 = res;
+  p.gate = gate; p.gated = (a_s || a_t || a_c) ? 1 : 0; p.relu = relu;
+  a.N = N; a.M = Cout; a.Kinner = Cin; a.in_rows = Cin; a.V = V;
+  a.T_src = T; a.T_out = tconv_out_frames(T, taps, stride, pad); a.T_full = a.T_out;
+  a.src_stride = stride; a.f_off = -pad; a.out_fs = 1; a.out_fo = 0;
+  p.w = w; p.sa_m = (long)Cin * taps; p.sa_i = 0; p.sa_c = taps; p.tap_flip_from = -1;
+  p.ws = workspace; p.ws_bytes = workspace_bytes;
+  return tconv_f32_infer_dispatch(taps, p, s);
+}
+
+// dx[n][c][t,v] (+)= sum_{o,k: (t + pad - k) = stride*tau} w[o][c][k] dy[n][o][tau, v]  (+ masked addends); frames no
+// window reaches get 0 (+ addends)
+int tconv_bwd_data_route(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
+                         const float* mask1, const float* add2, const float* mask2, void* workspace,
+                         size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride, int pad,
+                         const float* dy_absmax, hipStream_t s, AgcnDryRun* dry) {
+  if (!agcn_tconv_domain(T, taps, stride, pad)) return AGCN_ERR_UNSUPPORTED;
+  if (agcn_tconv_legacy(taps, stride, pad))
+    return conv_bwd_data_route(dy, w, dx, accumulate, add1, mask1, add2, mask2, workspace, workspace_bytes, N, Cin, Cout,
+                               T, V, taps, stride, dy_absmax, s, dry);
+  if (tconv_fast(taps, stride))
+    return agcn_bf16_tconv_bwd_data(dy, w, dx, accumulate, add1, mask1, add2, mask2, workspace, workspace_bytes, N, Cin,
+                                    Cout, T, V, taps, pad, agcn_gemm_precision(), s, dy_absmax, dry);
+  // output frames t = stride*tau + r of one residue r form a stride-1 problem over tau: only the taps
+  // k = k0 + stride*i (k0 = (r + pad) mod stride) reach them,  dx[stride*tau + r] = sum_j W[k0 + stride*(J-1-j)]
+  // dy[tau + (r + pad - k0)/stride - (J-1) + j],  J = number of such taps (0: the residue receives no signal)
+  Problem p = {};
+  p.dry = dry;
+  ConvGemmArgs& a = p.a;
+  a.in = dy; a.out = dx; a.accumulate = accumulate;
+  a.add1 = add1; a.mask1 = mask1; a.add2 = add2; a.mask2 = mask2;
+  a.N = N; a.M = Cin; a.in_rows = Cout; a.V = V;
+  a.T_src = tconv_out_frames(T, taps, stride, pad); a.T_full = T; a.src_stride = 1; a.out_fs = stride;
+  p.w = w; p.sa_m = taps; p.sa_i = 0; p.sa_c = (long)Cin * taps;
+  p.ws = workspace; p.ws_bytes = workspace_bytes;
+  for (int r = 0; r < stride && r < T; ++r) {
+    const int k0 = (r + pad) % stride;
+    const int J = k0 < taps ? (taps - k0 + stride - 1) / stride : 0;
+    a.T_out = (T - r + stride - 1) / stride;
+    a.out_fo = r;
+    a.Kinner = J > 0 ? Cout : 0;          // no K chunks: the epilogue writes 0 (+accumulate/addends)
+    a.f_off = J > 0 ? (r + pad - k0) / stride - (J - 1) : 0;
+    p.tap_mul = stride; p.tap_add = 0; p.tap_flip_from = k0 + stride * (J > 0 ? J - 1 : 0);
+    const int rc = tconv_f32_dispatch(J > 0 ? J : 1, p, s);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+// frames per tile / tiles per sample used by the stats-partial layout of the conv kernels
+int agcn_conv_tile_frames(int V, int T_out) {
+  int tt = 256 / V;
+  return tt > T_out ? T_out : tt;
+}
+// diagnostic: kernel instantiation the calling thread's last contraction launch used ("" if none)
+const char* agcn_last_kernel(void) { return agcn_last_kernel_buf; }
+// "bf16x6" | "f32" | "bf16x3": the arithmetic of the channel contractions, fixed per process by AGCN_GEMM
+const char* agcn_gemm_mode(void) {
+  const int m = agcn_gemm_precision();
+  return m == 3 ? "bf16x6" : (m == 0 ? "f32" : (m == 1 ? "bf16" : "bf16x3"));
+}
+// *out = max |x| over n floats: the streaming pass the f16x3 kernels run themselves when no producer supplied the maximum
+int agcn_absmax(const float* x, long n, float* out, void* stream) {
+  if (!x || !out || n <= 0) return AGCN_ERR_ARG;
+  return agcn_launch_absmax(x, n, reinterpret_cast<unsigned*>(out), (hipStream_t)stream);
+}
+// arithmetic of unit_gcn's aggregate+project chain (forward and backward-data): "f16x3" in the default fp32-equivalent
+// mode (AGCN_CHAIN_F16X3=0: "bf16x6"), else AGCN_GEMM's mode
+const char* agcn_chain_mode(void) { return agcn_chain_f16x3() ? "f16x3" : agcn_gemm_mode(); }
+int agcn_conv_num_tiles(int V, int T_out) {
+  int tt = agcn_conv_tile_frames(V, T_out);
+  return (T_out + tt - 1) / tt;
+}
+
+// ---- size queries: dry runs of the launches they size (agcn_common.h).  Per-sample counts run with N = 1; a shape the
+// launch refuses has no slots; a workspace query serving several operations returns the largest of their dry runs,
+// plus 256 bytes of slack (the f16x3 temporal convolutions park the operand maximum in the workspace tail). ----
+
+// slots per sample of the (sum, sumsq) partials agcn_tconv_fwd writes for these sizes
+int agcn_tconv_stats_tiles(int Cin, int Cout, int T_out, int V, int taps, int stride, int pad) {
+  if (!agcn_sizes_ok(1, Cin, Cout, T_out, V)) return 0;
+  AgcnDryRun d = {};
+  const int T = (T_out - 1) * stride + taps - 2 * pad;       // a source length with T_out output frames
+  if (T <= 0 || tconv_fwd_route(nullptr, nullptr, nullptr, nullptr, agcn_dry_present(), nullptr, 0, 1, Cin, Cout, T, V, taps,
+                                stride, pad, nullptr, nullptr, &d))
+    return 0;
+  return (int)d.slab_slots;
+}
+// same for agcn_conv_fwd (taps 1 or 9, padding (taps-1)/2, stride 1 or 2)
+int agcn_conv_stats_tiles(int Cin, int Cout, int T_out, int V, int taps, int stride) {
+  if (!agcn_tconv_legacy(taps, stride, (taps - 1) / 2)) return 0;
+  return agcn_tconv_stats_tiles(Cin, Cout, T_out, V, taps, stride, (taps - 1) / 2);
+}
+// slots per (sample, subset) of the adjacency-gradient partials agcn_gcn_dadj writes (its tiling does not depend on Cout)
+int agcn_dadj_num_slots(int C, int V, int T) {
+  if (!agcn_sizes_ok(1, C, C, T, V)) return 0;
+  AgcnDryRun d = {};
+  if (gcn_dadj_route(nullptr, nullptr, nullptr, agcn_dry_present(), nullptr, 0, 1, C, C, T, V, nullptr, nullptr, nullptr, &d))
+    return 0;
+  return (int)(d.slab_slots / 3);
+}
+
+// bytes of workspace (packed weight images) agcn_tconv_fwd, agcn_tconv_bwd_data and agcn_tconv_infer need
+size_t agcn_tconv_workspace(int Cin, int Cout, int T, int V, int taps, int stride, int pad) {
+  AgcnDryRun d = {};
+  if (agcn_sizes_ok(1, Cin, Cout, T, V)) {
+    tconv_fwd_route(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1, Cin, Cout, T, V, taps, stride, pad, nullptr,
+                    nullptr, &d);
+    tconv_bwd_data_route(nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1, Cin, Cout, T, V,
+                         taps, stride, pad, nullptr, nullptr, &d);
+    // ungated and gated: the gate image takes LDS, which can move a shape down the ladder (placeholders, as for a slab)
+    for (const float* g : {(const float*)nullptr, (const float*)agcn_dry_present()})
+      tconv_infer_route(nullptr, nullptr, nullptr, g, g, g, nullptr, 0, nullptr, nullptr, 0, 1, Cin, Cout, T, V, taps,
+                        stride, pad, nullptr, nullptr, &d);
+  }
+  return d.ws_bytes + 256;
+}
+// same for agcn_conv_fwd / agcn_conv_bwd_data / agcn_conv9_infer (the shapes they cover)
+size_t agcn_conv_workspace(int Cin, int Cout, int T, int V, int taps, int stride) {
+  if (!agcn_tconv_legacy(taps, stride, (taps - 1) / 2)) return 256;
+  return agcn_tconv_workspace(Cin, Cout, T, V, taps, stride, (taps - 1) / 2);
+}
+// aggregate+project forward, backward-data (with room for the fused theta/phi term of 6*(Cout/4) channels) and dadj
+size_t agcn_gcn_workspace(int C, int Cout, int T, int V) {
+  AgcnDryRun d = {};
+  if (agcn_sizes_ok(1, C, Cout, T, V)) {
+    gcn_fwd_route(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1, C, Cout, T, V, nullptr, nullptr, &d);
+    gcn_bwd_data_route(nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0,
+                       nullptr, 0, 1, C, Cout, T, V, nullptr, nullptr, nullptr, &d);
+    const int K2 = 6 * (Cout / 4);
+    if (K2 > 0)      // (a null operand means "no fused term": the dry run names them by a placeholder)
+      gcn_bwd_data_route(nullptr, nullptr, nullptr, agcn_dry_present(), agcn_dry_present(), K2, nullptr, 0, nullptr, nullptr,
+                         nullptr, nullptr, 0, nullptr, 0, 1, C, Cout, T, V, nullptr, nullptr, nullptr, &d);
+    gcn_dadj_route(nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1, C, Cout, T, V, nullptr, nullptr, nullptr, &d);
+  }
+  return d.ws_bytes + 256;
+}
+
+// slots per sample of the (sum, sumsq) partials of the TILE-PER-WORKGROUP aggregate+project kernels.  No caller: the
+// persistent kernel's count depends on N, which this signature cannot describe, so it is not a dry run and keeps the
+// values it always returned.  What a caller allocates is agcn_gcn_stats_slots.
+int agcn_gcn_stats_tiles(int C, int Cout, int T, int V) {
+  if (agcn_chained() && C >= 32 && agcn_gcn_chain_supported(Cout, C, V)) return agcn_gcn_chain_tiles(T);
+  return agcn_conv_num_tiles(V, T);
+}
+
+// total slots (all samples) agcn_gcn_aggregate_project_fwd writes: what the caller allocates (the persistent chain kernel
+// writes one slot per (sample, frame split), whose count depends on N)
+int agcn_gcn_stats_slots(int N, int C, int Cout, int T, int V) {
+  if (!agcn_sizes_ok(N, C, Cout, T, V)) return 0;
+  AgcnDryRun d = {};
+  if (gcn_fwd_route(nullptr, nullptr, nullptr, nullptr, nullptr, agcn_dry_present(), nullptr, 0, N, C, Cout, T, V, nullptr,
+                    nullptr, &d))
+    return 0;
+  return (int)d.slab_slots;
+}
+
+int agcn_conv_fwd_ex(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* workspace,
+                     size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride,
+                     const float* x_absmax, void* stream);
+int agcn_conv_fwd(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* workspace,
+                  size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride,
+                  void* stream) {
+  return agcn_conv_fwd_ex(x, w, bias, y, stats_part, workspace, workspace_bytes, N, Cin, Cout, T, V, taps, stride, nullptr,
+                          stream);
+}
+
+// same; x_absmax (optional): device scalar max |x| left by agcn_bn_act_fwd_ex when it produced x -- saves the split-fp16
+// temporal convolution its own pass over x for the range scale
+int agcn_conv_fwd_ex(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* workspace,
+                     size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride,
+                     const float* x_absmax, void* stream) {
+  if (!x || !w || !y || !workspace || !agcn_sizes_ok(N, Cin, Cout, T, V)) return AGCN_ERR_ARG;
+  return conv_fwd_route(x, w, bias, y, stats_part, workspace, workspace_bytes, N, Cin, Cout, T, V, taps, stride, x_absmax,
+                        (hipStream_t)stream, nullptr);
+}
+
+int agcn_conv_bwd_data_ex(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
+                          const float* mask1, const float* add2, const float* mask2, void* workspace,
+                          size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride,
+                          const float* dy_absmax, void* stream);
+int agcn_conv_bwd_data(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
+                       const float* mask1, const float* add2, const float* mask2, void* workspace,
+                       size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride,
+                       void* stream) {
+  return agcn_conv_bwd_data_ex(dy, w, dx, accumulate, add1, mask1, add2, mask2, workspace, workspace_bytes, N, Cin, Cout, T,
+                               V, taps, stride, nullptr, stream);
+}
+
+// same; dy_absmax (optional): device scalar max |dy| left by agcn_bn_bwd_apply_ex
+int agcn_conv_bwd_data_ex(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
+                          const float* mask1, const float* add2, const float* mask2, void* workspace,
+                          size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride,
+                          const float* dy_absmax, void* stream) {
+  if (!dy || !w || !dx || !workspace || !agcn_sizes_ok(N, Cin, Cout, T, V)) return AGCN_ERR_ARG;
+  return conv_bwd_data_route(dy, w, dx, accumulate, add1, mask1, add2, mask2, workspace, workspace_bytes, N, Cin, Cout, T,
+                             V, taps, stride, dy_absmax, (hipStream_t)stream, nullptr);
+}
+
 int agcn_gcn_aggregate_project_fwd_ex(const float* x, const float* adj, const float* wcat, const float* bias, float* y,
                                       float* stats_part, void* workspace, size_t workspace_bytes, int N, int C, int Cout,
                                       int T, int V, const float* x_absmax, void* stream);
@@ -915,20 +1097,9 @@ int agcn_gcn_aggregate_project_fwd(const float* x, const float* adj, const float
 int agcn_gcn_aggregate_project_fwd_ex(const float* x, const float* adj, const float* wcat, const float* bias, float* y,
                                       float* stats_part, void* workspace, size_t workspace_bytes, int N, int C, int Cout,
                                       int T, int V, const float* x_absmax, void* stream) {
-  if (!x || !adj || !wcat || !y || !workspace || N <= 0 || C <= 0 || Cout <= 0 || T <= 0 || V <= 0 || V > 32)
-    return AGCN_ERR_ARG;
-  // (the 3-channel first layer's forward stays on the f32 kernel: measured 193 us against 260 us chained)
-  if (agcn_chained() && C >= 32 && agcn_gcn_chain_supported(Cout, C, V))
-    return agcn_gcn_chain(0, x, adj, wcat, bias, y, stats_part, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
-                          0, workspace, workspace_bytes, N, C, Cout, T, V, (hipStream_t)stream, 0, 0, x_absmax, nullptr);
-  Problem p = {};
-  ConvGemmArgs& a = p.a;
-  a.in = x; a.bias = bias; a.out = y; a.adj = adj; a.stats = stats_part;
-  a.N = N; a.M = Cout; a.Kinner = C; a.in_rows = C; a.V = V; a.T_src = T; a.T_out = T; a.T_full = T;
-  a.src_stride = 1; a.f_off = 0; a.out_fs = 1; a.out_fo = 0;
-  p.w = wcat; p.sa_m = 3L * C; p.sa_i = C; p.sa_c = 1; p.tap_flip_from = -1;
-  p.ws = workspace; p.ws_bytes = workspace_bytes;
-  return DISPATCH_BM(1, 1, CKA, CKA, 4, p, (hipStream_t)stream);
+  if (!x || !adj || !wcat || !y || !workspace || !agcn_sizes_ok(N, C, Cout, T, V)) return AGCN_ERR_ARG;
+  return gcn_fwd_route(x, adj, wcat, bias, y, stats_part, workspace, workspace_bytes, N, C, Cout, T, V, x_absmax,
+                       (hipStream_t)stream, nullptr);
 }
 
 // ---- BN-folded inference (eval mode): the BatchNorm that follows a contraction is folded into its weights and bias
@@ -938,33 +1109,32 @@ int agcn_gcn_aggregate_project_fwd_ex(const float* x, const float* adj, const fl
 int agcn_gcn_unit_infer(const float* x, const float* adj, const float* wcat, const float* bias, const float* res,
                         const float* x2, const float* w2, int K2, int relu, float* y, void* workspace,
                         size_t workspace_bytes, int N, int C, int Cout, int T, int V, void* stream) {
-  if (!x || !adj || !wcat || !y || !workspace || N <= 0 || C <= 0 || Cout <= 0 || T <= 0 || V <= 0 || V > 32)
-    return AGCN_ERR_ARG;
+  if (!x || !adj || !wcat || !y || !workspace || !agcn_sizes_ok(N, C, Cout, T, V)) return AGCN_ERR_ARG;
   if ((x2 == nullptr) != (w2 == nullptr) || (x2 && K2 <= 0)) return AGCN_ERR_ARG;
-  if (!(agcn_chained() && C >= 32 && agcn_gcn_chain_supported(Cout, C, V))) return AGCN_ERR_UNSUPPORTED;
-  if (x2 && K2 % 32 != 0) return AGCN_ERR_UNSUPPORTED;
-  if (agcn_gcn_chain_workspace(Cout, C, x2 ? K2 : 0, T, V) > workspace_bytes) return AGCN_ERR_WORKSPACE;
-  return agcn_gcn_chain(0, x, adj, wcat, bias, y, nullptr, 0, res, nullptr, nullptr, nullptr, 0, x2, w2, x2 ? K2 : 0,
-                        workspace, workspace_bytes, N, C, Cout, T, V, (hipStream_t)stream, relu, 1);
+  return gcn_unit_infer_route(x, adj, wcat, bias, res, x2, w2, K2, relu, y, workspace, workspace_bytes, N, C, Cout, T, V,
+                              (hipStream_t)stream, nullptr);
 }
 
 size_t agcn_gcn_unit_infer_workspace(int C, int Cout, int K2, int T, int V) {
-  return agcn_gcn_chain_workspace(Cout, C, K2, T, V) + 256;
+  AgcnDryRun d = {};
+  const float* x2 = K2 > 0 ? agcn_dry_present() : nullptr;
+  if (agcn_sizes_ok(1, C, Cout, T, V))
+    gcn_unit_infer_route(nullptr, nullptr, nullptr, nullptr, nullptr, x2, x2, K2, 0, nullptr, nullptr, 0, 1, C, Cout, T, V,
+                         nullptr, &d);
+  return d.ws_bytes + 256;
 }
 
 // y = act( bias + conv9x1(x; w, stride) [+ res] ),  res (N, Cout, T_out, V).  Split-bf16 modes only.
 int agcn_conv9_infer(const float* x, const float* w, const float* bias, const float* res, int relu, float* y,
                      void* workspace, size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int stride,
                      void* stream) {
-  if (!x || !w || !y || !workspace || N <= 0 || Cin <= 0 || Cout <= 0 || T <= 0 || V <= 0 || V > 32)
-    return AGCN_ERR_ARG;
+  if (!x || !w || !y || !workspace || !agcn_sizes_ok(N, Cin, Cout, T, V)) return AGCN_ERR_ARG;
   if (stride != 1 && stride != 2) return AGCN_ERR_UNSUPPORTED;
   if (agcn_gemm_precision() == 0) return AGCN_ERR_UNSUPPORTED;
   return agcn_bf16_conv9_fwd(x, w, bias, y, nullptr, workspace, workspace_bytes, N, Cin, Cout, T, V, stride,
                              agcn_gemm_precision(), (hipStream_t)stream, res, relu);
 }
 
-// dx[n][c][t,u] (+)= sum_i sum_o wcat[o][i*C+c] * sum_v dy[n][o][t,v] adj[n][i][u][v]   (+ masked addends)
 int agcn_gcn_bwd_data_fused_supported(int C, int Cout, int V);
 int agcn_gcn_aggregate_project_bwd_data_ex(const float* dy, const float* adj, const float* wcat, const float* dtp,
                                            const float* w2, int K2, float* dx, int accumulate, const float* add1,
@@ -987,29 +1157,10 @@ int agcn_gcn_aggregate_project_bwd_data_ex(const float* dy, const float* adj, co
                                            const float* mask1, const float* add2, const float* mask2, int mask_bits,
                                            void* workspace, size_t workspace_bytes, int N, int C, int Cout, int T, int V,
                                            const float* dy_absmax, const float* dtp_absmax, void* stream) {
-  if (!dy || !adj || !wcat || !dx || !workspace || N <= 0 || C <= 0 || Cout <= 0 || T <= 0 || V <= 0 || V > 32)
-    return AGCN_ERR_ARG;
-  if (dtp) {
-    if (!w2 || K2 <= 0) return AGCN_ERR_ARG;
-    if (!agcn_gcn_bwd_data_fused_supported(C, Cout, V)) return AGCN_ERR_UNSUPPORTED;
-    if (agcn_gcn_chain_workspace(C, Cout, K2, T, V) > workspace_bytes) return AGCN_ERR_WORKSPACE;
-    return agcn_gcn_chain(1, dy, adj, wcat, nullptr, dx, nullptr, accumulate, add1, mask1, add2, mask2, mask_bits, dtp,
-                          w2, K2, workspace, workspace_bytes, N, C, Cout, T, V, (hipStream_t)stream, 0, 0, dy_absmax,
-                          dtp_absmax);
-  }
-  if (agcn_chained() && agcn_gcn_chain_supported(C, Cout, V))
-    return agcn_gcn_chain(1, dy, adj, wcat, nullptr, dx, nullptr, accumulate, add1, mask1, add2, mask2, mask_bits,
-                          nullptr, nullptr, 0, workspace, workspace_bytes, N, C, Cout, T, V, (hipStream_t)stream, 0, 0,
-                          dy_absmax, nullptr);
-  Problem p = {};
-  ConvGemmArgs& a = p.a;
-  a.in = dy; a.out = dx; a.adj = adj; a.accumulate = accumulate;
-  a.add1 = add1; a.mask1 = mask1; a.add2 = add2; a.mask2 = mask2; a.mask_bits = mask_bits;
-  a.N = N; a.M = C; a.Kinner = Cout; a.in_rows = Cout; a.V = V; a.T_src = T; a.T_out = T; a.T_full = T;
-  a.src_stride = 1; a.f_off = 0; a.out_fs = 1; a.out_fo = 0;
-  p.w = wcat; p.sa_m = 1; p.sa_i = C; p.sa_c = 3L * C; p.tap_flip_from = -1;
-  p.ws = workspace; p.ws_bytes = workspace_bytes;
-  return DISPATCH_BM(1, 2, CKA, CKA, 4, p, (hipStream_t)stream);
+  if (!dy || !adj || !wcat || !dx || !workspace || !agcn_sizes_ok(N, C, Cout, T, V)) return AGCN_ERR_ARG;
+  if (dtp && (!w2 || K2 <= 0)) return AGCN_ERR_ARG;
+  return gcn_bwd_data_route(dy, adj, wcat, dtp, w2, K2, dx, accumulate, add1, mask1, add2, mask2, mask_bits, workspace,
+                            workspace_bytes, N, C, Cout, T, V, dy_absmax, dtp_absmax, (hipStream_t)stream, nullptr);
 }
 
 // Same, plus the 1x1 term of the adaptive branch in one pass:  dx (+)= ... + W2^T dtp  with dtp (N, K2, T, V) and
@@ -1029,7 +1180,6 @@ int agcn_gcn_aggregate_project_bwd_data_fused(const float* dy, const float* adj,
                                                 stream);
 }
 
-// dadj_part[n][i][slot][u][v] = sum over the slot's (c,t) of x[n][c][t,u] * (sum_o wcat[o][i*C+c] dy[n][o][t,v])
 int agcn_gcn_dadj_ex(const float* dy, const float* wcat, const float* x, float* dadj_part, void* workspace,
                      size_t workspace_bytes, int N, int C, int Cout, int T, int V, const float* dy_absmax,
                      const float* x_absmax, void* stream);
@@ -1042,65 +1192,20 @@ int agcn_gcn_dadj(const float* dy, const float* wcat, const float* x, float* dad
 int agcn_gcn_dadj_ex(const float* dy, const float* wcat, const float* x, float* dadj_part, void* workspace,
                      size_t workspace_bytes, int N, int C, int Cout, int T, int V, const float* dy_absmax,
                      const float* x_absmax, void* stream) {
-  if (!dy || !wcat || !x || !dadj_part || !workspace || N <= 0 || C <= 0 || Cout <= 0 || T <= 0 || V <= 0 || V > 32)
-    return AGCN_ERR_ARG;
-  if (agcn_chained() && agcn_gcn_dadj_chain_supported(C, V))
-    return agcn_gcn_dadj_chain(dy, wcat, x, dadj_part, workspace, workspace_bytes, N, C, Cout, T, V, (hipStream_t)stream,
-                               dy_absmax, x_absmax);
-  if (C >= 64 && C % 64 != 0) return AGCN_ERR_UNSUPPORTED;
-  Problem p = {};
-  ConvGemmArgs& a = p.a;
-  a.in = dy; a.xin = x; a.dadj = dadj_part;
-  a.N = N; a.M = 3 * C; a.Kinner = Cout; a.in_rows = Cout; a.V = V; a.T_src = T; a.T_out = T; a.T_full = T;
-  a.src_stride = 1; a.f_off = 0; a.out_fs = 1; a.out_fo = 0; a.C = C;
-  p.w = wcat; p.sa_m = 1; p.sa_i = 0; p.sa_c = 3L * C; p.tap_flip_from = -1;
-  p.ws = workspace; p.ws_bytes = workspace_bytes;
-  return launch_cfg<1, 0, 1, 4, 2, 1, CKD, 2, 1>(p, (hipStream_t)stream);
+  if (!dy || !wcat || !x || !dadj_part || !workspace || !agcn_sizes_ok(N, C, Cout, T, V)) return AGCN_ERR_ARG;
+  return gcn_dadj_route(dy, wcat, x, dadj_part, workspace, workspace_bytes, N, C, Cout, T, V, dy_absmax, x_absmax,
+                        (hipStream_t)stream, nullptr);
 }
 
 
 // ---- temporal convolution with explicit padding (reference aagcn.py:184-207 TCNUnit(kernel_size, stride, pad),
 // agcn.py:36-50 unit_tcn(kernel_size, stride)): taps 1..9, stride 1..9, pad 0..(taps-1)/2 ----
-size_t agcn_tconv_workspace(int Cin, int Cout, int T, int V, int taps, int stride, int pad) {
-  if (tconv_domain(T, taps, stride, pad)) return 256;
-  if (tconv_legacy(taps, stride, pad)) return agcn_conv_workspace(Cin, Cout, T, V, taps, stride);
-  // upper bound of every packed weight image the paths below build: rows rounded to 128, K to 16, 6 bytes per element
-  // (three bf16 planes; the f32 image takes 4)
-  const size_t a = round_up(Cout, 128) * round_up(Cin, 16), b = round_up(Cin, 128) * round_up(Cout, 16);
-  return (a > b ? a : b) * (size_t)taps * 6 + 256;
-}
-
-int agcn_tconv_stats_tiles(int Cin, int Cout, int T_out, int V, int taps, int stride, int pad) {
-  if (T_out <= 0 || V <= 0) return 0;
-  if (tconv_legacy(taps, stride, pad)) return agcn_conv_stats_tiles(Cin, Cout, T_out, V, taps, stride);
-  const int tt = tconv_fast(taps, stride) ? agcn_bf16_tconv_tile_frames(taps, Cout, V, T_out, agcn_gemm_precision())
-                                          : tconv_f32_tt(V, T_out, taps, stride);
-  return (T_out + tt - 1) / tt;
-}
-
-// y[n][o][t,v] = bias[o] + sum_{c,k} w[o][c][k] x[n][c][t*stride + k - pad, v],  T_out = (T + 2 pad - taps)/stride + 1
 int agcn_tconv_fwd(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* workspace,
                    size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride, int pad,
                    const float* x_absmax, void* stream) {
-  if (!x || !w || !y || !workspace || N <= 0 || Cin <= 0 || Cout <= 0 || T <= 0 || V <= 0 || V > 32)
-    return AGCN_ERR_ARG;
-  if (int rc = tconv_domain(T, taps, stride, pad)) return rc;
-  if (tconv_legacy(taps, stride, pad))
-    return agcn_conv_fwd_ex(x, w, bias, y, stats_part, workspace, workspace_bytes, N, Cin, Cout, T, V, taps, stride,
-                            x_absmax, stream);
-  hipStream_t s = (hipStream_t)stream;
-  if (tconv_fast(taps, stride))
-    return agcn_bf16_tconv_fwd(x, w, bias, y, stats_part, workspace, workspace_bytes, N, Cin, Cout, T, V, taps, pad,
-                               agcn_gemm_precision(), s, x_absmax);
-  Problem p = {};
-  ConvGemmArgs& a = p.a;
-  a.in = x; a.bias = bias; a.out = y; a.stats = stats_part;
-  a.N = N; a.M = Cout; a.Kinner = Cin; a.in_rows = Cin; a.V = V;
-  a.T_src = T; a.T_out = tconv_out_frames(T, taps, stride, pad); a.T_full = a.T_out;
-  a.src_stride = stride; a.f_off = -pad; a.out_fs = 1; a.out_fo = 0;
-  p.w = w; p.sa_m = (long)Cin * taps; p.sa_i = 0; p.sa_c = taps; p.tap_flip_from = -1;
-  p.ws = workspace; p.ws_bytes = workspace_bytes;
-  return tconv_f32_dispatch(taps, p, s);
+  if (!x || !w || !y || !workspace || !agcn_sizes_ok(N, Cin, Cout, T, V)) return AGCN_ERR_ARG;
+  return tconv_fwd_route(x, w, bias, y, stats_part, workspace, workspace_bytes, N, Cin, Cout, T, V, taps, stride, pad,
+                         x_absmax, (hipStream_t)stream, nullptr);
 }
 
 // BN-folded inference form (eval mode; reference aagcn.py:264-271 gates, :194-201 TCNUnit, :316-321 unit tail):
@@ -1108,75 +1213,24 @@ int agcn_tconv_fwd(const float* x, const float* w, const float* bias, float* y, 
 // The caller has folded the BatchNorm into w and bias.  a_s (N,V), a_t (N,T), a_c (N,Cin): each optional, null = ones;
 // they multiply x where its tile is staged for the matrix cores (gate.h), so the gated tensor is never stored.  res
 // (N, Cout, T_out, V) or null; x_absmax: optional device scalar max |x| (of the UNGATED x) for the f16x3 range scale.
-// Same domain and workspace as agcn_tconv_fwd.  9 taps / pad 4 / stride 1-2 and stride-1 3/5/7 taps run on the
-// split-bf16 / f16x3 kernels, everything else (and AGCN_GEMM=f32) on the exact-f32 kernel; one epilogue (epilogue.h).
+// Same domain and workspace as agcn_tconv_fwd.  As everywhere, it is the launcher that compares its need with
+// workspace_bytes (AGCN_ERR_WORKSPACE): there is no separate comparison with the query's answer up front.
 int agcn_tconv_infer(const float* x, const float* w, const float* bias, const float* a_s, const float* a_t,
                      const float* a_c, const float* res, int relu, float* y, void* workspace, size_t workspace_bytes,
                      int N, int Cin, int Cout, int T, int V, int taps, int stride, int pad, const float* x_absmax,
                      void* stream) {
-  if (!x || !w || !y || !workspace || N <= 0 || Cin <= 0 || Cout <= 0 || T <= 0 || V <= 0 || V > 32)
-    return AGCN_ERR_ARG;
-  if (int rc = tconv_domain(T, taps, stride, pad)) return rc;
-  if (workspace_bytes < agcn_tconv_workspace(Cin, Cout, T, V, taps, stride, pad)) return AGCN_ERR_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  GateArgs gate = {a_s, a_t, a_c};
-  if (agcn_gemm_precision() != 0 && agcn_bf16_tconv_infer_supported(taps, stride, pad)) {
-    const int rc = agcn_bf16_tconv_infer(x, w, bias, y, workspace, workspace_bytes, N, Cin, Cout, T, V, taps, stride, pad,
-                                         agcn_gemm_precision(), s, res, relu, x_absmax, &gate);
-    // (a window too long for their LDS is refused before anything is launched there: the exact kernel below)
-    if (rc != AGCN_ERR_UNSUPPORTED) return rc;
-  }
-  Problem p = {};
-  ConvGemmArgs& a = p.a;
-  a.in = x; a.bias = bias; a.out = y; a.add1 = res;
-  p.gate = gate; p.gated = (a_s || a_t || a_c) ? 1 : 0; p.relu = relu;
-  a.N = N; a.M = Cout; a.Kinner = Cin; a.in_rows = Cin; a.V = V;
-  a.T_src = T; a.T_out = tconv_out_frames(T, taps, stride, pad); a.T_full = a.T_out;
-  a.src_stride = stride; a.f_off = -pad; a.out_fs = 1; a.out_fo = 0;
-  p.w = w; p.sa_m = (long)Cin * taps; p.sa_i = 0; p.sa_c = taps; p.tap_flip_from = -1;
-  p.ws = workspace; p.ws_bytes = workspace_bytes;
-  return tconv_f32_infer_dispatch(taps, p, s);
+  if (!x || !w || !y || !workspace || !agcn_sizes_ok(N, Cin, Cout, T, V)) return AGCN_ERR_ARG;
+  return tconv_infer_route(x, w, bias, a_s, a_t, a_c, res, relu, y, workspace, workspace_bytes, N, Cin, Cout, T, V, taps,
+                           stride, pad, x_absmax, (hipStream_t)stream, nullptr);
 }
 
-// dx[n][c][t,v] (+)= sum_{o,k: (t + pad - k) = stride*tau} w[o][c][k] dy[n][o][tau, v]  (+ masked addends); frames no
-// window reaches get 0 (+ addends)
 int agcn_tconv_bwd_data(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
                         const float* mask1, const float* add2, const float* mask2, void* workspace,
                         size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride, int pad,
                         const float* dy_absmax, void* stream) {
-  if (!dy || !w || !dx || !workspace || N <= 0 || Cin <= 0 || Cout <= 0 || T <= 0 || V <= 0 || V > 32)
-    return AGCN_ERR_ARG;
-  if (int rc = tconv_domain(T, taps, stride, pad)) return rc;
-  if (tconv_legacy(taps, stride, pad))
-    return agcn_conv_bwd_data_ex(dy, w, dx, accumulate, add1, mask1, add2, mask2, workspace, workspace_bytes, N, Cin,
-                                 Cout, T, V, taps, stride, dy_absmax, stream);
-  hipStream_t s = (hipStream_t)stream;
-  if (tconv_fast(taps, stride))
-    return agcn_bf16_tconv_bwd_data(dy, w, dx, accumulate, add1, mask1, add2, mask2, workspace, workspace_bytes, N, Cin,
-                                    Cout, T, V, taps, pad, agcn_gemm_precision(), s, dy_absmax);
-  // output frames t = stride*tau + r of one residue r form a stride-1 problem over tau: only the taps
-  // k = k0 + stride*i (k0 = (r + pad) mod stride) reach them,  dx[stride*tau + r] = sum_j W[k0 + stride*(J-1-j)]
-  // dy[tau + (r + pad - k0)/stride - (J-1) + j],  J = number of such taps (0: the residue receives no signal)
-  Problem p = {};
-  ConvGemmArgs& a = p.a;
-  a.in = dy; a.out = dx; a.accumulate = accumulate;
-  a.add1 = add1; a.mask1 = mask1; a.add2 = add2; a.mask2 = mask2;
-  a.N = N; a.M = Cin; a.in_rows = Cout; a.V = V;
-  a.T_src = tconv_out_frames(T, taps, stride, pad); a.T_full = T; a.src_stride = 1; a.out_fs = stride;
-  p.w = w; p.sa_m = taps; p.sa_i = 0; p.sa_c = (long)Cin * taps;
-  p.ws = workspace; p.ws_bytes = workspace_bytes;
-  for (int r = 0; r < stride && r < T; ++r) {
-    const int k0 = (r + pad) % stride;
-    const int J = k0 < taps ? (taps - k0 + stride - 1) / stride : 0;
-    a.T_out = (T - r + stride - 1) / stride;
-    a.out_fo = r;
-    a.Kinner = J > 0 ? Cout : 0;          // no K chunks: the epilogue writes 0 (+accumulate/addends)
-    a.f_off = J > 0 ? (r + pad - k0) / stride - (J - 1) : 0;
-    p.tap_mul = stride; p.tap_add = 0; p.tap_flip_from = k0 + stride * (J > 0 ? J - 1 : 0);
-    const int rc = tconv_f32_dispatch(J > 0 ? J : 1, p, s);
-    if (rc) return rc;
-  }
-  return 0;
+  if (!dy || !w || !dx || !workspace || !agcn_sizes_ok(N, Cin, Cout, T, V)) return AGCN_ERR_ARG;
+  return tconv_bwd_data_route(dy, w, dx, accumulate, add1, mask1, add2, mask2, workspace, workspace_bytes, N, Cin, Cout, T,
+                              V, taps, stride, pad, dy_absmax, (hipStream_t)stream, nullptr);
 }
 
 }  // extern "C"

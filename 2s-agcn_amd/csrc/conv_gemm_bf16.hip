@@ -702,7 +702,7 @@ struct BfProblem {
   int tap_mul, tap_add, tap_flip_from;
   void* ws;
   size_t ws_bytes;
-  int stats_tiles;             // > 0: tiles per sample the caller sized the stats partials for (agcn_tconv_stats_tiles)
+  AgcnDryRun* dry;             // non-null: a size query (agcn_common.h), nothing is launched
 };
 
 // bytes of the gate vectors' LDS image behind the bias row (gate.h)
@@ -721,8 +721,8 @@ int launch_bf(BfProblem& p, hipStream_t stream) {
   }
   if (g.smem_bytes > 160 * 1024) return AGCN_ERR_UNSUPPORTED;
   if ((g.FW * a.V + 3) / 4 > WQ * 64) return AGCN_ERR_UNSUPPORTED;
+  if (p.dry) return agcn_dry_note(p.dry, a.stats ? (long)a.N * g.ntiles : 0, g.pack_bytes);
   if (g.pack_bytes > p.ws_bytes) return AGCN_ERR_WORKSPACE;
-  if (a.stats && p.stats_tiles > 0 && g.ntiles != p.stats_tiles) return AGCN_ERR_ARG;   // (never write past the partials)
   a.tt = g.tt; a.ntiles = g.ntiles; a.FW = g.FW; a.WLR = g.WLR; a.nchunks = g.nchunks; a.nmb = g.nmb;
   a.off_b = g.off_b; a.off_bias = g.off_bias;
   a.wp = (const unsigned short*)p.ws;
@@ -792,8 +792,8 @@ int launch_pc(BfProblem& p, hipStream_t stream) {
     g.smem_bytes += gate_bytes(g);
   }
   if (g.smem_bytes > 160 * 1024) return AGCN_ERR_UNSUPPORTED;
+  if (p.dry) return agcn_dry_note(p.dry, a.stats ? (long)a.N * g.ntiles : 0, g.pack_bytes);
   if (g.pack_bytes > p.ws_bytes) return AGCN_ERR_WORKSPACE;
-  if (a.stats && p.stats_tiles > 0 && g.ntiles != p.stats_tiles) return AGCN_ERR_ARG;   // (never write past the partials)
   a.tt = g.tt; a.ntiles = g.ntiles; a.FW = g.FW; a.WLR = g.WLR; a.nchunks = g.nchunks; a.nmb = g.nmb;
   a.off_b = g.off_b; a.off_bias = g.off_bias;
   a.wp = (const unsigned short*)p.ws;
@@ -871,15 +871,6 @@ bool agcn_bf16_conv_wide(int taps, int M) {
 }
 
 // internal entry points used by conv_gemm.hip's dispatch (precision: 3 = bf16x6, 2 = bf16x3)
-size_t agcn_bf16_conv_workspace(int Cin, int Cout, int T, int V, int stride) {
-  const int To = (T + 8 - 9) / stride + 1;
-  size_t b = bf_geometry<9, 64>(V, To, stride, Cout, Cin).pack_bytes, t;
-  t = bf_geometry<9, 64>(V, T, 1, Cin, Cout).pack_bytes; if (t > b) b = t;
-  t = bf_geometry<9, 128>(V, To, stride, Cout, Cin).pack_bytes; if (t > b) b = t;
-  t = bf_geometry<9, 128>(V, T, 1, Cin, Cout).pack_bytes; if (t > b) b = t;
-  return b + 256;
-}
-
 namespace {
 
 // f16x3 range scale of the streamed operand: the maximum its producer left behind, or a streaming pass of our own whose
@@ -889,6 +880,7 @@ int bf16_in_absmax(BfProblem& p, const float* given, const float* in, long n, hi
     p.a.in_absmax = given;
     return 0;
   }
+  if (p.dry) return 0;         // (the size queries carry the slack for the scalar)
   if (p.ws_bytes < 64) return AGCN_ERR_WORKSPACE;
   unsigned* amax = reinterpret_cast<unsigned*>(static_cast<char*>(p.ws) + ((p.ws_bytes - 16) & ~(size_t)15));
   if (hipMemsetAsync(amax, 0, 4, s) != hipSuccess) return AGCN_ERR_ARG;
@@ -908,9 +900,10 @@ int bf16_fwd_f16x3(int npl) {   // AGCN_CONV_F16X3=0 keeps the temporal convolut
 template <int TAPS, int WQ, bool GATE = false>
 int bf16_tconv_fwd(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* ws,
                    size_t ws_bytes, int N, int Cin, int Cout, int T, int V, int stride, int pad, int npl, hipStream_t s,
-                   const float* add, int relu, const float* x_absmax, const GateArgs* gate = nullptr) {
+                   const float* add, int relu, const float* x_absmax, AgcnDryRun* dry, const GateArgs* gate = nullptr) {
   BfProblem p = {};
   BfArgs& a = p.a;
+  p.dry = dry;
   a.in = x; a.bias = bias; a.out = y; a.stats = stats_part; a.add1 = add; a.relu = relu;
   if (GATE) p.gate = *gate;
   p.fwd_f16 = bf16_fwd_f16x3(npl);
@@ -921,10 +914,6 @@ int bf16_tconv_fwd(const float* x, const float* w, const float* bias, float* y, 
   a.T_src = T; a.T_out = (T + 2 * pad - TAPS) / stride + 1; a.T_full = a.T_out;
   a.src_stride = stride; a.f_off = -pad; a.out_fs = 1; a.out_fo = 0;
   p.w = w; p.sa_m = (long)Cin * TAPS; p.sa_c = TAPS; p.tap_flip_from = -1;
-  if (TAPS != 9 && stats_part) {     // the caller sized the partials by agcn_bf16_tconv_tile_frames: the launch checks it
-    const int tt = agcn_bf16_tconv_tile_frames(TAPS, Cout, V, a.T_out, npl);
-    p.stats_tiles = (a.T_out + tt - 1) / tt;
-  }
   return launch_npl<TAPS, WQ, GATE>(p, npl, s);
 }
 
@@ -932,9 +921,11 @@ int bf16_tconv_fwd(const float* x, const float* w, const float* bias, float* y, 
 template <int TAPS>
 int bf16_tconv_bwd_data_s1(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
                            const float* mask1, const float* add2, const float* mask2, void* ws, size_t ws_bytes, int N,
-                           int Cin, int Cout, int T, int V, int pad, int npl, hipStream_t s, const float* dy_absmax) {
+                           int Cin, int Cout, int T, int V, int pad, int npl, hipStream_t s, const float* dy_absmax,
+                           AgcnDryRun* dry) {
   BfProblem p = {};
   BfArgs& a = p.a;
+  p.dry = dry;
   p.fwd_f16 = bf16_fwd_f16x3(npl);     // f16x3 with the gradient normalised by its maximum
   p.ws = ws; p.ws_bytes = ws_bytes;
   const int To = T + 2 * pad - TAPS + 1;
@@ -954,23 +945,24 @@ int bf16_tconv_bwd_data_s1(const float* dy, const float* w, float* dx, int accum
 
 int agcn_bf16_conv9_fwd(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* ws,
                         size_t ws_bytes, int N, int Cin, int Cout, int T, int V, int stride, int npl,
-                        hipStream_t s, const float* add, int relu, const float* x_absmax) {
+                        hipStream_t s, const float* add, int relu, const float* x_absmax, AgcnDryRun* dry) {
   if (stride == 1)
     return bf16_tconv_fwd<9, 2>(x, w, bias, y, stats_part, ws, ws_bytes, N, Cin, Cout, T, V, 1, 4, npl, s, add, relu,
-                                x_absmax);
+                                x_absmax, dry);
   return bf16_tconv_fwd<9, 3>(x, w, bias, y, stats_part, ws, ws_bytes, N, Cin, Cout, T, V, stride, 4, npl, s, add, relu,
-                              x_absmax);
+                              x_absmax, dry);
 }
 
 int agcn_bf16_conv9_bwd_data(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
                              const float* mask1, const float* add2, const float* mask2, void* ws, size_t ws_bytes,
                              int N, int Cin, int Cout, int T, int V, int stride, int npl, hipStream_t s,
-                             const float* dy_absmax) {
+                             const float* dy_absmax, AgcnDryRun* dry) {
   if (stride == 1)
     return bf16_tconv_bwd_data_s1<9>(dy, w, dx, accumulate, add1, mask1, add2, mask2, ws, ws_bytes, N, Cin, Cout, T, V,
-                                     4, npl, s, dy_absmax);
+                                     4, npl, s, dy_absmax, dry);
   BfProblem p = {};
   BfArgs& a = p.a;
+  p.dry = dry;
   p.fwd_f16 = bf16_fwd_f16x3(npl);
   p.ws = ws; p.ws_bytes = ws_bytes;
   if (p.fwd_f16)
@@ -996,14 +988,14 @@ bool agcn_bf16_tconv_supported(int taps, int stride) { return stride == 1 && (ta
 
 int agcn_bf16_tconv_fwd(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* ws,
                         size_t ws_bytes, int N, int Cin, int Cout, int T, int V, int taps, int pad, int npl,
-                        hipStream_t s, const float* x_absmax) {
+                        hipStream_t s, const float* x_absmax, AgcnDryRun* dry) {
   switch (taps) {
     case 3: return bf16_tconv_fwd<3, 2>(x, w, bias, y, stats_part, ws, ws_bytes, N, Cin, Cout, T, V, 1, pad, npl, s,
-                                        nullptr, 0, x_absmax);
+                                        nullptr, 0, x_absmax, dry);
     case 5: return bf16_tconv_fwd<5, 2>(x, w, bias, y, stats_part, ws, ws_bytes, N, Cin, Cout, T, V, 1, pad, npl, s,
-                                        nullptr, 0, x_absmax);
+                                        nullptr, 0, x_absmax, dry);
     case 7: return bf16_tconv_fwd<7, 2>(x, w, bias, y, stats_part, ws, ws_bytes, N, Cin, Cout, T, V, 1, pad, npl, s,
-                                        nullptr, 0, x_absmax);
+                                        nullptr, 0, x_absmax, dry);
     default: return AGCN_ERR_UNSUPPORTED;
   }
 }
@@ -1011,14 +1003,14 @@ int agcn_bf16_tconv_fwd(const float* x, const float* w, const float* bias, float
 int agcn_bf16_tconv_bwd_data(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
                              const float* mask1, const float* add2, const float* mask2, void* ws, size_t ws_bytes,
                              int N, int Cin, int Cout, int T, int V, int taps, int pad, int npl, hipStream_t s,
-                             const float* dy_absmax) {
+                             const float* dy_absmax, AgcnDryRun* dry) {
   switch (taps) {
     case 3: return bf16_tconv_bwd_data_s1<3>(dy, w, dx, accumulate, add1, mask1, add2, mask2, ws, ws_bytes, N, Cin, Cout,
-                                             T, V, pad, npl, s, dy_absmax);
+                                             T, V, pad, npl, s, dy_absmax, dry);
     case 5: return bf16_tconv_bwd_data_s1<5>(dy, w, dx, accumulate, add1, mask1, add2, mask2, ws, ws_bytes, N, Cin, Cout,
-                                             T, V, pad, npl, s, dy_absmax);
+                                             T, V, pad, npl, s, dy_absmax, dry);
     case 7: return bf16_tconv_bwd_data_s1<7>(dy, w, dx, accumulate, add1, mask1, add2, mask2, ws, ws_bytes, N, Cin, Cout,
-                                             T, V, pad, npl, s, dy_absmax);
+                                             T, V, pad, npl, s, dy_absmax, dry);
     default: return AGCN_ERR_UNSUPPORTED;
   }
 }
@@ -1029,7 +1021,7 @@ int agcn_bf16_tconv_bwd_data(const float* dy, const float* w, float* dx, int acc
 template <int TAPS, int WQ>
 static int bf16_tconv_infer_t(const float* x, const float* w, const float* bias, float* y, void* ws, size_t ws_bytes, int N,
                               int Cin, int Cout, int T, int V, int stride, int pad, int npl, hipStream_t s,
-                              const float* add, int relu, const float* x_absmax, const GateArgs* gate) {
+                              const float* add, int relu, const float* x_absmax, const GateArgs* gate, AgcnDryRun* dry) {
   // the narrowest tile these kernels fall back to must hold the window (launch_bf's own checks): decided here, before
   // the f16x3 maximum is taken, so that a shape handed on to the exact kernel has launched nothing
   const bool gated = gate && (gate->gs || gate->gt || gate->gc);
@@ -1040,9 +1032,9 @@ static int bf16_tconv_infer_t(const float* x, const float* w, const float* bias,
   }
   if (gated)
     return bf16_tconv_fwd<TAPS, WQ, true>(x, w, bias, y, nullptr, ws, ws_bytes, N, Cin, Cout, T, V, stride, pad, npl, s, add,
-                                          relu, x_absmax, gate);
+                                          relu, x_absmax, dry, gate);
   return bf16_tconv_fwd<TAPS, WQ>(x, w, bias, y, nullptr, ws, ws_bytes, N, Cin, Cout, T, V, stride, pad, npl, s, add, relu,
-                                  x_absmax);
+                                  x_absmax, dry);
 }
 
 bool agcn_bf16_tconv_infer_supported(int taps, int stride, int pad) {
@@ -1052,10 +1044,10 @@ bool agcn_bf16_tconv_infer_supported(int taps, int stride, int pad) {
 
 int agcn_bf16_tconv_infer(const float* x, const float* w, const float* bias, float* y, void* ws, size_t ws_bytes, int N,
                           int Cin, int Cout, int T, int V, int taps, int stride, int pad, int npl, hipStream_t s,
-                          const float* add, int relu, const float* x_absmax, const GateArgs* gate) {
+                          const float* add, int relu, const float* x_absmax, const GateArgs* gate, AgcnDryRun* dry) {
   if (!agcn_bf16_tconv_infer_supported(taps, stride, pad)) return AGCN_ERR_UNSUPPORTED;
 #define AGCN_INFER_CASE(TAPS, WQ) \
-  return bf16_tconv_infer_t<TAPS, WQ>(x, w, bias, y, ws, ws_bytes, N, Cin, Cout, T, V, stride, pad, npl, s, add, relu, x_absmax, gate)
+  return bf16_tconv_infer_t<TAPS, WQ>(x, w, bias, y, ws, ws_bytes, N, Cin, Cout, T, V, stride, pad, npl, s, add, relu, x_absmax, gate, dry)
   switch (taps) {
     case 3: AGCN_INFER_CASE(3, 2);
     case 5: AGCN_INFER_CASE(5, 2);
@@ -1067,32 +1059,13 @@ int agcn_bf16_tconv_infer(const float* x, const float* w, const float* bias, flo
 #undef AGCN_INFER_CASE
 }
 
-// frames per stats tile of agcn_bf16_tconv_fwd (the wide 64-row tile covers 512 positions, every other one 256)
-int agcn_bf16_tconv_tile_frames(int taps, int M, int V, int T_out, int npl) {
-  int tt = 256 / V;
-  if (M <= 64 && agcn_bf16_conv_wide(taps, M) && (npl == 3 || npl == 1)) {
-    bool ok = false;
-    switch (taps) {
-      case 3: ok = bf_geometry<3, 64, 2>(V, T_out, 1, M, 16).smem_bytes <= 160 * 1024; break;
-      case 5: ok = bf_geometry<5, 64, 2>(V, T_out, 1, M, 16).smem_bytes <= 160 * 1024; break;
-      case 7: ok = bf_geometry<7, 64, 2>(V, T_out, 1, M, 16).smem_bytes <= 160 * 1024; break;
-      default: break;
-    }
-    int tw = 512 / V;
-    if (tw > T_out) tw = T_out;
-    if (ok && ((tw - 1) + taps) * V <= 3 * 64 * 4) tt = 512 / V;     // (launch_bf's WQ = 3 window bound)
-  }
-  if (tt > T_out) tt = T_out;
-  if (tt < 1) tt = 1;
-  return tt;
-}
-
 // 1x1 convolutions (conv_a/conv_b/down/residual; reference agcn.py:66-75,122-125) on the same kernel, TAPS = 1
 int agcn_bf16_conv1_fwd(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* ws,
                         size_t ws_bytes, int N, int Cin, int Cout, int T, int V, int stride, int npl,
-                        hipStream_t s, const float* add, int relu) {
+                        hipStream_t s, const float* add, int relu, AgcnDryRun* dry) {
   BfProblem p = {};
   BfArgs& a = p.a;
+  p.dry = dry;
   a.in = x; a.bias = bias; a.out = y; a.stats = stats_part; a.add1 = add; a.relu = relu;
   a.N = N; a.M = Cout; a.Kinner = Cin; a.in_rows = Cin; a.V = V;
   a.T_src = T; a.T_out = (T - 1) / stride + 1; a.T_full = a.T_out;
@@ -1106,9 +1079,10 @@ int agcn_bf16_conv1_fwd(const float* x, const float* w, const float* bias, float
 // stride 1 only (the stride-2 1x1 backward is a scatter to even frames: conv_gemm.hip keeps it)
 int agcn_bf16_conv1_bwd_data(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
                              const float* mask1, const float* add2, const float* mask2, void* ws, size_t ws_bytes,
-                             int N, int Cin, int Cout, int T, int V, int npl, hipStream_t s) {
+                             int N, int Cin, int Cout, int T, int V, int npl, hipStream_t s, AgcnDryRun* dry) {
   BfProblem p = {};
   BfArgs& a = p.a;
+  p.dry = dry;
   a.in = dy; a.out = dx; a.accumulate = accumulate;
   a.add1 = add1; a.mask1 = mask1; a.add2 = add2; a.mask2 = mask2;
   a.N = N; a.M = Cin; a.Kinner = Cout; a.in_rows = Cout; a.V = V;
@@ -1117,13 +1091,4 @@ int agcn_bf16_conv1_bwd_data(const float* dy, const float* w, float* dx, int acc
   p.w = w; p.sa_m = 1; p.sa_c = Cin; p.tap_mul = 1; p.tap_add = 0; p.tap_flip_from = 0;
   p.ws = ws; p.ws_bytes = ws_bytes;
   return launch_npl<1, 2>(p, npl, s);
-}
-
-size_t agcn_bf16_conv1_workspace(int Cin, int Cout, int T, int V, int stride) {
-  const int To = (T - 1) / stride + 1;
-  size_t b = bf_geometry<1, 64>(V, To, stride, Cout, Cin).pack_bytes, t;
-  t = bf_geometry<1, 64>(V, T, 1, Cin, Cout).pack_bytes; if (t > b) b = t;
-  t = bf_geometry<1, 128>(V, To, stride, Cout, Cin).pack_bytes; if (t > b) b = t;
-  t = bf_geometry<1, 128>(V, T, 1, Cin, Cout).pack_bytes; if (t > b) b = t;
-  return b + 256;
 }

@@ -342,11 +342,13 @@ WGeom wgeom(int N, int M, int C, int V, int T_out, int stride, int tt_cap = 0) {
   return g;
 }
 
+// dry non-null: a size query (agcn_common.h); the partial slab is the workspace, its slots are the slabs
 template <int TAPS, int AGG, int MW, int CW, int TH, bool KSPLIT, int WBX>
-int launch_wgrad(WgradArgs a, float* dw, void* ws, size_t ws_bytes, hipStream_t stream, int tt_cap = 0) {
+int launch_wgrad(WgradArgs a, float* dw, void* ws, size_t ws_bytes, hipStream_t stream, AgcnDryRun* dry, int tt_cap = 0) {
   const WGeom g = wgeom<TAPS, AGG, MW, CW, TH, KSPLIT>(a.N, a.M, a.C, a.V, a.T_out, a.stride, tt_cap);
   if (g.smem_bytes > 160 * 1024) return AGCN_ERR_UNSUPPORTED;
   if (g.WLP > WBX * 64 || g.tt * a.V > 128) return AGCN_ERR_UNSUPPORTED;
+  if (dry) return agcn_dry_note(dry, g.nslabs, (size_t)g.nslabs * a.wsize * 4);
   if ((size_t)g.nslabs * a.wsize * 4 > ws_bytes) return AGCN_ERR_WORKSPACE;
   a.part = (float*)ws;
   a.tt = g.tt; a.ntiles = g.ntiles; a.FW = g.FW; a.WLP = g.WLP; a.DAP = g.DAP; a.GP = g.GP;
@@ -361,19 +363,13 @@ int launch_wgrad(WgradArgs a, float* dw, void* ws, size_t ws_bytes, hipStream_t 
   return launch_reduce((const float*)ws, dw, a.wsize, g.nslabs, a.M, a.C, a.so_m, a.so_t, a.so_c, stream);
 }
 
-template <int TAPS, int AGG, int MW, int CW, int TH, bool KSPLIT>
-size_t ws_wgrad(int N, int M, int C, int V, int T_out, int stride, long wsize, int tt_cap = 0) {
-  const WGeom g = wgeom<TAPS, AGG, MW, CW, TH, KSPLIT>(N, M, C, V, T_out, stride, tt_cap);
-  return (size_t)g.nslabs * wsize * 4;
-}
-
 // split-bf16 path (wgrad_chain.hip) + the same fixed-order slab reduction
 int chain_wgrad_and_reduce(int agg, const WgradArgs& a, float* dw, void* ws, size_t ws_bytes, hipStream_t stream,
-                           const float* dy_absmax = nullptr, const float* x_absmax = nullptr) {
+                           const float* dy_absmax, const float* x_absmax, AgcnDryRun* dry) {
   int nslabs = 0;
   int rc = agcn_wgrad_chain(agg, a.dy, a.in, a.adj, ws, ws_bytes, &nslabs, a.N, a.M, a.C, a.V, a.T_src, a.T_out,
-                            a.stride, stream, dy_absmax, x_absmax);
-  if (rc) return rc;
+                            a.stride, stream, dy_absmax, x_absmax, dry);
+  if (rc || dry) return rc;
   return launch_reduce((const float*)ws, dw, a.wsize, nslabs, a.M, a.C, a.so_m, a.so_t, a.so_c, stream);
 }
 
@@ -399,44 +395,31 @@ inline int tconv_w_tt(int V, int T_out, int taps, int stride) {
 
 // the 8 waves split the taps (TAPS >= 2) or the positions (1 tap) in two, as the 9- and 1-tap gradients do
 template <int TAPS>
-int tconv_wgrad(WgradArgs a, float* dw, void* ws, size_t ws_bytes, hipStream_t s, size_t* ws_need) {
+int tconv_wgrad(WgradArgs a, float* dw, void* ws, size_t ws_bytes, hipStream_t s, AgcnDryRun* dry) {
   const int cap = tconv_w_tt(a.V, a.T_out, TAPS, a.stride);
-  if (!ws_need) AGCN_NOTE_KERNEL("conv_wgrad_kernel<%d, 0>", TAPS);
+  if (!dry) AGCN_NOTE_KERNEL("conv_wgrad_kernel<%d, 0>", TAPS);
   if (TAPS == 1) {
-    if (a.M % 128 == 0) {
-      if (ws_need) { *ws_need = ws_wgrad<1, 0, 4, 2, 1, false>(a.N, a.M, a.C, a.V, a.T_out, a.stride, a.wsize, cap); return 0; }
-      return launch_wgrad<1, 0, 4, 2, 1, false, WBXT>(a, dw, ws, ws_bytes, s, cap);
-    }
-    if (ws_need) { *ws_need = ws_wgrad<1, 0, 2, 2, 2, true>(a.N, a.M, a.C, a.V, a.T_out, a.stride, a.wsize, cap); return 0; }
-    return launch_wgrad<1, 0, 2, 2, 2, true, WBXT>(a, dw, ws, ws_bytes, s, cap);
+    if (a.M % 128 == 0) return launch_wgrad<1, 0, 4, 2, 1, false, WBXT>(a, dw, ws, ws_bytes, s, dry, cap);
+    return launch_wgrad<1, 0, 2, 2, 2, true, WBXT>(a, dw, ws, ws_bytes, s, dry, cap);
   }
-  if (a.M % 128 == 0) {
-    if (ws_need) { *ws_need = ws_wgrad<TAPS, 0, 4, 1, 2, false>(a.N, a.M, a.C, a.V, a.T_out, a.stride, a.wsize, cap); return 0; }
-    return launch_wgrad<TAPS, 0, 4, 1, 2, false, WBXT>(a, dw, ws, ws_bytes, s, cap);
-  }
-  if (ws_need) { *ws_need = ws_wgrad<TAPS, 0, 2, 2, 2, false>(a.N, a.M, a.C, a.V, a.T_out, a.stride, a.wsize, cap); return 0; }
-  return launch_wgrad<TAPS, 0, 2, 2, 2, false, WBXT>(a, dw, ws, ws_bytes, s, cap);
+  if (a.M % 128 == 0) return launch_wgrad<TAPS, 0, 4, 1, 2, false, WBXT>(a, dw, ws, ws_bytes, s, dry, cap);
+  return launch_wgrad<TAPS, 0, 2, 2, 2, false, WBXT>(a, dw, ws, ws_bytes, s, dry, cap);
 }
 
-// ws_need non-null: only report the workspace bytes
 int tconv_wgrad_dispatch(int taps, const WgradArgs& a, float* dw, void* ws, size_t ws_bytes, hipStream_t s,
-                         size_t* ws_need) {
+                         AgcnDryRun* dry) {
   switch (taps) {
-    case 1: return tconv_wgrad<1>(a, dw, ws, ws_bytes, s, ws_need);
-    case 2: return tconv_wgrad<2>(a, dw, ws, ws_bytes, s, ws_need);
-    case 3: return tconv_wgrad<3>(a, dw, ws, ws_bytes, s, ws_need);
-    case 4: return tconv_wgrad<4>(a, dw, ws, ws_bytes, s, ws_need);
-    case 5: return tconv_wgrad<5>(a, dw, ws, ws_bytes, s, ws_need);
-    case 6: return tconv_wgrad<6>(a, dw, ws, ws_bytes, s, ws_need);
-    case 7: return tconv_wgrad<7>(a, dw, ws, ws_bytes, s, ws_need);
-    case 8: return tconv_wgrad<8>(a, dw, ws, ws_bytes, s, ws_need);
-    case 9: return tconv_wgrad<9>(a, dw, ws, ws_bytes, s, ws_need);
+    case 1: return tconv_wgrad<1>(a, dw, ws, ws_bytes, s, dry);
+    case 2: return tconv_wgrad<2>(a, dw, ws, ws_bytes, s, dry);
+    case 3: return tconv_wgrad<3>(a, dw, ws, ws_bytes, s, dry);
+    case 4: return tconv_wgrad<4>(a, dw, ws, ws_bytes, s, dry);
+    case 5: return tconv_wgrad<5>(a, dw, ws, ws_bytes, s, dry);
+    case 6: return tconv_wgrad<6>(a, dw, ws, ws_bytes, s, dry);
+    case 7: return tconv_wgrad<7>(a, dw, ws, ws_bytes, s, dry);
+    case 8: return tconv_wgrad<8>(a, dw, ws, ws_bytes, s, dry);
+    case 9: return tconv_wgrad<9>(a, dw, ws, ws_bytes, s, dry);
     default: return AGCN_ERR_UNSUPPORTED;
   }
-}
-
-inline bool tconv_w_domain(int T, int taps, int stride, int pad) {
-  return taps >= 1 && taps <= 9 && stride >= 1 && stride <= 9 && pad >= 0 && pad <= (taps - 1) / 2 && T + 2 * pad >= taps;
 }
 
 inline bool chain_wgrad_enabled() {
@@ -448,34 +431,103 @@ inline bool chain_wgrad_enabled() {
   return v == 1 && agcn_chained();
 }
 
+// ---- the routing of each entry point, after its argument checks; the *_workspace queries walk the same functions with
+// null tensors (or placeholders, agcn_dry_present) and a dry-run record (agcn_common.h).  The f16x3 tap kernels of wgrad9_bf16.hip size themselves by the
+// geometry function they launch with. ----
+
+// dw[o][c][k] = sum_{n,t,v} dy[n][o][t,v] * x[n][c][(t*stride + k - pad), v]
+int conv_wgrad_route(const float* dy, const float* x, float* dw, void* workspace, size_t workspace_bytes, int N, int Cin,
+                     int Cout, int T, int V, int taps, int stride, const float* dy_absmax, const float* x_absmax,
+                     hipStream_t s, AgcnDryRun* dry) {
+  if ((taps != 1 && taps != 9) || (stride != 1 && stride != 2)) return AGCN_ERR_UNSUPPORTED;
+  const int pad = (taps - 1) / 2;
+  WgradArgs a = {};
+  a.dy = dy; a.in = x; a.N = N; a.M = Cout; a.C = Cin; a.V = V; a.T_src = T;
+  a.T_out = (T + 2 * pad - taps) / stride + 1; a.stride = stride; a.pad = pad;
+  a.so_m = (long)Cin * taps; a.so_t = 1; a.so_c = taps; a.wsize = (long)Cout * Cin * taps;
+  if (taps == 9) {
+    if (wgrad9_bf16_enabled() && agcn_wgrad9_bf16_supported(Cout, Cin, V, stride)) {
+      if (dry) return agcn_dry_note(dry, 0, agcn_wgrad9_bf16_workspace(N, Cout, Cin, V, T, stride));
+      int nslabs = 0;
+      int rc = agcn_wgrad9_bf16(dy, x, workspace, workspace_bytes, &nslabs, N, Cout, Cin, V, T, stride, s, dy_absmax, x_absmax);
+      if (rc) return rc;
+      return launch_reduce((const float*)workspace, dw, a.wsize, nslabs, a.M, a.C, a.so_m, a.so_t, a.so_c, s);
+    }
+    if (stride == 1) {
+      if (Cout % 128 == 0) return launch_wgrad<9, 0, 4, 1, 2, false, 6>(a, dw, workspace, workspace_bytes, s, dry);
+      return launch_wgrad<9, 0, 2, 2, 2, false, 6>(a, dw, workspace, workspace_bytes, s, dry);
+    }
+    if (Cout % 128 == 0) return launch_wgrad<9, 0, 4, 1, 2, false, 7>(a, dw, workspace, workspace_bytes, s, dry);
+    return launch_wgrad<9, 0, 2, 2, 2, false, 7>(a, dw, workspace, workspace_bytes, s, dry);
+  }
+  if (chain_wgrad_enabled() && agcn_wgrad_chain_supported(Cout, Cin, V))
+    return chain_wgrad_and_reduce(0, a, dw, workspace, workspace_bytes, s, dy_absmax, x_absmax, dry);
+  if (Cout % 128 == 0) return launch_wgrad<1, 0, 4, 2, 1, false, 4>(a, dw, workspace, workspace_bytes, s, dry);
+  return launch_wgrad<1, 0, 2, 2, 2, true, 4>(a, dw, workspace, workspace_bytes, s, dry);
+}
+
+// dwcat[o][i*C+c] = sum_{n,t,v} dy[n][o][t,v] * sum_u x[n][c][t,u] adj[n][i][u][v]
+int gcn_wgrad_route(const float* dy, const float* x, const float* adj, float* dwcat, void* workspace,
+                    size_t workspace_bytes, int N, int C, int Cout, int T, int V, const float* dy_absmax,
+                    const float* x_absmax, hipStream_t s, AgcnDryRun* dry) {
+  WgradArgs a = {};
+  a.dy = dy; a.in = x; a.adj = adj; a.N = N; a.M = Cout; a.C = C; a.V = V; a.T_src = T; a.T_out = T; a.stride = 1;
+  a.so_m = 3L * C; a.so_t = C; a.so_c = 1; a.wsize = 3L * Cout * C;
+  if (chain_wgrad_enabled() && agcn_wgrad_chain_supported(Cout, C, V))
+    return chain_wgrad_and_reduce(1, a, dwcat, workspace, workspace_bytes, s, dy_absmax, x_absmax, dry);
+  if (Cout % 128 == 0) return launch_wgrad<1, 1, 4, 2, 1, false, 2>(a, dwcat, workspace, workspace_bytes, s, dry);
+  return launch_wgrad<1, 1, 2, 2, 2, true, 2>(a, dwcat, workspace, workspace_bytes, s, dry);
+}
+
+// dw[o][c][k] = sum_{n,t,v} dy[n][o][t,v] * x[n][c][t*stride + k - pad, v]   (fixed-order slab reduction)
+int tconv_wgrad_route(const float* dy, const float* x, float* dw, void* workspace, size_t workspace_bytes, int N, int Cin,
+                      int Cout, int T, int V, int taps, int stride, int pad, const float* dy_absmax,
+                      const float* x_absmax, hipStream_t s, AgcnDryRun* dry) {
+  if (!agcn_tconv_domain(T, taps, stride, pad)) return AGCN_ERR_UNSUPPORTED;
+  if (agcn_tconv_legacy(taps, stride, pad))
+    return conv_wgrad_route(dy, x, dw, workspace, workspace_bytes, N, Cin, Cout, T, V, taps, stride, dy_absmax, x_absmax, s,
+                            dry);
+  WgradArgs a = {};
+  a.dy = dy; a.in = x; a.N = N; a.M = Cout; a.C = Cin; a.V = V; a.T_src = T;
+  a.T_out = (T + 2 * pad - taps) / stride + 1; a.stride = stride; a.pad = pad;
+  a.so_m = (long)Cin * taps; a.so_t = 1; a.so_c = taps; a.wsize = (long)Cout * Cin * taps;
+  if (agcn_wgrad_tconv_f16_supported(Cout, Cin, V, taps, stride, pad)) {     // stride 1, 3/5/7 taps: f16x3
+    if (dry) return agcn_dry_note(dry, 0, agcn_wgrad_tconv_f16_workspace(N, Cout, Cin, V, T, taps, pad));
+    int nslabs = 0;
+    const int rc = agcn_wgrad_tconv_f16(dy, x, workspace, workspace_bytes, &nslabs, N, Cout, Cin, V, T, taps, pad, s,
+                                        dy_absmax, x_absmax);
+    if (rc) return rc;
+    return launch_reduce((const float*)workspace, dw, a.wsize, nslabs, a.M, a.C, a.so_m, a.so_t, a.so_c, s);
+  }
+  return tconv_wgrad_dispatch(taps, a, dw, workspace, workspace_bytes, s, dry);
+}
+
 }  // namespace
 
 extern "C" {
 
-// bytes of workspace agcn_conv_bwd_weight / agcn_gcn_project_bwd_weight need
+// bytes of workspace (the partial slabs) the weight gradients need: dry runs of their launches, without and with the
+// operand maxima (which select the f16x3 kernels, with their own LDS needs); 0 for a shape they refuse
+size_t agcn_tconv_bwd_weight_workspace(int N, int Cin, int Cout, int T, int V, int taps, int stride, int pad) {
+  AgcnDryRun d = {};
+  if (agcn_sizes_ok(N, Cin, Cout, T, V))
+    for (const float* amax : {(const float*)nullptr, (const float*)agcn_dry_present()})    // without and with the maxima
+      tconv_wgrad_route(nullptr, nullptr, nullptr, nullptr, 0, N, Cin, Cout, T, V, taps, stride, pad, amax, amax, nullptr,
+                        &d);
+  return d.ws_bytes;
+}
 size_t agcn_conv_bwd_weight_workspace(int N, int Cin, int Cout, int T, int V, int taps, int stride) {
-  const int pad = (taps - 1) / 2;
-  const int T_out = (T + 2 * pad - taps) / stride + 1;
-  const long wsize = (long)Cout * Cin * taps;
-  if (taps == 9) {
-    size_t b9 = (Cout % 128 == 0) ? ws_wgrad<9, 0, 4, 1, 2, false>(N, Cout, Cin, V, T_out, stride, wsize)
-                                  : ws_wgrad<9, 0, 2, 2, 2, false>(N, Cout, Cin, V, T_out, stride, wsize);
-    if (agcn_wgrad9_bf16_supported(Cout, Cin, V, stride)) {
-      const size_t t = agcn_wgrad9_bf16_workspace(N, Cout, Cin, V, T, stride);
-      if (t > b9) b9 = t;
-    }
-    return b9;
-  }
-  size_t b = (Cout % 128 == 0) ? ws_wgrad<1, 0, 4, 2, 1, false>(N, Cout, Cin, V, T_out, stride, wsize)
-                              : ws_wgrad<1, 0, 2, 2, 2, true>(N, Cout, Cin, V, T_out, stride, wsize);
-  if (agcn_wgrad_chain_supported(Cout, Cin, V)) {
-    const size_t t = agcn_wgrad_chain_workspace(0, N, Cout, Cin, V, T_out);
-    if (t > b) b = t;
-  }
-  return b;
+  if (!agcn_tconv_legacy(taps, stride, (taps - 1) / 2)) return 0;
+  return agcn_tconv_bwd_weight_workspace(N, Cin, Cout, T, V, taps, stride, (taps - 1) / 2);
+}
+size_t agcn_gcn_project_bwd_weight_workspace(int N, int C, int Cout, int T, int V) {
+  AgcnDryRun d = {};
+  if (agcn_sizes_ok(N, C, Cout, T, V))
+    for (const float* amax : {(const float*)nullptr, (const float*)agcn_dry_present()})
+      gcn_wgrad_route(nullptr, nullptr, nullptr, nullptr, nullptr, 0, N, C, Cout, T, V, amax, amax, nullptr, &d);
+  return d.ws_bytes;
 }
 
-// dw[o][c][k] = sum_{n,t,v} dy[n][o][t,v] * x[n][c][(t*stride + k - pad), v]
 int agcn_conv_bwd_weight_ex(const float* dy, const float* x, float* dw, void* workspace, size_t workspace_bytes, int N,
                             int Cin, int Cout, int T, int V, int taps, int stride, const float* dy_absmax,
                             const float* x_absmax, void* stream);
@@ -489,47 +541,11 @@ int agcn_conv_bwd_weight(const float* dy, const float* x, float* dw, void* works
 int agcn_conv_bwd_weight_ex(const float* dy, const float* x, float* dw, void* workspace, size_t workspace_bytes, int N,
                             int Cin, int Cout, int T, int V, int taps, int stride, const float* dy_absmax,
                             const float* x_absmax, void* stream) {
-  if (!dy || !x || !dw || !workspace || N <= 0 || Cin <= 0 || Cout <= 0 || T <= 0 || V <= 0 || V > 32)
-    return AGCN_ERR_ARG;
-  if ((taps != 1 && taps != 9) || (stride != 1 && stride != 2)) return AGCN_ERR_UNSUPPORTED;
-  const int pad = (taps - 1) / 2;
-  WgradArgs a = {};
-  a.dy = dy; a.in = x; a.N = N; a.M = Cout; a.C = Cin; a.V = V; a.T_src = T;
-  a.T_out = (T + 2 * pad - taps) / stride + 1; a.stride = stride; a.pad = pad;
-  a.so_m = (long)Cin * taps; a.so_t = 1; a.so_c = taps; a.wsize = (long)Cout * Cin * taps;
-  hipStream_t s = (hipStream_t)stream;
-  if (taps == 9) {
-    if (wgrad9_bf16_enabled() && agcn_wgrad9_bf16_supported(Cout, Cin, V, stride)) {
-      int nslabs = 0;
-      int rc = agcn_wgrad9_bf16(dy, x, workspace, workspace_bytes, &nslabs, N, Cout, Cin, V, T, stride, s, dy_absmax, x_absmax);
-      if (rc) return rc;
-      return launch_reduce((const float*)workspace, dw, a.wsize, nslabs, a.M, a.C, a.so_m, a.so_t, a.so_c, s);
-    }
-    if (stride == 1) {
-      if (Cout % 128 == 0) return launch_wgrad<9, 0, 4, 1, 2, false, 6>(a, dw, workspace, workspace_bytes, s);
-      return launch_wgrad<9, 0, 2, 2, 2, false, 6>(a, dw, workspace, workspace_bytes, s);
-    }
-    if (Cout % 128 == 0) return launch_wgrad<9, 0, 4, 1, 2, false, 7>(a, dw, workspace, workspace_bytes, s);
-    return launch_wgrad<9, 0, 2, 2, 2, false, 7>(a, dw, workspace, workspace_bytes, s);
-  }
-  if (chain_wgrad_enabled() && agcn_wgrad_chain_supported(Cout, Cin, V))
-    return chain_wgrad_and_reduce(0, a, dw, workspace, workspace_bytes, s, dy_absmax, x_absmax);
-  if (Cout % 128 == 0) return launch_wgrad<1, 0, 4, 2, 1, false, 4>(a, dw, workspace, workspace_bytes, s);
-  return launch_wgrad<1, 0, 2, 2, 2, true, 4>(a, dw, workspace, workspace_bytes, s);
+  if (!dy || !x || !dw || !workspace || !agcn_sizes_ok(N, Cin, Cout, T, V)) return AGCN_ERR_ARG;
+  return conv_wgrad_route(dy, x, dw, workspace, workspace_bytes, N, Cin, Cout, T, V, taps, stride, dy_absmax, x_absmax,
+                          (hipStream_t)stream, nullptr);
 }
 
-size_t agcn_gcn_project_bwd_weight_workspace(int N, int C, int Cout, int T, int V) {
-  const long wsize = 3L * Cout * C;
-  size_t b = (Cout % 128 == 0) ? ws_wgrad<1, 1, 4, 2, 1, false>(N, Cout, C, V, T, 1, wsize)
-                              : ws_wgrad<1, 1, 2, 2, 2, true>(N, Cout, C, V, T, 1, wsize);
-  if (agcn_wgrad_chain_supported(Cout, C, V)) {
-    const size_t t = agcn_wgrad_chain_workspace(1, N, Cout, C, V, T);
-    if (t > b) b = t;
-  }
-  return b;
-}
-
-// dwcat[o][i*C+c] = sum_{n,t,v} dy[n][o][t,v] * sum_u x[n][c][t,u] adj[n][i][u][v]
 int agcn_gcn_project_bwd_weight_ex(const float* dy, const float* x, const float* adj, float* dwcat, void* workspace,
                                    size_t workspace_bytes, int N, int C, int Cout, int T, int V, const float* dy_absmax,
                                    const float* x_absmax, void* stream);
@@ -542,59 +558,18 @@ int agcn_gcn_project_bwd_weight(const float* dy, const float* x, const float* ad
 int agcn_gcn_project_bwd_weight_ex(const float* dy, const float* x, const float* adj, float* dwcat, void* workspace,
                                    size_t workspace_bytes, int N, int C, int Cout, int T, int V, const float* dy_absmax,
                                    const float* x_absmax, void* stream) {
-  if (!dy || !x || !adj || !dwcat || !workspace || N <= 0 || C <= 0 || Cout <= 0 || T <= 0 || V <= 0 || V > 32)
-    return AGCN_ERR_ARG;
-  WgradArgs a = {};
-  a.dy = dy; a.in = x; a.adj = adj; a.N = N; a.M = Cout; a.C = C; a.V = V; a.T_src = T; a.T_out = T; a.stride = 1;
-  a.so_m = 3L * C; a.so_t = C; a.so_c = 1; a.wsize = 3L * Cout * C;
-  hipStream_t s = (hipStream_t)stream;
-  if (chain_wgrad_enabled() && agcn_wgrad_chain_supported(Cout, C, V))
-    return chain_wgrad_and_reduce(1, a, dwcat, workspace, workspace_bytes, s, dy_absmax, x_absmax);
-  if (Cout % 128 == 0) return launch_wgrad<1, 1, 4, 2, 1, false, 2>(a, dwcat, workspace, workspace_bytes, s);
-  return launch_wgrad<1, 1, 2, 2, 2, true, 2>(a, dwcat, workspace, workspace_bytes, s);
+  if (!dy || !x || !adj || !dwcat || !workspace || !agcn_sizes_ok(N, C, Cout, T, V)) return AGCN_ERR_ARG;
+  return gcn_wgrad_route(dy, x, adj, dwcat, workspace, workspace_bytes, N, C, Cout, T, V, dy_absmax, x_absmax,
+                         (hipStream_t)stream, nullptr);
 }
-
 
 // ---- weight gradient of the temporal convolution with explicit padding (reference aagcn.py:184-207) ----
-size_t agcn_tconv_bwd_weight_workspace(int N, int Cin, int Cout, int T, int V, int taps, int stride, int pad) {
-  if (N <= 0 || Cin <= 0 || Cout <= 0 || T <= 0 || V <= 0 || !tconv_w_domain(T, taps, stride, pad)) return 0;
-  if (pad == (taps - 1) / 2 && (taps == 1 || taps == 9) && (stride == 1 || stride == 2))
-    return agcn_conv_bwd_weight_workspace(N, Cin, Cout, T, V, taps, stride);
-  WgradArgs a = {};
-  a.N = N; a.M = Cout; a.C = Cin; a.V = V; a.T_src = T; a.T_out = (T + 2 * pad - taps) / stride + 1; a.stride = stride;
-  a.pad = pad; a.wsize = (long)Cout * Cin * taps;
-  size_t need = 0;
-  tconv_wgrad_dispatch(taps, a, nullptr, nullptr, 0, nullptr, &need);
-  if (agcn_wgrad_tconv_f16_supported(Cout, Cin, V, taps, stride, pad)) {
-    const size_t t = agcn_wgrad_tconv_f16_workspace(N, Cout, Cin, V, T, taps, pad);
-    if (t > need) need = t;
-  }
-  return need;
-}
-
-// dw[o][c][k] = sum_{n,t,v} dy[n][o][t,v] * x[n][c][t*stride + k - pad, v]   (fixed-order slab reduction)
 int agcn_tconv_bwd_weight(const float* dy, const float* x, float* dw, void* workspace, size_t workspace_bytes, int N,
                           int Cin, int Cout, int T, int V, int taps, int stride, int pad, const float* dy_absmax,
                           const float* x_absmax, void* stream) {
-  if (!dy || !x || !dw || !workspace || N <= 0 || Cin <= 0 || Cout <= 0 || T <= 0 || V <= 0 || V > 32)
-    return AGCN_ERR_ARG;
-  if (!tconv_w_domain(T, taps, stride, pad)) return AGCN_ERR_UNSUPPORTED;
-  if (pad == (taps - 1) / 2 && (taps == 1 || taps == 9) && (stride == 1 || stride == 2))
-    return agcn_conv_bwd_weight_ex(dy, x, dw, workspace, workspace_bytes, N, Cin, Cout, T, V, taps, stride, dy_absmax,
-                                   x_absmax, stream);
-  WgradArgs a = {};
-  a.dy = dy; a.in = x; a.N = N; a.M = Cout; a.C = Cin; a.V = V; a.T_src = T;
-  a.T_out = (T + 2 * pad - taps) / stride + 1; a.stride = stride; a.pad = pad;
-  a.so_m = (long)Cin * taps; a.so_t = 1; a.so_c = taps; a.wsize = (long)Cout * Cin * taps;
-  hipStream_t s = (hipStream_t)stream;
-  if (agcn_wgrad_tconv_f16_supported(Cout, Cin, V, taps, stride, pad)) {     // stride 1, 3/5/7 taps: f16x3
-    int nslabs = 0;
-    const int rc = agcn_wgrad_tconv_f16(dy, x, workspace, workspace_bytes, &nslabs, N, Cout, Cin, V, T, taps, pad, s,
-                                        dy_absmax, x_absmax);
-    if (rc) return rc;
-    return launch_reduce((const float*)workspace, dw, a.wsize, nslabs, a.M, a.C, a.so_m, a.so_t, a.so_c, s);
-  }
-  return tconv_wgrad_dispatch(taps, a, dw, workspace, workspace_bytes, s, nullptr);
+  if (!dy || !x || !dw || !workspace || !agcn_sizes_ok(N, Cin, Cout, T, V)) return AGCN_ERR_ARG;
+  return tconv_wgrad_route(dy, x, dw, workspace, workspace_bytes, N, Cin, Cout, T, V, taps, stride, pad, dy_absmax,
+                           x_absmax, (hipStream_t)stream, nullptr);
 }
 
 }  // extern "C"

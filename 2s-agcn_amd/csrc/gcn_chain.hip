@@ -1130,7 +1130,7 @@ struct ChainW2 {
 
 template <int TM, int VS, int NW, bool F16 = false>
 int chain_launch(ChainArgs a, const float* w, long sa_m, long sa_i, long sa_c, const ChainW2& g_w2, void* ws,
-                 size_t ws_bytes, hipStream_t stream) {
+                 size_t ws_bytes, hipStream_t stream, AgcnDryRun* dry) {
   constexpr int PL = F16 ? 2 : 3;
   const ChainGeom g = chain_geometry<TM, NW>(a.V, a.T, a.M, a.K, VS == 0, PL);
   if (g.smem_bytes > 160 * 1024) return AGCN_ERR_UNSUPPORTED;
@@ -1138,6 +1138,7 @@ int chain_launch(ChainArgs a, const float* w, long sa_m, long sa_i, long sa_c, c
   const int s_total = 3 * g.ncb + a.ncb2;
   const size_t a_img = (size_t)PL * 2 * TM * 1024;
   const size_t img_bytes = (size_t)g.nmb * s_total * a_img;
+  if (dry) return agcn_dry_note(dry, a.stats ? (long)a.N * g.ntiles : 0, img_bytes + (F16 ? 16 : 0));
   if (img_bytes + (F16 ? 16 : 0) > ws_bytes) return AGCN_ERR_WORKSPACE;
   if constexpr (F16) {
     // maxima the caller did not supply: one streaming pass each, into the 16 bytes behind the weight images (the
@@ -1195,11 +1196,12 @@ static inline bool ws_shape_ok(int M, int K, int K2, int V) {
 
 template <int TM, int NCB2, int KCB = 2>
 int ws_launch(ChainArgs a, const float* w, long sa_m, long sa_i, long sa_c, const ChainW2& g_w2, void* ws, size_t ws_bytes,
-              hipStream_t stream) {
+              hipStream_t stream, AgcnDryRun* dry) {
   const WsGeom g = ws_geometry<TM>(a.N, a.M, a.K, a.K2, a.T, a.V);
   if (g.smem_bytes > 160 * 1024) return AGCN_ERR_UNSUPPORTED;
   if (NCB2 > 0 && a.stats) return AGCN_ERR_UNSUPPORTED;            // (BatchNorm partials: plain-stage-free forward only)
   const size_t img_total = (size_t)g.nmb * g.img_bytes;
+  if (dry) return agcn_dry_note(dry, a.stats ? (long)a.N * g.nsplit : 0, img_total + 16);
   if (img_total + 16 > ws_bytes) return AGCN_ERR_WORKSPACE;
   unsigned* amax = reinterpret_cast<unsigned*>(static_cast<char*>(ws) + img_total);
   if (!a.in_absmax) {
@@ -1251,36 +1253,36 @@ int ws_launch(ChainArgs a, const float* w, long sa_m, long sa_i, long sa_c, cons
 
 template <int TM>
 int ws_dispatch(const ChainArgs& a, const float* w, long sa_m, long sa_i, long sa_c, const ChainW2& w2, void* ws,
-                size_t ws_bytes, hipStream_t stream) {
+                size_t ws_bytes, hipStream_t stream, AgcnDryRun* dry) {
   const int ncb2 = a.in2 ? (a.K2 + CB - 1) / CB : 0;
   if (a.K > 64) {
     if constexpr (TM == 2) {
-      if (ncb2 == 0) return ws_launch<2, 0, 4>(a, w, sa_m, sa_i, sa_c, w2, ws, ws_bytes, stream);
+      if (ncb2 == 0) return ws_launch<2, 0, 4>(a, w, sa_m, sa_i, sa_c, w2, ws, ws_bytes, stream, dry);
     }
     return AGCN_ERR_UNSUPPORTED;
   }
   switch (ncb2) {
-    case 0: return ws_launch<TM, 0>(a, w, sa_m, sa_i, sa_c, w2, ws, ws_bytes, stream);
-    case 1: return ws_launch<TM, 1>(a, w, sa_m, sa_i, sa_c, w2, ws, ws_bytes, stream);
-    case 2: return ws_launch<TM, 2>(a, w, sa_m, sa_i, sa_c, w2, ws, ws_bytes, stream);
-    case 3: return ws_launch<TM, 3>(a, w, sa_m, sa_i, sa_c, w2, ws, ws_bytes, stream);
+    case 0: return ws_launch<TM, 0>(a, w, sa_m, sa_i, sa_c, w2, ws, ws_bytes, stream, dry);
+    case 1: return ws_launch<TM, 1>(a, w, sa_m, sa_i, sa_c, w2, ws, ws_bytes, stream, dry);
+    case 2: return ws_launch<TM, 2>(a, w, sa_m, sa_i, sa_c, w2, ws, ws_bytes, stream, dry);
+    case 3: return ws_launch<TM, 3>(a, w, sa_m, sa_i, sa_c, w2, ws, ws_bytes, stream, dry);
   }
   return AGCN_ERR_UNSUPPORTED;
 }
 
 template <int TM, int NW>
 int chain_dispatch_vs(const ChainArgs& a, const float* w, long sa_m, long sa_i, long sa_c, const ChainW2& w2, void* ws,
-                      size_t ws_bytes, hipStream_t stream) {
+                      size_t ws_bytes, hipStream_t stream, AgcnDryRun* dry) {
   // split-bf16 aggregation unless AGCN_CHAIN_F32=1 (exact-f32 MFMA chain, VS = ceil(V/2) steps) or AGCN_GEMM=bf16
   // (one product: keep the aggregation exact)
   static const int f32chain = getenv("AGCN_CHAIN_F32") ? atoi(getenv("AGCN_CHAIN_F32")) : 0;
   if (!f32chain && a.npl == 3 && agcn_chain_f16x3())
-    return chain_launch<TM, 0, NW, true>(a, w, sa_m, sa_i, sa_c, w2, ws, ws_bytes, stream);
-  if (!f32chain && a.npl == 3) return chain_launch<TM, 0, NW>(a, w, sa_m, sa_i, sa_c, w2, ws, ws_bytes, stream);
+    return chain_launch<TM, 0, NW, true>(a, w, sa_m, sa_i, sa_c, w2, ws, ws_bytes, stream, dry);
+  if (!f32chain && a.npl == 3) return chain_launch<TM, 0, NW>(a, w, sa_m, sa_i, sa_c, w2, ws, ws_bytes, stream, dry);
   const int vs = (a.V + 1) / 2;
-  if (vs == 13) return chain_launch<TM, 13, NW>(a, w, sa_m, sa_i, sa_c, w2, ws, ws_bytes, stream);
-  if (vs == 9) return chain_launch<TM, 9, NW>(a, w, sa_m, sa_i, sa_c, w2, ws, ws_bytes, stream);
-  return chain_launch<TM, 16, NW>(a, w, sa_m, sa_i, sa_c, w2, ws, ws_bytes, stream);
+  if (vs == 13) return chain_launch<TM, 13, NW>(a, w, sa_m, sa_i, sa_c, w2, ws, ws_bytes, stream, dry);
+  if (vs == 9) return chain_launch<TM, 9, NW>(a, w, sa_m, sa_i, sa_c, w2, ws, ws_bytes, stream, dry);
+  return chain_launch<TM, 16, NW>(a, w, sa_m, sa_i, sa_c, w2, ws, ws_bytes, stream, dry);
 }
 
 
@@ -1575,7 +1577,7 @@ __global__ void __launch_bounds__(NW * 64, 2) gcn_dadj_chain_kernel(const DadjAr
 }
 
 template <int TM, int NW, bool F16 = false>
-int dadj_chain_launch(DadjArgs a, const float* wcat, void* ws, size_t ws_bytes, hipStream_t stream) {
+int dadj_chain_launch(DadjArgs a, const float* wcat, void* ws, size_t ws_bytes, hipStream_t stream, AgcnDryRun* dry) {
   constexpr int BM = TM * 32, FT = NW;
   constexpr int PL = F16 ? 2 : 3;
   a.ntiles = (a.T + FT - 1) / FT;
@@ -1590,6 +1592,7 @@ int dadj_chain_launch(DadjArgs a, const float* wcat, void* ws, size_t ws_bytes, 
   if (epi > smem_bytes) smem_bytes = epi;
   if (smem_bytes > 160 * 1024) return AGCN_ERR_UNSUPPORTED;
   const size_t pack_bytes = (size_t)a.nmb * a.nkc * a_img;
+  if (dry) return agcn_dry_note(dry, a.dpart ? 3L * a.N * a.nslots : 0, pack_bytes + (F16 ? 16 : 0));
   if (pack_bytes + (F16 ? 16 : 0) > ws_bytes) return AGCN_ERR_WORKSPACE;
   a.wp = (const unsigned short*)ws;
   if constexpr (F16) {
@@ -1644,30 +1647,12 @@ bool agcn_gcn_chain_supported(int M, int K, int V) { return M >= 1 && K >= 1 && 
 
 int agcn_gcn_chain_tiles(int T) { return (T + chain_waves() - 1) / chain_waves(); }
 
-// total (sum, sumsq) slots of the forward's BatchNorm partials: N * tiles for the tile-per-workgroup kernel, one per
-// (sample, frame split) for the persistent one
-int agcn_gcn_chain_stats_slots(int N, int M, int K, int T, int V) {
-  if (ws_shape_ok(M, K, 0, V)) {
-    const WsGeom g = (M <= 32) ? ws_geometry<1>(N, M, K, 0, T, V) : ws_geometry<2>(N, M, K, 0, T, V);
-    if (g.smem_bytes <= 160 * 1024) return N * g.nsplit;
-  }
-  return N * agcn_gcn_chain_tiles(T);
-}
-
-// packed weight images; K2 = channels of the optional plain second source (0: none)
-size_t agcn_gcn_chain_workspace(int M, int K, int K2, int T, int V) {
-  (void)T; (void)V;
-  const int tm = chain_tm(M), bm = 32 * tm;
-  const size_t a_img = (size_t)3 * 2 * tm * 1024;
-  return (size_t)((M + bm - 1) / bm) * (3 * ((K + CB - 1) / CB) + (K2 + CB - 1) / CB) * a_img;
-}
-
 // mode 0: forward (in = x, K = C, M = Cout); mode 1: backward-data (in = dy, K = Cout, M = C)
 int agcn_gcn_chain(int mode, const float* in, const float* adj, const float* wcat, const float* bias, float* out,
                    float* stats_part, int accumulate, const float* add1, const float* mask1, const float* add2,
                    const float* mask2, int mask_bits, const float* in2, const float* w2, int K2, void* ws, size_t ws_bytes,
                    int N, int C, int Cout, int T, int V, hipStream_t stream, int relu, int w2_rows_are_outputs,
-                   const float* in_absmax, const float* in2_absmax) {
+                   const float* in_absmax, const float* in2_absmax, AgcnDryRun* dry) {
   ChainArgs a = {};
   a.relu = relu;
   a.in_absmax = in_absmax; a.in2_absmax = in2_absmax;   // f16x3: maxima the producers left behind (null: a pre-pass)
@@ -1687,18 +1672,20 @@ int agcn_gcn_chain(int mode, const float* in, const float* adj, const float* wca
   cw2.sa_c = a.M;        // W2[m][k] = w2[k*M + m]
   if (w2_rows_are_outputs) { cw2.sa_m = a.K2; cw2.sa_c = 1; }   // w2 (M, K2) row-major (forward: a folded 1x1 conv)
   if (!a.dbg && ws_shape_ok(a.M, a.K, a.K2, V)) {
-    if (const char* e = getenv("AGCN_WS_DBG")) a.dbg = atoi(e);   // profiling switches of gcn_ws_kernel (read per call)              // persistent, weight-stationary kernel (64 streamed channels)
-    const int rc = (a.M <= 32) ? ws_dispatch<1>(a, wcat, sa_m, sa_i, sa_c, cw2, ws, ws_bytes, stream)
-                               : ws_dispatch<2>(a, wcat, sa_m, sa_i, sa_c, cw2, ws, ws_bytes, stream);
+    // persistent, weight-stationary kernel (up to 128 streamed channels); its profiling switches are read per call
+    if (!dry)
+      if (const char* e = getenv("AGCN_WS_DBG")) a.dbg = atoi(e);
+    const int rc = (a.M <= 32) ? ws_dispatch<1>(a, wcat, sa_m, sa_i, sa_c, cw2, ws, ws_bytes, stream, dry)
+                               : ws_dispatch<2>(a, wcat, sa_m, sa_i, sa_c, cw2, ws, ws_bytes, stream, dry);
     if (rc != AGCN_ERR_UNSUPPORTED) return rc;
   }
   if (chain_waves() == 8 && chain_tm(a.M) != 1) {
-    if (chain_tm(a.M) == 4) return chain_dispatch_vs<4, 8>(a, wcat, sa_m, sa_i, sa_c, cw2, ws, ws_bytes, stream);
-    return chain_dispatch_vs<2, 8>(a, wcat, sa_m, sa_i, sa_c, cw2, ws, ws_bytes, stream);
+    if (chain_tm(a.M) == 4) return chain_dispatch_vs<4, 8>(a, wcat, sa_m, sa_i, sa_c, cw2, ws, ws_bytes, stream, dry);
+    return chain_dispatch_vs<2, 8>(a, wcat, sa_m, sa_i, sa_c, cw2, ws, ws_bytes, stream, dry);
   }
-  if (chain_tm(a.M) == 4) return chain_dispatch_vs<4, 4>(a, wcat, sa_m, sa_i, sa_c, cw2, ws, ws_bytes, stream);
-  if (chain_tm(a.M) == 1) return chain_dispatch_vs<1, 4>(a, wcat, sa_m, sa_i, sa_c, cw2, ws, ws_bytes, stream);
-  return chain_dispatch_vs<2, 4>(a, wcat, sa_m, sa_i, sa_c, cw2, ws, ws_bytes, stream);
+  if (chain_tm(a.M) == 4) return chain_dispatch_vs<4, 4>(a, wcat, sa_m, sa_i, sa_c, cw2, ws, ws_bytes, stream, dry);
+  if (chain_tm(a.M) == 1) return chain_dispatch_vs<1, 4>(a, wcat, sa_m, sa_i, sa_c, cw2, ws, ws_bytes, stream, dry);
+  return chain_dispatch_vs<2, 4>(a, wcat, sa_m, sa_i, sa_c, cw2, ws, ws_bytes, stream, dry);
 }
 
 // ---- adjacency gradient (gcn_dadj_chain_kernel): C a multiple of 64; row block 128 when C is a multiple of 128 ----
@@ -1706,31 +1693,21 @@ constexpr int DADJ_NW = 8;    // 128-row blocks: 8 frames per workgroup (one per
 constexpr int DADJ_NW64 = 4;  // 64-row blocks: 4 frames, two workgroups per CU
 bool agcn_gcn_dadj_chain_supported(int C, int V) { return C >= 64 && C % 64 == 0 && V <= 32; }
 
-int agcn_gcn_dadj_chain_slots(int C, int T) {
-  const int bm = (C % 128 == 0) ? 128 : 64;
-  const int nw = (bm == 128) ? DADJ_NW : DADJ_NW64;
-  return ((T + nw - 1) / nw) * (C / bm);
-}
-
-size_t agcn_gcn_dadj_chain_workspace(int C, int Cout) {
-  const int bm = (C % 128 == 0) ? 128 : 64;
-  return (size_t)(3 * C / bm) * ((Cout + KC - 1) / KC) * 3 * 2 * (bm / 32) * 1024;
-}
-
 int agcn_gcn_dadj_chain(const float* dy, const float* wcat, const float* x, float* dadj_part, void* ws, size_t ws_bytes,
                         int N, int C, int Cout, int T, int V, hipStream_t stream, const float* dy_absmax,
-                        const float* x_absmax) {
+                        const float* x_absmax, AgcnDryRun* dry) {
   DadjArgs a = {};
   a.npl = agcn_npl();
   a.dy = dy; a.x = x; a.dpart = dadj_part; a.N = N; a.C = C; a.Cout = Cout; a.T = T; a.V = V;
   a.dy_absmax = dy_absmax;
   a.x_absmax = x_absmax;       // (null: taken by a pass inside; AGCN_DADJ_RED16=0: exact-f32 reduction MFMA)
-  if (const char* e = getenv("AGCN_DADJ_DBG")) a.dbg = atoi(e);
+  if (!dry)                    // (a profiling switch of the kernel: no part of the routing)
+    if (const char* e = getenv("AGCN_DADJ_DBG")) a.dbg = atoi(e);
   static const int f16 = getenv("AGCN_DADJ_F16X3") ? atoi(getenv("AGCN_DADJ_F16X3")) : 1;   // 0: bf16x6 (A/B)
   if (agcn_chain_f16x3() && f16) {
-    if (C % 128 == 0) return dadj_chain_launch<4, DADJ_NW, true>(a, wcat, ws, ws_bytes, stream);
-    return dadj_chain_launch<2, DADJ_NW64, true>(a, wcat, ws, ws_bytes, stream);
+    if (C % 128 == 0) return dadj_chain_launch<4, DADJ_NW, true>(a, wcat, ws, ws_bytes, stream, dry);
+    return dadj_chain_launch<2, DADJ_NW64, true>(a, wcat, ws, ws_bytes, stream, dry);
   }
-  if (C % 128 == 0) return dadj_chain_launch<4, DADJ_NW>(a, wcat, ws, ws_bytes, stream);
-  return dadj_chain_launch<2, DADJ_NW64>(a, wcat, ws, ws_bytes, stream);
+  if (C % 128 == 0) return dadj_chain_launch<4, DADJ_NW>(a, wcat, ws, ws_bytes, stream, dry);
+  return dadj_chain_launch<2, DADJ_NW64>(a, wcat, ws, ws_bytes, stream, dry);
 }

@@ -698,9 +698,10 @@ WcGeom wc_geom(int N, int M, int C, int V, int T_out) {
 }
 
 template <int AGG, int TM, int NCB, int VS, int NW = 8>
-int wc_launch(WcArgs a, void* ws, size_t ws_bytes, int* nslabs_out, hipStream_t stream) {
+int wc_launch(WcArgs a, void* ws, size_t ws_bytes, int* nslabs_out, hipStream_t stream, AgcnDryRun* dry) {
   const WcGeom g = wc_geom<AGG, TM, NCB, NW>(a.N, a.M, a.C, a.V, a.T_out);
   if (g.smem_bytes > 160 * 1024) return AGCN_ERR_UNSUPPORTED;
+  if (dry) return agcn_dry_note(dry, g.nslabs, (size_t)g.nslabs * a.wsize * 4);
   if ((size_t)g.nslabs * a.wsize * 4 > ws_bytes) return AGCN_ERR_WORKSPACE;
   a.part = (float*)ws;
   a.ntiles = g.ntiles; a.pairs_per_split = g.pairs_per_split; a.ncg = g.ncg; a.XP = g.XP;
@@ -713,14 +714,14 @@ int wc_launch(WcArgs a, void* ws, size_t ws_bytes, int* nslabs_out, hipStream_t 
 }
 
 template <int AGG, int TM, int NCB>
-int wc_dispatch_vs(const WcArgs& a, void* ws, size_t ws_bytes, int* nslabs, hipStream_t s) {
+int wc_dispatch_vs(const WcArgs& a, void* ws, size_t ws_bytes, int* nslabs, hipStream_t s, AgcnDryRun* dry) {
   const int vs = (a.V + 1) / 2;
   if constexpr (!AGG) {
-    return wc_launch<AGG, TM, NCB, 1>(a, ws, ws_bytes, nslabs, s);
+    return wc_launch<AGG, TM, NCB, 1>(a, ws, ws_bytes, nslabs, s, dry);
   } else {
-    if (vs == 13) return wc_launch<AGG, TM, NCB, 13>(a, ws, ws_bytes, nslabs, s);
-    if (vs == 9) return wc_launch<AGG, TM, NCB, 9>(a, ws, ws_bytes, nslabs, s);
-    return wc_launch<AGG, TM, NCB, 16>(a, ws, ws_bytes, nslabs, s);
+    if (vs == 13) return wc_launch<AGG, TM, NCB, 13>(a, ws, ws_bytes, nslabs, s, dry);
+    if (vs == 9) return wc_launch<AGG, TM, NCB, 9>(a, ws, ws_bytes, nslabs, s, dry);
+    return wc_launch<AGG, TM, NCB, 16>(a, ws, ws_bytes, nslabs, s, dry);
   }
 }
 
@@ -734,39 +735,26 @@ static inline bool wc_four_waves() {
 }
 
 template <int AGG, int TM, int NCB, int NW>
-int wc_dispatch_vs4(const WcArgs& a, void* ws, size_t ws_bytes, int* nslabs, hipStream_t s) {
+int wc_dispatch_vs4(const WcArgs& a, void* ws, size_t ws_bytes, int* nslabs, hipStream_t s, AgcnDryRun* dry) {
   const int vs = (a.V + 1) / 2;
   if constexpr (!AGG) {
-    return wc_launch<AGG, TM, NCB, 1, NW>(a, ws, ws_bytes, nslabs, s);
+    return wc_launch<AGG, TM, NCB, 1, NW>(a, ws, ws_bytes, nslabs, s, dry);
   } else {
-    if (vs == 13) return wc_launch<AGG, TM, NCB, 13, NW>(a, ws, ws_bytes, nslabs, s);
-    if (vs == 9) return wc_launch<AGG, TM, NCB, 9, NW>(a, ws, ws_bytes, nslabs, s);
-    return wc_launch<AGG, TM, NCB, 16, NW>(a, ws, ws_bytes, nslabs, s);
+    if (vs == 13) return wc_launch<AGG, TM, NCB, 13, NW>(a, ws, ws_bytes, nslabs, s, dry);
+    if (vs == 9) return wc_launch<AGG, TM, NCB, 9, NW>(a, ws, ws_bytes, nslabs, s, dry);
+    return wc_launch<AGG, TM, NCB, 16, NW>(a, ws, ws_bytes, nslabs, s, dry);
   }
 }
 
 template <int AGG, int TM>
-int wc_dispatch_ncb(const WcArgs& a, void* ws, size_t ws_bytes, int* nslabs, hipStream_t s) {
+int wc_dispatch_ncb(const WcArgs& a, void* ws, size_t ws_bytes, int* nslabs, hipStream_t s, AgcnDryRun* dry) {
   // (the aggregated variant at 128+ channels runs out of registers with 4-wave workgroups: measured 8 % slower)
-  if (wc_four_waves() && !AGG && a.C % 128 == 0) return wc_dispatch_vs4<AGG, TM, 4, 4>(a, ws, ws_bytes, nslabs, s);
-  if (wc_four_waves() && a.C % 64 == 0 && !(AGG && a.C % 128 == 0)) return wc_dispatch_vs4<AGG, TM, 2, 4>(a, ws, ws_bytes, nslabs, s);
-  if (a.C % 256 == 0) return wc_dispatch_vs<AGG, TM, 8>(a, ws, ws_bytes, nslabs, s);
-  if (a.C % 128 == 0) return wc_dispatch_vs<AGG, TM, 4>(a, ws, ws_bytes, nslabs, s);
-  if (a.C % 64 == 0) return wc_dispatch_vs<AGG, TM, 2>(a, ws, ws_bytes, nslabs, s);
-  return wc_dispatch_vs<AGG, TM, 1>(a, ws, ws_bytes, nslabs, s);     // few channels (first layer): one zero-padded block
-}
-
-template <int AGG>
-size_t wc_slabs(int N, int M, int C, int V, int T_out) {
-  const bool tm4 = M > 64 && C % 64 == 0;     // the single-block (few channels) variant stages 8 frames: 64 rows only
-  int n;
-  if (wc_four_waves() && !AGG && C % 128 == 0) n = tm4 ? wc_geom<AGG, 4, 4, 4>(N, M, C, V, T_out).nslabs : wc_geom<AGG, 2, 4, 4>(N, M, C, V, T_out).nslabs;
-  else if (wc_four_waves() && C % 64 == 0 && !(AGG && C % 128 == 0)) n = tm4 ? wc_geom<AGG, 4, 2, 4>(N, M, C, V, T_out).nslabs : wc_geom<AGG, 2, 2, 4>(N, M, C, V, T_out).nslabs;
-  else if (C % 256 == 0) n = tm4 ? wc_geom<AGG, 4, 8>(N, M, C, V, T_out).nslabs : wc_geom<AGG, 2, 8>(N, M, C, V, T_out).nslabs;
-  else if (C % 128 == 0) n = tm4 ? wc_geom<AGG, 4, 4>(N, M, C, V, T_out).nslabs : wc_geom<AGG, 2, 4>(N, M, C, V, T_out).nslabs;
-  else if (C % 64 == 0) n = tm4 ? wc_geom<AGG, 4, 2>(N, M, C, V, T_out).nslabs : wc_geom<AGG, 2, 2>(N, M, C, V, T_out).nslabs;
-  else n = tm4 ? wc_geom<AGG, 4, 1>(N, M, C, V, T_out).nslabs : wc_geom<AGG, 2, 1>(N, M, C, V, T_out).nslabs;
-  return (size_t)n;
+  if (wc_four_waves() && !AGG && a.C % 128 == 0) return wc_dispatch_vs4<AGG, TM, 4, 4>(a, ws, ws_bytes, nslabs, s, dry);
+  if (wc_four_waves() && a.C % 64 == 0 && !(AGG && a.C % 128 == 0)) return wc_dispatch_vs4<AGG, TM, 2, 4>(a, ws, ws_bytes, nslabs, s, dry);
+  if (a.C % 256 == 0) return wc_dispatch_vs<AGG, TM, 8>(a, ws, ws_bytes, nslabs, s, dry);
+  if (a.C % 128 == 0) return wc_dispatch_vs<AGG, TM, 4>(a, ws, ws_bytes, nslabs, s, dry);
+  if (a.C % 64 == 0) return wc_dispatch_vs<AGG, TM, 2>(a, ws, ws_bytes, nslabs, s, dry);
+  return wc_dispatch_vs<AGG, TM, 1>(a, ws, ws_bytes, nslabs, s, dry);     // few channels (first layer): one zero-padded block
 }
 
 
@@ -799,55 +787,50 @@ static inline bool wc_f16x3() {
 }
 
 template <int AGG, int TM, int NCB, int NRB, int VS, int NWP = 4>
-int wc_launch_pc(WcArgs a, void* ws, size_t ws_bytes, int* nslabs_out, hipStream_t stream) {
+int wc_launch_pc(WcArgs a, void* ws, size_t ws_bytes, int* nslabs_out, hipStream_t stream, AgcnDryRun* dry) {
   // f16x3 when the caller supplied both operand maxima (fp32-equivalent mode); VS == 0: the aggregation on f16x3 too
-  {
-    if (a.dy_absmax && a.in_absmax && a.npl == 3 && wc_f16x3()) {
-      const WcGeom g = wc_geom_pc<AGG, TM, NCB, NRB>(a.N, a.M, a.C, a.V, a.T_out, AGG && VS == 0, 2);
-      if (g.smem_bytes > 160 * 1024) return AGCN_ERR_UNSUPPORTED;
-      if ((size_t)g.nslabs * a.wsize * 4 > ws_bytes) return AGCN_ERR_WORKSPACE;
-      a.part = (float*)ws;
-      a.ntiles = g.ntiles; a.pairs_per_split = g.pairs_per_split; a.ncg = g.ncg; a.XP = g.XP;
-      auto kern = wgrad_pc_kernel<AGG, TM, NCB, VS, NRB, 8, NWP, true>;
-      static unsigned char lds_ok[AGCN_MAX_DEVICES] = {};
-      if (int e = agcn_allow_big_lds_rt(reinterpret_cast<const void*>(kern), lds_ok)) return e;
-      AGCN_NOTE_KERNEL("wgrad_pc_kernel<%d, %d, %d, %d, %d, 8, %d, true>", AGG, TM, NCB, VS, NRB, NWP);
-      hipLaunchKernelGGL(kern, dim3(g.grid_x, g.nsplit), dim3((8 + NWP) * 64), g.smem_bytes, stream, a);
-      *nslabs_out = g.nslabs;
-      return agcn_check_launch();
-    }
-  }
-  const WcGeom g = wc_geom_pc<AGG, TM, NCB, NRB>(a.N, a.M, a.C, a.V, a.T_out, AGG && VS == 0);
+  const bool f16 = a.dy_absmax && a.in_absmax && a.npl == 3 && wc_f16x3();
+  const WcGeom g = wc_geom_pc<AGG, TM, NCB, NRB>(a.N, a.M, a.C, a.V, a.T_out, AGG && VS == 0, f16 ? 2 : 3);
   if (g.smem_bytes > 160 * 1024) return AGCN_ERR_UNSUPPORTED;
+  if (dry) return agcn_dry_note(dry, g.nslabs, (size_t)g.nslabs * a.wsize * 4);
   if ((size_t)g.nslabs * a.wsize * 4 > ws_bytes) return AGCN_ERR_WORKSPACE;
   a.part = (float*)ws;
   a.ntiles = g.ntiles; a.pairs_per_split = g.pairs_per_split; a.ncg = g.ncg; a.XP = g.XP;
-  auto kern = wgrad_pc_kernel<AGG, TM, NCB, VS, NRB, 8, NWP>;
-  static unsigned char lds_ok[AGCN_MAX_DEVICES] = {};
-  if (int e = agcn_allow_big_lds_rt(reinterpret_cast<const void*>(kern), lds_ok)) return e;
-  AGCN_NOTE_KERNEL("wgrad_pc_kernel<%d, %d, %d, %d, %d, 8, %d>", AGG, TM, NCB, VS, NRB, NWP);
-  hipLaunchKernelGGL(kern, dim3(g.grid_x, g.nsplit), dim3((8 + NWP) * 64), g.smem_bytes, stream, a);
+  const dim3 grid(g.grid_x, g.nsplit), block((8 + NWP) * 64);
+  if (f16) {
+    auto kern = wgrad_pc_kernel<AGG, TM, NCB, VS, NRB, 8, NWP, true>;
+    static unsigned char lds_ok[AGCN_MAX_DEVICES] = {};
+    if (int e = agcn_allow_big_lds_rt(reinterpret_cast<const void*>(kern), lds_ok)) return e;
+    AGCN_NOTE_KERNEL("wgrad_pc_kernel<%d, %d, %d, %d, %d, 8, %d, true>", AGG, TM, NCB, VS, NRB, NWP);
+    hipLaunchKernelGGL(kern, grid, block, g.smem_bytes, stream, a);
+  } else {
+    auto kern = wgrad_pc_kernel<AGG, TM, NCB, VS, NRB, 8, NWP>;
+    static unsigned char lds_ok[AGCN_MAX_DEVICES] = {};
+    if (int e = agcn_allow_big_lds_rt(reinterpret_cast<const void*>(kern), lds_ok)) return e;
+    AGCN_NOTE_KERNEL("wgrad_pc_kernel<%d, %d, %d, %d, %d, 8, %d>", AGG, TM, NCB, VS, NRB, NWP);
+    hipLaunchKernelGGL(kern, grid, block, g.smem_bytes, stream, a);
+  }
   *nslabs_out = g.nslabs;
   return agcn_check_launch();
 }
 
 template <int AGG, int TM, int NCB, int NRB>
-int wc_dispatch_pc_vs(const WcArgs& a, void* ws, size_t ws_bytes, int* nslabs, hipStream_t s) {
+int wc_dispatch_pc_vs(const WcArgs& a, void* ws, size_t ws_bytes, int* nslabs, hipStream_t s, AgcnDryRun* dry) {
   const int vs = (a.V + 1) / 2;
   if constexpr (!AGG) {
-    return wc_launch_pc<AGG, TM, NCB, NRB, 1>(a, ws, ws_bytes, nslabs, s);
+    return wc_launch_pc<AGG, TM, NCB, NRB, 1>(a, ws, ws_bytes, nslabs, s, dry);
   } else {
     // (the split-bf16 aggregation measured 3-7 % SLOWER here: the consumer re-splits its x fragment for every subset
     // and becomes VALU-bound; AGCN_WC_BCH=1 selects it)
     static const int bch = getenv("AGCN_WC_BCH") ? atoi(getenv("AGCN_WC_BCH")) : 0;
-    if (bch && a.npl == 3) return wc_launch_pc<AGG, TM, NCB, NRB, 0>(a, ws, ws_bytes, nslabs, s);
+    if (bch && a.npl == 3) return wc_launch_pc<AGG, TM, NCB, NRB, 0>(a, ws, ws_bytes, nslabs, s, dry);
     // with both maxima: the aggregation on f16x3 as well (AGCN_WC_AGG16=0: exact-f32 aggregation chain, round 2)
     static const int agg16 = getenv("AGCN_WC_AGG16") ? atoi(getenv("AGCN_WC_AGG16")) : 1;
     if (agg16 && a.dy_absmax && a.in_absmax && a.npl == 3 && wc_f16x3())
-      return wc_launch_pc<AGG, TM, NCB, NRB, 0>(a, ws, ws_bytes, nslabs, s);
-    if (vs == 13) return wc_launch_pc<AGG, TM, NCB, NRB, 13>(a, ws, ws_bytes, nslabs, s);
-    if (vs == 9) return wc_launch_pc<AGG, TM, NCB, NRB, 9>(a, ws, ws_bytes, nslabs, s);
-    return wc_launch_pc<AGG, TM, NCB, NRB, 16>(a, ws, ws_bytes, nslabs, s);
+      return wc_launch_pc<AGG, TM, NCB, NRB, 0>(a, ws, ws_bytes, nslabs, s, dry);
+    if (vs == 13) return wc_launch_pc<AGG, TM, NCB, NRB, 13>(a, ws, ws_bytes, nslabs, s, dry);
+    if (vs == 9) return wc_launch_pc<AGG, TM, NCB, NRB, 9>(a, ws, ws_bytes, nslabs, s, dry);
+    return wc_launch_pc<AGG, TM, NCB, NRB, 16>(a, ws, ws_bytes, nslabs, s, dry);
   }
 }
 
@@ -866,37 +849,22 @@ static inline bool wc_pc_applies(int C) { return wc_pc_enabled() && C % 64 == 0;
 // 128 channels x 64 rows, or 64 channels x 128 rows.  Plain: 128 channels x 128 rows (4 row tiles per wave), or
 // 64 channels x 2 row blocks of 128.
 template <int AGG>
-int wc_dispatch_pc(const WcArgs& a, void* ws, size_t ws_bytes, int* nslabs, hipStream_t s) {
+int wc_dispatch_pc(const WcArgs& a, void* ws, size_t ws_bytes, int* nslabs, hipStream_t s, AgcnDryRun* dry) {
   if constexpr (AGG) {
-    if (a.C % 128 == 0) return wc_dispatch_pc_vs<1, 2, 4, 1>(a, ws, ws_bytes, nslabs, s);
-    return wc_dispatch_pc_vs<1, 2, 2, 2>(a, ws, ws_bytes, nslabs, s);
+    if (a.C % 128 == 0) return wc_dispatch_pc_vs<1, 2, 4, 1>(a, ws, ws_bytes, nslabs, s, dry);
+    return wc_dispatch_pc_vs<1, 2, 2, 2>(a, ws, ws_bytes, nslabs, s, dry);
   } else {
     // The plain 1x1 gradients are producer-bound (both operands split by the 4 producers).  Up to 192 rows, 8 producer
     // waves on 64-row blocks (4 waves per SIMD, 128 VGPRs) win: l6 shape 390 -> 322 us; with more rows the extra
     // passes over x cost more than the producers gain (l9: 628 -> 697 us).  AGCN_WC_NWP8=0 / 1 forces either.
     static const int nwp8 = getenv("AGCN_WC_NWP8") ? atoi(getenv("AGCN_WC_NWP8")) : -1;
     if (a.C % 128 == 0 && (nwp8 == 1 || (nwp8 < 0 && a.M > 64 && a.M <= 192)))
-      return wc_launch_pc<0, 2, 4, 1, 1, 8>(a, ws, ws_bytes, nslabs, s);
+      return wc_launch_pc<0, 2, 4, 1, 1, 8>(a, ws, ws_bytes, nslabs, s, dry);
     if (a.C % 128 == 0) {
-      if (a.M > 64) return wc_dispatch_pc_vs<0, 4, 4, 1>(a, ws, ws_bytes, nslabs, s);
-      return wc_dispatch_pc_vs<0, 2, 4, 1>(a, ws, ws_bytes, nslabs, s);
+      if (a.M > 64) return wc_dispatch_pc_vs<0, 4, 4, 1>(a, ws, ws_bytes, nslabs, s, dry);
+      return wc_dispatch_pc_vs<0, 2, 4, 1>(a, ws, ws_bytes, nslabs, s, dry);
     }
-    return wc_dispatch_pc_vs<0, 2, 2, 2>(a, ws, ws_bytes, nslabs, s);
-  }
-}
-
-template <int AGG>
-size_t wc_slabs_pc(int N, int M, int C, int V, int T_out) {
-  if constexpr (AGG) {
-    if (C % 128 == 0) return (size_t)wc_geom_pc<1, 2, 4, 1>(N, M, C, V, T_out).nslabs;
-    return (size_t)wc_geom_pc<1, 2, 2, 2>(N, M, C, V, T_out).nslabs;
-  } else {
-    if (C % 128 == 0) {
-      const size_t n4 = (size_t)wc_geom_pc<0, 4, 4, 1>(N, M, C, V, T_out).nslabs;
-      const size_t n2 = (size_t)wc_geom_pc<0, 2, 4, 1>(N, M, C, V, T_out).nslabs;
-      return n4 > n2 ? n4 : n2;
-    }
-    return (size_t)wc_geom_pc<0, 2, 2, 2>(N, M, C, V, T_out).nslabs;
+    return wc_dispatch_pc_vs<0, 2, 2, 2>(a, ws, ws_bytes, nslabs, s, dry);
   }
 }
 
@@ -905,30 +873,22 @@ size_t wc_slabs_pc(int N, int M, int C, int V, int T_out) {
 // C a multiple of 64, or at most 32 (one zero-padded channel block)
 bool agcn_wgrad_chain_supported(int M, int C, int V) { return M >= 64 && (C % 64 == 0 || C <= 32) && C >= 1 && V <= 32; }
 
-size_t agcn_wgrad_chain_workspace(int agg, int N, int M, int C, int V, int T_out) {
-  const long wsize = (long)(agg ? 3 : 1) * M * C;
-  size_t n = agg ? wc_slabs<1>(N, M, C, V, T_out) : wc_slabs<0>(N, M, C, V, T_out);
-  if (C % 64 == 0) {                            // either variant may run (AGCN_WC_PC): size for the larger
-    const size_t m = agg ? wc_slabs_pc<1>(N, M, C, V, T_out) : wc_slabs_pc<0>(N, M, C, V, T_out);
-    if (m > n) n = m;
-  }
-  return n * (size_t)wsize * 4;
-}
-
 // writes the partial slabs into ws; *nslabs = number of slabs for the reduce kernel.  agg: x . adj_i operand, z = subset
 int agcn_wgrad_chain(int agg, const float* dy, const float* x, const float* adj, void* ws, size_t ws_bytes, int* nslabs,
                      int N, int M, int C, int V, int T_src, int T_out, int stride, hipStream_t s, const float* dy_absmax,
-                     const float* x_absmax) {
+                     const float* x_absmax, AgcnDryRun* dry) {
   WcArgs a = {};
   a.dy_absmax = dy_absmax; a.in_absmax = x_absmax;
   a.npl = agcn_npl();
-  { const char* e = getenv("AGCN_WC_PAD"); a.pad = (e && atoi(e) == 0) ? 0 : 1; }
-  { const char* e = getenv("AGCN_WC_DBG"); a.dbg = e ? atoi(e) : 0; }
+  if (!dry) {                  // kernel switches, read per call: no part of the routing
+    { const char* e = getenv("AGCN_WC_PAD"); a.pad = (e && atoi(e) == 0) ? 0 : 1; }
+    { const char* e = getenv("AGCN_WC_DBG"); a.dbg = e ? atoi(e) : 0; }
+  }
   a.dy = dy; a.in = x; a.adj = adj; a.N = N; a.M = M; a.C = C; a.V = V; a.T_src = T_src; a.T_out = T_out;
   a.stride = stride; a.wsize = (long)(agg ? 3 : 1) * M * C;
   // (64 channels x 64 rows with aggregation: the two-row-block tile of the producer/consumer kernel would be half empty)
-  if (wc_pc_applies(C) && stride == 1 && !(agg && C % 128 != 0 && M <= 64)) return agg ? wc_dispatch_pc<1>(a, ws, ws_bytes, nslabs, s) : wc_dispatch_pc<0>(a, ws, ws_bytes, nslabs, s);
+  if (wc_pc_applies(C) && stride == 1 && !(agg && C % 128 != 0 && M <= 64)) return agg ? wc_dispatch_pc<1>(a, ws, ws_bytes, nslabs, s, dry) : wc_dispatch_pc<0>(a, ws, ws_bytes, nslabs, s, dry);
   const bool tm4 = M > 64 && C % 64 == 0;
-  if (agg) return tm4 ? wc_dispatch_ncb<1, 4>(a, ws, ws_bytes, nslabs, s) : wc_dispatch_ncb<1, 2>(a, ws, ws_bytes, nslabs, s);
-  return tm4 ? wc_dispatch_ncb<0, 4>(a, ws, ws_bytes, nslabs, s) : wc_dispatch_ncb<0, 2>(a, ws, ws_bytes, nslabs, s);
+  if (agg) return tm4 ? wc_dispatch_ncb<1, 4>(a, ws, ws_bytes, nslabs, s, dry) : wc_dispatch_ncb<1, 2>(a, ws, ws_bytes, nslabs, s, dry);
+  return tm4 ? wc_dispatch_ncb<0, 4>(a, ws, ws_bytes, nslabs, s, dry) : wc_dispatch_ncb<0, 2>(a, ws, ws_bytes, nslabs, s, dry);
 }
