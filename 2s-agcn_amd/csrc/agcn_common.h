@@ -86,50 +86,28 @@ static inline bool agcn_sizes_ok(int N, int a, int b, int T, int V) {
   return N > 0 && a > 0 && b > 0 && T > 0 && V > 0 && V <= 32;
 }
 
-// temporal convolutions (agcn_tconv_*): the supported domain, and the shapes the agcn_conv_* entry points cover (routed
-// there unchanged: same kernels, same bits)
-static inline bool agcn_tconv_domain(int T, int taps, int stride, int pad) {
-  return taps >= 1 && taps <= 9 && stride >= 1 && stride <= 9 && pad >= 0 && pad <= (taps - 1) / 2 && T + 2 * pad >= taps;
-}
-static inline bool agcn_tconv_legacy(int taps, int stride, int pad) {
-  return pad == (taps - 1) / 2 && (taps == 1 || taps == 9) && (stride == 1 || stride == 2);
-}
+// temporal convolutions (agcn_tconv_*, and agcn_conv_* as the 1- and 9-tap "same"-padded rows of it): the domain, the
+// output-frame count and the launch plan every ladder consumes
+#include "tconv_plan.h"
 
-// split-bf16 temporal convolution (conv_gemm_bf16.hip); npl: 3 = bf16x6 (fp32-equivalent), 2 = bf16x3
+// split-bf16 / f16x3 temporal convolution (conv_gemm_bf16.hip); npl: 3 = bf16x6 (fp32-equivalent), 2 = bf16x3, 1 = bf16.
+// Shapes these kernels are tuned for: 9 taps with padding 4 at stride 1 or 2, stride-1 3/5/7 taps with any padding, and
+// the stride-1 1x1 backward-data.  The callers add the arithmetic mode (and, for the 1x1, the channel counts).
 bool agcn_bf16_conv_wide(int taps, int M);
-int agcn_bf16_conv9_fwd(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* ws,
-                        size_t ws_bytes, int N, int Cin, int Cout, int T, int V, int stride, int npl, hipStream_t s,
-                        const float* add = nullptr, int relu = 0, const float* x_absmax = nullptr,
-                        AgcnDryRun* dry = nullptr);
-int agcn_bf16_conv9_bwd_data(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
-                             const float* mask1, const float* add2, const float* mask2, void* ws, size_t ws_bytes,
-                             int N, int Cin, int Cout, int T, int V, int stride, int npl, hipStream_t s,
-                             const float* dy_absmax = nullptr, AgcnDryRun* dry = nullptr);
-
-// stride-1 3/5/7-tap temporal convolutions with explicit padding on the same kernels (agcn_tconv_*)
-bool agcn_bf16_tconv_supported(int taps, int stride);
+enum AgcnTconvOp { AGCN_TCONV_FWD, AGCN_TCONV_BWD_DATA };
+bool agcn_bf16_tconv_supported(AgcnTconvOp op, int taps, int stride, int pad);
+// y = act( bias + tconv(x * gate) [+ add] ): the training forward (stats_part; add, gate null) and the BN-folded inference
+// form (agcn_tconv_infer, agcn_conv9_infer), the attention gates of gate.h applied while the operand is staged.  A window
+// too long for these kernels' LDS is refused (AGCN_ERR_UNSUPPORTED) before anything is launched.
+struct GateArgs;
 int agcn_bf16_tconv_fwd(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* ws,
-                        size_t ws_bytes, int N, int Cin, int Cout, int T, int V, int taps, int pad, int npl,
-                        hipStream_t s, const float* x_absmax, AgcnDryRun* dry = nullptr);
+                        size_t ws_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride, int pad, int npl,
+                        hipStream_t s, const float* add, int relu, const float* x_absmax, const GateArgs* gate,
+                        AgcnDryRun* dry);
 int agcn_bf16_tconv_bwd_data(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
                              const float* mask1, const float* add2, const float* mask2, void* ws, size_t ws_bytes,
-                             int N, int Cin, int Cout, int T, int V, int taps, int pad, int npl, hipStream_t s,
-                             const float* dy_absmax, AgcnDryRun* dry = nullptr);
-
-// BN-folded inference on the same kernels, the attention gates of gate.h applied while the operand is staged
-struct GateArgs;
-bool agcn_bf16_tconv_infer_supported(int taps, int stride, int pad);
-int agcn_bf16_tconv_infer(const float* x, const float* w, const float* bias, float* y, void* ws, size_t ws_bytes, int N,
-                          int Cin, int Cout, int T, int V, int taps, int stride, int pad, int npl, hipStream_t s,
-                          const float* add, int relu, const float* x_absmax, const GateArgs* gate,
-                          AgcnDryRun* dry = nullptr);
-
-int agcn_bf16_conv1_fwd(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* ws,
-                        size_t ws_bytes, int N, int Cin, int Cout, int T, int V, int stride, int npl, hipStream_t s,
-                        const float* add = nullptr, int relu = 0, AgcnDryRun* dry = nullptr);
-int agcn_bf16_conv1_bwd_data(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
-                             const float* mask1, const float* add2, const float* mask2, void* ws, size_t ws_bytes,
-                             int N, int Cin, int Cout, int T, int V, int npl, hipStream_t s, AgcnDryRun* dry = nullptr);
+                             int N, int Cin, int Cout, int T, int V, int taps, int stride, int pad, int npl,
+                             hipStream_t s, const float* dy_absmax, AgcnDryRun* dry);
 
 // register-chained aggregate+project (gcn_chain.hip); mode 0 = forward, 1 = backward-data
 bool agcn_gcn_chain_supported(int M, int K, int V);

@@ -629,11 +629,6 @@ constexpr int CK9 = 8, CK1 = 16, CKA = 8, CKD = 64;
 // ---- temporal convolution with any taps (1..9), stride (1..9) and padding (0..(taps-1)/2): agcn_tconv_* ----
 constexpr int WBT = 12;                 // window bound of the exact-f32 kernel (768 floats per staged row)
 
-inline int tconv_out_frames(int T, int taps, int stride, int pad) { return (T + 2 * pad - taps) / stride + 1; }
-
-// the split-bf16 / f16x3 kernels of conv_gemm_bf16.hip (stride 1, 3/5/7 taps) in the split-bf16 modes
-inline bool tconv_fast(int taps, int stride) { return agcn_gemm_precision() != 0 && agcn_bf16_tconv_supported(taps, stride); }
-
 // frames per tile of the exact-f32 kernel: a staged window row of (tt-1)*stride + taps frames must fit WBT*64 floats
 inline int tconv_f32_tt(int V, int T_out, int taps, int stride) {
   int tt = 256 / V;
@@ -642,26 +637,19 @@ inline int tconv_f32_tt(int V, int T_out, int taps, int stride) {
   return tt < 1 ? 1 : tt;
 }
 
+// One pass of a plan (tconv_plan.h) on the exact-f32 kernel.  The passes of the legacy shapes (1 or 9 taps, "same"
+// padding, stride 1 or 2; backward: 9, or 5 and 4 at stride 2, or 1, the empty pass included) keep the window bounds they
+// were tuned with and the full tile; every other pass takes WBT and as many frames per tile as its window allows.
 template <int TAPS>
-int tconv_f32_launch(Problem& p, hipStream_t s) {
+int tconv_f32_launch(Problem& p, bool legacy, bool bwd, hipStream_t s) {
   constexpr int CK = TAPS == 1 ? CK1 : CK9;
+  if (legacy) {
+    if constexpr (TAPS == 9) return bwd ? DISPATCH_BM(9, 0, CK9, CK9, 8, p, s) : DISPATCH_BM(9, 0, CK9, CK9, 11, p, s);
+    if constexpr (TAPS == 5 || TAPS == 4) return DISPATCH_BM(TAPS, 0, CK9, CK9, 8, p, s);
+    if constexpr (TAPS == 1) return p.a.src_stride == 2 ? DISPATCH_BM(1, 0, CK1, CK1, 8, p, s) : DISPATCH_BM(1, 0, CK1, CK1, 4, p, s);
+  }
   p.tt_cap = tconv_f32_tt(p.a.V, p.a.T_out, TAPS, p.a.src_stride);
   return DISPATCH_BM(TAPS, 0, CK, CK, WBT, p, s);
-}
-
-int tconv_f32_dispatch(int taps, Problem& p, hipStream_t s) {
-  switch (taps) {
-    case 1: return tconv_f32_launch<1>(p, s);
-    case 2: return tconv_f32_launch<2>(p, s);
-    case 3: return tconv_f32_launch<3>(p, s);
-    case 4: return tconv_f32_launch<4>(p, s);
-    case 5: return tconv_f32_launch<5>(p, s);
-    case 6: return tconv_f32_launch<6>(p, s);
-    case 7: return tconv_f32_launch<7>(p, s);
-    case 8: return tconv_f32_launch<8>(p, s);
-    case 9: return tconv_f32_launch<9>(p, s);
-    default: return AGCN_ERR_UNSUPPORTED;
-  }
 }
 
 // folded inference on the exact-f32 kernel: 64-row blocks (the epilogue tile of epilogue.h is 64 x 257 floats of LDS)
@@ -672,101 +660,9 @@ int tconv_f32_infer_launch(Problem& p, hipStream_t s) {
   return launch_cfg<TAPS, 0, 1, 4, 2, 2, CK, WBT, 2>(p, s);
 }
 
-int tconv_f32_infer_dispatch(int taps, Problem& p, hipStream_t s) {
-  switch (taps) {
-    case 1: return tconv_f32_infer_launch<1>(p, s);
-    case 2: return tconv_f32_infer_launch<2>(p, s);
-    case 3: return tconv_f32_infer_launch<3>(p, s);
-    case 4: return tconv_f32_infer_launch<4>(p, s);
-    case 5: return tconv_f32_infer_launch<5>(p, s);
-    case 6: return tconv_f32_infer_launch<6>(p, s);
-    case 7: return tconv_f32_infer_launch<7>(p, s);
-    case 8: return tconv_f32_infer_launch<8>(p, s);
-    case 9: return tconv_f32_infer_launch<9>(p, s);
-    default: return AGCN_ERR_UNSUPPORTED;
-  }
-}
-
 // ---- the routing of each entry point, after its argument checks.  The size queries walk the same functions with null
 // tensors and a dry-run record (agcn_common.h): there is one copy of every routing decision.  In a dry run an operand
 // whose presence steers the routing may be a placeholder (agcn_dry_present): no route function dereferences a tensor. ----
-
-// y[n][o][t,v] = bias[o] + sum_{c,k} w[o][c][k] x[n][c][(t*stride + k - pad), v]      (unit_tcn conv, 1x1 convs)
-int conv_fwd_route(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* workspace,
-                   size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride,
-                   const float* x_absmax, hipStream_t s, AgcnDryRun* dry) {
-  if ((taps != 1 && taps != 9) || (stride != 1 && stride != 2)) return AGCN_ERR_UNSUPPORTED;
-  const int pad = (taps - 1) / 2;
-  if (taps == 9 && agcn_gemm_precision() != 0)
-    return agcn_bf16_conv9_fwd(x, w, bias, y, stats_part, workspace, workspace_bytes, N, Cin, Cout, T, V, stride,
-                               agcn_gemm_precision(), s, nullptr, 0, x_absmax, dry);
-  Problem p = {};
-  p.dry = dry;
-  ConvGemmArgs& a = p.a;
-  a.in = x; a.bias = bias; a.out = y; a.stats = stats_part;
-  a.N = N; a.M = Cout; a.Kinner = Cin; a.in_rows = Cin; a.V = V;
-  a.T_src = T; a.T_out = (T + 2 * pad - taps) / stride + 1; a.T_full = a.T_out;
-  a.src_stride = stride; a.f_off = -pad; a.out_fs = 1; a.out_fo = 0;
-  p.w = w; p.sa_m = (long)Cin * taps; p.sa_i = 0; p.sa_c = taps; p.tap_flip_from = -1;
-  p.ws = workspace; p.ws_bytes = workspace_bytes;
-  if (taps == 9) return DISPATCH_BM(9, 0, CK9, CK9, 11, p, s);
-  if (stride == 1) return DISPATCH_BM(1, 0, CK1, CK1, 4, p, s);
-  return DISPATCH_BM(1, 0, CK1, CK1, 8, p, s);
-}
-
-// dx[n][c][t,v] (+)= sum_{o,k} w[o][c][k] dy[n][o][(t + pad - k)/stride, v]  (+ masked addends)
-int conv_bwd_data_route(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
-                        const float* mask1, const float* add2, const float* mask2, void* workspace,
-                        size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride,
-                        const float* dy_absmax, hipStream_t s, AgcnDryRun* dry) {
-  if ((taps != 1 && taps != 9) || (stride != 1 && stride != 2)) return AGCN_ERR_UNSUPPORTED;
-  const int pad = (taps - 1) / 2;
-  if (taps == 9 && agcn_gemm_precision() != 0)
-    return agcn_bf16_conv9_bwd_data(dy, w, dx, accumulate, add1, mask1, add2, mask2, workspace, workspace_bytes, N, Cin,
-                                    Cout, T, V, stride, agcn_gemm_precision(), s, dy_absmax, dry);
-  // 1x1 backward-data: measured 10-17% faster on the split-bf16 kernel; the 1x1 forward (store-bound) is not
-  if (taps == 1 && stride == 1 && agcn_chained() && Cin >= 64 && Cout >= 32)
-    return agcn_bf16_conv1_bwd_data(dy, w, dx, accumulate, add1, mask1, add2, mask2, workspace, workspace_bytes, N, Cin,
-                                    Cout, T, V, agcn_gemm_precision(), s, dry);
-  Problem p = {};
-  p.dry = dry;
-  ConvGemmArgs& a = p.a;
-  a.in = dy; a.out = dx; a.accumulate = accumulate;
-  a.add1 = add1; a.mask1 = mask1; a.add2 = add2; a.mask2 = mask2;
-  a.N = N; a.M = Cin; a.Kinner = Cout; a.in_rows = Cout; a.V = V;
-  a.T_src = (T + 2 * pad - taps) / stride + 1; a.T_full = T; a.src_stride = 1;
-  p.w = w; p.sa_m = taps; p.sa_i = 0; p.sa_c = (long)Cin * taps;
-  p.ws = workspace; p.ws_bytes = workspace_bytes;
-  if (stride == 1) {
-    // dx[t] = sum_j W[taps-1-j] dy[t + j - pad]
-    a.T_out = T; a.out_fs = 1; a.out_fo = 0; a.f_off = -pad;
-    p.tap_mul = 1; p.tap_add = 0; p.tap_flip_from = taps - 1;
-    if (taps == 9) return DISPATCH_BM(9, 0, CK9, CK9, 8, p, s);
-    return DISPATCH_BM(1, 0, CK1, CK1, 4, p, s);
-  }
-  // stride 2: output frames of parity `par` form a stride-1 problem over tau (t = 2*tau + par):
-  //   dx[2tau+par] = sum_j W[k = taps-1-(2j+par')] dy[tau + j + off]   with only the taps of matching parity
-  int rc;
-  if (taps == 9) {
-    // even t: tap' = 2j (j<5), source tau + j - 2 ; odd t: tap' = 2j+1 (j<4), source tau + j - 1
-    a.T_out = (T + 1) / 2; a.out_fs = 2; a.out_fo = 0; a.f_off = -2;
-    p.tap_mul = 2; p.tap_add = 0; p.tap_flip_from = 8;
-    rc = DISPATCH_BM(5, 0, CK9, CK9, 8, p, s);
-    if (rc) return rc;
-    a.T_out = T / 2; a.out_fo = 1; a.f_off = -1;
-    p.tap_add = 1;
-    if (a.T_out > 0) rc = DISPATCH_BM(4, 0, CK9, CK9, 8, p, s);
-    return rc;
-  }
-  // 1x1 stride 2: even t takes dy[t/2]; odd t receives no signal (zero + addends)
-  a.T_out = (T + 1) / 2; a.out_fs = 2; a.out_fo = 0; a.f_off = 0;
-  p.tap_mul = 1; p.tap_add = 0; p.tap_flip_from = 0;
-  rc = DISPATCH_BM(1, 0, CK1, CK1, 4, p, s);
-  if (rc) return rc;
-  a.T_out = T / 2; a.out_fo = 1; a.Kinner = 0;      // no K chunks: the epilogue writes 0 (+accumulate/addends)
-  if (a.T_out > 0) rc = DISPATCH_BM(1, 0, CK1, CK1, 4, p, s);
-  return rc;
-}
 
 // y[n][o][t,v] = bias[o] + sum_i sum_c wcat[o][i*C+c] * sum_u x[n][c][t,u] adj[n][i][u][v]
 int gcn_fwd_route(const float* x, const float* adj, const float* wcat, const float* bias, float* y, float* stats_part,
@@ -840,93 +736,84 @@ int gcn_unit_infer_route(const float* x, const float* adj, const float* wcat, co
                         workspace, workspace_bytes, N, C, Cout, T, V, s, relu, 1, nullptr, nullptr, dry);
 }
 
+// The temporal convolution's three data routes.  Each builds the plan of tconv_plan.h and hands its passes to one rung:
+// the split-bf16 / f16x3 kernels of conv_gemm_bf16.hip for the shapes they are tuned for (unless AGCN_GEMM=f32), else the
+// exact-f32 kernel with the window bound of tconv_f32_launch.
+
 // y[n][o][t,v] = bias[o] + sum_{c,k} w[o][c][k] x[n][c][t*stride + k - pad, v],  T_out = (T + 2 pad - taps)/stride + 1
 int tconv_fwd_route(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* workspace,
                     size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride, int pad,
                     const float* x_absmax, hipStream_t s, AgcnDryRun* dry) {
   if (!agcn_tconv_domain(T, taps, stride, pad)) return AGCN_ERR_UNSUPPORTED;
-  if (agcn_tconv_legacy(taps, stride, pad))
-    return conv_fwd_route(x, w, bias, y, stats_part, workspace, workspace_bytes, N, Cin, Cout, T, V, taps, stride, x_absmax,
-                          s, dry);
-  if (tconv_fast(taps, stride))
-    return agcn_bf16_tconv_fwd(x, w, bias, y, stats_part, workspace, workspace_bytes, N, Cin, Cout, T, V, taps, pad,
-                               agcn_gemm_precision(), s, x_absmax, dry);
+  // (the 1x1 forward is store-bound and stays on the exact kernel)
+  if (agcn_gemm_precision() != 0 && agcn_bf16_tconv_supported(AGCN_TCONV_FWD, taps, stride, pad))
+    return agcn_bf16_tconv_fwd(x, w, bias, y, stats_part, workspace, workspace_bytes, N, Cin, Cout, T, V, taps, stride, pad,
+                               agcn_gemm_precision(), s, nullptr, 0, x_absmax, nullptr, dry);
   Problem p = {};
   p.dry = dry;
+  p.w = w; p.ws = workspace; p.ws_bytes = workspace_bytes;
   ConvGemmArgs& a = p.a;
   a.in = x; a.bias = bias; a.out = y; a.stats = stats_part;
-  a.N = N; a.M = Cout; a.Kinner = Cin; a.in_rows = Cin; a.V = V;
-  a.T_src = T; a.T_out = tconv_out_frames(T, taps, stride, pad); a.T_full = a.T_out;
-  a.src_stride = stride; a.f_off = -pad; a.out_fs = 1; a.out_fo = 0;
-  p.w = w; p.sa_m = (long)Cin * taps; p.sa_i = 0; p.sa_c = taps; p.tap_flip_from = -1;
-  p.ws = workspace; p.ws_bytes = workspace_bytes;
-  return tconv_f32_dispatch(taps, p, s);
+  a.N = N; a.V = V;
+  const TconvPlan plan = tconv_plan_fwd(T, taps, stride, pad);
+  tconv_fill(p, plan, plan.pass[0], Cin, Cout);
+  const bool legacy = agcn_tconv_legacy(taps, stride, pad);
+  return dispatch_taps(taps, [&](auto K) { return tconv_f32_launch<decltype(K)::value>(p, legacy, false, s); });
 }
 
-// 9 taps / pad 4 / stride 1-2 and stride-1 3/5/7 taps run on the split-bf16 / f16x3 kernels, everything else (and
-// AGCN_GEMM=f32) on the exact-f32 kernel; one epilogue (epilogue.h)
+// y = act( bias + tconv(x * gate) [+ res] ): the same ladder with one epilogue (epilogue.h); a window too long for the
+// split kernels' LDS is refused there before anything is launched and runs on the exact kernel
 int tconv_infer_route(const float* x, const float* w, const float* bias, const float* a_s, const float* a_t,
                       const float* a_c, const float* res, int relu, float* y, void* workspace, size_t workspace_bytes,
                       int N, int Cin, int Cout, int T, int V, int taps, int stride, int pad, const float* x_absmax,
                       hipStream_t s, AgcnDryRun* dry) {
   if (!agcn_tconv_domain(T, taps, stride, pad)) return AGCN_ERR_UNSUPPORTED;
   GateArgs gate = {a_s, a_t, a_c};
-  if (agcn_gemm_precision() != 0 && agcn_bf16_tconv_infer_supported(taps, stride, pad)) {
-    const int rc = agcn_bf16_tconv_infer(x, w, bias, y, workspace, workspace_bytes, N, Cin, Cout, T, V, taps, stride, pad,
-                                         agcn_gemm_precision(), s, res, relu, x_absmax, &gate, dry);
-    // (a window too long for their LDS is refused before anything is launched there: the exact kernel below)
+  if (agcn_gemm_precision() != 0 && agcn_bf16_tconv_supported(AGCN_TCONV_FWD, taps, stride, pad)) {
+    const int rc = agcn_bf16_tconv_fwd(x, w, bias, y, nullptr, workspace, workspace_bytes, N, Cin, Cout, T, V, taps, stride,
+                                       pad, agcn_gemm_precision(), s, res, relu, x_absmax, &gate, dry);
     if (rc != AGCN_ERR_UNSUPPORTED) return rc;
   }
   Problem p = {};
   p.dry = dry;
+  p.w = w; p.ws = workspace; p.ws_bytes = workspace_bytes;
   ConvGemmArgs& a = p.a;
   a.in = x; a.bias = bias; a.out = y; a.add1 = res;
   p.gate = gate; p.gated = (a_s || a_t || a_c) ? 1 : 0; p.relu = relu;
-  a.N = N; a.M = Cout; a.Kinner = Cin; a.in_rows = Cin; a.V = V;
-  a.T_src = T; a.T_out = tconv_out_frames(T, taps, stride, pad); a.T_full = a.T_out;
-  a.src_stride = stride; a.f_off = -pad; a.out_fs = 1; a.out_fo = 0;
-  p.w = w; p.sa_m = (long)Cin * taps; p.sa_i = 0; p.sa_c = taps; p.tap_flip_from = -1;
-  p.ws = workspace; p.ws_bytes = workspace_bytes;
-  return tconv_f32_infer_dispatch(taps, p, s);
+  a.N = N; a.V = V;
+  const TconvPlan plan = tconv_plan_fwd(T, taps, stride, pad);
+  tconv_fill(p, plan, plan.pass[0], Cin, Cout);
+  return dispatch_taps(taps, [&](auto K) { return tconv_f32_infer_launch<decltype(K)::value>(p, s); });
 }
 
-// dx[n][c][t,v] (+)= sum_{o,k: (t + pad - k) = stride*tau} w[o][c][k] dy[n][o][tau, v]  (+ masked addends); frames no
-// window reaches get 0 (+ addends)
+// dx[n][c][t,v] (+)= sum_{o,k: (t + pad - k) = stride*tau} w[o][c][k] dy[n][o][tau, v]  (+ masked addends): one stride-1
+// pass per output-frame residue (tconv_plan_bwd_data); frames no window reaches get 0 (+ addends)
 int tconv_bwd_data_route(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
                          const float* mask1, const float* add2, const float* mask2, void* workspace,
                          size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride, int pad,
                          const float* dy_absmax, hipStream_t s, AgcnDryRun* dry) {
   if (!agcn_tconv_domain(T, taps, stride, pad)) return AGCN_ERR_UNSUPPORTED;
-  if (agcn_tconv_legacy(taps, stride, pad))
-    return conv_bwd_data_route(dy, w, dx, accumulate, add1, mask1, add2, mask2, workspace, workspace_bytes, N, Cin, Cout,
-                               T, V, taps, stride, dy_absmax, s, dry);
-  if (tconv_fast(taps, stride))
+  // the 1x1 is measured 10-17% faster on the split-bf16 kernel at these widths, in the chained modes
+  if (agcn_gemm_precision() != 0 && agcn_bf16_tconv_supported(AGCN_TCONV_BWD_DATA, taps, stride, pad) &&
+      (taps > 1 || (agcn_chained() && Cin >= 64 && Cout >= 32)))
     return agcn_bf16_tconv_bwd_data(dy, w, dx, accumulate, add1, mask1, add2, mask2, workspace, workspace_bytes, N, Cin,
-                                    Cout, T, V, taps, pad, agcn_gemm_precision(), s, dy_absmax, dry);
-  // output frames t = stride*tau + r of one residue r form a stride-1 problem over tau: only the taps
-  // k = k0 + stride*i (k0 = (r + pad) mod stride) reach them,  dx[stride*tau + r] = sum_j W[k0 + stride*(J-1-j)]
-  // dy[tau + (r + pad - k0)/stride - (J-1) + j],  J = number of such taps (0: the residue receives no signal)
+                                    Cout, T, V, taps, stride, pad, agcn_gemm_precision(), s, dy_absmax, dry);
   Problem p = {};
   p.dry = dry;
+  p.w = w; p.ws = workspace; p.ws_bytes = workspace_bytes;
   ConvGemmArgs& a = p.a;
   a.in = dy; a.out = dx; a.accumulate = accumulate;
   a.add1 = add1; a.mask1 = mask1; a.add2 = add2; a.mask2 = mask2;
-  a.N = N; a.M = Cin; a.in_rows = Cout; a.V = V;
-  a.T_src = tconv_out_frames(T, taps, stride, pad); a.T_full = T; a.src_stride = 1; a.out_fs = stride;
-  p.w = w; p.sa_m = taps; p.sa_i = 0; p.sa_c = (long)Cin * taps;
-  p.ws = workspace; p.ws_bytes = workspace_bytes;
-  for (int r = 0; r < stride && r < T; ++r) {
-    const int k0 = (r + pad) % stride;
-    const int J = k0 < taps ? (taps - k0 + stride - 1) / stride : 0;
-    a.T_out = (T - r + stride - 1) / stride;
-    a.out_fo = r;
-    a.Kinner = J > 0 ? Cout : 0;          // no K chunks: the epilogue writes 0 (+accumulate/addends)
-    a.f_off = J > 0 ? (r + pad - k0) / stride - (J - 1) : 0;
-    p.tap_mul = stride; p.tap_add = 0; p.tap_flip_from = k0 + stride * (J > 0 ? J - 1 : 0);
-    const int rc = tconv_f32_dispatch(J > 0 ? J : 1, p, s);
+  a.N = N; a.V = V;
+  const TconvPlan plan = tconv_plan_bwd_data(T, taps, stride, pad);
+  const bool legacy = agcn_tconv_legacy(taps, stride, pad);
+  for (int i = 0; i < plan.npasses; ++i) {
+    tconv_fill(p, plan, plan.pass[i], Cin, Cout);
+    const int rc = dispatch_taps(plan.pass[i].taps,
+                                 [&](auto K) { return tconv_f32_launch<decltype(K)::value>(p, legacy, true, s); });
     if (rc) return rc;
   }
-  return 0;
+  return AGCN_OK;
 }
 
 }  // namespace
@@ -1057,8 +944,9 @@ int agcn_conv_fwd_ex(const float* x, const float* w, const float* bias, float* y
                      size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride,
                      const float* x_absmax, void* stream) {
   if (!x || !w || !y || !workspace || !agcn_sizes_ok(N, Cin, Cout, T, V)) return AGCN_ERR_ARG;
-  return conv_fwd_route(x, w, bias, y, stats_part, workspace, workspace_bytes, N, Cin, Cout, T, V, taps, stride, x_absmax,
-                        (hipStream_t)stream, nullptr);
+  if (!agcn_tconv_legacy(taps, stride, (taps - 1) / 2)) return AGCN_ERR_UNSUPPORTED;
+  return tconv_fwd_route(x, w, bias, y, stats_part, workspace, workspace_bytes, N, Cin, Cout, T, V, taps, stride,
+                         (taps - 1) / 2, x_absmax, (hipStream_t)stream, nullptr);
 }
 
 int agcn_conv_bwd_data_ex(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
@@ -1079,8 +967,9 @@ int agcn_conv_bwd_data_ex(const float* dy, const float* w, float* dx, int accumu
                           size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride,
                           const float* dy_absmax, void* stream) {
   if (!dy || !w || !dx || !workspace || !agcn_sizes_ok(N, Cin, Cout, T, V)) return AGCN_ERR_ARG;
-  return conv_bwd_data_route(dy, w, dx, accumulate, add1, mask1, add2, mask2, workspace, workspace_bytes, N, Cin, Cout, T,
-                             V, taps, stride, dy_absmax, (hipStream_t)stream, nullptr);
+  if (!agcn_tconv_legacy(taps, stride, (taps - 1) / 2)) return AGCN_ERR_UNSUPPORTED;
+  return tconv_bwd_data_route(dy, w, dx, accumulate, add1, mask1, add2, mask2, workspace, workspace_bytes, N, Cin, Cout, T,
+                              V, taps, stride, (taps - 1) / 2, dy_absmax, (hipStream_t)stream, nullptr);
 }
 
 int agcn_gcn_aggregate_project_fwd_ex(const float* x, const float* adj, const float* wcat, const float* bias, float* y,
@@ -1131,8 +1020,8 @@ int agcn_conv9_infer(const float* x, const float* w, const float* bias, const fl
   if (!x || !w || !y || !workspace || !agcn_sizes_ok(N, Cin, Cout, T, V)) return AGCN_ERR_ARG;
   if (stride != 1 && stride != 2) return AGCN_ERR_UNSUPPORTED;
   if (agcn_gemm_precision() == 0) return AGCN_ERR_UNSUPPORTED;
-  return agcn_bf16_conv9_fwd(x, w, bias, y, nullptr, workspace, workspace_bytes, N, Cin, Cout, T, V, stride,
-                             agcn_gemm_precision(), (hipStream_t)stream, res, relu);
+  return agcn_bf16_tconv_fwd(x, w, bias, y, nullptr, workspace, workspace_bytes, N, Cin, Cout, T, V, 9, stride, 4,
+                             agcn_gemm_precision(), (hipStream_t)stream, res, relu, nullptr, nullptr, nullptr);
 }
 
 int agcn_gcn_bwd_data_fused_supported(int C, int Cout, int V);

@@ -896,199 +896,81 @@ int bf16_fwd_f16x3(int npl) {   // AGCN_CONV_F16X3=0 keeps the temporal convolut
   return f16x3 && npl == 3;
 }
 
-// y = bias + conv_TAPS(x; stride, pad) [+ add] (reference agcn.py:40-41,49; aagcn.py:194-201)
-template <int TAPS, int WQ, bool GATE = false>
-int bf16_tconv_fwd(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* ws,
-                   size_t ws_bytes, int N, int Cin, int Cout, int T, int V, int stride, int pad, int npl, hipStream_t s,
-                   const float* add, int relu, const float* x_absmax, AgcnDryRun* dry, const GateArgs* gate = nullptr) {
-  BfProblem p = {};
-  BfArgs& a = p.a;
-  p.dry = dry;
-  a.in = x; a.bias = bias; a.out = y; a.stats = stats_part; a.add1 = add; a.relu = relu;
-  if (GATE) p.gate = *gate;
+// the forward on its <TAPS, WQ> ladder, ungated or gated
+template <int TAPS, int WQ>
+int bf16_fwd_launch(BfProblem& p, bool gated, int npl, const float* x_absmax, hipStream_t s) {
+  const BfArgs& a = p.a;
+  // the narrowest tile these kernels fall back to must hold the window (launch_bf's own checks): decided here, before
+  // the f16x3 maximum is taken, so that a shape handed on to the exact kernel has launched nothing
+  const BfGeom g = bf_geometry<TAPS, 64>(a.V, a.T_out, a.src_stride, a.M, a.Kinner);
+  if (g.smem_bytes + (gated ? gate_bytes(g) : 0) > 160 * 1024 || (g.FW * a.V + 3) / 4 > WQ * 64) return AGCN_ERR_UNSUPPORTED;
   p.fwd_f16 = bf16_fwd_f16x3(npl);
-  p.ws = ws; p.ws_bytes = ws_bytes;
   if (p.fwd_f16)
-    if (int rc = bf16_in_absmax(p, x_absmax, x, (long)N * Cin * T * V, s)) return rc;
-  a.N = N; a.M = Cout; a.Kinner = Cin; a.in_rows = Cin; a.V = V;
-  a.T_src = T; a.T_out = (T + 2 * pad - TAPS) / stride + 1; a.T_full = a.T_out;
-  a.src_stride = stride; a.f_off = -pad; a.out_fs = 1; a.out_fo = 0;
-  p.w = w; p.sa_m = (long)Cin * TAPS; p.sa_c = TAPS; p.tap_flip_from = -1;
-  return launch_npl<TAPS, WQ, GATE>(p, npl, s);
-}
-
-// stride-1 backward-data: dx[t] = sum_j W[TAPS-1-j] dy[t + j - (TAPS-1-pad)]   (+ masked addends)
-template <int TAPS>
-int bf16_tconv_bwd_data_s1(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
-                           const float* mask1, const float* add2, const float* mask2, void* ws, size_t ws_bytes, int N,
-                           int Cin, int Cout, int T, int V, int pad, int npl, hipStream_t s, const float* dy_absmax,
-                           AgcnDryRun* dry) {
-  BfProblem p = {};
-  BfArgs& a = p.a;
-  p.dry = dry;
-  p.fwd_f16 = bf16_fwd_f16x3(npl);     // f16x3 with the gradient normalised by its maximum
-  p.ws = ws; p.ws_bytes = ws_bytes;
-  const int To = T + 2 * pad - TAPS + 1;
-  if (p.fwd_f16)
-    if (int rc = bf16_in_absmax(p, dy_absmax, dy, (long)N * Cout * To * V, s)) return rc;
-  a.in = dy; a.out = dx; a.accumulate = accumulate;
-  a.add1 = add1; a.mask1 = mask1; a.add2 = add2; a.mask2 = mask2;
-  a.N = N; a.M = Cin; a.Kinner = Cout; a.in_rows = Cout; a.V = V;
-  a.T_src = To; a.T_full = T; a.src_stride = 1;
-  a.T_out = T; a.out_fs = 1; a.out_fo = 0; a.f_off = pad - (TAPS - 1);
-  p.w = w; p.sa_m = TAPS; p.sa_c = (long)Cin * TAPS;
-  p.tap_mul = 1; p.tap_add = 0; p.tap_flip_from = TAPS - 1;
-  return launch_npl<TAPS, 2>(p, npl, s);
+    if (int rc = bf16_in_absmax(p, x_absmax, a.in, (long)a.N * a.in_rows * a.T_src * a.V, s)) return rc;
+  return gated ? launch_npl<TAPS, WQ, true>(p, npl, s) : launch_npl<TAPS, WQ>(p, npl, s);
 }
 
 }  // namespace
 
-int agcn_bf16_conv9_fwd(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* ws,
-                        size_t ws_bytes, int N, int Cin, int Cout, int T, int V, int stride, int npl,
-                        hipStream_t s, const float* add, int relu, const float* x_absmax, AgcnDryRun* dry) {
-  if (stride == 1)
-    return bf16_tconv_fwd<9, 2>(x, w, bias, y, stats_part, ws, ws_bytes, N, Cin, Cout, T, V, 1, 4, npl, s, add, relu,
-                                x_absmax, dry);
-  return bf16_tconv_fwd<9, 3>(x, w, bias, y, stats_part, ws, ws_bytes, N, Cin, Cout, T, V, stride, 4, npl, s, add, relu,
-                              x_absmax, dry);
+bool agcn_bf16_tconv_supported(AgcnTconvOp op, int taps, int stride, int pad) {
+  if (taps == 9) return pad == 4 && (stride == 1 || stride == 2);
+  if (taps == 1) return op == AGCN_TCONV_BWD_DATA && stride == 1;   // (the store-bound 1x1 forward gains nothing here)
+  return stride == 1 && (taps == 3 || taps == 5 || taps == 7);
 }
 
-int agcn_bf16_conv9_bwd_data(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
-                             const float* mask1, const float* add2, const float* mask2, void* ws, size_t ws_bytes,
-                             int N, int Cin, int Cout, int T, int V, int stride, int npl, hipStream_t s,
-                             const float* dy_absmax, AgcnDryRun* dry) {
-  if (stride == 1)
-    return bf16_tconv_bwd_data_s1<9>(dy, w, dx, accumulate, add1, mask1, add2, mask2, ws, ws_bytes, N, Cin, Cout, T, V,
-                                     4, npl, s, dy_absmax, dry);
+// y = act( bias + conv(x * gate; stride, pad) [+ add] ) (reference agcn.py:40-41,49; aagcn.py:194-201).  gate null (or
+// all three factors null): the ungated kernels.  WQ = 3 (windows up to 768 rows) for the stride-2 forward.
+int agcn_bf16_tconv_fwd(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* ws,
+                        size_t ws_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride, int pad, int npl,
+                        hipStream_t s, const float* add, int relu, const float* x_absmax, const GateArgs* gate,
+                        AgcnDryRun* dry) {
+  if (!agcn_bf16_tconv_supported(AGCN_TCONV_FWD, taps, stride, pad)) return AGCN_ERR_UNSUPPORTED;
   BfProblem p = {};
   BfArgs& a = p.a;
   p.dry = dry;
-  p.fwd_f16 = bf16_fwd_f16x3(npl);
-  p.ws = ws; p.ws_bytes = ws_bytes;
-  if (p.fwd_f16)
-    if (int rc = bf16_in_absmax(p, dy_absmax, dy, (long)N * Cout * ((T + 8 - 9) / stride + 1) * V, s)) return rc;
-  a.in = dy; a.out = dx; a.accumulate = accumulate;
-  a.add1 = add1; a.mask1 = mask1; a.add2 = add2; a.mask2 = mask2;
-  a.N = N; a.M = Cin; a.Kinner = Cout; a.in_rows = Cout; a.V = V;
-  a.T_src = (T + 8 - 9) / stride + 1; a.T_full = T; a.src_stride = 1;
-  p.w = w; p.sa_m = 9; p.sa_c = (long)Cin * 9;
-  a.T_out = (T + 1) / 2; a.out_fs = 2; a.out_fo = 0; a.f_off = -2;
-  p.tap_mul = 2; p.tap_add = 0; p.tap_flip_from = 8;
-  int rc = launch_npl<5, 2>(p, npl, s);
-  if (rc) return rc;
-  a.T_out = T / 2; a.out_fo = 1; a.f_off = -1;
-  p.tap_add = 1;
-  if (a.T_out > 0) rc = launch_npl<4, 2>(p, npl, s);
-  return rc;
+  p.w = w; p.ws = ws; p.ws_bytes = ws_bytes;
+  a.in = x; a.bias = bias; a.out = y; a.stats = stats_part; a.add1 = add; a.relu = relu;
+  a.N = N; a.V = V;
+  const TconvPlan plan = tconv_plan_fwd(T, taps, stride, pad);
+  tconv_fill(p, plan, plan.pass[0], Cin, Cout);
+  const bool gated = gate && (gate->gs || gate->gt || gate->gc);
+  if (gated) p.gate = *gate;
+  return dispatch_taps(taps, [&](auto K) -> int {
+    constexpr int TAPS = decltype(K)::value;
+    if constexpr (TAPS == 9) {
+      if (stride == 2) return bf16_fwd_launch<9, 3>(p, gated, npl, x_absmax, s);
+    }
+    if constexpr (TAPS == 3 || TAPS == 5 || TAPS == 7 || TAPS == 9) return bf16_fwd_launch<TAPS, 2>(p, gated, npl, x_absmax, s);
+    return AGCN_ERR_UNSUPPORTED;
+  });
 }
 
-// stride-1 temporal convolutions with 3, 5 or 7 taps and any padding on the same kernels (conv_pc_kernel where the
-// 9-tap layer takes it); AGCN_ERR_UNSUPPORTED for other shapes (the caller runs the exact-f32 kernel then)
-bool agcn_bf16_tconv_supported(int taps, int stride) { return stride == 1 && (taps == 3 || taps == 5 || taps == 7); }
-
-int agcn_bf16_tconv_fwd(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* ws,
-                        size_t ws_bytes, int N, int Cin, int Cout, int T, int V, int taps, int pad, int npl,
-                        hipStream_t s, const float* x_absmax, AgcnDryRun* dry) {
-  switch (taps) {
-    case 3: return bf16_tconv_fwd<3, 2>(x, w, bias, y, stats_part, ws, ws_bytes, N, Cin, Cout, T, V, 1, pad, npl, s,
-                                        nullptr, 0, x_absmax, dry);
-    case 5: return bf16_tconv_fwd<5, 2>(x, w, bias, y, stats_part, ws, ws_bytes, N, Cin, Cout, T, V, 1, pad, npl, s,
-                                        nullptr, 0, x_absmax, dry);
-    case 7: return bf16_tconv_fwd<7, 2>(x, w, bias, y, stats_part, ws, ws_bytes, N, Cin, Cout, T, V, 1, pad, npl, s,
-                                        nullptr, 0, x_absmax, dry);
-    default: return AGCN_ERR_UNSUPPORTED;
-  }
-}
-
+// dx (+)= the passes of tconv_plan_bwd_data (+ masked addends): one stride-1 problem, or the 5- and 4-tap halves of the
+// stride-2 9-tap layer.  f16x3 with the gradient normalised by its maximum, for convolutions of 3 taps and more.
 int agcn_bf16_tconv_bwd_data(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
                              const float* mask1, const float* add2, const float* mask2, void* ws, size_t ws_bytes,
-                             int N, int Cin, int Cout, int T, int V, int taps, int pad, int npl, hipStream_t s,
-                             const float* dy_absmax, AgcnDryRun* dry) {
-  switch (taps) {
-    case 3: return bf16_tconv_bwd_data_s1<3>(dy, w, dx, accumulate, add1, mask1, add2, mask2, ws, ws_bytes, N, Cin, Cout,
-                                             T, V, pad, npl, s, dy_absmax, dry);
-    case 5: return bf16_tconv_bwd_data_s1<5>(dy, w, dx, accumulate, add1, mask1, add2, mask2, ws, ws_bytes, N, Cin, Cout,
-                                             T, V, pad, npl, s, dy_absmax, dry);
-    case 7: return bf16_tconv_bwd_data_s1<7>(dy, w, dx, accumulate, add1, mask1, add2, mask2, ws, ws_bytes, N, Cin, Cout,
-                                             T, V, pad, npl, s, dy_absmax, dry);
-    default: return AGCN_ERR_UNSUPPORTED;
-  }
-}
-
-// BN-folded inference form of the same forward kernels (agcn_tconv_infer): y = act(bias + conv(x * gate) [+ add]) for
-// the shapes they are tuned for -- 9 taps with padding 4 at stride 1 or 2, and stride-1 3/5/7 taps with any padding.
-// gate null (or all three factors null): the ungated kernels (the very instantiations agcn_conv9_infer launches).
-template <int TAPS, int WQ>
-static int bf16_tconv_infer_t(const float* x, const float* w, const float* bias, float* y, void* ws, size_t ws_bytes, int N,
-                              int Cin, int Cout, int T, int V, int stride, int pad, int npl, hipStream_t s,
-                              const float* add, int relu, const float* x_absmax, const GateArgs* gate, AgcnDryRun* dry) {
-  // the narrowest tile these kernels fall back to must hold the window (launch_bf's own checks): decided here, before
-  // the f16x3 maximum is taken, so that a shape handed on to the exact kernel has launched nothing
-  const bool gated = gate && (gate->gs || gate->gt || gate->gc);
-  {
-    const int To = (T + 2 * pad - TAPS) / stride + 1;
-    const BfGeom g = bf_geometry<TAPS, 64>(V, To, stride, Cout, Cin);
-    if (g.smem_bytes + (gated ? gate_bytes(g) : 0) > 160 * 1024 || (g.FW * V + 3) / 4 > WQ * 64) return AGCN_ERR_UNSUPPORTED;
-  }
-  if (gated)
-    return bf16_tconv_fwd<TAPS, WQ, true>(x, w, bias, y, nullptr, ws, ws_bytes, N, Cin, Cout, T, V, stride, pad, npl, s, add,
-                                          relu, x_absmax, dry, gate);
-  return bf16_tconv_fwd<TAPS, WQ>(x, w, bias, y, nullptr, ws, ws_bytes, N, Cin, Cout, T, V, stride, pad, npl, s, add, relu,
-                                  x_absmax, dry);
-}
-
-bool agcn_bf16_tconv_infer_supported(int taps, int stride, int pad) {
-  if (taps == 9) return pad == 4 && (stride == 1 || stride == 2);
-  return agcn_bf16_tconv_supported(taps, stride);
-}
-
-int agcn_bf16_tconv_infer(const float* x, const float* w, const float* bias, float* y, void* ws, size_t ws_bytes, int N,
-                          int Cin, int Cout, int T, int V, int taps, int stride, int pad, int npl, hipStream_t s,
-                          const float* add, int relu, const float* x_absmax, const GateArgs* gate, AgcnDryRun* dry) {
-  if (!agcn_bf16_tconv_infer_supported(taps, stride, pad)) return AGCN_ERR_UNSUPPORTED;
-#define AGCN_INFER_CASE(TAPS, WQ) \
-  return bf16_tconv_infer_t<TAPS, WQ>(x, w, bias, y, ws, ws_bytes, N, Cin, Cout, T, V, stride, pad, npl, s, add, relu, x_absmax, gate, dry)
-  switch (taps) {
-    case 3: AGCN_INFER_CASE(3, 2);
-    case 5: AGCN_INFER_CASE(5, 2);
-    case 7: AGCN_INFER_CASE(7, 2);
-    default: break;
-  }
-  if (stride == 1) AGCN_INFER_CASE(9, 2);
-  AGCN_INFER_CASE(9, 3);
-#undef AGCN_INFER_CASE
-}
-
-// 1x1 convolutions (conv_a/conv_b/down/residual; reference agcn.py:66-75,122-125) on the same kernel, TAPS = 1
-int agcn_bf16_conv1_fwd(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* ws,
-                        size_t ws_bytes, int N, int Cin, int Cout, int T, int V, int stride, int npl,
-                        hipStream_t s, const float* add, int relu, AgcnDryRun* dry) {
+                             int N, int Cin, int Cout, int T, int V, int taps, int stride, int pad, int npl,
+                             hipStream_t s, const float* dy_absmax, AgcnDryRun* dry) {
+  if (!agcn_bf16_tconv_supported(AGCN_TCONV_BWD_DATA, taps, stride, pad)) return AGCN_ERR_UNSUPPORTED;
   BfProblem p = {};
   BfArgs& a = p.a;
   p.dry = dry;
-  a.in = x; a.bias = bias; a.out = y; a.stats = stats_part; a.add1 = add; a.relu = relu;
-  a.N = N; a.M = Cout; a.Kinner = Cin; a.in_rows = Cin; a.V = V;
-  a.T_src = T; a.T_out = (T - 1) / stride + 1; a.T_full = a.T_out;
-  a.src_stride = stride; a.f_off = 0; a.out_fs = 1; a.out_fo = 0;
-  p.w = w; p.sa_m = Cin; p.sa_c = 1; p.tap_flip_from = -1;
-  p.ws = ws; p.ws_bytes = ws_bytes;
-  if (stride == 1) return launch_npl<1, 2>(p, npl, s);
-  return launch_npl<1, 3>(p, npl, s);
-}
-
-// stride 1 only (the stride-2 1x1 backward is a scatter to even frames: conv_gemm.hip keeps it)
-int agcn_bf16_conv1_bwd_data(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
-                             const float* mask1, const float* add2, const float* mask2, void* ws, size_t ws_bytes,
-                             int N, int Cin, int Cout, int T, int V, int npl, hipStream_t s, AgcnDryRun* dry) {
-  BfProblem p = {};
-  BfArgs& a = p.a;
-  p.dry = dry;
+  p.w = w; p.ws = ws; p.ws_bytes = ws_bytes;
   a.in = dy; a.out = dx; a.accumulate = accumulate;
   a.add1 = add1; a.mask1 = mask1; a.add2 = add2; a.mask2 = mask2;
-  a.N = N; a.M = Cin; a.Kinner = Cout; a.in_rows = Cout; a.V = V;
-  a.T_src = T; a.T_full = T; a.src_stride = 1;
-  a.T_out = T; a.out_fs = 1; a.out_fo = 0; a.f_off = 0;
-  p.w = w; p.sa_m = 1; p.sa_c = Cin; p.tap_mul = 1; p.tap_add = 0; p.tap_flip_from = 0;
-  p.ws = ws; p.ws_bytes = ws_bytes;
-  return launch_npl<1, 2>(p, npl, s);
+  a.N = N; a.V = V;
+  const TconvPlan plan = tconv_plan_bwd_data(T, taps, stride, pad);
+  p.fwd_f16 = taps >= 3 && bf16_fwd_f16x3(npl);
+  if (p.fwd_f16)
+    if (int rc = bf16_in_absmax(p, dy_absmax, dy, (long)N * Cout * plan.T_src * V, s)) return rc;
+  for (int i = 0; i < plan.npasses; ++i) {
+    tconv_fill(p, plan, plan.pass[i], Cin, Cout);
+    const int rc = dispatch_taps(plan.pass[i].taps, [&](auto K) -> int {
+      constexpr int TAPS = decltype(K)::value;
+      if constexpr (TAPS == 1 || TAPS == 3 || TAPS == 4 || TAPS == 5 || TAPS == 7 || TAPS == 9) return launch_npl<TAPS, 2>(p, npl, s);
+      return AGCN_ERR_UNSUPPORTED;
+    });
+    if (rc) return rc;
+  }
+  return AGCN_OK;
 }

@@ -393,33 +393,33 @@ inline int tconv_w_tt(int V, int T_out, int taps, int stride) {
   return tt < 1 ? 1 : tt;
 }
 
-// the 8 waves split the taps (TAPS >= 2) or the positions (1 tap) in two, as the 9- and 1-tap gradients do
+// One exact-f32 rung: the 8 waves split the taps (TAPS >= 2) or the positions (1 tap) in two.  The legacy shapes (1 or 9
+// taps, "same" padding, stride 1 or 2) keep the window bounds they were tuned with and the full tile; every other shape
+// takes WBXT and as many frames per tile as its window allows.
 template <int TAPS>
-int tconv_wgrad(WgradArgs a, float* dw, void* ws, size_t ws_bytes, hipStream_t s, AgcnDryRun* dry) {
-  const int cap = tconv_w_tt(a.V, a.T_out, TAPS, a.stride);
+int tconv_wgrad(WgradArgs a, bool legacy, float* dw, void* ws, size_t ws_bytes, hipStream_t s, AgcnDryRun* dry) {
   if (!dry) AGCN_NOTE_KERNEL("conv_wgrad_kernel<%d, 0>", TAPS);
-  if (TAPS == 1) {
+  if (legacy) {
+    if constexpr (TAPS == 9) {
+      if (a.stride == 1) {
+        if (a.M % 128 == 0) return launch_wgrad<9, 0, 4, 1, 2, false, 6>(a, dw, ws, ws_bytes, s, dry);
+        return launch_wgrad<9, 0, 2, 2, 2, false, 6>(a, dw, ws, ws_bytes, s, dry);
+      }
+      if (a.M % 128 == 0) return launch_wgrad<9, 0, 4, 1, 2, false, 7>(a, dw, ws, ws_bytes, s, dry);
+      return launch_wgrad<9, 0, 2, 2, 2, false, 7>(a, dw, ws, ws_bytes, s, dry);
+    }
+    if constexpr (TAPS == 1) {
+      if (a.M % 128 == 0) return launch_wgrad<1, 0, 4, 2, 1, false, 4>(a, dw, ws, ws_bytes, s, dry);
+      return launch_wgrad<1, 0, 2, 2, 2, true, 4>(a, dw, ws, ws_bytes, s, dry);
+    }
+  }
+  const int cap = tconv_w_tt(a.V, a.T_out, TAPS, a.stride);
+  if constexpr (TAPS == 1) {
     if (a.M % 128 == 0) return launch_wgrad<1, 0, 4, 2, 1, false, WBXT>(a, dw, ws, ws_bytes, s, dry, cap);
     return launch_wgrad<1, 0, 2, 2, 2, true, WBXT>(a, dw, ws, ws_bytes, s, dry, cap);
   }
   if (a.M % 128 == 0) return launch_wgrad<TAPS, 0, 4, 1, 2, false, WBXT>(a, dw, ws, ws_bytes, s, dry, cap);
   return launch_wgrad<TAPS, 0, 2, 2, 2, false, WBXT>(a, dw, ws, ws_bytes, s, dry, cap);
-}
-
-int tconv_wgrad_dispatch(int taps, const WgradArgs& a, float* dw, void* ws, size_t ws_bytes, hipStream_t s,
-                         AgcnDryRun* dry) {
-  switch (taps) {
-    case 1: return tconv_wgrad<1>(a, dw, ws, ws_bytes, s, dry);
-    case 2: return tconv_wgrad<2>(a, dw, ws, ws_bytes, s, dry);
-    case 3: return tconv_wgrad<3>(a, dw, ws, ws_bytes, s, dry);
-    case 4: return tconv_wgrad<4>(a, dw, ws, ws_bytes, s, dry);
-    case 5: return tconv_wgrad<5>(a, dw, ws, ws_bytes, s, dry);
-    case 6: return tconv_wgrad<6>(a, dw, ws, ws_bytes, s, dry);
-    case 7: return tconv_wgrad<7>(a, dw, ws, ws_bytes, s, dry);
-    case 8: return tconv_wgrad<8>(a, dw, ws, ws_bytes, s, dry);
-    case 9: return tconv_wgrad<9>(a, dw, ws, ws_bytes, s, dry);
-    default: return AGCN_ERR_UNSUPPORTED;
-  }
 }
 
 inline bool chain_wgrad_enabled() {
@@ -435,37 +435,6 @@ inline bool chain_wgrad_enabled() {
 // null tensors (or placeholders, agcn_dry_present) and a dry-run record (agcn_common.h).  The f16x3 tap kernels of wgrad9_bf16.hip size themselves by the
 // geometry function they launch with. ----
 
-// dw[o][c][k] = sum_{n,t,v} dy[n][o][t,v] * x[n][c][(t*stride + k - pad), v]
-int conv_wgrad_route(const float* dy, const float* x, float* dw, void* workspace, size_t workspace_bytes, int N, int Cin,
-                     int Cout, int T, int V, int taps, int stride, const float* dy_absmax, const float* x_absmax,
-                     hipStream_t s, AgcnDryRun* dry) {
-  if ((taps != 1 && taps != 9) || (stride != 1 && stride != 2)) return AGCN_ERR_UNSUPPORTED;
-  const int pad = (taps - 1) / 2;
-  WgradArgs a = {};
-  a.dy = dy; a.in = x; a.N = N; a.M = Cout; a.C = Cin; a.V = V; a.T_src = T;
-  a.T_out = (T + 2 * pad - taps) / stride + 1; a.stride = stride; a.pad = pad;
-  a.so_m = (long)Cin * taps; a.so_t = 1; a.so_c = taps; a.wsize = (long)Cout * Cin * taps;
-  if (taps == 9) {
-    if (wgrad9_bf16_enabled() && agcn_wgrad9_bf16_supported(Cout, Cin, V, stride)) {
-      if (dry) return agcn_dry_note(dry, 0, agcn_wgrad9_bf16_workspace(N, Cout, Cin, V, T, stride));
-      int nslabs = 0;
-      int rc = agcn_wgrad9_bf16(dy, x, workspace, workspace_bytes, &nslabs, N, Cout, Cin, V, T, stride, s, dy_absmax, x_absmax);
-      if (rc) return rc;
-      return launch_reduce((const float*)workspace, dw, a.wsize, nslabs, a.M, a.C, a.so_m, a.so_t, a.so_c, s);
-    }
-    if (stride == 1) {
-      if (Cout % 128 == 0) return launch_wgrad<9, 0, 4, 1, 2, false, 6>(a, dw, workspace, workspace_bytes, s, dry);
-      return launch_wgrad<9, 0, 2, 2, 2, false, 6>(a, dw, workspace, workspace_bytes, s, dry);
-    }
-    if (Cout % 128 == 0) return launch_wgrad<9, 0, 4, 1, 2, false, 7>(a, dw, workspace, workspace_bytes, s, dry);
-    return launch_wgrad<9, 0, 2, 2, 2, false, 7>(a, dw, workspace, workspace_bytes, s, dry);
-  }
-  if (chain_wgrad_enabled() && agcn_wgrad_chain_supported(Cout, Cin, V))
-    return chain_wgrad_and_reduce(0, a, dw, workspace, workspace_bytes, s, dy_absmax, x_absmax, dry);
-  if (Cout % 128 == 0) return launch_wgrad<1, 0, 4, 2, 1, false, 4>(a, dw, workspace, workspace_bytes, s, dry);
-  return launch_wgrad<1, 0, 2, 2, 2, true, 4>(a, dw, workspace, workspace_bytes, s, dry);
-}
-
 // dwcat[o][i*C+c] = sum_{n,t,v} dy[n][o][t,v] * sum_u x[n][c][t,u] adj[n][i][u][v]
 int gcn_wgrad_route(const float* dy, const float* x, const float* adj, float* dwcat, void* workspace,
                     size_t workspace_bytes, int N, int C, int Cout, int T, int V, const float* dy_absmax,
@@ -479,27 +448,36 @@ int gcn_wgrad_route(const float* dy, const float* x, const float* adj, float* dw
   return launch_wgrad<1, 1, 2, 2, 2, true, 2>(a, dwcat, workspace, workspace_bytes, s, dry);
 }
 
-// dw[o][c][k] = sum_{n,t,v} dy[n][o][t,v] * x[n][c][t*stride + k - pad, v]   (fixed-order slab reduction)
+// dw[o][c][k] = sum_{n,t,v} dy[n][o][t,v] * x[n][c][t*stride + k - pad, v]   (fixed-order slab reduction).  The split
+// kernels where enabled and supported -- the f16x3 tap kernel (legacy 9 taps; stride-1 3/5/7 taps) or the tap-free chain
+// kernel (legacy 1 tap) -- else the exact-f32 rung of tconv_wgrad.
 int tconv_wgrad_route(const float* dy, const float* x, float* dw, void* workspace, size_t workspace_bytes, int N, int Cin,
                       int Cout, int T, int V, int taps, int stride, int pad, const float* dy_absmax,
                       const float* x_absmax, hipStream_t s, AgcnDryRun* dry) {
   if (!agcn_tconv_domain(T, taps, stride, pad)) return AGCN_ERR_UNSUPPORTED;
-  if (agcn_tconv_legacy(taps, stride, pad))
-    return conv_wgrad_route(dy, x, dw, workspace, workspace_bytes, N, Cin, Cout, T, V, taps, stride, dy_absmax, x_absmax, s,
-                            dry);
+  const bool legacy = agcn_tconv_legacy(taps, stride, pad);
   WgradArgs a = {};
   a.dy = dy; a.in = x; a.N = N; a.M = Cout; a.C = Cin; a.V = V; a.T_src = T;
-  a.T_out = (T + 2 * pad - taps) / stride + 1; a.stride = stride; a.pad = pad;
+  a.T_out = tconv_out_frames(T, taps, stride, pad); a.stride = stride; a.pad = pad;
   a.so_m = (long)Cin * taps; a.so_t = 1; a.so_c = taps; a.wsize = (long)Cout * Cin * taps;
-  if (agcn_wgrad_tconv_f16_supported(Cout, Cin, V, taps, stride, pad)) {     // stride 1, 3/5/7 taps: f16x3
-    if (dry) return agcn_dry_note(dry, 0, agcn_wgrad_tconv_f16_workspace(N, Cout, Cin, V, T, taps, pad));
+  const bool tap9 = legacy && taps == 9 && wgrad9_bf16_enabled() && agcn_wgrad9_bf16_supported(Cout, Cin, V, stride);
+  if (tap9 || (!legacy && agcn_wgrad_tconv_f16_supported(Cout, Cin, V, taps, stride, pad))) {
+    if (dry)
+      return agcn_dry_note(dry, 0, tap9 ? agcn_wgrad9_bf16_workspace(N, Cout, Cin, V, T, stride)
+                                        : agcn_wgrad_tconv_f16_workspace(N, Cout, Cin, V, T, taps, pad));
     int nslabs = 0;
-    const int rc = agcn_wgrad_tconv_f16(dy, x, workspace, workspace_bytes, &nslabs, N, Cout, Cin, V, T, taps, pad, s,
-                                        dy_absmax, x_absmax);
+    const int rc = tap9 ? agcn_wgrad9_bf16(dy, x, workspace, workspace_bytes, &nslabs, N, Cout, Cin, V, T, stride, s,
+                                           dy_absmax, x_absmax)
+                        : agcn_wgrad_tconv_f16(dy, x, workspace, workspace_bytes, &nslabs, N, Cout, Cin, V, T, taps, pad, s,
+                                               dy_absmax, x_absmax);
     if (rc) return rc;
     return launch_reduce((const float*)workspace, dw, a.wsize, nslabs, a.M, a.C, a.so_m, a.so_t, a.so_c, s);
   }
-  return tconv_wgrad_dispatch(taps, a, dw, workspace, workspace_bytes, s, dry);
+  if (legacy && taps == 1 && chain_wgrad_enabled() && agcn_wgrad_chain_supported(Cout, Cin, V))
+    return chain_wgrad_and_reduce(0, a, dw, workspace, workspace_bytes, s, dy_absmax, x_absmax, dry);
+  return dispatch_taps(taps, [&](auto K) {
+    return tconv_wgrad<decltype(K)::value>(a, legacy, dw, workspace, workspace_bytes, s, dry);
+  });
 }
 
 }  // namespace
@@ -542,8 +520,9 @@ int agcn_conv_bwd_weight_ex(const float* dy, const float* x, float* dw, void* wo
                             int Cin, int Cout, int T, int V, int taps, int stride, const float* dy_absmax,
                             const float* x_absmax, void* stream) {
   if (!dy || !x || !dw || !workspace || !agcn_sizes_ok(N, Cin, Cout, T, V)) return AGCN_ERR_ARG;
-  return conv_wgrad_route(dy, x, dw, workspace, workspace_bytes, N, Cin, Cout, T, V, taps, stride, dy_absmax, x_absmax,
-                          (hipStream_t)stream, nullptr);
+  if (!agcn_tconv_legacy(taps, stride, (taps - 1) / 2)) return AGCN_ERR_UNSUPPORTED;
+  return tconv_wgrad_route(dy, x, dw, workspace, workspace_bytes, N, Cin, Cout, T, V, taps, stride, (taps - 1) / 2, dy_absmax,
+                           x_absmax, (hipStream_t)stream, nullptr);
 }
 
 int agcn_gcn_project_bwd_weight_ex(const float* dy, const float* x, const float* adj, float* dwcat, void* workspace,
