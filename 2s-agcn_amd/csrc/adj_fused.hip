@@ -391,11 +391,8 @@ inline bool af_shape(int Ci, int& tm, int& nsub) {
 
 template <int TM, int NSUB, int MODE, int PD>
 int af_launch(AfArgs a, const AfGeom& g, hipStream_t s) {
-  constexpr auto kern = adj_fused_kernel<TM, NSUB, MODE, PD>;
-  int rc = agcn_allow_big_lds<kern>();
-  if (rc) return rc;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(a.N * g.ntiles * g.nsb)), dim3(NT), g.smem_bytes, s, a);
-  return agcn_check_launch();
+  return agcn_launch_big<adj_fused_kernel<TM, NSUB, MODE, PD>>(dim3((unsigned)(a.N * g.ntiles * g.nsb)), dim3(NT),
+                                                               g.smem_bytes, s, a);
 }
 
 template <int TM, int NSUB>
@@ -426,7 +423,7 @@ int af_run(int mode, AfArgs a, const float* wab, void* ws, size_t ws_bytes, hipS
   if (g.pack_bytes > ws_bytes) return AGCN_ERR_WORKSPACE;
   a.tt = g.tt; a.ntiles = g.ntiles; a.nchunks = g.nchunks; a.nsb = g.nsb;
   a.wp = (const unsigned short*)ws;
-  { const char* e = getenv("AGCN_AF_DBG"); a.dbg = e ? atoi(e) : 0; }
+  a.dbg = agcn_probe(AGCN_AF_DBG, nullptr);
   a.npl = agcn_npl();
   if (tm == 3) return af_go<3, 3>(mode, a, wab, ws, g, s);
   if (tm == 2) return af_go<2, 1>(mode, a, wab, ws, g, s);
@@ -478,14 +475,11 @@ int agcn_adjacency_fused_fwd_ex(const float* x, const float* wab, const float* b
     const size_t img = agcn_adj_ws_workspace(C, Ci);
     if (workspace_bytes < img + 16) return AGCN_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    const float* amax = x_absmax_in;
-    if (!amax) {
-      float* slot = x_absmax_out ? x_absmax_out : reinterpret_cast<float*>(static_cast<char*>(workspace) + img);
-      if (int rc = agcn_launch_absmax(x, (long)N * C * T * V, reinterpret_cast<unsigned*>(slot), s)) return rc;
-      amax = slot;
-    } else if (x_absmax_out && x_absmax_out != x_absmax_in) {
+    const float* amax;         // taken into the caller's slot where there is one, else behind the weight images
+    void* slot = x_absmax_out ? (void*)x_absmax_out : static_cast<char*>(workspace) + img;
+    if (int rc = agcn_operand_max(x_absmax_in, x, (long)N * C * T * V, slot, s, &amax)) return rc;
+    if (x_absmax_in && x_absmax_out && x_absmax_out != x_absmax_in)
       if (hipMemcpyAsync(x_absmax_out, x_absmax_in, 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return AGCN_ERR_ARG;
-    }
     const int tt = 256 / V > T ? T : 256 / V, slots = (T + tt - 1) / tt;
     int nused = 0;
     if (int rc = agcn_adj_ws_scores(x, wab, bab, tp_out, spart, slots, &nused, amax, workspace, img, N, C, Ci, T, V, s))

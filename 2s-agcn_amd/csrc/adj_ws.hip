@@ -265,7 +265,7 @@ inline bool aw_geometry(int N, int C, int Ci, int T, int V, AwGeom& g) {
   if (g.FT > T) g.FT = T;
   const int ntile = (T + g.FT - 1) / g.FT;
   long want = (256 + N - 1) / N;
-  if (const char* e = getenv("AGCN_AW_SPLIT")) want = atoi(e);     // test knob (read per call)
+  if (const int k = agcn_knob_now(AGCN_AW_SPLIT); k != AGCN_KNOB_UNSET) want = k;     // test knob
   if (want < 1) want = 1;
   if (want > ntile) want = ntile;
   const int tps = (int)((ntile + want - 1) / want);
@@ -286,12 +286,10 @@ inline bool aw_geometry(int N, int C, int Ci, int T, int V, AwGeom& g) {
 
 template <int TMS, int KS, int NSR, int TP>
 int aw_launch_tp(const AwArgs& a, const AwGeom& g, hipStream_t s) {
-  auto kern = adj_ws_kernel<TMS, KS, NSR, TP>;
-  static unsigned char lds_ok[AGCN_MAX_DEVICES] = {};
-  if (int e = agcn_allow_big_lds_rt(reinterpret_cast<const void*>(kern), lds_ok)) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(a.N * g.nsplit)), dim3(AW_NT), g.smem_bytes, s, a);
+  const int rc = agcn_launch_big<adj_ws_kernel<TMS, KS, NSR, TP>>(dim3((unsigned)(a.N * g.nsplit)), dim3(AW_NT),
+                                                                  g.smem_bytes, s, a);
   AGCN_NOTE_KERNEL("adj_ws_kernel<%d, %d, %d, %d>", TMS, KS, NSR, TP);
-  return agcn_check_launch();
+  return rc;
 }
 template <int TMS, int KS, int NSR>
 int aw_launch(const AwArgs& a, const AwGeom& g, hipStream_t s) {
@@ -301,8 +299,7 @@ int aw_launch(const AwArgs& a, const AwGeom& g, hipStream_t s) {
 }  // namespace
 
 static inline bool aw_enabled() {
-  static const int on = getenv("AGCN_ADJ_WS") ? atoi(getenv("AGCN_ADJ_WS")) : 1;
-  return on != 0 && agcn_chain_f16x3();       // (the fp32-equivalent default mode; AGCN_GEMM=f32 / bf16 keep the older kernels)
+  return agcn_knob(AGCN_ADJ_WS) != 0 && agcn_chain_f16x3();       // (the fp32-equivalent default mode; AGCN_GEMM=f32 / bf16 keep the older kernels)
 }
 
 // shapes the persistent forward takes

@@ -541,10 +541,7 @@ int scores_bwd_rows_launch(const float* tp, const float* dS, float* dtp, float* 
   return agcn_check_launch();
 }
 // AGCN_SCORES_ROWS=0 keeps the LDS-staged kernel (A/B)
-static inline bool scores_rows_enabled() {
-  static const int on = getenv("AGCN_SCORES_ROWS") ? atoi(getenv("AGCN_SCORES_ROWS")) : 1;
-  return on != 0;
-}
+static inline bool scores_rows_enabled() { return agcn_knob(AGCN_SCORES_ROWS) != 0; }
 
 inline int sc_tile_frames(int V, int T) {
   int tt = 256 / V;

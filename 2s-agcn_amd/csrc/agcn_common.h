@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
+#include "knobs.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -113,11 +114,22 @@ int agcn_bf16_tconv_bwd_data(const float* dy, const float* w, float* dx, int acc
 bool agcn_gcn_chain_supported(int M, int K, int V);
 int agcn_chain_f16x3();                       // 1: the chain runs on f16x3 (split_f16.h), 0: bf16x6 / AGCN_GEMM's mode
 int agcn_gcn_chain_tiles(int T);
-int agcn_gcn_chain(int mode, const float* in, const float* adj, const float* wcat, const float* bias, float* out,
-                   float* stats_part, int accumulate, const float* add1, const float* mask1, const float* add2,
-                   const float* mask2, int mask_bits, const float* in2, const float* w2, int K2, void* ws, size_t ws_bytes,
-                   int N, int C, int Cout, int T, int V, hipStream_t stream, int relu = 0, int w2_rows_are_outputs = 0,
-                   const float* in_absmax = nullptr, const float* in2_absmax = nullptr, AgcnDryRun* dry = nullptr);
+struct GcnChainCall {
+  int mode = 0;                                  // 0: in = x, K = C, M = Cout; 1: in = dy, K = Cout, M = C
+  const float *in = nullptr, *adj = nullptr, *wcat = nullptr, *bias = nullptr;
+  float *out = nullptr, *stats_part = nullptr;   // stats_part: BatchNorm partials of the forward
+  int accumulate = 0, relu = 0;
+  const float *add1 = nullptr, *mask1 = nullptr, *add2 = nullptr, *mask2 = nullptr;   // masked addends of the row store
+  int mask_bits = 0;
+  const float *in2 = nullptr, *w2 = nullptr;     // fused 1x1 term: out += W2 . in2, w2 (K2, M) row-major, or
+  int K2 = 0, w2_rows_are_outputs = 0;           //   (M, K2) with w2_rows_are_outputs
+  const float *in_absmax = nullptr, *in2_absmax = nullptr;   // f16x3: maxima the producers left behind
+  void* ws = nullptr;
+  size_t ws_bytes = 0;
+  int N = 0, C = 0, Cout = 0, T = 0, V = 0;
+  AgcnDryRun* dry = nullptr;
+};
+int agcn_gcn_chain(const GcnChainCall& c, hipStream_t stream);
 
 bool agcn_gcn_dadj_chain_supported(int C, int V);
 int agcn_gcn_dadj_chain(const float* dy, const float* wcat, const float* x, float* dadj_part, void* ws, size_t ws_bytes,
@@ -130,50 +142,26 @@ int agcn_wgrad_chain(int agg, const float* dy, const float* x, const float* adj,
                      int N, int M, int C, int V, int T_src, int T_out, int stride, hipStream_t s,
                      const float* dy_absmax = nullptr, const float* x_absmax = nullptr, AgcnDryRun* dry = nullptr);
 
-// split-bf16 weight gradient of the 9-tap temporal convolution (wgrad9_bf16.hip): slabs [nslabs][9][M][C] at ws
+// split-bf16 weight gradient of the 9-tap temporal convolution (wgrad9_bf16.hip): slabs [nslabs][9][M][C] at ws; T = frames
+// of x
 bool agcn_wgrad9_bf16_supported(int M, int C, int V, int stride);
-size_t agcn_wgrad9_bf16_workspace(int N, int M, int C, int V, int T, int stride);
 int agcn_wgrad9_bf16(const float* dy, const float* x, void* ws, size_t ws_bytes, int* nslabs, int N, int M, int C, int V,
-                     int T, int stride, hipStream_t s, const float* dy_absmax = nullptr, const float* x_absmax = nullptr);
+                     int T, int stride, hipStream_t s, const float* dy_absmax, const float* x_absmax, AgcnDryRun* dry);
 
 // the same f16x3 kernel for stride-1 3/5/7-tap gradients with taps - pad <= 5 (agcn_tconv_bwd_weight): slabs [taps][M][C]
 bool agcn_wgrad_tconv_f16_supported(int M, int C, int V, int taps, int stride, int pad);
-size_t agcn_wgrad_tconv_f16_workspace(int N, int M, int C, int V, int T, int taps, int pad);
 int agcn_wgrad_tconv_f16(const float* dy, const float* x, void* ws, size_t ws_bytes, int* nslabs, int N, int M, int C,
-                         int V, int T, int taps, int pad, hipStream_t s, const float* dy_absmax, const float* x_absmax);
+                         int V, int T, int taps, int pad, hipStream_t s, const float* dy_absmax, const float* x_absmax,
+                         AgcnDryRun* dry);
 
 // GEMM arithmetic of the channel contractions: 3 = bf16x6 (default: fp32-equivalent accuracy, measured), 0 = f32 MFMA,
 // 2 = bf16x3 (~5e-6 per GEMM; does NOT hold the 1e-4 parity bar end to end), 1 = bf16 (plain bf16 MFMA operands, ONE
 // product per fp32 product, fp32 accumulate and fp32 storage: BASELINE configs[3], ~2^-9 relative per product).
-// Chosen once per process from the environment variable AGCN_GEMM (bf16x6 | f32 | bf16x3 | bf16).
-static inline int agcn_gemm_precision() {
-  static int mode = -1;
-  if (mode < 0) {
-    const char* e = getenv("AGCN_GEMM");
-    mode = 3;
-    if (e && !strcmp(e, "f32")) mode = 0;
-    else if (e && !strcmp(e, "bf16x3")) mode = 2;
-    else if (e && !strcmp(e, "bf16")) mode = 1;
-  }
-  return mode;
-}
+// Chosen once per process from the environment variable AGCN_GEMM (knobs.h).
+static inline int agcn_gemm_precision() { return agcn_knob(AGCN_GEMM); }
 // the register-chained / split-plane kernel family serves bf16x6 (3 planes, 6 products) and bf16 (hi plane, 1 product)
 static inline bool agcn_chained() { const int m = agcn_gemm_precision(); return m == 3 || m == 1; }
 static inline int agcn_npl() { return agcn_gemm_precision() == 1 ? 1 : 3; }
-
-// Raise a kernel's dynamic-LDS limit to 160 KB on the CURRENT device, once per (kernel, device).  hipFuncSetAttribute
-// is per device, and forward / autograd-backward threads may reach a first launch together: the flags are atomics and
-// a lost race only repeats the idempotent call.  `done` is a static array owned by the launcher instantiation.
-#define AGCN_MAX_DEVICES 64
-static inline int agcn_allow_big_lds_rt(const void* kern, unsigned char* done) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= AGCN_MAX_DEVICES) dev = -1;
-  if (dev >= 0 && __atomic_load_n(&done[dev], __ATOMIC_ACQUIRE)) return AGCN_OK;
-  hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e != hipSuccess) return (int)e;
-  if (dev >= 0) __atomic_store_n(&done[dev], (unsigned char)1, __ATOMIC_RELEASE);
-  return AGCN_OK;
-}
 
 // Diagnostic only: the contraction launchers note which kernel instantiation they enqueued last ON THIS THREAD, so that
 // a benchmark can name the kernel it actually timed (agcn_last_kernel()).  Never read by any compute path.
@@ -184,4 +172,24 @@ inline thread_local char agcn_last_kernel_buf[192] = "";
 static inline int agcn_check_launch() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? AGCN_OK : (int)e;
+}
+
+// Launch a kernel that needs more than the default 64 KB of dynamic LDS: raise its limit to 160 KB on the CURRENT
+// device once per (kernel, device), launch, return agcn_check_launch().  Keyed by the kernel itself (instantiations of
+// one template share a function TYPE).  hipFuncSetAttribute is per device, and forward / autograd-backward threads may
+// reach a first launch together: the flags are atomics and a lost race only repeats the idempotent call.
+#define AGCN_MAX_DEVICES 64
+template <auto KERN, class... Args>
+static inline int agcn_launch_big(dim3 grid, dim3 block, size_t smem_bytes, hipStream_t stream, const Args&... args) {
+  static unsigned char done[AGCN_MAX_DEVICES] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= AGCN_MAX_DEVICES) dev = -1;
+  if (dev < 0 || !__atomic_load_n(&done[dev], __ATOMIC_ACQUIRE)) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       160 * 1024);
+    if (e != hipSuccess) return (int)e;
+    if (dev >= 0) __atomic_store_n(&done[dev], (unsigned char)1, __ATOMIC_RELEASE);
+  }
+  hipLaunchKernelGGL(KERN, grid, block, smem_bytes, stream, args...);
+  return agcn_check_launch();
 }

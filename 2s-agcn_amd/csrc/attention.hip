@@ -156,10 +156,7 @@ int agcn_stc_row_reduce(const float* y, const float* g, const float* wv, const f
   RowArgs a;
   a.y = y; a.g = g; a.wv = wv; a.wt = wt; a.out_t = out_t; a.out_v = out_v;
   a.scale_t = scale_t; a.scale_v = scale_v; a.N = N; a.C = C; a.T = T; a.V = V; a.wt_per_row = wt_per_row;
-  static unsigned char lds_ok[AGCN_MAX_DEVICES] = {};
-  if (int e = agcn_allow_big_lds_rt(reinterpret_cast<const void*>(stc_row_reduce_kernel), lds_ok)) return e;
-  hipLaunchKernelGGL(stc_row_reduce_kernel, dim3((unsigned)(N * C)), dim3(256), smem, (hipStream_t)stream, a);
-  return agcn_check_launch();
+  return agcn_launch_big<stc_row_reduce_kernel>(dim3((unsigned)(N * C)), dim3(256), smem, (hipStream_t)stream, a);
 }
 
 // out = y * a_s[n,v] * a_t[n,t] * a_c[n,c]      (a_* = 1 + sigmoid gate); N*C*T*V % 4 == 0

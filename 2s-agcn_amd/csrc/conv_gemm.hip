@@ -607,16 +607,12 @@ int launch_cfg(Problem& p, hipStream_t stream) {
     int rc = agcn_check_launch();
     if (rc) return rc;
   }
-  auto kern = conv_gemm_kernel<TAPS, AGG, WM, WN, TM, TN, CK, WB, EPI>;
-  static unsigned char lds_ok[AGCN_MAX_DEVICES] = {};   // per (kernel instantiation, device): the attribute is per device
-  if (int e = agcn_allow_big_lds_rt(reinterpret_cast<const void*>(kern), lds_ok)) return e;
-  dim3 grid((unsigned)(a.N * g.ntiles * g.nmb));
   if (EPI == 2 && p.gated)
     AGCN_NOTE_KERNEL("conv_gemm_kernel<%d, %d, %d, %d, %d, %d, %d, %d, %d> [gates on load]", TAPS, AGG, WM, WN, TM, TN, CK, WB, EPI);
   else
     AGCN_NOTE_KERNEL("conv_gemm_kernel<%d, %d, %d, %d, %d, %d, %d, %d, %d>", TAPS, AGG, WM, WN, TM, TN, CK, WB, EPI);
-  hipLaunchKernelGGL(kern, grid, dim3(WM * WN * 64), g.smem_bytes, stream, a);
-  return agcn_check_launch();
+  return agcn_launch_big<conv_gemm_kernel<TAPS, AGG, WM, WN, TM, TN, CK, WB, EPI>>(
+      dim3((unsigned)(a.N * g.ntiles * g.nmb)), dim3(WM * WN * 64), g.smem_bytes, stream, a);
 }
 
 // BM = 64 (4 waves) unless M is a multiple of 128 (8 waves, BM = 128)
@@ -664,14 +660,25 @@ int tconv_f32_infer_launch(Problem& p, hipStream_t s) {
 // tensors and a dry-run record (agcn_common.h): there is one copy of every routing decision.  In a dry run an operand
 // whose presence steers the routing may be a placeholder (agcn_dry_present): no route function dereferences a tensor. ----
 
+// what every call of the register-chained graph kernels (gcn_chain.hip) sets; the routes add their operands
+GcnChainCall gcn_chain_call(int mode, const float* adj, const float* wcat, void* ws, size_t ws_bytes, int N, int C,
+                            int Cout, int T, int V, AgcnDryRun* dry) {
+  GcnChainCall c;
+  c.mode = mode; c.adj = adj; c.wcat = wcat; c.ws = ws; c.ws_bytes = ws_bytes;
+  c.N = N; c.C = C; c.Cout = Cout; c.T = T; c.V = V; c.dry = dry;
+  return c;
+}
+
 // y[n][o][t,v] = bias[o] + sum_i sum_c wcat[o][i*C+c] * sum_u x[n][c][t,u] adj[n][i][u][v]
 int gcn_fwd_route(const float* x, const float* adj, const float* wcat, const float* bias, float* y, float* stats_part,
                   void* workspace, size_t workspace_bytes, int N, int C, int Cout, int T, int V, const float* x_absmax,
                   hipStream_t s, AgcnDryRun* dry) {
   // (the 3-channel first layer's forward stays on the f32 kernel: measured 193 us against 260 us chained)
-  if (agcn_chained() && C >= 32 && agcn_gcn_chain_supported(Cout, C, V))
-    return agcn_gcn_chain(0, x, adj, wcat, bias, y, stats_part, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
-                          0, workspace, workspace_bytes, N, C, Cout, T, V, s, 0, 0, x_absmax, nullptr, dry);
+  if (agcn_chained() && C >= 32 && agcn_gcn_chain_supported(Cout, C, V)) {
+    GcnChainCall c = gcn_chain_call(0, adj, wcat, workspace, workspace_bytes, N, C, Cout, T, V, dry);
+    c.in = x; c.in_absmax = x_absmax; c.bias = bias; c.out = y; c.stats_part = stats_part;
+    return agcn_gcn_chain(c, s);
+  }
   Problem p = {};
   p.dry = dry;
   ConvGemmArgs& a = p.a;
@@ -691,10 +698,13 @@ int gcn_bwd_data_route(const float* dy, const float* adj, const float* wcat, con
                        int T, int V, const float* dy_absmax, const float* dtp_absmax, hipStream_t s, AgcnDryRun* dry) {
   const bool chain = agcn_chained() && agcn_gcn_chain_supported(C, Cout, V);
   if (dtp && !chain) return AGCN_ERR_UNSUPPORTED;
-  if (chain)
-    return agcn_gcn_chain(1, dy, adj, wcat, nullptr, dx, nullptr, accumulate, add1, mask1, add2, mask2, mask_bits, dtp,
-                          dtp ? w2 : nullptr, dtp ? K2 : 0, workspace, workspace_bytes, N, C, Cout, T, V, s, 0, 0,
-                          dy_absmax, dtp ? dtp_absmax : nullptr, dry);
+  if (chain) {
+    GcnChainCall c = gcn_chain_call(1, adj, wcat, workspace, workspace_bytes, N, C, Cout, T, V, dry);
+    c.in = dy; c.in_absmax = dy_absmax; c.out = dx; c.accumulate = accumulate;
+    c.add1 = add1; c.mask1 = mask1; c.add2 = add2; c.mask2 = mask2; c.mask_bits = mask_bits;
+    if (dtp) { c.in2 = dtp; c.w2 = w2; c.K2 = K2; c.in2_absmax = dtp_absmax; }
+    return agcn_gcn_chain(c, s);
+  }
   Problem p = {};
   p.dry = dry;
   ConvGemmArgs& a = p.a;
@@ -732,8 +742,10 @@ int gcn_unit_infer_route(const float* x, const float* adj, const float* wcat, co
                          size_t workspace_bytes, int N, int C, int Cout, int T, int V, hipStream_t s, AgcnDryRun* dry) {
   if (!(agcn_chained() && C >= 32 && agcn_gcn_chain_supported(Cout, C, V))) return AGCN_ERR_UNSUPPORTED;
   if (x2 && K2 % 32 != 0) return AGCN_ERR_UNSUPPORTED;
-  return agcn_gcn_chain(0, x, adj, wcat, bias, y, nullptr, 0, res, nullptr, nullptr, nullptr, 0, x2, w2, x2 ? K2 : 0,
-                        workspace, workspace_bytes, N, C, Cout, T, V, s, relu, 1, nullptr, nullptr, dry);
+  GcnChainCall c = gcn_chain_call(0, adj, wcat, workspace, workspace_bytes, N, C, Cout, T, V, dry);
+  c.in = x; c.bias = bias; c.out = y; c.add1 = res; c.relu = relu;
+  c.in2 = x2; c.w2 = w2; c.K2 = x2 ? K2 : 0; c.w2_rows_are_outputs = 1;
+  return agcn_gcn_chain(c, s);
 }
 
 // The temporal convolution's three data routes.  Each builds the plan of tconv_plan.h and hands its passes to one rung:

@@ -726,8 +726,7 @@ int launch_bf(BfProblem& p, hipStream_t stream) {
   a.tt = g.tt; a.ntiles = g.ntiles; a.FW = g.FW; a.WLR = g.WLR; a.nchunks = g.nchunks; a.nmb = g.nmb;
   a.off_b = g.off_b; a.off_bias = g.off_bias;
   a.wp = (const unsigned short*)p.ws;
-  static const int dbg = getenv("AGCN_CB_DBG") ? atoi(getenv("AGCN_CB_DBG")) : 0;
-  a.dbg = dbg;
+  a.dbg = agcn_knob(AGCN_CB_DBG);
   if (g.nchunks > 0) {
     BfPackArgs pk;
     pk.w = p.w; pk.wp = (unsigned short*)p.ws; pk.M = a.M; pk.Kinner = a.Kinner; pk.nchunks = g.nchunks;
@@ -737,13 +736,10 @@ int launch_bf(BfProblem& p, hipStream_t stream) {
     int rc = agcn_check_launch();
     if (rc) return rc;
   }
-  auto kern = conv_gemm_bf16_kernel<TAPS, NPL, WQ, TM, TN, F16, GATE>;
-  static unsigned char lds_ok[AGCN_MAX_DEVICES] = {};   // per (kernel instantiation, device): the attribute is per device
-  if (int e = agcn_allow_big_lds_rt(reinterpret_cast<const void*>(kern), lds_ok)) return e;
   if (GATE) AGCN_NOTE_KERNEL("conv_gemm_bf16_kernel<%d, %d, %d, %d, %d, %s, true> [gates on load]", TAPS, NPL, WQ, TM, TN, F16 ? "true" : "false");
   else AGCN_NOTE_KERNEL("conv_gemm_bf16_kernel<%d, %d, %d, %d, %d, %s>", TAPS, NPL, WQ, TM, TN, F16 ? "true" : "false");
-  hipLaunchKernelGGL(kern, dim3((unsigned)(a.N * g.ntiles * g.nmb)), dim3(NT), g.smem_bytes, stream, a);
-  return agcn_check_launch();
+  return agcn_launch_big<conv_gemm_bf16_kernel<TAPS, NPL, WQ, TM, TN, F16, GATE>>(dim3((unsigned)(a.N * g.ntiles * g.nmb)),
+                                                                                  dim3(NT), g.smem_bytes, stream, a);
 }
 
 
@@ -771,14 +767,7 @@ BfGeom bf_geometry_pc(int V, int T_out, int M, int Kinner) {
 }
 
 // AGCN_CONV_PC=0 selects the single-role kernel (A/B measurement)
-static inline bool conv_pc_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("AGCN_CONV_PC");
-    v = (e && atoi(e) == 0) ? 0 : 1;
-  }
-  return v == 1;
-}
+static inline bool conv_pc_enabled() { return agcn_knob(AGCN_CONV_PC) == 1; }
 
 template <int TAPS, int NPL, int R = 5, int NWP = 4, bool F16 = false, bool GATE = false>
 int launch_pc(BfProblem& p, hipStream_t stream) {
@@ -804,15 +793,11 @@ int launch_pc(BfProblem& p, hipStream_t stream) {
   hipLaunchKernelGGL((pack_weights_slots_kernel<TAPS, BM, NPL, F16>), dim3(g.nmb * g.nchunks * TAPS), dim3(256), 0, stream, pk);
   int rc = agcn_check_launch();
   if (rc) return rc;
-  auto kern = conv_pc_kernel<TAPS, NPL, R, NWP, F16, GATE>;
-  static unsigned char lds_ok[AGCN_MAX_DEVICES] = {};
-  if (int e = agcn_allow_big_lds_rt(reinterpret_cast<const void*>(kern), lds_ok)) return e;
-  static const int dbg = getenv("AGCN_CB_DBG") ? atoi(getenv("AGCN_CB_DBG")) : 0;
-  a.dbg = dbg;
+  a.dbg = agcn_knob(AGCN_CB_DBG);
   if (GATE) AGCN_NOTE_KERNEL("conv_pc_kernel<%d, %d, %d, %d, %s, true> [gates on load]", TAPS, NPL, R, NWP, F16 ? "true" : "false");
   else AGCN_NOTE_KERNEL("conv_pc_kernel<%d, %d, %d, %d, %s>", TAPS, NPL, R, NWP, F16 ? "true" : "false");   // (as rocprofv3 prints it)
-  hipLaunchKernelGGL(kern, dim3((unsigned)(a.N * g.ntiles * g.nmb)), dim3((8 + NWP) * 64), g.smem_bytes, stream, a);
-  return agcn_check_launch();
+  return agcn_launch_big<conv_pc_kernel<TAPS, NPL, R, NWP, F16, GATE>>(dim3((unsigned)(a.N * g.ntiles * g.nmb)),
+                                                                       dim3((8 + NWP) * 64), g.smem_bytes, stream, a);
 }
 
 template <int TAPS>
@@ -830,8 +815,7 @@ int launch_npl(BfProblem& p, int npl, hipStream_t s) {
   const bool fits128 = g128.smem_bytes + (GATE ? gate_bytes(g128) : 0) <= 160 * 1024;
   if constexpr (TAPS >= 3) {
     if (pc_applies<TAPS>(p, npl, GATE)) {
-      static const int nwp2 = getenv("AGCN_CONV_NWP2") ? atoi(getenv("AGCN_CONV_NWP2")) : 0;
-      if (nwp2 && !GATE) return launch_pc<TAPS, 3, 5, 2>(p, s);
+      if (agcn_knob(AGCN_CONV_NWP2) && !GATE) return launch_pc<TAPS, 3, 5, 2>(p, s);
       if (p.fwd_f16) return launch_pc<TAPS, 2, 5, 4, true, GATE>(p, s);
       return launch_pc<TAPS, 3, 5, 4, false, GATE>(p, s);
     }
@@ -862,12 +846,7 @@ int launch_npl(BfProblem& p, int npl, hipStream_t s) {
 
 // 64-row problems with taps: 2 position tiles per wave (512-position workgroup tiles).  AGCN_CONV_WIDE=0 disables.
 bool agcn_bf16_conv_wide(int taps, int M) {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("AGCN_CONV_WIDE");
-    v = (e && atoi(e) == 0) ? 0 : 1;
-  }
-  return v == 1 && taps > 1 && M <= 64;
+  return agcn_knob(AGCN_CONV_WIDE) == 1 && taps > 1 && M <= 64;
 }
 
 // internal entry points used by conv_gemm.hip's dispatch (precision: 3 = bf16x6, 2 = bf16x3)
@@ -876,24 +855,16 @@ namespace {
 // f16x3 range scale of the streamed operand: the maximum its producer left behind, or a streaming pass of our own whose
 // result sits in the last 16 bytes of the workspace (its size carries 256 bytes of slack); shrinks ws_bytes accordingly
 int bf16_in_absmax(BfProblem& p, const float* given, const float* in, long n, hipStream_t s) {
-  if (given) {
-    p.a.in_absmax = given;
-    return 0;
+  if (!given) {
+    if (p.dry) return 0;       // (the size queries carry the slack for the scalar)
+    if (p.ws_bytes < 64) return AGCN_ERR_WORKSPACE;
+    p.ws_bytes = (p.ws_bytes - 16) & ~(size_t)15;
   }
-  if (p.dry) return 0;         // (the size queries carry the slack for the scalar)
-  if (p.ws_bytes < 64) return AGCN_ERR_WORKSPACE;
-  unsigned* amax = reinterpret_cast<unsigned*>(static_cast<char*>(p.ws) + ((p.ws_bytes - 16) & ~(size_t)15));
-  if (hipMemsetAsync(amax, 0, 4, s) != hipSuccess) return AGCN_ERR_ARG;
-  hipLaunchKernelGGL(absmax_kernel, dim3(2048), dim3(256), 0, s, in, n, amax);
-  if (int rc = agcn_check_launch()) return rc;
-  p.a.in_absmax = reinterpret_cast<const float*>(amax);
-  p.ws_bytes = (p.ws_bytes - 16) & ~(size_t)15;
-  return 0;
+  return agcn_operand_max(given, in, n, static_cast<char*>(p.ws) + p.ws_bytes, s, &p.a.in_absmax);
 }
 
 int bf16_fwd_f16x3(int npl) {   // AGCN_CONV_F16X3=0 keeps the temporal convolutions on bf16x6
-  static const int f16x3 = getenv("AGCN_CONV_F16X3") ? atoi(getenv("AGCN_CONV_F16X3")) : 1;
-  return f16x3 && npl == 3;
+  return agcn_knob(AGCN_CONV_F16X3) && npl == 3;
 }
 
 // the forward on its <TAPS, WQ> ladder, ungated or gated

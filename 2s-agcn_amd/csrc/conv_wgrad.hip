@@ -354,12 +354,9 @@ int launch_wgrad(WgradArgs a, float* dw, void* ws, size_t ws_bytes, hipStream_t 
   a.tt = g.tt; a.ntiles = g.ntiles; a.FW = g.FW; a.WLP = g.WLP; a.DAP = g.DAP; a.GP = g.GP;
   a.nsplit = g.nsplit; a.pairs_per_split = g.pairs_per_split;
   a.off_bx = g.off_bx; a.off_bg = g.off_bg; a.off_adj = g.off_adj; a.off_qoff = g.off_qoff;
-  auto kern = conv_wgrad_kernel<TAPS, AGG, MW, CW, TH, KSPLIT, WBX>;
-  static unsigned char lds_ok[AGCN_MAX_DEVICES] = {};   // per (kernel instantiation, device): the attribute is per device
-  if (int e = agcn_allow_big_lds_rt(reinterpret_cast<const void*>(kern), lds_ok)) return e;
-  hipLaunchKernelGGL(kern, dim3(g.grid_x, g.nsplit), dim3(512), g.smem_bytes, stream, a);
-  int rc = agcn_check_launch();
-  if (rc) return rc;
+  if (int rc = agcn_launch_big<conv_wgrad_kernel<TAPS, AGG, MW, CW, TH, KSPLIT, WBX>>(dim3(g.grid_x, g.nsplit), dim3(512),
+                                                                                      g.smem_bytes, stream, a))
+    return rc;
   return launch_reduce((const float*)ws, dw, a.wsize, g.nslabs, a.M, a.C, a.so_m, a.so_t, a.so_c, stream);
 }
 
@@ -374,14 +371,7 @@ int chain_wgrad_and_reduce(int agg, const WgradArgs& a, float* dw, void* ws, siz
 }
 
 // 9-tap weight gradient on the split-bf16 kernel (AGCN_WGRAD9_BF16=0 keeps the exact-f32 MFMA kernel)
-inline bool wgrad9_bf16_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("AGCN_WGRAD9_BF16");
-    v = (e && atoi(e) == 0) ? 0 : 1;
-  }
-  return v == 1;
-}
+inline bool wgrad9_bf16_enabled() { return agcn_knob(AGCN_WGRAD9_BF16) == 1; }
 
 // ---- agcn_tconv_bwd_weight: any taps (1..9), stride (1..9), padding (0..(taps-1)/2) on the exact-f32 kernel ----
 constexpr int WBXT = 8;                  // window bound: 512 floats per staged row
@@ -422,18 +412,10 @@ int tconv_wgrad(WgradArgs a, bool legacy, float* dw, void* ws, size_t ws_bytes, 
   return launch_wgrad<TAPS, 0, 2, 2, 2, false, WBXT>(a, dw, ws, ws_bytes, s, dry, cap);
 }
 
-inline bool chain_wgrad_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("AGCN_WGRAD_BF16");
-    v = (e && atoi(e) == 0) ? 0 : 1;
-  }
-  return v == 1 && agcn_chained();
-}
+inline bool chain_wgrad_enabled() { return agcn_knob(AGCN_WGRAD_BF16) == 1 && agcn_chained(); }
 
 // ---- the routing of each entry point, after its argument checks; the *_workspace queries walk the same functions with
-// null tensors (or placeholders, agcn_dry_present) and a dry-run record (agcn_common.h).  The f16x3 tap kernels of wgrad9_bf16.hip size themselves by the
-// geometry function they launch with. ----
+// null tensors (or placeholders, agcn_dry_present) and a dry-run record (agcn_common.h). ----
 
 // dwcat[o][i*C+c] = sum_{n,t,v} dy[n][o][t,v] * sum_u x[n][c][t,u] adj[n][i][u][v]
 int gcn_wgrad_route(const float* dy, const float* x, const float* adj, float* dwcat, void* workspace,
@@ -462,15 +444,12 @@ int tconv_wgrad_route(const float* dy, const float* x, float* dw, void* workspac
   a.so_m = (long)Cin * taps; a.so_t = 1; a.so_c = taps; a.wsize = (long)Cout * Cin * taps;
   const bool tap9 = legacy && taps == 9 && wgrad9_bf16_enabled() && agcn_wgrad9_bf16_supported(Cout, Cin, V, stride);
   if (tap9 || (!legacy && agcn_wgrad_tconv_f16_supported(Cout, Cin, V, taps, stride, pad))) {
-    if (dry)
-      return agcn_dry_note(dry, 0, tap9 ? agcn_wgrad9_bf16_workspace(N, Cout, Cin, V, T, stride)
-                                        : agcn_wgrad_tconv_f16_workspace(N, Cout, Cin, V, T, taps, pad));
     int nslabs = 0;
     const int rc = tap9 ? agcn_wgrad9_bf16(dy, x, workspace, workspace_bytes, &nslabs, N, Cout, Cin, V, T, stride, s,
-                                           dy_absmax, x_absmax)
+                                           dy_absmax, x_absmax, dry)
                         : agcn_wgrad_tconv_f16(dy, x, workspace, workspace_bytes, &nslabs, N, Cout, Cin, V, T, taps, pad, s,
-                                               dy_absmax, x_absmax);
-    if (rc) return rc;
+                                               dy_absmax, x_absmax, dry);
+    if (rc || dry) return rc;
     return launch_reduce((const float*)workspace, dw, a.wsize, nslabs, a.M, a.C, a.so_m, a.so_t, a.so_c, s);
   }
   if (legacy && taps == 1 && chain_wgrad_enabled() && agcn_wgrad_chain_supported(Cout, Cin, V))

@@ -553,7 +553,7 @@ static inline WsGeom ws_geometry(int N, int M, int K, int K2, int T, int V) {
   g.nmb = (M + BM - 1) / BM;
   const int ntile = (T + WS_NW - 1) / WS_NW;
   long want = (256 + (long)N * g.nmb - 1) / ((long)N * g.nmb);       // workgroups ~ one per CU
-  if (const char* e = getenv("AGCN_WS_SPLIT")) want = atoi(e);     // test knob: frame splits per sample (read per call)
+  if (const int k = agcn_knob_now(AGCN_WS_SPLIT); k != AGCN_KNOB_UNSET) want = k;   // test knob: frame splits per sample
   if (want < 1) want = 1;
   if (want > ntile) want = ntile;
   const int tps = (int)((ntile + want - 1) / want);                   // tiles per split
@@ -1128,9 +1128,47 @@ struct ChainW2 {
   long sa_m, sa_c;      // W2[m][k] = w[m*sa_m + k*sa_c]
 };
 
+// one aggregate+project launch as the host sees it (cf. BfProblem): the ladder hands it down unchanged
+struct ChainProblem {
+  ChainArgs a;
+  const float* w;              // W_i[m][k] = w[m*sa_m + i*sa_i + k*sa_c]
+  long sa_m, sa_i, sa_c;
+  ChainW2 w2;                  // weights of the plain stages (a.in2)
+  void* ws;
+  size_t ws_bytes;
+  AgcnDryRun* dry;             // non-null: a size query (agcn_common.h), nothing is launched
+};
+
+// the weight images at p.ws: 3 * ncb aggregated stages per row block, then ncb2 plain ones
+template <int TM, bool F16>
+int chain_pack(const ChainProblem& p, int ncb, int ncb2, int s_total, hipStream_t stream) {
+  const int nmb = (p.a.M + TM * 32 - 1) / (TM * 32);
+  ChainPackArgs pk;
+  pk.w = p.w; pk.wp = (unsigned short*)p.ws; pk.M = p.a.M; pk.K = p.a.K; pk.ncb = ncb;
+  pk.sa_m = p.sa_m; pk.sa_i = p.sa_i; pk.sa_c = p.sa_c;
+  pk.nsub = 3; pk.s_total = s_total; pk.s_off = 0;
+  hipLaunchKernelGGL((chain_pack_kernel<TM, F16>), dim3(nmb * ncb * 3), dim3(256), 0, stream, pk);
+  int rc = agcn_check_launch();
+  if (rc || ncb2 == 0) return rc;
+  pk.w = p.w2.w; pk.K = p.a.K2; pk.ncb = ncb2;
+  pk.sa_m = p.w2.sa_m; pk.sa_i = 0; pk.sa_c = p.w2.sa_c;
+  pk.nsub = 1; pk.s_off = 3 * ncb;
+  hipLaunchKernelGGL((chain_pack_kernel<TM, F16>), dim3(nmb * ncb2), dim3(256), 0, stream, pk);
+  return agcn_check_launch();
+}
+
+// the f16x3 range scales of the streamed operands, into the two words behind the weight images
+inline int chain_maxima(ChainArgs& a, void* slots, hipStream_t stream) {
+  unsigned* amax = static_cast<unsigned*>(slots);
+  if (int rc = agcn_operand_max(a.in_absmax, a.in, (long)a.N * a.K * a.T * a.V, amax, stream, &a.in_absmax)) return rc;
+  if (!a.in2) { a.in2_absmax = nullptr; return AGCN_OK; }
+  return agcn_operand_max(a.in2_absmax, a.in2, (long)a.N * a.K2 * a.T * a.V, amax + 1, stream, &a.in2_absmax);
+}
+
 template <int TM, int VS, int NW, bool F16 = false>
-int chain_launch(ChainArgs a, const float* w, long sa_m, long sa_i, long sa_c, const ChainW2& g_w2, void* ws,
-                 size_t ws_bytes, hipStream_t stream, AgcnDryRun* dry) {
+int chain_launch(const ChainProblem& p, hipStream_t stream) {
+  ChainArgs a = p.a;
+  void* const ws = p.ws;
   constexpr int PL = F16 ? 2 : 3;
   const ChainGeom g = chain_geometry<TM, NW>(a.V, a.T, a.M, a.K, VS == 0, PL);
   if (g.smem_bytes > 160 * 1024) return AGCN_ERR_UNSUPPORTED;
@@ -1138,151 +1176,85 @@ int chain_launch(ChainArgs a, const float* w, long sa_m, long sa_i, long sa_c, c
   const int s_total = 3 * g.ncb + a.ncb2;
   const size_t a_img = (size_t)PL * 2 * TM * 1024;
   const size_t img_bytes = (size_t)g.nmb * s_total * a_img;
-  if (dry) return agcn_dry_note(dry, a.stats ? (long)a.N * g.ntiles : 0, img_bytes + (F16 ? 16 : 0));
-  if (img_bytes + (F16 ? 16 : 0) > ws_bytes) return AGCN_ERR_WORKSPACE;
-  if constexpr (F16) {
-    // maxima the caller did not supply: one streaming pass each, into the 16 bytes behind the weight images (the
-    // workspace is sized for three planes, the f16x3 images take two)
-    unsigned* amax = reinterpret_cast<unsigned*>(static_cast<char*>(ws) + img_bytes);
-    if (!a.in_absmax) {
-      if (int rc = agcn_launch_absmax(a.in, (long)a.N * a.K * a.T * a.V, amax, stream)) return rc;
-      a.in_absmax = reinterpret_cast<const float*>(amax);
-    }
-    if (a.in2 && !a.in2_absmax) {
-      if (int rc = agcn_launch_absmax(a.in2, (long)a.N * a.K2 * a.T * a.V, amax + 1, stream)) return rc;
-      a.in2_absmax = reinterpret_cast<const float*>(amax + 1);
-    }
-    if (!a.in2) a.in2_absmax = nullptr;
-  }
+  if (p.dry) return agcn_dry_note(p.dry, a.stats ? (long)a.N * g.ntiles : 0, img_bytes + (F16 ? 16 : 0));
+  if (img_bytes + (F16 ? 16 : 0) > p.ws_bytes) return AGCN_ERR_WORKSPACE;
+  if constexpr (F16)     // (the workspace is sized for three planes, the f16x3 images take two)
+    if (int rc = chain_maxima(a, static_cast<char*>(ws) + img_bytes, stream)) return rc;
   a.ntiles = g.ntiles; a.ncb = g.ncb; a.nmb = g.nmb; a.XP = g.XP; a.off_bias = g.off_bias;
   a.wp = (const unsigned short*)ws;
-  ChainPackArgs pk;
-  pk.w = w; pk.wp = (unsigned short*)ws; pk.M = a.M; pk.K = a.K; pk.ncb = g.ncb;
-  pk.sa_m = sa_m; pk.sa_i = sa_i; pk.sa_c = sa_c;
-  pk.nsub = 3; pk.s_total = s_total; pk.s_off = 0;
-  hipLaunchKernelGGL((chain_pack_kernel<TM, F16>), dim3(g.nmb * g.ncb * 3), dim3(256), 0, stream, pk);
-  int rc = agcn_check_launch();
-  if (rc) return rc;
-  if (a.ncb2 > 0) {        // images of the plain stages, after the aggregated ones of each row block
-    ChainPackArgs p2;
-    p2.w = g_w2.w; p2.wp = (unsigned short*)ws; p2.M = a.M; p2.K = a.K2; p2.ncb = a.ncb2;
-    p2.sa_m = g_w2.sa_m; p2.sa_i = 0; p2.sa_c = g_w2.sa_c;
-    p2.nsub = 1; p2.s_total = s_total; p2.s_off = 3 * g.ncb;
-    hipLaunchKernelGGL((chain_pack_kernel<TM, F16>), dim3(g.nmb * a.ncb2), dim3(256), 0, stream, p2);
-    rc = agcn_check_launch();
-    if (rc) return rc;
-  }
-  auto kern = gcn_chain_kernel<TM, VS, NW, F16>;
-  static unsigned char lds_ok[AGCN_MAX_DEVICES] = {};   // per (kernel instantiation, device): the attribute is per device
-  if (int e = agcn_allow_big_lds_rt(reinterpret_cast<const void*>(kern), lds_ok)) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(a.N * g.ntiles * g.nmb)), dim3(NW * 64), g.smem_bytes, stream, a);
+  if (int rc = chain_pack<TM, F16>(p, g.ncb, a.ncb2, s_total, stream)) return rc;
+  const int rc = agcn_launch_big<gcn_chain_kernel<TM, VS, NW, F16>>(dim3((unsigned)(a.N * g.ntiles * g.nmb)), dim3(NW * 64),
+                                                                    g.smem_bytes, stream, a);
   AGCN_NOTE_KERNEL("gcn_chain_kernel<%d, %d, %d, %s>", TM, VS, NW, F16 ? "true" : "false");
-  return agcn_check_launch();
+  return rc;
 }
 
 
 // ---- weight-stationary launch (see gcn_ws_kernel) ----
-static inline bool ws_enabled() {
-  static const int on = getenv("AGCN_CHAIN_WS") ? atoi(getenv("AGCN_CHAIN_WS")) : 1;
-  return on != 0;
-}
 // shapes the persistent kernel takes: f16x3 chain, 33..64 streamed channels with up to three plain 32-channel stages, or
 // 65..128 streamed channels without plain stages (96 KB of resident weights per 64-row block, single O tile)
 static inline bool ws_shape_ok(int M, int K, int K2, int V) {
-  if (!(agcn_chain_f16x3() && ws_enabled() && V <= 32 && M >= 1 && K > 32)) return false;
-  static const int k128 = getenv("AGCN_WS_K128") ? atoi(getenv("AGCN_WS_K128")) : 1;
-  return (K <= 64 && K2 >= 0 && K2 <= 96) || (k128 && K <= 128 && K2 == 0 && M > 32);
+  if (!(agcn_chain_f16x3() && agcn_knob(AGCN_CHAIN_WS) && V <= 32 && M >= 1 && K > 32)) return false;
+  return (K <= 64 && K2 >= 0 && K2 <= 96) || (agcn_knob(AGCN_WS_K128) && K <= 128 && K2 == 0 && M > 32);
 }
 
 template <int TM, int NCB2, int KCB = 2>
-int ws_launch(ChainArgs a, const float* w, long sa_m, long sa_i, long sa_c, const ChainW2& g_w2, void* ws, size_t ws_bytes,
-              hipStream_t stream, AgcnDryRun* dry) {
+int ws_launch(const ChainProblem& p, hipStream_t stream) {
+  ChainArgs a = p.a;
+  void* const ws = p.ws;
   const WsGeom g = ws_geometry<TM>(a.N, a.M, a.K, a.K2, a.T, a.V);
   if (g.smem_bytes > 160 * 1024) return AGCN_ERR_UNSUPPORTED;
   if (NCB2 > 0 && a.stats) return AGCN_ERR_UNSUPPORTED;            // (BatchNorm partials: plain-stage-free forward only)
   const size_t img_total = (size_t)g.nmb * g.img_bytes;
-  if (dry) return agcn_dry_note(dry, a.stats ? (long)a.N * g.nsplit : 0, img_total + 16);
-  if (img_total + 16 > ws_bytes) return AGCN_ERR_WORKSPACE;
-  unsigned* amax = reinterpret_cast<unsigned*>(static_cast<char*>(ws) + img_total);
-  if (!a.in_absmax) {
-    if (int rc = agcn_launch_absmax(a.in, (long)a.N * a.K * a.T * a.V, amax, stream)) return rc;
-    a.in_absmax = reinterpret_cast<const float*>(amax);
-  }
-  if (a.in2 && !a.in2_absmax) {
-    if (int rc = agcn_launch_absmax(a.in2, (long)a.N * a.K2 * a.T * a.V, amax + 1, stream)) return rc;
-    a.in2_absmax = reinterpret_cast<const float*>(amax + 1);
-  }
-  if (!a.in2) a.in2_absmax = nullptr;
+  if (p.dry) return agcn_dry_note(p.dry, a.stats ? (long)a.N * g.nsplit : 0, img_total + 16);
+  if (img_total + 16 > p.ws_bytes) return AGCN_ERR_WORKSPACE;
+  if (int rc = chain_maxima(a, static_cast<char*>(ws) + img_total, stream)) return rc;
   a.ncb = KCB; a.ncb2 = NCB2; a.nmb = g.nmb;
   a.wp = (const unsigned short*)ws;
-  const int s_total = 3 * KCB + NCB2;
-  ChainPackArgs pk;
-  pk.w = w; pk.wp = (unsigned short*)ws; pk.M = a.M; pk.K = a.K; pk.ncb = KCB;
-  pk.sa_m = sa_m; pk.sa_i = sa_i; pk.sa_c = sa_c;
-  pk.nsub = 3; pk.s_total = s_total; pk.s_off = 0;
-  hipLaunchKernelGGL((chain_pack_kernel<TM, true>), dim3(g.nmb * KCB * 3), dim3(256), 0, stream, pk);
-  int rc = agcn_check_launch();
-  if (rc) return rc;
-  if (NCB2 > 0) {
-    ChainPackArgs p2;
-    p2.w = g_w2.w; p2.wp = (unsigned short*)ws; p2.M = a.M; p2.K = a.K2; p2.ncb = NCB2;
-    p2.sa_m = g_w2.sa_m; p2.sa_i = 0; p2.sa_c = g_w2.sa_c;
-    p2.nsub = 1; p2.s_total = s_total; p2.s_off = 3 * KCB;
-    hipLaunchKernelGGL((chain_pack_kernel<TM, true>), dim3(g.nmb * NCB2), dim3(256), 0, stream, p2);
-    rc = agcn_check_launch();
-    if (rc) return rc;
-  }
+  if (int rc = chain_pack<TM, true>(p, KCB, NCB2, 3 * KCB + NCB2, stream)) return rc;
   const bool extras = NCB2 > 0 || a.accumulate || a.add1 || a.add2 || a.relu;
   const dim3 grid((unsigned)(a.N * g.nmb * g.nsplit)), block(NCB2 == 0 ? WS_NT : WS_NW * 64);
+  int rc = AGCN_OK;
   if (extras) {
-    auto kern = gcn_ws_kernel<TM, KCB, NCB2, true>;
-    static unsigned char lds_ok[AGCN_MAX_DEVICES] = {};
-    if (int e = agcn_allow_big_lds_rt(reinterpret_cast<const void*>(kern), lds_ok)) return e;
-    hipLaunchKernelGGL(kern, grid, block, g.smem_bytes, stream, a, g);
+    rc = agcn_launch_big<gcn_ws_kernel<TM, KCB, NCB2, true>>(grid, block, g.smem_bytes, stream, a, g);
   } else {
-    if constexpr (NCB2 == 0) {
-      auto kern = gcn_ws_kernel<TM, KCB, 0, false>;
-      static unsigned char lds_ok[AGCN_MAX_DEVICES] = {};
-      if (int e = agcn_allow_big_lds_rt(reinterpret_cast<const void*>(kern), lds_ok)) return e;
-      hipLaunchKernelGGL(kern, grid, block, g.smem_bytes, stream, a, g);
-    }
+    if constexpr (NCB2 == 0) rc = agcn_launch_big<gcn_ws_kernel<TM, KCB, 0, false>>(grid, block, g.smem_bytes, stream, a, g);
   }
   AGCN_NOTE_KERNEL("gcn_ws_kernel<%d, %d, %d>", TM, KCB, NCB2);
-  return agcn_check_launch();
+  return rc;
 }
 
 template <int TM>
-int ws_dispatch(const ChainArgs& a, const float* w, long sa_m, long sa_i, long sa_c, const ChainW2& w2, void* ws,
-                size_t ws_bytes, hipStream_t stream, AgcnDryRun* dry) {
+int ws_dispatch(const ChainProblem& p, hipStream_t stream) {
+  const ChainArgs& a = p.a;
   const int ncb2 = a.in2 ? (a.K2 + CB - 1) / CB : 0;
   if (a.K > 64) {
     if constexpr (TM == 2) {
-      if (ncb2 == 0) return ws_launch<2, 0, 4>(a, w, sa_m, sa_i, sa_c, w2, ws, ws_bytes, stream, dry);
+      if (ncb2 == 0) return ws_launch<2, 0, 4>(p, stream);
     }
     return AGCN_ERR_UNSUPPORTED;
   }
   switch (ncb2) {
-    case 0: return ws_launch<TM, 0>(a, w, sa_m, sa_i, sa_c, w2, ws, ws_bytes, stream, dry);
-    case 1: return ws_launch<TM, 1>(a, w, sa_m, sa_i, sa_c, w2, ws, ws_bytes, stream, dry);
-    case 2: return ws_launch<TM, 2>(a, w, sa_m, sa_i, sa_c, w2, ws, ws_bytes, stream, dry);
-    case 3: return ws_launch<TM, 3>(a, w, sa_m, sa_i, sa_c, w2, ws, ws_bytes, stream, dry);
+    case 0: return ws_launch<TM, 0>(p, stream);
+    case 1: return ws_launch<TM, 1>(p, stream);
+    case 2: return ws_launch<TM, 2>(p, stream);
+    case 3: return ws_launch<TM, 3>(p, stream);
   }
   return AGCN_ERR_UNSUPPORTED;
 }
 
 template <int TM, int NW>
-int chain_dispatch_vs(const ChainArgs& a, const float* w, long sa_m, long sa_i, long sa_c, const ChainW2& w2, void* ws,
-                      size_t ws_bytes, hipStream_t stream, AgcnDryRun* dry) {
+int chain_dispatch_vs(const ChainProblem& p, hipStream_t stream) {
+  const ChainArgs& a = p.a;
   // split-bf16 aggregation unless AGCN_CHAIN_F32=1 (exact-f32 MFMA chain, VS = ceil(V/2) steps) or AGCN_GEMM=bf16
   // (one product: keep the aggregation exact)
-  static const int f32chain = getenv("AGCN_CHAIN_F32") ? atoi(getenv("AGCN_CHAIN_F32")) : 0;
-  if (!f32chain && a.npl == 3 && agcn_chain_f16x3())
-    return chain_launch<TM, 0, NW, true>(a, w, sa_m, sa_i, sa_c, w2, ws, ws_bytes, stream, dry);
-  if (!f32chain && a.npl == 3) return chain_launch<TM, 0, NW>(a, w, sa_m, sa_i, sa_c, w2, ws, ws_bytes, stream, dry);
+  const int f32chain = agcn_knob(AGCN_CHAIN_F32);
+  if (!f32chain && a.npl == 3 && agcn_chain_f16x3()) return chain_launch<TM, 0, NW, true>(p, stream);
+  if (!f32chain && a.npl == 3) return chain_launch<TM, 0, NW>(p, stream);
   const int vs = (a.V + 1) / 2;
-  if (vs == 13) return chain_launch<TM, 13, NW>(a, w, sa_m, sa_i, sa_c, w2, ws, ws_bytes, stream, dry);
-  if (vs == 9) return chain_launch<TM, 9, NW>(a, w, sa_m, sa_i, sa_c, w2, ws, ws_bytes, stream, dry);
-  return chain_launch<TM, 16, NW>(a, w, sa_m, sa_i, sa_c, w2, ws, ws_bytes, stream, dry);
+  if (vs == 13) return chain_launch<TM, 13, NW>(p, stream);
+  if (vs == 9) return chain_launch<TM, 9, NW>(p, stream);
+  return chain_launch<TM, 16, NW>(p, stream);
 }
 
 
@@ -1595,19 +1567,13 @@ int dadj_chain_launch(DadjArgs a, const float* wcat, void* ws, size_t ws_bytes, 
   if (dry) return agcn_dry_note(dry, a.dpart ? 3L * a.N * a.nslots : 0, pack_bytes + (F16 ? 16 : 0));
   if (pack_bytes + (F16 ? 16 : 0) > ws_bytes) return AGCN_ERR_WORKSPACE;
   a.wp = (const unsigned short*)ws;
-  if constexpr (F16) {
-    if (!a.dy_absmax) {      // behind the (two-plane) weight images of a workspace sized for three planes
-      unsigned* amax = reinterpret_cast<unsigned*>(static_cast<char*>(ws) + pack_bytes);
-      if (int rc = agcn_launch_absmax(a.dy, (long)a.N * a.Cout * a.T * a.V, amax, stream)) return rc;
-      a.dy_absmax = reinterpret_cast<const float*>(amax);
-    }
-    static const int red16 = getenv("AGCN_DADJ_RED16") ? atoi(getenv("AGCN_DADJ_RED16")) : 1;   // 0: exact-f32 reduction (A/B)
-    if (!red16) {
-      a.x_absmax = nullptr;
-    } else if (!a.x_absmax) {  // the same arithmetic with or without the producer's maximum: a pass of our own
-      unsigned* amax = reinterpret_cast<unsigned*>(static_cast<char*>(ws) + pack_bytes) + 1;
-      if (int rc = agcn_launch_absmax(a.x, (long)a.N * a.C * a.T * a.V, amax, stream)) return rc;
-      a.x_absmax = reinterpret_cast<const float*>(amax);
+  if constexpr (F16) {       // the maxima sit behind the (two-plane) weight images of a workspace sized for three planes
+    unsigned* amax = reinterpret_cast<unsigned*>(static_cast<char*>(ws) + pack_bytes);
+    if (int rc = agcn_operand_max(a.dy_absmax, a.dy, (long)a.N * a.Cout * a.T * a.V, amax, stream, &a.dy_absmax)) return rc;
+    if (!agcn_knob(AGCN_DADJ_RED16)) {
+      a.x_absmax = nullptr;    // exact-f32 reduction (A/B)
+    } else {                   // the same arithmetic with or without the producer's maximum
+      if (int rc = agcn_operand_max(a.x_absmax, a.x, (long)a.N * a.C * a.T * a.V, amax + 1, stream, &a.x_absmax)) return rc;
     }
   }
   DadjPackArgs pk;
@@ -1615,11 +1581,8 @@ int dadj_chain_launch(DadjArgs a, const float* wcat, void* ws, size_t ws_bytes, 
   hipLaunchKernelGGL((dadj_pack_kernel<TM, F16>), dim3(a.nmb * a.nkc), dim3(256), 0, stream, pk);
   int rc = agcn_check_launch();
   if (rc) return rc;
-  auto kern = gcn_dadj_chain_kernel<TM, NW, F16>;
-  static unsigned char lds_ok[AGCN_MAX_DEVICES] = {};   // per (kernel instantiation, device): the attribute is per device
-  if (int e = agcn_allow_big_lds_rt(reinterpret_cast<const void*>(kern), lds_ok)) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(a.N * a.ntiles * a.nmb)), dim3(NW * 64), smem_bytes, stream, a);
-  return agcn_check_launch();
+  return agcn_launch_big<gcn_dadj_chain_kernel<TM, NW, F16>>(dim3((unsigned)(a.N * a.ntiles * a.nmb)), dim3(NW * 64),
+                                                             smem_bytes, stream, a);
 }
 
 }  // namespace
@@ -1628,64 +1591,48 @@ int dadj_chain_launch(DadjArgs a, const float* wcat, void* ws, size_t ws_bytes, 
 static inline int chain_tm(int M) { return (M % 128 == 0) ? 4 : (M <= 32 ? 1 : 2); }
 
 // waves (= frames) per workgroup: 4 (two workgroups per CU overlap each other's prologue/epilogue) or 8
-static inline int chain_waves() {
-  static int nw = 0;
-  if (!nw) {
-    const char* e = getenv("AGCN_CHAIN_WAVES");
-    nw = (e && atoi(e) == 8) ? 8 : 4;
-  }
-  return nw;
-}
+static inline int chain_waves() { return agcn_knob(AGCN_CHAIN_WAVES); }
 
 // 1 (default): aggregate+project forward / backward-data on f16x3 in the fp32-equivalent mode; AGCN_CHAIN_F16X3=0: bf16x6
-int agcn_chain_f16x3() {
-  static const int on = getenv("AGCN_CHAIN_F16X3") ? atoi(getenv("AGCN_CHAIN_F16X3")) : 1;
-  return on && agcn_npl() == 3;
-}
+int agcn_chain_f16x3() { return agcn_knob(AGCN_CHAIN_F16X3) && agcn_npl() == 3; }
 
 bool agcn_gcn_chain_supported(int M, int K, int V) { return M >= 1 && K >= 1 && V <= 32; }
 
 int agcn_gcn_chain_tiles(int T) { return (T + chain_waves() - 1) / chain_waves(); }
 
 // mode 0: forward (in = x, K = C, M = Cout); mode 1: backward-data (in = dy, K = Cout, M = C)
-int agcn_gcn_chain(int mode, const float* in, const float* adj, const float* wcat, const float* bias, float* out,
-                   float* stats_part, int accumulate, const float* add1, const float* mask1, const float* add2,
-                   const float* mask2, int mask_bits, const float* in2, const float* w2, int K2, void* ws, size_t ws_bytes,
-                   int N, int C, int Cout, int T, int V, hipStream_t stream, int relu, int w2_rows_are_outputs,
-                   const float* in_absmax, const float* in2_absmax, AgcnDryRun* dry) {
-  ChainArgs a = {};
-  a.relu = relu;
-  a.in_absmax = in_absmax; a.in2_absmax = in2_absmax;   // f16x3: maxima the producers left behind (null: a pre-pass)
+int agcn_gcn_chain(const GcnChainCall& c, hipStream_t stream) {
+  ChainProblem p = {};
+  ChainArgs& a = p.a;
+  p.w = c.wcat; p.ws = c.ws; p.ws_bytes = c.ws_bytes; p.dry = c.dry;
+  a.relu = c.relu;
+  a.in_absmax = c.in_absmax; a.in2_absmax = c.in2_absmax;   // f16x3: maxima the producers left behind (null: a pre-pass)
   a.npl = agcn_npl();
-  { static const int dbg = getenv("AGCN_GC_DBG") ? atoi(getenv("AGCN_GC_DBG")) : 0; a.dbg = dbg; }
+  a.dbg = agcn_knob(AGCN_GC_DBG);
   // optional fused 1x1 term (backward-data only): out += W2^T . in2 with w2 (K2, M) row-major, e.g. the theta/phi
   // branch  dx += Wab^T dtp  (reference agcn.py:99-100 differentiated)
-  a.in2 = (in2 && w2 && K2 > 0) ? in2 : nullptr;
-  a.K2 = a.in2 ? K2 : 0;
-  ChainW2 cw2 = {w2, 1, 0};
-  a.in = in; a.adj = adj; a.bias = bias; a.out = out; a.stats = stats_part;
-  a.accumulate = accumulate; a.add1 = add1; a.mask1 = mask1; a.add2 = add2; a.mask2 = mask2; a.mask_bits = mask_bits;
-  a.N = N; a.T = T; a.V = V;
-  long sa_m, sa_i, sa_c;
-  if (mode == 0) { a.M = Cout; a.K = C; a.adj_t = 0; sa_m = 3L * C; sa_i = C; sa_c = 1; }
-  else           { a.M = C; a.K = Cout; a.adj_t = 1; sa_m = 1; sa_i = C; sa_c = 3L * C; }
-  cw2.sa_c = a.M;        // W2[m][k] = w2[k*M + m]
-  if (w2_rows_are_outputs) { cw2.sa_m = a.K2; cw2.sa_c = 1; }   // w2 (M, K2) row-major (forward: a folded 1x1 conv)
-  if (!a.dbg && ws_shape_ok(a.M, a.K, a.K2, V)) {
-    // persistent, weight-stationary kernel (up to 128 streamed channels); its profiling switches are read per call
-    if (!dry)
-      if (const char* e = getenv("AGCN_WS_DBG")) a.dbg = atoi(e);
-    const int rc = (a.M <= 32) ? ws_dispatch<1>(a, wcat, sa_m, sa_i, sa_c, cw2, ws, ws_bytes, stream, dry)
-                               : ws_dispatch<2>(a, wcat, sa_m, sa_i, sa_c, cw2, ws, ws_bytes, stream, dry);
+  a.in2 = (c.in2 && c.w2 && c.K2 > 0) ? c.in2 : nullptr;
+  a.K2 = a.in2 ? c.K2 : 0;
+  a.in = c.in; a.adj = c.adj; a.bias = c.bias; a.out = c.out; a.stats = c.stats_part;
+  a.accumulate = c.accumulate; a.add1 = c.add1; a.mask1 = c.mask1; a.add2 = c.add2; a.mask2 = c.mask2;
+  a.mask_bits = c.mask_bits;
+  a.N = c.N; a.T = c.T; a.V = c.V;
+  const long C = c.C;
+  if (c.mode == 0) { a.M = c.Cout; a.K = c.C; a.adj_t = 0; p.sa_m = 3 * C; p.sa_i = C; p.sa_c = 1; }
+  else             { a.M = c.C; a.K = c.Cout; a.adj_t = 1; p.sa_m = 1; p.sa_i = C; p.sa_c = 3 * C; }
+  p.w2 = {c.w2, 1, a.M};                                               // W2[m][k] = w2[k*M + m]
+  if (c.w2_rows_are_outputs) { p.w2.sa_m = a.K2; p.w2.sa_c = 1; }      // w2 (M, K2) row-major (forward: a folded 1x1 conv)
+  if (!a.dbg && ws_shape_ok(a.M, a.K, a.K2, a.V)) {
+    // persistent, weight-stationary kernel (up to 128 streamed channels)
+    if (const int k = agcn_probe(AGCN_WS_DBG, p.dry); k != AGCN_KNOB_UNSET) a.dbg = k;
+    const int rc = (a.M <= 32) ? ws_dispatch<1>(p, stream) : ws_dispatch<2>(p, stream);
     if (rc != AGCN_ERR_UNSUPPORTED) return rc;
   }
-  if (chain_waves() == 8 && chain_tm(a.M) != 1) {
-    if (chain_tm(a.M) == 4) return chain_dispatch_vs<4, 8>(a, wcat, sa_m, sa_i, sa_c, cw2, ws, ws_bytes, stream, dry);
-    return chain_dispatch_vs<2, 8>(a, wcat, sa_m, sa_i, sa_c, cw2, ws, ws_bytes, stream, dry);
-  }
-  if (chain_tm(a.M) == 4) return chain_dispatch_vs<4, 4>(a, wcat, sa_m, sa_i, sa_c, cw2, ws, ws_bytes, stream, dry);
-  if (chain_tm(a.M) == 1) return chain_dispatch_vs<1, 4>(a, wcat, sa_m, sa_i, sa_c, cw2, ws, ws_bytes, stream, dry);
-  return chain_dispatch_vs<2, 4>(a, wcat, sa_m, sa_i, sa_c, cw2, ws, ws_bytes, stream, dry);
+  if (chain_waves() == 8 && chain_tm(a.M) != 1)
+    return chain_tm(a.M) == 4 ? chain_dispatch_vs<4, 8>(p, stream) : chain_dispatch_vs<2, 8>(p, stream);
+  if (chain_tm(a.M) == 4) return chain_dispatch_vs<4, 4>(p, stream);
+  if (chain_tm(a.M) == 1) return chain_dispatch_vs<1, 4>(p, stream);
+  return chain_dispatch_vs<2, 4>(p, stream);
 }
 
 // ---- adjacency gradient (gcn_dadj_chain_kernel): C a multiple of 64; row block 128 when C is a multiple of 128 ----
@@ -1701,10 +1648,8 @@ int agcn_gcn_dadj_chain(const float* dy, const float* wcat, const float* x, floa
   a.dy = dy; a.x = x; a.dpart = dadj_part; a.N = N; a.C = C; a.Cout = Cout; a.T = T; a.V = V;
   a.dy_absmax = dy_absmax;
   a.x_absmax = x_absmax;       // (null: taken by a pass inside; AGCN_DADJ_RED16=0: exact-f32 reduction MFMA)
-  if (!dry)                    // (a profiling switch of the kernel: no part of the routing)
-    if (const char* e = getenv("AGCN_DADJ_DBG")) a.dbg = atoi(e);
-  static const int f16 = getenv("AGCN_DADJ_F16X3") ? atoi(getenv("AGCN_DADJ_F16X3")) : 1;   // 0: bf16x6 (A/B)
-  if (agcn_chain_f16x3() && f16) {
+  a.dbg = agcn_probe(AGCN_DADJ_DBG, dry);
+  if (agcn_chain_f16x3() && agcn_knob(AGCN_DADJ_F16X3)) {
     if (C % 128 == 0) return dadj_chain_launch<4, DADJ_NW, true>(a, wcat, ws, ws_bytes, stream, dry);
     return dadj_chain_launch<2, DADJ_NW64, true>(a, wcat, ws, ws_bytes, stream, dry);
   }

@@ -38,9 +38,3 @@ __device__ __forceinline__ f32x16 sb_mfma6(bf16x8 a0, bf16x8 a1, bf16x8 a2, bf16
   c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, c, 0, 0, 0);
   return c;
 }
-
-template <auto KERN>      // keyed by the kernel itself (instantiations of one template share a function TYPE)
-static inline int agcn_allow_big_lds() {
-  static unsigned char done[AGCN_MAX_DEVICES] = {};
-  return agcn_allow_big_lds_rt(reinterpret_cast<const void*>(KERN), done);
-}

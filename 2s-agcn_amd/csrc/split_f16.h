@@ -102,3 +102,17 @@ static inline int agcn_launch_absmax(const float* x, long n, unsigned* out, hipS
   hipLaunchKernelGGL(absmax_kernel, dim3(2048), dim3(256), 0, stream, x, n, out);
   return agcn_check_launch();
 }
+
+// The range-scale maximum of an f16x3 operand: the one its producer left behind (`given`; nothing is launched), else a
+// streaming pass of our own into `slot`.  Where a launcher keeps its slots (each size query carries the matching slack):
+//   graph chain, adjacency gradient:         the 16 bytes behind the weight images (query: +16)
+//   temporal convolutions (bf16_in_absmax):  the last 16 bytes of the workspace (query: +256)
+//   tap weight gradients (w9_run):           two words behind the transposed copies (query: +512, alignment included)
+//   fused adjacency forward:                 the caller's output slot, else behind the weight images (query: +256)
+static inline int agcn_operand_max(const float* given, const float* tensor, long n, void* slot, hipStream_t stream,
+                                   const float** out) {
+  if (given) { *out = given; return AGCN_OK; }
+  if (int rc = agcn_launch_absmax(tensor, n, static_cast<unsigned*>(slot), stream)) return rc;
+  *out = static_cast<const float*>(slot);
+  return AGCN_OK;
+}

@@ -552,69 +552,48 @@ int w9_transpose(const float* in, float* out, int N, int R, int T, int V, int Tp
 
 template <int RT, int CT, int STRIDE, int TAPS = 9, int SH0 = 0>
 int w9_launch_f16(const W9Args& a, const W9Geom& g, hipStream_t s) {
-  constexpr auto kern = wgrad9_f16_kernel<RT, CT, STRIDE, TAPS, SH0>;
-  int rc = agcn_allow_big_lds<kern>();
-  if (rc) return rc;
   if (TAPS == 9) AGCN_NOTE_KERNEL("wgrad9_f16_kernel<%d, %d, %d>", RT, CT, STRIDE);
   else AGCN_NOTE_KERNEL("wgrad9_f16_kernel<%d, %d, %d, %d, %d>", RT, CT, STRIDE, TAPS, SH0);
-  hipLaunchKernelGGL(kern, dim3((unsigned)(g.nmb * g.ncb), (unsigned)g.nsplit), dim3(256), g.smem_f16, s, a);
-  return agcn_check_launch();
+  return agcn_launch_big<wgrad9_f16_kernel<RT, CT, STRIDE, TAPS, SH0>>(dim3((unsigned)(g.nmb * g.ncb), (unsigned)g.nsplit),
+                                                                       dim3(256), g.smem_f16, s, a);
 }
 
 template <int RT, int CT, int STRIDE>
 int w9_launch(const W9Args& a, const W9Geom& g, hipStream_t s) {
-  constexpr auto kern = wgrad9_bf16_kernel<RT, CT, STRIDE>;
-  int rc = agcn_allow_big_lds<kern>();
-  if (rc) return rc;
   AGCN_NOTE_KERNEL("wgrad9_bf16_kernel<%d, %d, %d>", RT, CT, STRIDE);
-  hipLaunchKernelGGL(kern, dim3((unsigned)(g.nmb * g.ncb), (unsigned)g.nsplit), dim3(256), g.smem_bytes, s, a);
-  return agcn_check_launch();
+  return agcn_launch_big<wgrad9_bf16_kernel<RT, CT, STRIDE>>(dim3((unsigned)(g.nmb * g.ncb), (unsigned)g.nsplit), dim3(256),
+                                                             g.smem_bytes, s, a);
 }
 
-}  // namespace
-
-// stride-1 9-tap problems whose rows and channels tile by 64 (every unit_tcn of the AGCN/AAGCN stacks except the two
-// stride-2 ones)
-bool agcn_wgrad9_bf16_supported(int M, int C, int V, int stride) {
-  if (M % 64 != 0 || C % 64 != 0 || V < 1 || V > 32 || !agcn_chained()) return false;
-  return stride == 1 || (stride == 2 && M % 128 == 0);      // (stride 2 only with the 128-row tile: LDS budget)
+template <int TAPS, int SH0>
+int w9_launch_taps(const W9Args& a, const W9Geom& g, hipStream_t s) {
+  return g.rt == 4 ? w9_launch_f16<4, 1, 1, TAPS, SH0>(a, g, s) : w9_launch_f16<2, 2, 1, TAPS, SH0>(a, g, s);
 }
 
-// T = frames of x; the convolution output has (T - 1) / stride + 1 frames
-size_t agcn_wgrad9_bf16_workspace(int N, int M, int C, int V, int T, int stride) {
-  const W9Geom g = w9_geometry(N, M, C, V, (T - 1) / stride + 1, stride);
-  return g.slab_bytes + g.dyT_bytes + g.xT_bytes + 512;      // (alignment of the copies + two scalars behind them)
-}
+// AGCN_WGRAD9_F16X3=0 keeps the tap weight gradients on bf16x6 (A/B)
+inline bool w9_f16x3() { return agcn_knob(AGCN_WGRAD9_F16X3) != 0; }
 
-// AGCN_WGRAD9_F16X3=0 keeps the 9-tap weight gradient on bf16x6 (A/B)
-static inline bool w9_f16x3() {
-  static const int on = getenv("AGCN_WGRAD9_F16X3") ? atoi(getenv("AGCN_WGRAD9_F16X3")) : 1;
-  return on != 0;
-}
-
-// writes *nslabs slabs [9][M][C] at the start of ws (to be summed by the caller's slab reduction).
-// dy_absmax / x_absmax: device scalars max |dy| / max |x| where their producers left them behind (f16x3 range scales; a
-// reduction pass takes a missing one).
-int agcn_wgrad9_bf16(const float* dy, const float* x, void* ws, size_t ws_bytes, int* nslabs, int N, int M, int C, int V,
-                     int T, int stride, hipStream_t s, const float* dy_absmax, const float* x_absmax) {
-  const int To = (T - 1) / stride + 1;
-  const W9Geom g = w9_geometry(N, M, C, V, To, stride);
-  if (g.slab_bytes + g.dyT_bytes + g.xT_bytes + 512 > ws_bytes) return AGCN_ERR_WORKSPACE;
+// Both entry points: *nslabs slabs [taps][M][C] at the start of ws (summed by the caller's slab reduction), behind them
+// the transposed copies of dy and x and the two maxima.  T = frames of x.  9 taps: pad 4, stride 1 or 2, bf16x6 or f16x3
+// (f16); 3/5/7 taps: stride 1, f16x3 only, tap k reads the window shifted by 4 - pad + k.  dy_absmax / x_absmax: device
+// scalars where the producers left them behind (f16x3 range scales; a reduction pass takes a missing one).
+int w9_run(const float* dy, const float* x, void* ws, size_t ws_bytes, int* nslabs, int N, int M, int C, int V, int T,
+           int taps, int stride, int pad, bool f16, const float* dy_absmax, const float* x_absmax, hipStream_t s,
+           AgcnDryRun* dry) {
+  const int To = (T + 2 * pad - taps) / stride + 1;
+  if (To < 1 || (taps != 9 && !f16)) return AGCN_ERR_UNSUPPORTED;
+  const W9Geom g = w9_geometry(N, M, C, V, To, stride, taps, taps == 9 ? 0 : T);
+  const size_t bytes = g.slab_bytes + g.dyT_bytes + g.xT_bytes + 512;      // (alignment of the copies + the two scalars)
+  if (dry) return agcn_dry_note(dry, 0, bytes);
+  if (bytes > ws_bytes) return AGCN_ERR_WORKSPACE;
   unsigned char* base = (unsigned char*)ws;
   float* dyT = (float*)(base + ((g.slab_bytes + 255) & ~(size_t)255));
   float* xT = (float*)((unsigned char*)dyT + g.dyT_bytes);
   if ((size_t)((unsigned char*)xT - base) + g.xT_bytes + 8 > ws_bytes) return AGCN_ERR_WORKSPACE;
-  const bool f16 = agcn_npl() == 3 && w9_f16x3();
   if (f16) {
-    unsigned* scr = reinterpret_cast<unsigned*>((unsigned char*)xT + g.xT_bytes);     // two scalars behind the copies
-    if (!dy_absmax) {
-      if (int rc = agcn_launch_absmax(dy, (long)N * M * To * V, scr, s)) return rc;
-      dy_absmax = reinterpret_cast<const float*>(scr);
-    }
-    if (!x_absmax) {
-      if (int rc = agcn_launch_absmax(x, (long)N * C * T * V, scr + 1, s)) return rc;
-      x_absmax = reinterpret_cast<const float*>(scr + 1);
-    }
+    unsigned* scr = reinterpret_cast<unsigned*>((unsigned char*)xT + g.xT_bytes);
+    if (int rc = agcn_operand_max(dy_absmax, dy, (long)N * M * To * V, scr, s, &dy_absmax)) return rc;
+    if (int rc = agcn_operand_max(x_absmax, x, (long)N * C * T * V, scr + 1, s, &x_absmax)) return rc;
   }
   int rc = w9_transpose(dy, dyT, N, M, To, V, g.Tp, 1, s, f16 ? dy_absmax : nullptr);
   if (rc) return rc;
@@ -626,81 +605,20 @@ int agcn_wgrad9_bf16(const float* dy, const float* x, void* ws, size_t ws_bytes,
   a.nchunk = g.nchunk; a.units = g.units; a.units_per_split = g.units_per_split; a.ncb = g.ncb;
   a.npl = agcn_npl();
   *nslabs = g.nsplit;
-  if (f16) {
-    a.dyH = reinterpret_cast<const unsigned short*>(dyT);
-    a.xH = reinterpret_cast<const unsigned short*>(xT);
-    a.dy_plane = (long)N * V * M * g.Tp;
-    a.x_plane = (long)N * V * C * stride * g.Tp;
-    a.dy_absmax = dy_absmax; a.x_absmax = x_absmax;
-    if (stride == 2) return w9_launch_f16<4, 1, 2>(a, g, s);
-    return g.rt == 4 ? w9_launch_f16<4, 1, 1>(a, g, s) : w9_launch_f16<2, 2, 1>(a, g, s);
+  if (!f16) {
+    if (stride == 2) return w9_launch<4, 1, 2>(a, g, s);
+    return g.rt == 4 ? w9_launch<4, 1, 1>(a, g, s) : w9_launch<2, 2, 1>(a, g, s);
   }
-  if (stride == 2) return w9_launch<4, 1, 2>(a, g, s);
-  return g.rt == 4 ? w9_launch<4, 1, 1>(a, g, s) : w9_launch<2, 2, 1>(a, g, s);
-}
-
-// ---- stride-1 3/5/7-tap weight gradients (agcn_tconv_bwd_weight) on the same f16x3 kernel: tap k reads the window
-// shifted by 4 - pad + k, so every tap's frames lie in the 16-frame window while taps - pad <= 5 ("same" padding, and
-// pad 0 up to 5 taps).  Only in the default split mode (the f16x3 arithmetic); the caller runs the exact-f32 kernel
-// otherwise. ----
-bool agcn_wgrad_tconv_f16_supported(int M, int C, int V, int taps, int stride, int pad) {
-  if (stride != 1 || (taps != 3 && taps != 5 && taps != 7) || pad < 0 || pad > (taps - 1) / 2 || taps - pad > 5)
-    return false;
-  return agcn_gemm_precision() == 3 && w9_f16x3() && M % 64 == 0 && C % 64 == 0 && V >= 1 && V <= 32;
-}
-
-// T = frames of x
-size_t agcn_wgrad_tconv_f16_workspace(int N, int M, int C, int V, int T, int taps, int pad) {
-  const int To = T + 2 * pad - taps + 1;
-  const W9Geom g = w9_geometry(N, M, C, V, To, 1, taps, T);
-  return g.slab_bytes + g.dyT_bytes + g.xT_bytes + 512;
-}
-
-namespace {
-template <int TAPS, int SH0>
-int w9_launch_taps(const W9Args& a, const W9Geom& g, hipStream_t s) {
-  return g.rt == 4 ? w9_launch_f16<4, 1, 1, TAPS, SH0>(a, g, s) : w9_launch_f16<2, 2, 1, TAPS, SH0>(a, g, s);
-}
-}  // namespace
-
-// writes *nslabs slabs [taps][M][C] at the start of ws (summed by the caller's slab reduction); the maxima as for 9 taps
-int agcn_wgrad_tconv_f16(const float* dy, const float* x, void* ws, size_t ws_bytes, int* nslabs, int N, int M, int C,
-                         int V, int T, int taps, int pad, hipStream_t s, const float* dy_absmax, const float* x_absmax) {
-  if (!agcn_wgrad_tconv_f16_supported(M, C, V, taps, 1, pad)) return AGCN_ERR_UNSUPPORTED;
-  const int To = T + 2 * pad - taps + 1;
-  if (To < 1) return AGCN_ERR_UNSUPPORTED;
-  const W9Geom g = w9_geometry(N, M, C, V, To, 1, taps, T);
-  if (g.slab_bytes + g.dyT_bytes + g.xT_bytes + 512 > ws_bytes) return AGCN_ERR_WORKSPACE;
-  unsigned char* base = (unsigned char*)ws;
-  float* dyT = (float*)(base + ((g.slab_bytes + 255) & ~(size_t)255));
-  float* xT = (float*)((unsigned char*)dyT + g.dyT_bytes);
-  if ((size_t)((unsigned char*)xT - base) + g.xT_bytes + 8 > ws_bytes) return AGCN_ERR_WORKSPACE;
-  unsigned* scr = reinterpret_cast<unsigned*>((unsigned char*)xT + g.xT_bytes);     // two scalars behind the copies
-  if (!dy_absmax) {
-    if (int rc = agcn_launch_absmax(dy, (long)N * M * To * V, scr, s)) return rc;
-    dy_absmax = reinterpret_cast<const float*>(scr);
-  }
-  if (!x_absmax) {
-    if (int rc = agcn_launch_absmax(x, (long)N * C * T * V, scr + 1, s)) return rc;
-    x_absmax = reinterpret_cast<const float*>(scr + 1);
-  }
-  int rc = w9_transpose(dy, dyT, N, M, To, V, g.Tp, 1, s, dy_absmax);
-  if (rc) return rc;
-  rc = w9_transpose(x, xT, N, C, T, V, g.Tp, 1, s, x_absmax);
-  if (rc) return rc;
-  W9Args a = {};
-  a.dyT = dyT; a.xT = xT; a.part = (float*)ws;
-  a.N = N; a.M = M; a.C = C; a.V = V; a.T = To; a.Tp = g.Tp;
-  a.nchunk = g.nchunk; a.units = g.units; a.units_per_split = g.units_per_split; a.ncb = g.ncb;
-  a.npl = 3;
   a.dyH = reinterpret_cast<const unsigned short*>(dyT);
   a.xH = reinterpret_cast<const unsigned short*>(xT);
   a.dy_plane = (long)N * V * M * g.Tp;
-  a.x_plane = (long)N * V * C * g.Tp;
+  a.x_plane = (long)N * V * C * stride * g.Tp;
   a.dy_absmax = dy_absmax; a.x_absmax = x_absmax;
-  *nslabs = g.nsplit;
-  const int sh0 = 4 - pad;
-  switch (taps * 16 + sh0) {
+  if (taps == 9) {
+    if (stride == 2) return w9_launch_f16<4, 1, 2>(a, g, s);
+    return g.rt == 4 ? w9_launch_f16<4, 1, 1>(a, g, s) : w9_launch_f16<2, 2, 1>(a, g, s);
+  }
+  switch (taps * 16 + 4 - pad) {
     case 3 * 16 + 3: return w9_launch_taps<3, 3>(a, g, s);      // pad 1
     case 3 * 16 + 4: return w9_launch_taps<3, 4>(a, g, s);      // pad 0
     case 5 * 16 + 2: return w9_launch_taps<5, 2>(a, g, s);      // pad 2
@@ -710,4 +628,35 @@ int agcn_wgrad_tconv_f16(const float* dy, const float* x, void* ws, size_t ws_by
     case 7 * 16 + 2: return w9_launch_taps<7, 2>(a, g, s);      // pad 2
     default: return AGCN_ERR_UNSUPPORTED;
   }
+}
+
+}  // namespace
+
+// stride-1 9-tap problems whose rows and channels tile by 64 (every unit_tcn of the AGCN/AAGCN stacks except the two
+// stride-2 ones)
+bool agcn_wgrad9_bf16_supported(int M, int C, int V, int stride) {
+  if (M % 64 != 0 || C % 64 != 0 || V < 1 || V > 32 || !agcn_chained()) return false;
+  return stride == 1 || (stride == 2 && M % 128 == 0);      // (stride 2 only with the 128-row tile: LDS budget)
+}
+
+int agcn_wgrad9_bf16(const float* dy, const float* x, void* ws, size_t ws_bytes, int* nslabs, int N, int M, int C, int V,
+                     int T, int stride, hipStream_t s, const float* dy_absmax, const float* x_absmax, AgcnDryRun* dry) {
+  return w9_run(dy, x, ws, ws_bytes, nslabs, N, M, C, V, T, 9, stride, 4, agcn_npl() == 3 && w9_f16x3(), dy_absmax,
+                x_absmax, s, dry);
+}
+
+// ---- stride-1 3/5/7-tap weight gradients (agcn_tconv_bwd_weight) on the same f16x3 kernel: every tap's frames lie in
+// the 16-frame window while taps - pad <= 5 ("same" padding, and pad 0 up to 5 taps).  Only in the default split mode
+// (the f16x3 arithmetic); the caller runs the exact-f32 kernel otherwise. ----
+bool agcn_wgrad_tconv_f16_supported(int M, int C, int V, int taps, int stride, int pad) {
+  if (stride != 1 || (taps != 3 && taps != 5 && taps != 7) || pad < 0 || pad > (taps - 1) / 2 || taps - pad > 5)
+    return false;
+  return agcn_gemm_precision() == 3 && w9_f16x3() && M % 64 == 0 && C % 64 == 0 && V >= 1 && V <= 32;
+}
+
+int agcn_wgrad_tconv_f16(const float* dy, const float* x, void* ws, size_t ws_bytes, int* nslabs, int N, int M, int C,
+                         int V, int T, int taps, int pad, hipStream_t s, const float* dy_absmax, const float* x_absmax,
+                         AgcnDryRun* dry) {
+  if (!agcn_wgrad_tconv_f16_supported(M, C, V, taps, 1, pad)) return AGCN_ERR_UNSUPPORTED;
+  return w9_run(dy, x, ws, ws_bytes, nslabs, N, M, C, V, T, taps, 1, pad, true, dy_absmax, x_absmax, s, dry);
 }

@@ -705,37 +705,15 @@ int wc_launch(WcArgs a, void* ws, size_t ws_bytes, int* nslabs_out, hipStream_t 
   if ((size_t)g.nslabs * a.wsize * 4 > ws_bytes) return AGCN_ERR_WORKSPACE;
   a.part = (float*)ws;
   a.ntiles = g.ntiles; a.pairs_per_split = g.pairs_per_split; a.ncg = g.ncg; a.XP = g.XP;
-  auto kern = wgrad_chain_kernel<AGG, TM, NCB, VS, NW>;
-  static unsigned char lds_ok[AGCN_MAX_DEVICES] = {};   // per (kernel instantiation, device): the attribute is per device
-  if (int e = agcn_allow_big_lds_rt(reinterpret_cast<const void*>(kern), lds_ok)) return e;
-  hipLaunchKernelGGL(kern, dim3(g.grid_x, g.nsplit), dim3(NW * 64), g.smem_bytes, stream, a);
   *nslabs_out = g.nslabs;
-  return agcn_check_launch();
+  return agcn_launch_big<wgrad_chain_kernel<AGG, TM, NCB, VS, NW>>(dim3(g.grid_x, g.nsplit), dim3(NW * 64), g.smem_bytes,
+                                                                   stream, a);
 }
 
-template <int AGG, int TM, int NCB>
+static inline bool wc_four_waves() { return agcn_knob(AGCN_WGRAD_NW) != 8; }
+
+template <int AGG, int TM, int NCB, int NW = 8>
 int wc_dispatch_vs(const WcArgs& a, void* ws, size_t ws_bytes, int* nslabs, hipStream_t s, AgcnDryRun* dry) {
-  const int vs = (a.V + 1) / 2;
-  if constexpr (!AGG) {
-    return wc_launch<AGG, TM, NCB, 1>(a, ws, ws_bytes, nslabs, s, dry);
-  } else {
-    if (vs == 13) return wc_launch<AGG, TM, NCB, 13>(a, ws, ws_bytes, nslabs, s, dry);
-    if (vs == 9) return wc_launch<AGG, TM, NCB, 9>(a, ws, ws_bytes, nslabs, s, dry);
-    return wc_launch<AGG, TM, NCB, 16>(a, ws, ws_bytes, nslabs, s, dry);
-  }
-}
-
-static inline bool wc_four_waves() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("AGCN_WGRAD_NW");
-    v = (e && atoi(e) == 8) ? 0 : 1;
-  }
-  return v == 1;
-}
-
-template <int AGG, int TM, int NCB, int NW>
-int wc_dispatch_vs4(const WcArgs& a, void* ws, size_t ws_bytes, int* nslabs, hipStream_t s, AgcnDryRun* dry) {
   const int vs = (a.V + 1) / 2;
   if constexpr (!AGG) {
     return wc_launch<AGG, TM, NCB, 1, NW>(a, ws, ws_bytes, nslabs, s, dry);
@@ -749,8 +727,8 @@ int wc_dispatch_vs4(const WcArgs& a, void* ws, size_t ws_bytes, int* nslabs, hip
 template <int AGG, int TM>
 int wc_dispatch_ncb(const WcArgs& a, void* ws, size_t ws_bytes, int* nslabs, hipStream_t s, AgcnDryRun* dry) {
   // (the aggregated variant at 128+ channels runs out of registers with 4-wave workgroups: measured 8 % slower)
-  if (wc_four_waves() && !AGG && a.C % 128 == 0) return wc_dispatch_vs4<AGG, TM, 4, 4>(a, ws, ws_bytes, nslabs, s, dry);
-  if (wc_four_waves() && a.C % 64 == 0 && !(AGG && a.C % 128 == 0)) return wc_dispatch_vs4<AGG, TM, 2, 4>(a, ws, ws_bytes, nslabs, s, dry);
+  if (wc_four_waves() && !AGG && a.C % 128 == 0) return wc_dispatch_vs<AGG, TM, 4, 4>(a, ws, ws_bytes, nslabs, s, dry);
+  if (wc_four_waves() && a.C % 64 == 0 && !(AGG && a.C % 128 == 0)) return wc_dispatch_vs<AGG, TM, 2, 4>(a, ws, ws_bytes, nslabs, s, dry);
   if (a.C % 256 == 0) return wc_dispatch_vs<AGG, TM, 8>(a, ws, ws_bytes, nslabs, s, dry);
   if (a.C % 128 == 0) return wc_dispatch_vs<AGG, TM, 4>(a, ws, ws_bytes, nslabs, s, dry);
   if (a.C % 64 == 0) return wc_dispatch_vs<AGG, TM, 2>(a, ws, ws_bytes, nslabs, s, dry);
@@ -781,10 +759,7 @@ WcGeom wc_geom_pc(int N, int M, int C, int V, int T_out, bool bch = false, int p
 }
 
 // AGCN_WGRAD_F16X3=0 keeps the weight gradients on bf16x6 (A/B)
-static inline bool wc_f16x3() {
-  static const int on = getenv("AGCN_WGRAD_F16X3") ? atoi(getenv("AGCN_WGRAD_F16X3")) : 1;
-  return on != 0;
-}
+static inline bool wc_f16x3() { return agcn_knob(AGCN_WGRAD_F16X3) != 0; }
 
 template <int AGG, int TM, int NCB, int NRB, int VS, int NWP = 4>
 int wc_launch_pc(WcArgs a, void* ws, size_t ws_bytes, int* nslabs_out, hipStream_t stream, AgcnDryRun* dry) {
@@ -797,21 +772,13 @@ int wc_launch_pc(WcArgs a, void* ws, size_t ws_bytes, int* nslabs_out, hipStream
   a.part = (float*)ws;
   a.ntiles = g.ntiles; a.pairs_per_split = g.pairs_per_split; a.ncg = g.ncg; a.XP = g.XP;
   const dim3 grid(g.grid_x, g.nsplit), block((8 + NWP) * 64);
-  if (f16) {
-    auto kern = wgrad_pc_kernel<AGG, TM, NCB, VS, NRB, 8, NWP, true>;
-    static unsigned char lds_ok[AGCN_MAX_DEVICES] = {};
-    if (int e = agcn_allow_big_lds_rt(reinterpret_cast<const void*>(kern), lds_ok)) return e;
-    AGCN_NOTE_KERNEL("wgrad_pc_kernel<%d, %d, %d, %d, %d, 8, %d, true>", AGG, TM, NCB, VS, NRB, NWP);
-    hipLaunchKernelGGL(kern, grid, block, g.smem_bytes, stream, a);
-  } else {
-    auto kern = wgrad_pc_kernel<AGG, TM, NCB, VS, NRB, 8, NWP>;
-    static unsigned char lds_ok[AGCN_MAX_DEVICES] = {};
-    if (int e = agcn_allow_big_lds_rt(reinterpret_cast<const void*>(kern), lds_ok)) return e;
-    AGCN_NOTE_KERNEL("wgrad_pc_kernel<%d, %d, %d, %d, %d, 8, %d>", AGG, TM, NCB, VS, NRB, NWP);
-    hipLaunchKernelGGL(kern, grid, block, g.smem_bytes, stream, a);
-  }
   *nslabs_out = g.nslabs;
-  return agcn_check_launch();
+  if (f16) {
+    AGCN_NOTE_KERNEL("wgrad_pc_kernel<%d, %d, %d, %d, %d, 8, %d, true>", AGG, TM, NCB, VS, NRB, NWP);
+    return agcn_launch_big<wgrad_pc_kernel<AGG, TM, NCB, VS, NRB, 8, NWP, true>>(grid, block, g.smem_bytes, stream, a);
+  }
+  AGCN_NOTE_KERNEL("wgrad_pc_kernel<%d, %d, %d, %d, %d, 8, %d>", AGG, TM, NCB, VS, NRB, NWP);
+  return agcn_launch_big<wgrad_pc_kernel<AGG, TM, NCB, VS, NRB, 8, NWP>>(grid, block, g.smem_bytes, stream, a);
 }
 
 template <int AGG, int TM, int NCB, int NRB>
@@ -822,11 +789,9 @@ int wc_dispatch_pc_vs(const WcArgs& a, void* ws, size_t ws_bytes, int* nslabs, h
   } else {
     // (the split-bf16 aggregation measured 3-7 % SLOWER here: the consumer re-splits its x fragment for every subset
     // and becomes VALU-bound; AGCN_WC_BCH=1 selects it)
-    static const int bch = getenv("AGCN_WC_BCH") ? atoi(getenv("AGCN_WC_BCH")) : 0;
-    if (bch && a.npl == 3) return wc_launch_pc<AGG, TM, NCB, NRB, 0>(a, ws, ws_bytes, nslabs, s, dry);
+    if (agcn_knob(AGCN_WC_BCH) && a.npl == 3) return wc_launch_pc<AGG, TM, NCB, NRB, 0>(a, ws, ws_bytes, nslabs, s, dry);
     // with both maxima: the aggregation on f16x3 as well (AGCN_WC_AGG16=0: exact-f32 aggregation chain, round 2)
-    static const int agg16 = getenv("AGCN_WC_AGG16") ? atoi(getenv("AGCN_WC_AGG16")) : 1;
-    if (agg16 && a.dy_absmax && a.in_absmax && a.npl == 3 && wc_f16x3())
+    if (agcn_knob(AGCN_WC_AGG16) && a.dy_absmax && a.in_absmax && a.npl == 3 && wc_f16x3())
       return wc_launch_pc<AGG, TM, NCB, NRB, 0>(a, ws, ws_bytes, nslabs, s, dry);
     if (vs == 13) return wc_launch_pc<AGG, TM, NCB, NRB, 13>(a, ws, ws_bytes, nslabs, s, dry);
     if (vs == 9) return wc_launch_pc<AGG, TM, NCB, NRB, 9>(a, ws, ws_bytes, nslabs, s, dry);
@@ -835,14 +800,7 @@ int wc_dispatch_pc_vs(const WcArgs& a, void* ws, size_t ws_bytes, int* nslabs, h
 }
 
 // AGCN_WC_PC=0 selects the single-role kernel (A/B measurement)
-static inline bool wc_pc_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("AGCN_WC_PC");
-    v = (e && atoi(e) == 0) ? 0 : 1;
-  }
-  return v == 1;
-}
+static inline bool wc_pc_enabled() { return agcn_knob(AGCN_WC_PC) == 1; }
 static inline bool wc_pc_applies(int C) { return wc_pc_enabled() && C % 64 == 0; }
 
 // Tiles (8 consumer waves, 2 frames per stage).  AGG: a consumer wave holds 3 subsets x 2 row tiles of accumulators:
@@ -857,7 +815,7 @@ int wc_dispatch_pc(const WcArgs& a, void* ws, size_t ws_bytes, int* nslabs, hipS
     // The plain 1x1 gradients are producer-bound (both operands split by the 4 producers).  Up to 192 rows, 8 producer
     // waves on 64-row blocks (4 waves per SIMD, 128 VGPRs) win: l6 shape 390 -> 322 us; with more rows the extra
     // passes over x cost more than the producers gain (l9: 628 -> 697 us).  AGCN_WC_NWP8=0 / 1 forces either.
-    static const int nwp8 = getenv("AGCN_WC_NWP8") ? atoi(getenv("AGCN_WC_NWP8")) : -1;
+    const int nwp8 = agcn_knob(AGCN_WC_NWP8);
     if (a.C % 128 == 0 && (nwp8 == 1 || (nwp8 < 0 && a.M > 64 && a.M <= 192)))
       return wc_launch_pc<0, 2, 4, 1, 1, 8>(a, ws, ws_bytes, nslabs, s, dry);
     if (a.C % 128 == 0) {
@@ -880,10 +838,7 @@ int agcn_wgrad_chain(int agg, const float* dy, const float* x, const float* adj,
   WcArgs a = {};
   a.dy_absmax = dy_absmax; a.in_absmax = x_absmax;
   a.npl = agcn_npl();
-  if (!dry) {                  // kernel switches, read per call: no part of the routing
-    { const char* e = getenv("AGCN_WC_PAD"); a.pad = (e && atoi(e) == 0) ? 0 : 1; }
-    { const char* e = getenv("AGCN_WC_DBG"); a.dbg = e ? atoi(e) : 0; }
-  }
+  a.pad = agcn_probe(AGCN_WC_PAD, dry); a.dbg = agcn_probe(AGCN_WC_DBG, dry);   // kernel switches: no part of the routing
   a.dy = dy; a.in = x; a.adj = adj; a.N = N; a.M = M; a.C = C; a.V = V; a.T_src = T_src; a.T_out = T_out;
   a.stride = stride; a.wsize = (long)(agg ? 3 : 1) * M * C;
   // (64 channels x 64 rows with aggregation: the two-row-block tile of the producer/consumer kernel would be half empty)

@@ -179,6 +179,47 @@ def test_gcn_dadj_writes_the_queried_slots(C, Cout):
     assert rel(part.double().sum(2), ref) < _tol(L)
 
 
+TAP_WGRAD_CASES = [
+    # Cin, Cout, T, V, taps, stride, pad, kernel of the default mode (the smallest shape that reaches each instantiation class)
+    (64, 64, 20, 25, 9, 1, 4, 'wgrad9_f16_kernel<2, 2, 1>'),
+    (128, 128, 20, 25, 9, 2, 4, 'wgrad9_f16_kernel<4, 1, 2>'),
+    (64, 64, 20, 18, 3, 1, 1, 'wgrad9_f16_kernel<2, 2, 1, 3, 3>'),
+]
+GUARD_BYTES = 4096
+
+
+@pytest.mark.parametrize('case', TAP_WGRAD_CASES)
+def test_tap_wgrad_writes_inside_the_queried_workspace(case):
+    """The tap weight gradients keep their slabs, transposed copies and the two maxima they take themselves (no maxima
+    are passed) inside the bytes agcn_tconv_bwd_weight_workspace reports: a guard behind them keeps its pattern."""
+    dev = _gpu()
+    lib, L = _lib()
+    Cin, Cout, T, V, taps, stride, pad, kernel = case
+    N = 2
+    g = torch.Generator().manual_seed(17 + taps + stride + Cout)
+    x = rnd(g, N, Cin, T, V)
+    w = torch.zeros(Cout, Cin, taps, 1, dtype=torch.float64, requires_grad=True)
+    y = F.conv2d(x, w, None, stride=(stride, 1), padding=(pad, 0))
+    dy = rnd(g, *y.shape)
+    y.backward(dy)
+    dw_ref = w.grad.reshape(Cout, Cin, taps)
+    xg, dyg = x.float().to(dev), dy.float().to(dev)
+    nb = L.agcn_tconv_bwd_weight_workspace(N, Cin, Cout, T, V, taps, stride, pad)
+    assert nb > 0
+    words = (nb + 3) // 4
+    ws = torch.full((words + GUARD_BYTES // 4,), PATTERN, dtype=torch.int32, device=dev)
+    dw = torch.empty((Cout, Cin, taps), dtype=torch.float32, device=dev)
+    lib.check(L.agcn_tconv_bwd_weight(lib.ptr(dyg), lib.ptr(xg), lib.ptr(dw), ws.data_ptr(), nb, N, Cin, Cout, T, V, taps,
+                                      stride, pad, None, None, lib.stream()), 'agcn_tconv_bwd_weight')
+    torch.cuda.synchronize()
+    assert bool((ws[words:] == PATTERN).all()), "the launch wrote past the queried workspace"
+    if L.agcn_gemm_mode().decode() == 'bf16x6':
+        assert L.agcn_last_kernel().decode() == kernel, L.agcn_last_kernel().decode()
+    err = rel(dw, dw_ref)
+    print(f"tap wgrad {case[:7]}: rel err {err:.3e} (tol {_tol(L):.1e})")
+    assert err < _tol(L)
+
+
 @pytest.mark.parametrize('mode', ['f32', 'bf16'])
 def test_slab_contract_other_gemm_modes_subprocess(mode):
     """The contract holds in every arithmetic mode: this file once more in a process with AGCN_GEMM=<mode>."""

@@ -23,10 +23,9 @@ Checked by calling the entry point itself with placeholder tensors and a ZERO-by
 AGCN_ERR_UNSUPPORTED, any shape with a route answers AGCN_ERR_WORKSPACE; neither reaches a HIP call.
 
 What the probe relies on, since its placeholder is a host buffer and the file also runs on GPU machines: every launcher
-compares its need with workspace_bytes (here 0) before its first HIP call.  The leaves that take a dry run do so right
-after the feasibility checks; agcn_wgrad9_bf16 and agcn_wgrad_tconv_f16 (wgrad9_bf16.hip) return AGCN_ERR_WORKSPACE from
-their first statement after the geometry.  A shape that was wrongly listed would so fail the assertion with -2, never
-reach a launch.  The operand maxima are passed so that no entry point starts an absmax pass of its own.
+compares its need with workspace_bytes (here 0) before its first HIP call: every leaf takes the dry run, or makes that
+comparison, right after its feasibility checks.  A shape that was wrongly listed would so fail the assertion with -2,
+never reach a launch.  The operand maxima are passed so that no entry point starts an absmax pass of its own.
 """
 import ctypes
 import importlib.util
