@@ -110,6 +110,12 @@ SIGNATURES = {
     "agcn_prenorm_windows": (_I, [_P] * 7 + [_I] * 16 + [_P]),
     "agcn_skel_smooth": (_I, [_P, _P] + [_I] * 4 + [_P]),
     "agcn_skel_append_many": (_I, [_P] * 4 + [_I] * 5 + [_P]),
+    "agcn_tokens_fwd": (_I, [_P, _P, _P, _I, _P] + [_I] * 5 + [_P]),
+    "agcn_tokens_bwd": (_I, [_P] * 4 + [_I] * 7 + [_P]),
+    "agcn_mha_fwd": (_I, [_P, _P, _I, _P, _F, _P, _P, _P] + [_I] * 4 + [_P]),
+    "agcn_mha_bwd": (_I, [_P] * 4 + [_F, _P, _P, _Z] + [_I] * 4 + [_P]),
+    "agcn_ln_fwd": (_I, [_P] * 4 + [_F, _P, _P, _P, ctypes.c_long, _I, _P]),
+    "agcn_ln_bwd": (_I, [_P] * 9 + [_P, _Z, ctypes.c_long, _I, _P]),
 }
 
 _lib = None

@@ -1538,3 +1538,166 @@ class TCNGCNUnitFunction(torch.autograd.Function):
 # the names above are the forward signatures: an argument added to one and not to the other fails here, at import
 for _f in (UnitGCNFunction, UnitTCNFunction, TCNResidualFunction, TCNGCNUnitFunction):
     assert _f.forward.__code__.co_varnames[1:_f.forward.__code__.co_argcount] == _f.ARGS.names, _f.__name__
+
+
+# ------------------------------------------------------------------------------------------------
+# transformer-encoder head of aagcn_v17 (csrc/encoder.hip): tokens, attention core, add + LayerNorm
+# ------------------------------------------------------------------------------------------------
+def encoder_hip_enabled():
+    """AGCN_ENCODER_HIP=0 runs the encoder head as the tensor-code composition of the same maths (``tokens_ref``,
+    ``mha_ref``, ``add_ln_ref``): for A/B, and as the in-process comparison of the dropout path."""
+    return os.environ.get('AGCN_ENCODER_HIP', '1') != '0'
+
+
+# diagnostic counters (never read by a compute path): encoder layers that ran on the HIP kernels / as tensor code
+ENCODER_STATS = {'layers_hip': 0, 'layers_tensor': 0}
+
+
+def _ptr_u8(t):
+    if t is None:
+        return None
+    if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.uint8):
+        raise RuntimeError(f"agcn_amd: expected a contiguous uint8 GPU tensor, got {t.dtype} on {t.device}")
+    return t.data_ptr()
+
+
+class TokensFunction(torch.autograd.Function):
+    """x (N*M, C, T', V), cls (1, 1, D) or None, pe (1, rows >= L, D) or None -> tok (N, L, D): token cls + m*T' + t,
+    feature v*C + c, plus the positional rows (reference aagcn_v17.py:290-299).  args: x, cls, pe, M"""
+
+    @staticmethod
+    def forward(ctx, x, cls, pe, M):
+        x = x.contiguous()
+        NM, C, Tp, V = x.shape
+        N, D = NM // M, V * C
+        L = M * Tp + (cls is not None)
+        cls_ = None if cls is None else cls.contiguous()
+        pe_ = None if pe is None else pe.contiguous()
+        tok = _empty((N, L, D), x)
+        _lib.check(_L().agcn_tokens_fwd(_lib.ptr(x), _lib.ptr(cls_), _lib.ptr(pe_), 0 if pe is None else pe.shape[-2],
+                                        _lib.ptr(tok), N, M, C, Tp, V, _lib.stream()), "agcn_tokens_fwd")
+        ctx.dims = (N, M, C, Tp, V, cls is not None, None if pe is None else tuple(pe.shape))
+        return tok
+
+    @staticmethod
+    def backward(ctx, dtok):
+        N, M, C, Tp, V, has_cls, pe_shape = ctx.dims
+        dtok = dtok.contiguous()
+        ng = ctx.needs_input_grad
+        dx = _empty((N * M, C, Tp, V), dtok) if ng[0] else None
+        dcls = _empty((1, 1, V * C), dtok) if (has_cls and ng[1]) else None
+        dpe = _empty(pe_shape, dtok) if (pe_shape is not None and ng[2]) else None
+        _lib.check(_L().agcn_tokens_bwd(_lib.ptr(dtok), _lib.ptr(dx), _lib.ptr(dcls), _lib.ptr(dpe), int(has_cls),
+                                        0 if dpe is None else pe_shape[-2], N, M, C, Tp, V, _lib.stream()),
+                   "agcn_tokens_bwd")
+        return dx, dcls, dpe, None
+
+
+def tokens_ref(x, cls, pe, M):
+    """The tensor-code form of TokensFunction (any device, any dtype)."""
+    NM, C, Tp, V = x.shape
+    N = NM // M
+    tok = x.reshape(N, M, C, Tp, V).permute(0, 1, 3, 4, 2).reshape(N, M * Tp, V * C)
+    if cls is not None:
+        tok = torch.cat((cls.expand(N, 1, V * C), tok), dim=1)
+    if pe is not None:
+        tok = tok + pe[:, :tok.size(1), :]
+    return tok
+
+
+class MHAFunction(torch.autograd.Function):
+    """The attention core of one encoder layer on the packed in_proj output.
+    args: qkv (N, L, 3D), H, null_tok (N, L) uint8 or None, causal (0 none, 1 j <= i, 2 j >= i), keep (N, H, L, L) uint8
+    or None, keep_scale, need_avg -> ctx (N, L, D), avg (N, L, L) or None (head mean after dropout; not differentiable)"""
+
+    @staticmethod
+    def forward(ctx, qkv, H, null_tok, causal, keep, keep_scale, need_avg):
+        qkv = qkv.contiguous()
+        N, L, D3 = qkv.shape
+        D = D3 // 3
+        dh = D // H
+        out = _empty((N, L, D), qkv)
+        need_bwd = ctx.needs_input_grad[0]
+        prob = _empty((N, H, L, L), qkv) if need_bwd else None
+        avg = _empty((N, L, L), qkv) if need_avg else None
+        _lib.check(_L().agcn_mha_fwd(_lib.ptr(qkv), _ptr_u8(null_tok), int(causal), _ptr_u8(keep), float(keep_scale),
+                                     _lib.ptr(out), _lib.ptr(prob), _lib.ptr(avg), N, L, H, dh, _lib.stream()),
+                   "agcn_mha_fwd")
+        if need_bwd:
+            ctx.save_for_backward(qkv, prob, keep)
+        ctx.dims, ctx.keep_scale = (N, L, H, dh), float(keep_scale)
+        if avg is not None:
+            ctx.mark_non_differentiable(avg)
+        return out, avg
+
+    @staticmethod
+    def backward(ctx, dout, _davg):
+        qkv, prob, keep = ctx.saved_tensors
+        N, L, H, dh = ctx.dims
+        dout = dout.contiguous()
+        dqkv = torch.empty_like(qkv)
+        ws = _empty((N, H, L, L), qkv)
+        _lib.check(_L().agcn_mha_bwd(_lib.ptr(dout), _lib.ptr(qkv), _lib.ptr(prob), _ptr_u8(keep), ctx.keep_scale,
+                                     _lib.ptr(dqkv), ws.data_ptr(), ws.numel() * 4, N, L, H, dh, _lib.stream()),
+                   "agcn_mha_bwd")
+        return dqkv, None, None, None, None, None, None
+
+
+def mha_ref(qkv, H, null_tok=None, causal=0, keep=None, keep_scale=1.0, need_avg=False, want_prob=False):
+    """The tensor-code form of MHAFunction (any device, any dtype); want_prob also returns the softmax before dropout."""
+    N, L, D3 = qkv.shape
+    D = D3 // 3
+    dh = D // H
+    q, k, v = (t.reshape(N, L, H, dh).transpose(1, 2) for t in qkv.split(D, dim=-1))
+    s = (q @ k.transpose(-1, -2)) / (dh ** 0.5)
+    masked = torch.zeros(N, 1, L, L, dtype=torch.bool, device=qkv.device)
+    if null_tok is not None:
+        nt = null_tok.bool()
+        masked = masked | (nt[:, None, :, None] & nt[:, None, None, :])
+    if causal:
+        i = torch.arange(L, device=qkv.device)
+        masked = masked | ((i[None, :] > i[:, None]) if causal == 1 else (i[None, :] < i[:, None]))[None, None]
+    s = s.masked_fill(masked, float('-inf'))
+    dead = masked.all(-1, keepdim=True)
+    p = torch.softmax(s.masked_fill(dead, 0.0), dim=-1).masked_fill(dead, 0.0)
+    pd = p if keep is None else p * (keep.to(p.dtype) * keep_scale)
+    out = (pd @ v).transpose(1, 2).reshape(N, L, D)
+    avg = pd.mean(1) if need_avg else None
+    return (out, avg, p) if want_prob else (out, avg)
+
+
+class AddLayerNormFunction(torch.autograd.Function):
+    """out = LayerNorm(a + b) over the last dimension (b None: of a).  args: a, b, weight, bias, eps"""
+
+    @staticmethod
+    def forward(ctx, a, b, weight, bias, eps):
+        a = a.contiguous()
+        b = None if b is None else b.contiguous()
+        D = a.shape[-1]
+        R = a.numel() // D
+        out = torch.empty_like(a)
+        mean, rstd = _empty((R,), a), _empty((R,), a)
+        _lib.check(_L().agcn_ln_fwd(_lib.ptr(a), _lib.ptr(b), _lib.ptr(weight), _lib.ptr(bias), float(eps), _lib.ptr(out),
+                                    _lib.ptr(mean), _lib.ptr(rstd), R, D, _lib.stream()), "agcn_ln_fwd")
+        ctx.save_for_backward(a, b, weight, mean, rstd)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        a, b, weight, mean, rstd = ctx.saved_tensors
+        dout = dout.contiguous()
+        D = a.shape[-1]
+        R = a.numel() // D
+        dx = torch.empty_like(a)
+        dg, db = _empty((D,), a), _empty((D,), a)
+        ws = _empty(((min(R, 1024) + 3) * 2 * D,), a)      # one (dgamma, dbeta) row per wave: encoder_plan.h
+        _lib.check(_L().agcn_ln_bwd(_lib.ptr(dout), _lib.ptr(a), _lib.ptr(b), _lib.ptr(weight), _lib.ptr(mean),
+                                    _lib.ptr(rstd), _lib.ptr(dx), _lib.ptr(dg), _lib.ptr(db), ws.data_ptr(),
+                                    ws.numel() * 4, R, D, _lib.stream()), "agcn_ln_bwd")
+        return dx, (dx if b is not None else None), dg, db, None
+
+
+def add_ln_ref(a, b, weight, bias, eps):
+    """The tensor-code form of AddLayerNormFunction."""
+    x = a if b is None else a + b
+    return torch.nn.functional.layer_norm(x, (x.shape[-1],), weight, bias, eps)

@@ -438,6 +438,44 @@ int agcn_skel_smooth(const float* raw, float* out, int Mmax, int L, int V, int k
 int agcn_skel_append_many(const float* frames, float* rings, const int* slot, const int* count, int S, int Mmax,
                           int Tmax, int V, int k, void* stream);
 
+/* ---- transformer-encoder head of aagcn_v17 (csrc/encoder.hip; geometry in csrc/encoder_plan.h) ----
+ * fp32 FMA in every AGCN_GEMM mode; no float atomics: every sum over rows, samples or heads has a fixed order, so all
+ * outputs are bitwise reproducible.  Argument checks (AGCN_ERR_ARG: null pointer, size < 1, bad flag) and domain checks
+ * (AGCN_ERR_UNSUPPORTED) come before any HIP call.  Domain: 1 <= L <= 640, 1 <= dh <= 256, D = H*dh <= 2048.
+ *
+ * tokens_fwd: x (N*M, C, T', V), cls (D) or NULL, pe (pe_rows >= L, D) or NULL -> tok (N, L, D), L = (cls ? 1 : 0) + M*T',
+ *   D = V*C: tok[n, cls + m*T' + t, v*C + c] = x[n*M + m, c, t, v] + pe[l, v*C + c], tok[n, 0] = cls + pe[0]; the
+ *   (C, T'*V) -> (T', V*C) transpose goes through LDS.
+ * tokens_bwd: dtok -> dx (or NULL), dcls (D) = sum_n dtok[n, 0] (or NULL; needs has_cls), dpe (pe_rows, D) = sum_n dtok[n, l]
+ *   for l < L and 0 for the rows behind (or NULL); n ascending.
+ *
+ * mha_fwd: qkv (N, L, 3D) as in_proj leaves it (q | k | v, head h at columns [h*dh, (h+1)*dh)); null_tok (N, L) uint8 or
+ *   NULL: logit (i, j) is masked where both tokens are null; causal 0 none, 1 keeps j <= i, 2 keeps j >= i; keep
+ *   (N, H, L, L) uint8 or NULL with keep_scale: the dropout of the probabilities.  Logits q.k / sqrt(dh); masked logits
+ *   are removed before a max-subtracted softmax; a fully masked row has all-zero probabilities and a zero ctx row.
+ *   Outputs: ctx (N, L, D); prob (N, H, L, L) or NULL, the softmax BEFORE dropout (what mha_bwd reads); avg (N, L, L) or
+ *   NULL, the mean over heads of the probabilities AFTER dropout.
+ * mha_bwd: dctx, qkv, prob, keep, keep_scale as in the forward -> dqkv (N, L, 3D), every element written:
+ *   dV = P_d^T dctx, dP = (dctx V^T) * keep * keep_scale, dS = P o (dP - rowsum(dP o P)), dQ = dS K / sqrt(dh),
+ *   dK = dS^T Q / sqrt(dh).  ws: scratch of N*H*L*L floats (dS), else AGCN_ERR_WORKSPACE.
+ *
+ * ln_fwd: out = LayerNorm(a + b) over rows of D (b NULL: of a), biased variance; mean, rstd (R) are kept for ln_bwd.
+ * ln_bwd: dy -> dx = d(a + b), dgamma, dbeta (D); the normalised value is recomputed from a, b, mean, rstd (gamma may be
+ *   0).  ws: (min(R, 1024) + 3) * 2 * D floats suffice for the partial sums (one row per wave, reduced in order), else
+ *   AGCN_ERR_WORKSPACE.  D <= 2048. */
+int agcn_tokens_fwd(const float* x, const float* cls, const float* pe, int pe_rows, float* tok, int N, int M, int C,
+                    int Tp, int V, void* stream);
+int agcn_tokens_bwd(const float* dtok, float* dx, float* dcls, float* dpe, int has_cls, int pe_rows, int N, int M, int C,
+                    int Tp, int V, void* stream);
+int agcn_mha_fwd(const float* qkv, const unsigned char* null_tok, int causal, const unsigned char* keep, float keep_scale,
+                 float* ctx, float* prob, float* avg, int N, int L, int H, int dh, void* stream);
+int agcn_mha_bwd(const float* dctx, const float* qkv, const float* prob, const unsigned char* keep, float keep_scale,
+                 float* dqkv, void* ws, size_t ws_bytes, int N, int L, int H, int dh, void* stream);
+int agcn_ln_fwd(const float* a, const float* b, const float* gamma, const float* beta, float eps, float* out, float* mean,
+                float* rstd, long R, int D, void* stream);
+int agcn_ln_bwd(const float* dy, const float* a, const float* b, const float* gamma, const float* mean, const float* rstd,
+                float* dx, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, long R, int D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
