@@ -1,0 +1,144 @@
+// Geometry and index arithmetic of the SGN inference kernels (sgn.hip): the layout of the folded weight images, the LDS
+// carve of the joint-level kernel, the row tiles of the frame-level kernel and the interval plan of the sampler.
+// Plain C++17 without HIP: sgn.hip includes it for the launchers AND the kernels (SGN_HD), and tests/sgn_plan_check.cpp
+// compiles it with the host compiler.
+#pragma once
+#include <math.h>
+#include <stddef.h>
+
+#if defined(__HIPCC__)
+#define SGN_HD __host__ __device__ __forceinline__
+#else
+#define SGN_HD static inline
+#endif
+
+#define SGN_THREADS 256
+#define SGN_WAVES 4
+#define SGN_VP 32              // joint rows of a frame padded to the height of v_mfma_f32_32x32x2_f32
+#define SGN_MAX_V 32
+#define SGN_C1 64              // widths fixed by the class (reference sgn.py:23-25)
+#define SGN_C2 128
+#define SGN_C3 256
+#define SGN_C4 512             // local.cnn2 output = fc input
+#define SGN_MAX_CLASS 4096
+#define SGN_LDS_LIMIT (160 * 1024)
+
+SGN_HD bool sgn_frames_domain(long N, int seg, int V) {
+  return N >= 1 && seg >= 1 && V >= 2 && V <= SGN_MAX_V && N * (long)seg <= 0x7fffffffL / (SGN_MAX_V * SGN_MAX_V);
+}
+SGN_HD bool sgn_clip_domain(long N, int seg, int num_class) {
+  return N >= 1 && N <= 0x7fffffffL / SGN_MAX_CLASS && seg >= 1 && seg <= (1 << 20) && num_class >= 1 &&
+         num_class <= SGN_MAX_CLASS;
+}
+
+// ---- folded weight image of agcn_sgn_frames (floats).  Every matrix is stored (K, N) row-major: row k = the input
+// channel, so the 32 lanes of an MFMA B operand read 32 consecutive floats. ----
+struct SgnFramesW {
+  int aff;                     // (4, V, 3): joint scale, joint shift, dif scale, dif shift of the two norm_data, [v*3 + c]
+  int je1_w, je1_b, je2_w, je2_b;      // joint_embed: (3, 64), (64), (64, 64), (64)
+  int de1_w, de1_b, de2_w, de2_b;      // dif_embed
+  int spa1;                    // (V, 64): spa_embed of the one-hot joints, input independent
+  int g_w, g_b;                // compute_g1: [g1 | g2] side by side, (128, 512), (512)
+  int c1_w, c1_b;              // gcn1 with its BatchNorm folded: ([W ; W1] (256, 128)), (128)
+  int c2_w, c2_b;              // gcn2: (256, 256), (256)
+  int c3_w, c3_b;              // gcn3: (512, 256), (256)
+  int total;
+};
+SGN_HD SgnFramesW sgn_frames_w(int V) {
+  SgnFramesW w;
+  int o = 0;
+  w.aff = o;   o += 4 * V * 3;
+  w.je1_w = o; o += 3 * SGN_C1;
+  w.je1_b = o; o += SGN_C1;
+  w.je2_w = o; o += SGN_C1 * SGN_C1;
+  w.je2_b = o; o += SGN_C1;
+  w.de1_w = o; o += 3 * SGN_C1;
+  w.de1_b = o; o += SGN_C1;
+  w.de2_w = o; o += SGN_C1 * SGN_C1;
+  w.de2_b = o; o += SGN_C1;
+  w.spa1 = o;  o += V * SGN_C1;
+  w.g_w = o;   o += SGN_C2 * 2 * SGN_C3;
+  w.g_b = o;   o += 2 * SGN_C3;
+  w.c1_w = o;  o += 2 * SGN_C2 * SGN_C2;
+  w.c1_b = o;  o += SGN_C2;
+  w.c2_w = o;  o += 2 * SGN_C2 * SGN_C3;
+  w.c2_b = o;  o += SGN_C3;
+  w.c3_w = o;  o += 2 * SGN_C3 * SGN_C3;
+  w.c3_b = o;  o += SGN_C3;
+  w.total = o;
+  return w;
+}
+
+// ---- LDS of agcn_sgn_frames (floats): two activation buffers of SGN_VP rows x SGN_BUF_STRIDE, the four K-split
+// partials of g3, the adjacency, and the normalised input.  Row strides are odd: the 32 lanes of an MFMA A operand
+// (one row each, same column) fall into 32 different banks of ds_read_b32. ----
+#define SGN_BUF_STRIDE (2 * SGN_C3 + 1)        // 513: [g.x | x] of gcn3
+#define SGN_G_STRIDE (SGN_VP + 1)              // 33
+#define SGN_LDS_BUF_A 0
+#define SGN_LDS_BUF_B (SGN_LDS_BUF_A + SGN_VP * SGN_BUF_STRIDE)
+#define SGN_LDS_PART (SGN_LDS_BUF_B + SGN_VP * SGN_BUF_STRIDE)          // (SGN_WAVES, SGN_VP, SGN_G_STRIDE)
+#define SGN_LDS_G (SGN_LDS_PART + SGN_WAVES * SGN_VP * SGN_G_STRIDE)    // (SGN_VP, SGN_G_STRIDE)
+#define SGN_LDS_XIN (SGN_LDS_G + SGN_VP * SGN_G_STRIDE)                 // (2, SGN_VP, 4): joint, dif after norm_data
+#define SGN_FRAMES_LDS_FLOATS (SGN_LDS_XIN + 2 * SGN_VP * 4)
+static_assert(SGN_FRAMES_LDS_FLOATS * 4 <= SGN_LDS_LIMIT, "agcn_sgn_frames: LDS");
+
+// ---- folded weight image of agcn_sgn_clip ----
+struct SgnClipW {
+  int tem1;                    // (seg, 256): tem_embed of the one-hot frames
+  int t1_w, t1_b;              // local.cnn1 + bn1: (3 * 256, 256) with row dt * 256 + c, (256)
+  int t2_w, t2_b;              // local.cnn2 + bn2: (256, 512), (512)
+  int fc_w, fc_b;              // fc: (512, num_class), (num_class)
+  long total;
+};
+SGN_HD SgnClipW sgn_clip_w(int seg, int num_class) {
+  SgnClipW w;
+  long o = 0;
+  w.tem1 = (int)o; o += (long)seg * SGN_C3;
+  w.t1_w = (int)o; o += 3 * SGN_C3 * SGN_C3;
+  w.t1_b = (int)o; o += SGN_C3;
+  w.t2_w = (int)o; o += SGN_C3 * SGN_C4;
+  w.t2_b = (int)o; o += SGN_C4;
+  w.fc_w = (int)o; o += (long)SGN_C4 * num_class;
+  w.fc_b = (int)o; o += num_class;
+  w.total = o;
+  return w;
+}
+
+// LDS of agcn_sgn_clip: a tile of 32 frames with one halo frame on either side, its conv output, the running maximum
+#define SGN_CLIP_STRIDE (SGN_C3 + 1)           // 257
+#define SGN_CLIP_LDS_H 0                                               // (SGN_VP + 2, SGN_CLIP_STRIDE)
+#define SGN_CLIP_LDS_Y (SGN_CLIP_LDS_H + (SGN_VP + 2) * SGN_CLIP_STRIDE)   // (SGN_VP, SGN_CLIP_STRIDE)
+#define SGN_CLIP_LDS_MAX (SGN_CLIP_LDS_Y + SGN_VP * SGN_CLIP_STRIDE)   // (512)
+#define SGN_CLIP_LDS_FLOATS (SGN_CLIP_LDS_MAX + SGN_C4)
+static_assert(SGN_CLIP_LDS_FLOATS * 4 <= SGN_LDS_LIMIT, "agcn_sgn_clip: LDS");
+SGN_HD int sgn_clip_tiles(int seg) { return (seg + SGN_VP - 1) / SGN_VP; }
+
+// ---- the sampler (reference feeders/loader.py:203-232, 302-358, equal-interval branch) ----
+#define SGN_SAMPLE_MAX_T 2048                  // = agcn_prenorm_max_frames()
+#define SGN_SAMPLE_MAX_ROWS (2 * SGN_SAMPLE_MAX_T)
+#define SGN_SAMPLE_CHUNK (SGN_SAMPLE_MAX_ROWS / SGN_THREADS)      // rows (t, m) one thread flags and compacts: 16
+SGN_HD bool sgn_sample_domain(long N, int T, int V, int K, long S, int seg) {
+  return N >= 1 && N <= 0x7fffffffL && T >= 1 && T <= SGN_SAMPLE_MAX_T && V >= 2 && V <= SGN_MAX_V && K == 2 && S >= 1 &&
+         seg >= 1 && S * seg <= (1 << 20);
+}
+// rows of the sequence that is sampled: the kept rows, followed by zero rows up to seg (pad_to_segment_length)
+SGN_HD int sgn_sample_rows(int kept, int seg) { return kept < seg ? seg : kept; }
+// interval boundary k of L rows in seg intervals: np.multiply(range(seg + 1), L / seg).round(), this expression order
+SGN_HD int sgn_interval(int k, int L, int seg) { return (int)rint((double)k * ((double)L / (double)seg)); }
+// the row a draw r picks in interval k, clamped into [0, L): a wrong plan gives a wrong number, never a wild read
+SGN_HD int sgn_pick(int k, int L, int seg, unsigned r) {
+  const int lo = sgn_interval(k, L, seg);
+  int width = sgn_interval(k + 1, L, seg) - lo;
+  if (width < 1) width = 1;
+  int idx = lo + (int)(r % (unsigned)width);
+  if (idx < 0) idx = 0;
+  if (idx > L - 1) idx = L - 1;
+  return idx;
+}
+// window (N, 3, T, V, 2) and output (N, S, seg, V * 3)
+SGN_HD long sgn_win_index(long n, int c, int t, int v, int m, int T, int V) {
+  return ((((n * 3 + c) * T + t) * V + v) << 1) + m;
+}
+SGN_HD long sgn_sample_out_index(long n, int s, int k, int f, int S, int seg, int V) {
+  return ((n * S + s) * seg + k) * (long)(V * 3) + f;
+}

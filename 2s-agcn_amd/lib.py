@@ -116,6 +116,11 @@ SIGNATURES = {
     "agcn_mha_bwd": (_I, [_P] * 4 + [_F, _P, _P, _Z] + [_I] * 4 + [_P]),
     "agcn_ln_fwd": (_I, [_P] * 4 + [_F, _P, _P, _P, ctypes.c_long, _I, _P]),
     "agcn_ln_bwd": (_I, [_P] * 9 + [_P, _Z, ctypes.c_long, _I, _P]),
+    "agcn_sgn_frames_weights": (_Z, [_I]),
+    "agcn_sgn_clip_weights": (_Z, [_I, _I]),
+    "agcn_sgn_frames": (_I, [_P, _P, _Z, _P, _P, _I, _I, _I, _P]),
+    "agcn_sgn_clip": (_I, [_P, _P, _Z, _P, _I, _I, _I, _P]),
+    "agcn_sgn_sample": (_I, [_P] * 4 + [_I] * 6 + [_P]),
 }
 
 _lib = None

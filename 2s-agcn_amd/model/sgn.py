@@ -1,0 +1,241 @@
+"""Base SGN (reference model/architecture/sgn/archiv/sgn.py), the model the reference's online recogniser deploys
+(infer/inference.py:129-150).  Module tree, parameter names, initialisation and state_dict are the reference's, so a
+trained ``SGN-*.pt`` loads as it is; ``spa`` and ``tem`` are non-persistent buffers (the reference keeps them as plain
+attributes), and the class constructs without a GPU.
+
+Two forwards:
+
+* eval mode under ``no_grad`` on the GPU with ``step == seg``: three HIP launches (csrc/sgn.hip) on weight images with
+  every BatchNorm folded -- ``ops.sgn_frames`` (joint-level module), ``ops.sgn_clip`` (frame-level module + fc).  The
+  images are cached under ``ops._cache_key`` and rebuilt after any parameter or running statistic changes.
+* everything else (grad mode, ``train()``, a CPU tensor, ``step != seg``, ``AGCN_SGN_HIP=0``): the tensor-code
+  composition below, channels last, ``F.linear`` / ``matmul`` on views and ``nn.BatchNorm`` modules.  It makes the class
+  a complete ``nn.Module`` any torch optimiser can fine-tune and is the comparison of the fused path; it is NOT the hot
+  path and is counted in ``ops.SGN_STATS['forward_tensor']``.
+
+Activations of the composition are (bs, step, V, C); the reference's are (bs, C, V, step)."""
+import math
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from .. import ops
+
+
+def _cl_to_cf(x):
+    """(bs, step, V, C) -> (bs, C, V, step): the layout the reference's BatchNorm / pooling modules see."""
+    return x.permute(0, 3, 2, 1)
+
+
+class norm_data(nn.Module):
+    """BatchNorm1d over the C*V features of a frame, feature c*V + v (reference sgn.py:107-117)."""
+
+    def __init__(self, dim=64):
+        super().__init__()
+        self.bn = nn.BatchNorm1d(dim)
+
+    def forward(self, x):
+        bs, step, V, C = x.shape
+        y = self.bn(_cl_to_cf(x).reshape(bs, C * V, step))
+        return y.reshape(bs, C, V, step).permute(0, 3, 2, 1)
+
+
+class cnn1x1(nn.Module):
+    """The Conv2d holds the parameters under the reference's names; it is applied as a linear map of the last dim."""
+
+    def __init__(self, dim1=3, dim2=3, bias=True):
+        super().__init__()
+        self.cnn = nn.Conv2d(dim1, dim2, kernel_size=1, bias=bias)
+
+    def forward(self, x):
+        return F.linear(x, self.cnn.weight.flatten(1), self.cnn.bias)
+
+
+class embed(nn.Module):
+    def __init__(self, dim=3, dim1=128, norm_dim=75, bias=False):
+        super().__init__()
+        layers = [cnn1x1(dim, 64, bias=bias), nn.ReLU(), cnn1x1(64, dim1, bias=bias), nn.ReLU()]
+        self.cnn = nn.Sequential(*([norm_data(norm_dim)] if norm_dim > 0 else []), *layers)
+
+    def forward(self, x):
+        return self.cnn(x)
+
+
+class local(nn.Module):
+    """Frame-level module (reference sgn.py:155-177): maximum over the joints (adaptive in time when step != seg),
+    3-tap temporal conv, 1x1 conv, each with BatchNorm + ReLU."""
+
+    def __init__(self, dim1=3, dim2=3, bias=False, seg=20):
+        super().__init__()
+        self.maxpool = nn.AdaptiveMaxPool2d((1, seg))
+        self.cnn1 = nn.Conv2d(dim1, dim1, kernel_size=(1, 3), padding=(0, 1), bias=bias)
+        self.bn1 = nn.BatchNorm2d(dim1)
+        self.relu = nn.ReLU()
+        self.cnn2 = nn.Conv2d(dim1, dim2, kernel_size=1, bias=bias)
+        self.bn2 = nn.BatchNorm2d(dim2)
+        self.dropout = nn.Dropout2d(0.2)
+        self.seg = seg
+
+    @staticmethod
+    def _bn(bn, x):
+        """BatchNorm2d of x (bs, T, C) seen as (bs, C, 1, T)."""
+        return bn(x.transpose(1, 2).unsqueeze(2)).squeeze(2).transpose(1, 2)
+
+    def forward(self, x):
+        if x.shape[1] == self.seg:
+            h = x.amax(2)                                                  # (bs, T, C)
+        else:
+            h = self.maxpool(_cl_to_cf(x)).squeeze(2).transpose(1, 2)
+        hp = F.pad(h, (0, 0, 1, 1))
+        T = h.shape[1]
+        taps = torch.cat([hp[:, dt:dt + T] for dt in range(3)], dim=2)     # feature dt * C + c
+        w = self.cnn1.weight[:, :, 0, :].permute(0, 2, 1).flatten(1)
+        y = self.relu(self._bn(self.bn1, F.linear(taps, w, self.cnn1.bias)))
+        y = self.dropout(y.transpose(1, 2).unsqueeze(2)).squeeze(2).transpose(1, 2)
+        y = F.linear(y, self.cnn2.weight.flatten(1), self.cnn2.bias)
+        return self.relu(self._bn(self.bn2, y))
+
+
+class gcn_spa(nn.Module):
+    def __init__(self, in_feature, out_feature, bias=False):
+        super().__init__()
+        self.bn = nn.BatchNorm2d(out_feature)
+        self.relu = nn.ReLU()
+        self.w = cnn1x1(in_feature, out_feature, bias=False)
+        self.w1 = cnn1x1(in_feature, out_feature, bias=bias)
+
+    def forward(self, x1, g):
+        y = self.w(g.matmul(x1)) + self.w1(x1)
+        return self.relu(_cl_to_cf(self.bn(_cl_to_cf(y))))
+
+
+class compute_g_spa(nn.Module):
+    def __init__(self, dim1=64 * 3, dim2=64 * 3, bias=False):
+        super().__init__()
+        self.dim1, self.dim2 = dim1, dim2
+        self.g1 = cnn1x1(dim1, dim2, bias=bias)
+        self.g2 = cnn1x1(dim1, dim2, bias=bias)
+        self.softmax = nn.Softmax(dim=-1)
+
+    def forward(self, x1):
+        return self.softmax(self.g1(x1).matmul(self.g2(x1).transpose(-1, -2)))
+
+
+def _t(w):
+    """Conv / linear weight (Cout, Cin, ...) -> the (Cin, Cout) row-major image the kernels read."""
+    return w.flatten(1).t()
+
+
+def _bias(conv, n, like):
+    return conv.bias if conv.bias is not None else like.new_zeros(n)
+
+
+class SGN(nn.Module):
+    def __init__(self, num_class=60, num_point=25, in_channels=3, seg=20, bias=True):
+        super().__init__()
+        self.c1, self.c2, self.c3 = 64, 128, 256
+        self.seg, self.num_point, self.in_channels, self.num_class = seg, num_point, in_channels, num_class
+
+        self.joint_embed = embed(in_channels, self.c1, norm_dim=in_channels * num_point, bias=bias)
+        self.dif_embed = embed(in_channels, self.c1, norm_dim=in_channels * num_point, bias=bias)
+        # the reference's one-hot tensors, in its shapes: spa (1, V, V, seg) one-hot over the joint, tem (1, seg, V, seg)
+        # one-hot over the frame
+        self.register_buffer('spa', torch.eye(num_point)[None, :, :, None].repeat(1, 1, 1, seg), persistent=False)
+        self.register_buffer('tem', torch.eye(seg)[None, :, None, :].repeat(1, 1, num_point, 1), persistent=False)
+        self.tem_embed = embed(seg, self.c3, norm_dim=0, bias=bias)
+        self.spa_embed = embed(num_point, self.c1, norm_dim=0, bias=bias)
+
+        self.compute_g1 = compute_g_spa(self.c2, self.c3, bias=bias)
+        self.gcn1 = gcn_spa(self.c2, self.c2, bias=bias)
+        self.gcn2 = gcn_spa(self.c2, self.c3, bias=bias)
+        self.gcn3 = gcn_spa(self.c3, self.c3, bias=bias)
+
+        self.cnn = local(self.c3, self.c3 * 2, bias=bias, seg=seg)
+        self.maxpool = nn.AdaptiveMaxPool2d((1, 1))
+        self.fc = nn.Linear(self.c3 * 2, num_class)
+
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                n = m.kernel_size[0] * m.kernel_size[1] * m.out_channels
+                m.weight.data.normal_(0, math.sqrt(2. / n))
+        for gcn in (self.gcn1, self.gcn2, self.gcn3):
+            nn.init.constant_(gcn.w.cnn.weight, 0)
+        self._infer_cache = {}
+
+    # ---- the input-independent embeddings (reference sgn.py:78-79) ----
+    def _spa1(self):
+        return self.spa_embed(self.spa[0, :, :, 0].t())                    # (V, 64)
+
+    def _tem1(self):
+        return self.tem_embed(self.tem[0, :, 0, :].t())                    # (seg, 256)
+
+    # ---- tensor-code composition ----
+    def forward_tensor(self, x):
+        bs, step, dim = x.shape
+        V = dim // self.in_channels
+        if step != self.seg:           # the reference cannot add tem1 (seg frames) to step frames either (sgn.py:89)
+            raise ValueError(f"agcn_amd: SGN was built for seg = {self.seg} frames (tem is one-hot over them), got {step}")
+        x = x.reshape(bs, step, V, self.in_channels)
+        dif = torch.cat([x.new_zeros(bs, 1, V, self.in_channels), x[:, 1:] - x[:, :-1]], dim=1)
+        dy = self.joint_embed(x) + self.dif_embed(dif)
+        h = torch.cat([dy, self._spa1().expand(bs, step, V, self.c1)], dim=3)
+        g = self.compute_g1(h)
+        h = self.gcn3(self.gcn2(self.gcn1(h, g), g), g)
+        h = h + self._tem1()[None, :, None, :]
+        y = self.cnn(h)                                                    # (bs, seg, 512)
+        return self.fc(y.amax(1)), g
+
+    # ---- folded weight images of the HIP path ----
+    def _images(self):
+        srcs = list(self.parameters()) + list(self.buffers())
+        key = ops._cache_key(srcs)
+        f = self._infer_cache.get('images')
+        if f is not None and f[0] == key:
+            return f[1], f[2]
+        V, like = self.num_point, self.fc.weight
+
+        def fold(bn):
+            return ops._fold((bn.weight, bn.bias, bn.running_mean, bn.running_var))
+
+        def first(e, i):                       # the two 1x1 layers of an embedding: (w1, b1, w2, b2) images
+            a, b = e.cnn[i].cnn, e.cnn[i + 2].cnn
+            return [_t(a.weight), _bias(a, 64, like), _t(b.weight), _bias(b, b.out_channels, like)]
+
+        def gcn(m):
+            s, sh = fold(m.bn)
+            wcat = torch.cat([_t(m.w.cnn.weight), _t(m.w1.cnn.weight)]) * s[None, :]
+            return [wcat, _bias(m.w1.cnn, s.numel(), like) * s + sh]
+
+        aff = []
+        for e in (self.joint_embed, self.dif_embed):        # BatchNorm feature c*V + v -> [v*3 + c]
+            aff += [c.reshape(3, V).t() for c in fold(e.cnn[0].bn)]
+        g = self.compute_g1
+        frames = (aff + first(self.joint_embed, 1) + first(self.dif_embed, 1) + [self._spa1()]
+                  + [torch.cat([_t(g.g1.cnn.weight), _t(g.g2.cnn.weight)], dim=1),          # [g1 | g2]: (128, 512)
+                     torch.cat([_bias(g.g1.cnn, 256, like), _bias(g.g2.cnn, 256, like)])]
+                  + gcn(self.gcn1) + gcn(self.gcn2) + gcn(self.gcn3))
+        c = self.cnn
+        s1, sh1 = fold(c.bn1)
+        s2, sh2 = fold(c.bn2)
+        clip = [self._tem1(),
+                (c.cnn1.weight[:, :, 0, :] * s1[:, None, None]).permute(2, 1, 0), _bias(c.cnn1, 256, like) * s1 + sh1,
+                _t(c.cnn2.weight) * s2[None, :], _bias(c.cnn2, 512, like) * s2 + sh2,
+                self.fc.weight.t(), self.fc.bias]
+        wf = torch.cat([t.reshape(-1) for t in frames]).contiguous()
+        wc = torch.cat([t.reshape(-1) for t in clip]).contiguous()
+        self._infer_cache['images'] = (key, wf, wc)
+        return wf, wc
+
+    def _fused(self, x):
+        return (not self.training and not torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32
+                and x.dim() == 3 and x.shape[1] == self.seg and self.in_channels == 3
+                and x.shape[2] == 3 * self.num_point and ops.sgn_hip_enabled())
+
+    def forward(self, x):
+        if not self._fused(x):
+            ops.SGN_STATS['forward_tensor'] += 1
+            return self.forward_tensor(x)
+        wf, wc = self._images()
+        feat, g = ops.sgn_frames(x.contiguous(), wf, self.num_point)
+        return ops.sgn_clip(feat, wc, self.num_class), g

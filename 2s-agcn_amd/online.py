@@ -10,6 +10,10 @@ scores and the label, which is the only synchronisation.
 ``RecordingRecognition`` labels a whole recording and ``MultiStreamRecognition`` serves several streams: both normalise
 many windows in one launch (``ops.prenorm_windows``) and run them through the model as one batch.
 
+With ``sgn_preprocess=True`` the recognisers run the reference's deployed SGN (``model.sgn.SGN``) as its
+``inference.py:102-107, 148-150`` does: the normalised window goes through ``ops.sgn_sample`` (``NTUDataLoaders.to_fix_length``:
+``multi_test`` random subsamples of ``model.seg`` rows), the model runs on the subsamples and their logits are averaged.
+
 The frame handed to ``append_data`` always carries exactly ``max_num_skeleton`` bodies (absent ones as zeros), as the
 reference's main loop does; its ``M < max_person`` case, which leaves stale rows in the window, is not reproduced."""
 import numpy as np
@@ -59,9 +63,11 @@ class _Recogniser:
 
     def __init__(self, model, model_args=None, weights=None, max_frame=300, max_num_skeleton=4,
                  max_num_skeleton_true=2, num_joint=25, moving_avg=1, zaxis=(0, 1), xaxis=(8, 4), zaxis2=None,
-                 device='cuda:0'):
+                 device='cuda:0', sgn_preprocess=False, multi_test=5):
         if not 1 <= max_num_skeleton_true <= max_num_skeleton:
             raise ValueError("agcn_amd: need 1 <= max_num_skeleton_true <= max_num_skeleton")
+        if sgn_preprocess and (max_num_skeleton_true != 2 or multi_test < 1):
+            raise ValueError("agcn_amd: sgn_preprocess interleaves exactly two selected bodies and needs multi_test >= 1")
         if not 1 <= moving_avg <= max_frame:
             raise ValueError("agcn_amd: need 1 <= moving_avg <= max_frame")
         self.device = torch.device(device)
@@ -74,12 +80,37 @@ class _Recogniser:
         # what the last prediction left on the device: the normalised windows (N, 3, T, V, K), the selected bodies
         # (N, K) int32, the energies (N, Mmax) and the logits (N, num_class)
         self.window = self.selected = self.energy = self.logits = None
+        # reference inference.py:148-150 with an SGN: the normalised window goes through NTUDataLoaders.to_fix_length
+        # (ops.sgn_sample: multi_test random subsamples of model.seg rows) and the logits of the draws are averaged.
+        # aagcn_normalize=False (raw windows into the sampler) is not built.
+        self.sgn_preprocess, self.multi_test = bool(sgn_preprocess), int(multi_test)
+        self.seg = int(self.model.seg) if self.sgn_preprocess else None
+        self.draws = self.rows = None          # the last draws (N, multi_test, seg) int32 bit patterns, and row counts
 
-    def forward(self, window):
-        """The model in eval mode under no_grad (the folded path) -> (logits, scores, label) on the device; no sync."""
+    def _draws(self, draws, N):
+        """None -> fresh draws on the device; else (N, S, seg) (or (S, seg) for one window) uint32 / int32 patterns."""
+        if draws is None:
+            return ops.sgn_draws(N, self.multi_test, self.seg, self.device)
+        if isinstance(draws, np.ndarray):
+            draws = torch.from_numpy(np.ascontiguousarray(draws, dtype=np.uint32).view(np.int32))
+        if draws.dtype == torch.uint32:
+            draws = draws.view(torch.int32)
+        return draws.to(self.device).reshape(N, self.multi_test, self.seg).contiguous()
+
+    def forward(self, window, draws=None):
+        """The model in eval mode under no_grad (the folded path) -> (logits, scores, label) on the device; no sync.
+        With sgn_preprocess the window is sampled first and the logits are the mean over the draws (reference
+        inference.py:103-106); ``draws`` injects the random numbers."""
         with torch.no_grad(), torch.cuda.device(self.device):
-            out = self.model(window)
-            self.logits = out[0] if isinstance(out, tuple) else out
+            if self.sgn_preprocess:
+                N = window.shape[0]
+                self.draws = self._draws(draws, N)
+                rows, self.rows = ops.sgn_sample(window, self.draws, self.seg)
+                out = self.model(rows.view(N * self.multi_test, self.seg, -1))
+                self.logits = out[0].view(N, self.multi_test, -1).mean(1)
+            else:
+                out = self.model(window)
+                self.logits = out[0] if isinstance(out, tuple) else out
             scores = torch.softmax(self.logits, 1)
             return self.logits, scores, torch.argmax(scores, 1)
 
@@ -140,9 +171,9 @@ class ActionRecognition(_Recogniser):
                 zaxis2=self.zaxis2)
         return self.window
 
-    def predict(self):
+    def predict(self, draws=None):
         """-> (softmax scores of the current window as a list, label)."""
-        _, scores, label = self.forward(self.normalize())
+        _, scores, label = self.forward(self.normalize(), draws)
         both = torch.cat((scores[0], label.to(scores.dtype))).cpu()      # the one synchronising copy
         return both[:-1].tolist(), int(both[-1].item())
 
@@ -185,10 +216,11 @@ class RecordingRecognition(_Recogniser):
                                                                           **self._options())
         return self.window
 
-    def label(self, frames, interval=1, first=0, ends=None):
+    def label(self, frames, interval=1, first=0, ends=None, draws=None):
         """frames (L, max_num_skeleton, [1,] V, 3), numpy array or tensor.  Predicts after frames first, first + interval,
         ... (or after the frames listed in ``ends``, in any order) -> (scores (P, num_class) fp32, labels (P,) int64,
-        ends (P,) int64) as numpy arrays.  The logits of all P windows stay on the device in ``self.logits``; window,
+        ends (P,) int64) as numpy arrays.  ``draws`` (P, multi_test, seg): the sampler's random numbers with sgn_preprocess
+        (default: drawn on the device).  The logits of all P windows stay on the device in ``self.logits``; window,
         selected and energy are those of the last batch."""
         pool, L = self.prepare(frames)
         if ends is None:
@@ -203,7 +235,7 @@ class RecordingRecognition(_Recogniser):
         logits, scores, labels = [], [], []
         for b in range(0, len(ends), self.batch):
             win = self.normalize(pool, start[b:b + self.batch], length[b:b + self.batch])
-            lg, sc, lb = self.forward(win)
+            lg, sc, lb = self.forward(win, None if draws is None else draws[b:b + self.batch])
             logits.append(lg)
             scores.append(sc)
             labels.append(lb)
@@ -273,13 +305,13 @@ class MultiStreamRecognition(_Recogniser):
                                                                           **self._options())
         return self.window
 
-    def predict(self, streams=None):
+    def predict(self, streams=None, draws=None):
         """-> (scores (S', num_class) fp32, labels (S',) int64, streams (S',)) for the streams (default: all) that have
         received a frame, as numpy arrays."""
         win = self.normalize(streams)
         if win is None:
             self.logits = None
             return np.zeros((0, 0), dtype=np.float32), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
-        _, scores, labels = self.forward(win)
+        _, scores, labels = self.forward(win, draws)
         scores, labels = _fetch(scores, labels)                          # the one synchronising copy
         return scores, labels, np.asarray(self.streams, dtype=np.int64)

@@ -1701,3 +1701,74 @@ def add_ln_ref(a, b, weight, bias, eps):
     """The tensor-code form of AddLayerNormFunction."""
     x = a if b is None else a + b
     return torch.nn.functional.layer_norm(x, (x.shape[-1],), weight, bias, eps)
+
+
+# ------------------------------------------------------------------------------------------------
+# base SGN, eval-mode inference (csrc/sgn.hip): sampler, joint-level module, frame-level module + fc
+# ------------------------------------------------------------------------------------------------
+def sgn_hip_enabled():
+    """AGCN_SGN_HIP=0 runs SGN's eval forward as the tensor-code composition of the same maths (model/sgn.py): for A/B."""
+    return os.environ.get('AGCN_SGN_HIP', '1') != '0'
+
+
+# diagnostic counters (never read by a compute path): launches of the three kernels, and SGN forwards that ran as
+# tensor code (grad mode, train(), a CPU tensor, AGCN_SGN_HIP=0)
+SGN_STATS = {'frames_hip': 0, 'clip_hip': 0, 'sample_hip': 0, 'forward_tensor': 0}
+
+
+def sgn_frames(x, wimg, V, want_g=True):
+    """The joint-level module of SGN on x (N, seg, V*3) with the folded weight image ``wimg`` (model/sgn.py) ->
+    feat (N, seg, 256), the maximum over the joints of gcn3's output, and g (N, seg, V, V) (None without want_g)."""
+    if x.dim() != 3 or x.shape[2] != 3 * V:
+        raise ValueError(f"agcn_amd: sgn_frames takes (N, seg, {3 * V}), got {tuple(x.shape)}")
+    N, seg, _ = x.shape
+    feat = _empty((N, seg, 256), x)
+    g = _empty((N, seg, V, V), x) if want_g else None
+    rc = _L().agcn_sgn_frames(_lib.ptr(x), _lib.ptr(wimg), wimg.numel(), _lib.ptr(feat), _lib.ptr(g), N, seg, V,
+                              _lib.stream())
+    _lib.check(rc, "agcn_sgn_frames")
+    SGN_STATS['frames_hip'] += 1
+    return feat, g
+
+
+def sgn_clip(feat, wimg, num_class):
+    """The frame-level module and the classifier of SGN on feat (N, seg, 256) -> logits (N, num_class)."""
+    N, seg, C = feat.shape
+    if C != 256:
+        raise ValueError(f"agcn_amd: sgn_clip takes (N, seg, 256), got {tuple(feat.shape)}")
+    logits = _empty((N, num_class), feat)
+    rc = _L().agcn_sgn_clip(_lib.ptr(feat), _lib.ptr(wimg), wimg.numel(), _lib.ptr(logits), N, seg, num_class,
+                            _lib.stream())
+    _lib.check(rc, "agcn_sgn_clip")
+    SGN_STATS['clip_hip'] += 1
+    return logits
+
+
+def sgn_draws(N, S, seg, device):
+    """(N, S, seg) random 32-bit patterns for ``sgn_sample``, drawn on the device (no sync).  The sampler reduces them
+    modulo an interval width of at most a few hundred rows: the bias of that at 32 bits is below 1e-7."""
+    return torch.randint(0, 1 << 32, (N, S, seg), dtype=torch.int64, device=device).to(torch.int32)
+
+
+def sgn_sample(win, r, seg):
+    """NTUDataLoaders.to_fix_length (equal-interval branch) on normalised windows win (N, 3, T, V, 2) in ``prenorm``'s
+    output layout (agcn_sgn_sample): null rows dropped, the two bodies interleaved by frame, fewer than ``seg`` rows
+    zero-padded, and one row per interval and draw.  r (N, S, seg): the draws as 32-bit patterns in an int32 (or uint32)
+    tensor, read as unsigned.  Returns (out (N, S, seg, V*3), L (N,) int32 row counts), on the device."""
+    if win.dim() != 5 or win.shape[1] != 3:
+        raise ValueError(f"agcn_amd: sgn_sample takes windows (N, 3, T, V, 2), got {tuple(win.shape)}")
+    N, _, T, V, K = win.shape
+    if K != 2:
+        raise ValueError(f"agcn_amd: sgn_sample interleaves exactly two selected bodies, got {K}")
+    if r.dtype == torch.uint32:
+        r = r.view(torch.int32)
+    if r.dim() != 3 or r.shape[0] != N or r.shape[2] != seg or r.dtype != torch.int32:
+        raise ValueError(f"agcn_amd: sgn_sample takes draws ({N}, S, {seg}) int32, got {r.dtype} {tuple(r.shape)}")
+    S = r.shape[1]
+    out = _empty((N, S, seg, V * 3), win)
+    L = torch.empty((N,), dtype=torch.int32, device=win.device)
+    rc = _L().agcn_sgn_sample(_lib.ptr(win), _lib.ptr_bits(r), _lib.ptr(out), _lib.ptr_bits(L), N, T, V, K, S, seg,
+                              _lib.stream())
+    _lib.check(rc, "agcn_sgn_sample")
+    SGN_STATS['sample_hip'] += 1
+    return out, L

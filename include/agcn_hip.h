@@ -476,6 +476,45 @@ int agcn_ln_fwd(const float* a, const float* b, const float* gamma, const float*
 int agcn_ln_bwd(const float* dy, const float* a, const float* b, const float* gamma, const float* mean, const float* rstd,
                 float* dx, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, long R, int D, void* stream);
 
+/* ---- base SGN, eval-mode inference (csrc/sgn.hip; geometry and weight-image layouts in csrc/sgn_plan.h) ----
+ * The model the reference's online recogniser deploys (model/architecture/sgn/archiv/sgn.py, infer/inference.py:129-150)
+ * as three launches.  Exact-f32 MFMA in every AGCN_GEMM mode, fixed summation orders, no atomics: outputs are bitwise
+ * reproducible and a clip's result does not depend on the batch it is in.  Argument checks (AGCN_ERR_ARG) and domain
+ * checks (AGCN_ERR_UNSUPPORTED) come before any HIP call; none of the entries synchronises, allocates or reads the
+ * environment.
+ *
+ * sgn_frames_weights / sgn_clip_weights: floats of the folded weight images (0 outside the domain).  The images are
+ *   built by the caller (model/sgn.py::SGN._images): every BatchNorm folded, every matrix stored (K, N) row-major, in the order of
+ *   SgnFramesW / SgnClipW.
+ *
+ * sgn_frames: the joint-level module (sgn.py:69-87), one workgroup per frame.  x (N, seg, V*3) -> feat (N, seg, 256),
+ *   the maximum over the joints of gcn3's output (what local.maxpool, sgn.py:168, leaves when step == seg); g
+ *   (N, seg, V, V) = softmax(g1(x)^T g2(x)) (sgn.py:206-211) is stored unless g is NULL.  dif (sgn.py:73-75) is zero at
+ *   the first frame of every clip.  The V joint rows are padded to 32 for the matrix cores; padded rows enter neither
+ *   the softmax, nor g.x, nor the maximum.  V in [2, 32], seg >= 1, in_channels 3, widths 64 / 128 / 256.
+ *   AGCN_ERR_ARG: null x / w / feat, a size outside those limits, w_floats != sgn_frames_weights(V).
+ *
+ * sgn_clip: the frame-level module and the classifier (sgn.py:89-94, 167-177), one workgroup per clip.  feat
+ *   (N, seg, 256) + tem1 -> 3-tap zero-padded temporal conv + bn1 + relu -> 1x1 conv 256 -> 512 + bn2 + relu -> maximum
+ *   over the frames -> fc -> logits (N, num_class).  Dropout2d is the identity in eval.  num_class <= 4096.
+ *
+ * sgn_sample: NTUDataLoaders.to_fix_length, equal-interval branch (feeders/loader.py:203-232, 302-358), on normalised
+ *   windows win (N, 3, T, V, K = 2) in prenorm's output layout, one workgroup per window.  Row (t, m) is kept iff body
+ *   m's frame t is not all zero; kept rows in (t, m) order (zero-row deletion + turn_two_to_one); fewer than seg rows
+ *   are followed by zero rows and L := seg (pad_to_segment_length); boundaries b_k = rint((double)k * ((double)L /
+ *   (double)seg)); draw s takes row b_k + r[n, s, k] % (b_{k+1} - b_k) of interval k.  r (N, S, seg) uint32 -> out
+ *   (N, S, seg, V*3), a bit-exact gather, and L (N) int32.  An empty window gives zeros and L = 0 (the reference raises).
+ *   Every index is clamped: any r gives an in-range read.  T <= agcn_prenorm_max_frames().
+ *   AGCN_ERR_ARG: null pointer, K != 2, V outside [2, 32], T, S or seg < 1, T too long. */
+size_t agcn_sgn_frames_weights(int V);
+size_t agcn_sgn_clip_weights(int seg, int num_class);
+int agcn_sgn_frames(const float* x, const float* w, size_t w_floats, float* feat, float* g, int N, int seg, int V,
+                    void* stream);
+int agcn_sgn_clip(const float* feat, const float* w, size_t w_floats, float* logits, int N, int seg, int num_class,
+                  void* stream);
+int agcn_sgn_sample(const float* win, const unsigned* r, float* out, int* L, int N, int T, int V, int K, int S, int seg,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif
