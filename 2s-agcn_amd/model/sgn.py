@@ -3,12 +3,15 @@
 trained ``SGN-*.pt`` loads as it is; ``spa`` and ``tem`` are non-persistent buffers (the reference keeps them as plain
 attributes), and the class constructs without a GPU.
 
-Two forwards:
+Three routes:
 
 * eval mode under ``no_grad`` on the GPU with ``step == seg``: three HIP launches (csrc/sgn.hip) on weight images with
   every BatchNorm folded -- ``ops.sgn_frames`` (joint-level module), ``ops.sgn_clip`` (frame-level module + fc).  The
   images are cached under ``ops._cache_key`` and rebuilt after any parameter or running statistic changes.
-* everything else (grad mode, ``train()``, a CPU tensor, ``step != seg``, ``AGCN_SGN_HIP=0``): the tensor-code
+* the same launches in grad mode when x is the only tensor that asks for a gradient (every parameter frozen), behind
+  ``ops.SGNInputGradFunction`` whose backward is ``ops.sgn_clip_bwd`` + ``ops.sgn_frames_bwd`` (csrc/sgn_bwd.hip);
+  ``input_gradient(x, cot)`` is that without autograd state.  Parameter gradients are not built in HIP.
+* everything else (grad mode with trainable parameters, ``train()``, a CPU tensor, ``step != seg``, ``AGCN_SGN_HIP=0``): the tensor-code
   composition below, channels last, ``F.linear`` / ``matmul`` on views and ``nn.BatchNorm`` modules.  It makes the class
   a complete ``nn.Module`` any torch optimiser can fine-tune and is the comparison of the fused path; it is NOT the hot
   path and is counted in ``ops.SGN_STATS['forward_tensor']``.
@@ -187,12 +190,8 @@ class SGN(nn.Module):
         return self.fc(y.amax(1)), g
 
     # ---- folded weight images of the HIP path ----
-    def _images(self):
-        srcs = list(self.parameters()) + list(self.buffers())
-        key = ops._cache_key(srcs)
-        f = self._infer_cache.get('images')
-        if f is not None and f[0] == key:
-            return f[1], f[2]
+    def _folded(self):
+        """The folded tensors in the order of the weight images (csrc/sgn_plan.h): -> (frames list, clip list)."""
         V, like = self.num_point, self.fc.weight
 
         def fold(bn):
@@ -222,20 +221,75 @@ class SGN(nn.Module):
                 (c.cnn1.weight[:, :, 0, :] * s1[:, None, None]).permute(2, 1, 0), _bias(c.cnn1, 256, like) * s1 + sh1,
                 _t(c.cnn2.weight) * s2[None, :], _bias(c.cnn2, 512, like) * s2 + sh2,
                 self.fc.weight.t(), self.fc.bias]
-        wf = torch.cat([t.reshape(-1) for t in frames]).contiguous()
-        wc = torch.cat([t.reshape(-1) for t in clip]).contiguous()
-        self._infer_cache['images'] = (key, wf, wc)
-        return wf, wc
+        return frames, clip
 
-    def _fused(self, x):
-        return (not self.training and not torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32
+    def _images(self, transposed=False):
+        """-> (frames image, clip image); with ``transposed`` also the two images of the backward (csrc/sgn_bwd_plan.h: the
+        same folded matrices stored (N, K)).  Those are built on the first call that asks for them, under the same key:
+        a model that only predicts never builds them."""
+        srcs = list(self.parameters()) + list(self.buffers())
+        key = ops._cache_key(srcs)
+        f = self._infer_cache.get('images')
+        if f is None or f[0] != key:
+            frames, clip = self._folded()
+            wf = torch.cat([t.reshape(-1) for t in frames]).contiguous()
+            wc = torch.cat([t.reshape(-1) for t in clip]).contiguous()
+            f = self._infer_cache['images'] = (key, wf, wc)
+        if not transposed:
+            return f[1], f[2]
+        t = self._infer_cache.get('images_t')
+        if t is None or t[0] != key:
+            frames, clip = self._folded()
+            # W^T of je2, de2, [g1 | g2], gcn1..3 of the frames image; of the three taps of cnn1 and of cnn2
+            wf_t = torch.cat([frames[i].t().reshape(-1) for i in (6, 10, 13, 15, 17, 19)]).contiguous()
+            wc_t = torch.cat([clip[1].transpose(1, 2).reshape(-1), clip[3].t().reshape(-1)]).contiguous()
+            t = self._infer_cache['images_t'] = (key, wf_t, wc_t)
+        return f[1], f[2], t[1], t[2]
+
+    def _fusable(self, x):
+        """What the kernels take, whatever the grad mode."""
+        return (not self.training and x.is_cuda and x.dtype == torch.float32
                 and x.dim() == 3 and x.shape[1] == self.seg and self.in_channels == 3
                 and x.shape[2] == 3 * self.num_point and ops.sgn_hip_enabled())
 
+    def _fused(self, x):
+        return not torch.is_grad_enabled() and self._fusable(x)
+
+    def _fused_input_grad(self, x):
+        """Grad mode with x the only thing that asks for a gradient: the fused forward with the HIP input backward."""
+        return (torch.is_grad_enabled() and x.requires_grad and self._fusable(x)
+                and not any(p.requires_grad for p in self.parameters()))
+
     def forward(self, x):
+        if self._fused_input_grad(x):
+            with torch.no_grad():
+                images = self._images(transposed=True)
+            return ops.SGNInputGradFunction.apply(x, *images, self.num_point, self.num_class)
         if not self._fused(x):
             ops.SGN_STATS['forward_tensor'] += 1
             return self.forward_tensor(x)
         wf, wc = self._images()
         feat, g = ops.sgn_frames(x.contiguous(), wf, self.num_point)
         return ops.sgn_clip(feat, wc, self.num_class), g
+
+    def input_gradient(self, x, cot):
+        """-> (logits, g, dx) with dx = d sum(logits * cot) / dx, in eval mode.  Needs no autograd state and ignores the
+        parameters' requires_grad.  On the GPU (fp32, step == seg, in_channels == 3, AGCN_SGN_HIP != 0) it is four
+        launches: the two of the forward, ``ops.sgn_clip_bwd`` and ``ops.sgn_frames_bwd``; otherwise the composition with
+        torch autograd (counted in ``ops.SGN_STATS['forward_tensor']``)."""
+        if self.training:
+            raise ValueError("agcn_amd: SGN.input_gradient is the eval-mode gradient; call eval() first")
+        if not self._fusable(x):
+            ops.SGN_STATS['forward_tensor'] += 1
+            with torch.enable_grad():
+                xg = x.detach().requires_grad_(True)
+                logits, g = self.forward_tensor(xg)
+                dx, = torch.autograd.grad((logits * cot).sum(), xg)
+            return logits.detach(), g.detach(), dx
+        with torch.no_grad():
+            wf, wc, wf_t, wc_t = self._images(transposed=True)
+            x = x.detach().contiguous()
+            feat, g = ops.sgn_frames(x, wf, self.num_point)
+            logits = ops.sgn_clip(feat, wc, self.num_class)
+            dfeat = ops.sgn_clip_bwd(feat, wc, wc_t, cot.detach().to(logits).contiguous())
+            return logits, g, ops.sgn_frames_bwd(x, wf, wf_t, dfeat, self.num_point)

@@ -114,6 +114,65 @@ class _Recogniser:
             scores = torch.softmax(self.logits, 1)
             return self.logits, scores, torch.argmax(scores, 1)
 
+    def _explain_device(self, k=None):
+        """The input gradient behind ``explain`` on the device, no sync: -> (dwin (N, 3, T, V, K), classes (N,))."""
+        if self.window is None or self.logits is None:
+            raise RuntimeError("agcn_amd: explain needs a prediction: call predict / forward first")
+        window = self.window
+        N = window.shape[0]
+        if self.logits.shape[0] != N:
+            raise RuntimeError("agcn_amd: explain covers the windows of the last forward; the kept logits are those of "
+                               f"{self.logits.shape[0]} windows, the kept windows are {N}")
+        num_class = self.logits.shape[1]
+        if k is not None:
+            # checked here, on the host: one_hot does not check a device tensor, and an index outside the classes would
+            # only be caught by a device-side assertion that takes the whole process down
+            if isinstance(k, bool) or int(k) != k or not 0 <= int(k) < num_class:
+                raise ValueError(f"agcn_amd: explain takes a class index in [0, {num_class}) or None, got {k!r}")
+            k = int(k)
+        with torch.cuda.device(self.device):
+            classes = torch.argmax(self.logits, 1) if k is None else torch.full((N,), k, device=self.device)
+            onehot = torch.nn.functional.one_hot(classes, num_class).to(torch.float32)
+            if self.sgn_preprocess:
+                with torch.no_grad():
+                    S = self.multi_test
+                    rows, _ = ops.sgn_sample(window, self.draws, self.seg)
+                    cot = (onehot / S).repeat_interleave(S, 0)               # the mean logit of the draws
+                    _, _, dx = self.model.input_gradient(rows.view(N * S, self.seg, -1), cot)
+                    dwin = ops.sgn_sample_bwd(window, self.draws, dx.view(N, S, self.seg, -1), self.seg)
+            else:
+                # AGCN / AAGCN: the eval-mode backward with respect to the window alone (tools/saliency.py::saliency).
+                # The parameters' requires_grad is switched off for the call on purpose: the units' autograd Functions
+                # decide at forward time, from it, whether their backward computes weight gradients and the BatchNorm
+                # parameter sums (agcn_bn_bwd_eval with want_sums = 1); autograd.grad(inputs=x) alone would still run
+                # all of that and throw it away.  It is put back in the finally clause.
+                params = [p for p in self.model.parameters() if p.requires_grad]
+                for p in params:
+                    p.requires_grad_(False)
+                try:
+                    with torch.enable_grad():
+                        x = window.detach().clone().requires_grad_(True)
+                        out = self.model(x)
+                        out = out[0] if isinstance(out, tuple) else out
+                        dwin, = torch.autograd.grad((out * onehot).sum(), x)
+                finally:
+                    for p in params:
+                        p.requires_grad_(True)
+        return dwin, classes
+
+    def explain(self, k=None):
+        """Which joints and frames drove the last prediction: -> (saliency (N, T, K, V) float32 numpy, classes (N,) int64
+        numpy) for the windows of the last ``forward`` / ``predict``; ``k`` None explains each window's predicted class,
+        an int in [0, num_class) that class (ValueError otherwise, before any launch).  saliency[n, t, body, joint] is the L2 norm over xyz of the gradient of the (mean) logit with
+        respect to the normalised window; with sgn_preprocess it goes through the kept draws (``ops.sgn_sample`` again,
+        ``SGN.input_gradient``, ``ops.sgn_sample_bwd``), so frames no draw picked are zero.  The gradient is not taken
+        through the pre-normalisation.  One synchronising copy."""
+        dwin, classes = self._explain_device(k)
+        N, _, T, V, K = dwin.shape
+        sal = dwin.square().sum(1).sqrt().permute(0, 1, 3, 2).reshape(N, -1)
+        both = torch.cat((sal, classes.to(sal.dtype).unsqueeze(1)), 1).cpu().numpy()     # the one synchronising copy
+        return both[:, :-1].reshape(N, T, K, V).copy(), both[:, -1].astype(np.int64)
+
     def _frames(self, frames, lead, what):
         """``frames`` (lead, max_num_skeleton, [1,] V, 3), numpy array or tensor, ``lead`` None for any length ->
         contiguous fp32 (lead, max_num_skeleton, V, 3) on the device: the one upload."""

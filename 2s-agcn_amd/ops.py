@@ -1772,3 +1772,91 @@ def sgn_sample(win, r, seg):
     _lib.check(rc, "agcn_sgn_sample")
     SGN_STATS['sample_hip'] += 1
     return out, L
+
+
+# ------------------------------------------------------------------------------------------------
+# base SGN, input gradients in eval mode (csrc/sgn_bwd.hip): the backward of the two launches above with respect to x,
+# and the adjoint of the sampler.  Parameter gradients are not built.
+# ------------------------------------------------------------------------------------------------
+# diagnostic counters of the backward launches (a dict of its own: SGN_STATS is compared whole by its tests)
+SGN_GRAD_STATS = dict(clip_bwd=0, frames_bwd=0, sample_bwd=0)
+
+
+def sgn_clip_bwd(feat, wimg, wimg_t, dlogits):
+    """d logits (N, num_class) -> d feat (N, seg, 256) through fc, the maximum over the frames and the two convolutions
+    of the frame-level module, recomputed from feat (N, seg, 256).  wimg: the forward image, wimg_t: the transposed one."""
+    if feat.dim() != 3 or feat.shape[2] != 256:
+        raise ValueError(f"agcn_amd: sgn_clip_bwd takes feat (N, seg, 256), got {tuple(feat.shape)}")
+    N, seg, _ = feat.shape
+    if dlogits.dim() != 2 or dlogits.shape[0] != N:
+        raise ValueError(f"agcn_amd: sgn_clip_bwd takes dlogits ({N}, num_class), got {tuple(dlogits.shape)}")
+    dfeat = _empty((N, seg, 256), feat)
+    rc = _L().agcn_sgn_clip_bwd(_lib.ptr(feat), _lib.ptr(wimg), wimg.numel(), _lib.ptr(wimg_t), wimg_t.numel(),
+                                _lib.ptr(dlogits), _lib.ptr(dfeat), N, seg, dlogits.shape[1], _lib.stream())
+    _lib.check(rc, "agcn_sgn_clip_bwd")
+    SGN_GRAD_STATS['clip_bwd'] += 1
+    return dfeat
+
+
+def sgn_frames_bwd(x, wimg, wimg_t, dfeat, V):
+    """d feat (N, seg, 256) -> dx (N, seg, V*3) through the joint-level module, recomputed from x, and the dif coupling
+    between the frames of a clip."""
+    if x.dim() != 3 or x.shape[2] != 3 * V:
+        raise ValueError(f"agcn_amd: sgn_frames_bwd takes (N, seg, {3 * V}), got {tuple(x.shape)}")
+    N, seg, _ = x.shape
+    if tuple(dfeat.shape) != (N, seg, 256):
+        raise ValueError(f"agcn_amd: sgn_frames_bwd takes dfeat ({N}, {seg}, 256), got {tuple(dfeat.shape)}")
+    dx = _empty((N, seg, 3 * V), x)
+    ws = _empty((max(1, _L().agcn_sgn_frames_bwd_workspace(N, seg, V) // 4),), x)
+    rc = _L().agcn_sgn_frames_bwd(_lib.ptr(x), _lib.ptr(wimg), wimg.numel(), _lib.ptr(wimg_t), wimg_t.numel(),
+                                  _lib.ptr(dfeat), _lib.ptr(dx), ws.data_ptr(), ws.numel() * 4, N, seg, V, _lib.stream())
+    _lib.check(rc, "agcn_sgn_frames_bwd")
+    SGN_GRAD_STATS['frames_bwd'] += 1
+    return dx
+
+
+def sgn_sample_bwd(win, r, dout, seg):
+    """The adjoint of ``sgn_sample``: dout (N, S, seg, V*3) -> dwin (N, 3, T, V, 2).  Every picked row's gradient is added
+    to its source row of the window (a row picked by several draws accumulates, in the order s major, k minor); padding
+    rows and empty windows contribute nothing."""
+    if win.dim() != 5 or win.shape[1] != 3:
+        raise ValueError(f"agcn_amd: sgn_sample_bwd takes windows (N, 3, T, V, 2), got {tuple(win.shape)}")
+    N, _, T, V, K = win.shape
+    if K != 2:
+        raise ValueError(f"agcn_amd: sgn_sample_bwd interleaves exactly two selected bodies, got {K}")
+    if r.dtype == torch.uint32:
+        r = r.view(torch.int32)
+    if r.dim() != 3 or r.shape[0] != N or r.shape[2] != seg or r.dtype != torch.int32:
+        raise ValueError(f"agcn_amd: sgn_sample_bwd takes draws ({N}, S, {seg}) int32, got {r.dtype} {tuple(r.shape)}")
+    S = r.shape[1]
+    if tuple(dout.shape) != (N, S, seg, V * 3):
+        raise ValueError(f"agcn_amd: sgn_sample_bwd takes dout ({N}, {S}, {seg}, {V * 3}), got {tuple(dout.shape)}")
+    dwin = _empty(tuple(win.shape), win)
+    rc = _L().agcn_sgn_sample_bwd(_lib.ptr(win), _lib.ptr_bits(r), _lib.ptr(dout), _lib.ptr(dwin), N, T, V, K, S, seg,
+                                  _lib.stream())
+    _lib.check(rc, "agcn_sgn_sample_bwd")
+    SGN_GRAD_STATS['sample_bwd'] += 1
+    return dwin
+
+
+class SGNInputGradFunction(torch.autograd.Function):
+    """SGN's eval forward as the two fused launches, differentiable with respect to x alone (the parameters are frozen:
+    model/sgn.py routes here only then).  args: x, wf, wc, wf_t, wc_t, V, num_class -> logits, g (g is not
+    differentiable)."""
+
+    @staticmethod
+    def forward(ctx, x, wf, wc, wf_t, wc_t, V, num_class):
+        x = x.contiguous()
+        feat, g = sgn_frames(x, wf, V)
+        logits = sgn_clip(feat, wc, num_class)
+        ctx.save_for_backward(x, feat, wf, wc, wf_t, wc_t)
+        ctx.V = V
+        ctx.mark_non_differentiable(g)
+        return logits, g
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dlogits, _dg):
+        x, feat, wf, wc, wf_t, wc_t = ctx.saved_tensors
+        dfeat = sgn_clip_bwd(feat, wc, wc_t, dlogits.contiguous())
+        return sgn_frames_bwd(x, wf, wf_t, dfeat, ctx.V), None, None, None, None, None, None

@@ -515,6 +515,43 @@ int agcn_sgn_clip(const float* feat, const float* w, size_t w_floats, float* log
 int agcn_sgn_sample(const float* win, const unsigned* r, float* out, int* L, int N, int T, int V, int K, int S, int seg,
                     void* stream);
 
+/* ---- base SGN, input gradients in eval mode (csrc/sgn_bwd.hip; geometry in csrc/sgn_bwd_plan.h) ----
+ * What torch autograd does on the reference's eval forward (sgn.py:66-98) with respect to x; parameter gradients are not
+ * built.  Same arithmetic rules as the forward: exact-f32 MFMA in every AGCN_GEMM mode, fixed summation orders, no
+ * atomics, no launch reads another clip's intermediates, so a clip's gradient is the same bits alone and in any batch.
+ * Nothing of the forward is stored: each kernel recomputes what it needs from x / feat.  ReLU's derivative at 0 is 0; a
+ * maximum routes to its lowest index (MaxPool's choice; ties only happen at 0, where nothing flows).  Checks as above.
+ *
+ * sgn_frames_bwd_weights / sgn_clip_bwd_weights: floats of the TRANSPOSED weight images (0 outside the domain), built by
+ *   the caller next to the forward images (model/sgn.py::SGN._images) in the order of SgnFramesWT / SgnClipWT: every
+ *   matrix (N, K) row-major.  The kernels read the forward image as well (biases, 3 -> 64 layers, tem1, fc).
+ * sgn_frames_bwd_workspace: bytes of the caller-owned workspace of sgn_frames_bwd (dj and dd, below).
+ *
+ * sgn_clip_bwd: feat (N, seg, 256), dlogits (N, num_class) -> dfeat (N, seg, 256), one workgroup per clip: fc
+ *   (sgn.py:94), the maximum over the frames (sgn.py:92), local.cnn2 + bn2 + relu, local.cnn1 + bn1 + relu
+ *   (sgn.py:169-175), + tem1 (sgn.py:89).  The conv's zero padding receives nothing; for seg > 32 a tile's gradient
+ *   reaches one frame of either neighbouring tile, added in the order of the tiles.
+ *
+ * sgn_frames_bwd: x (N, seg, V*3), dfeat -> dx (N, seg, V*3), one workgroup per frame and a combining launch: the
+ *   maximum over the joints (sgn.py:168), gcn3..1 (sgn.py:188-194) with dG, the softmax and g1 / g2 (sgn.py:206-211),
+ *   the two embeddings and norm_data (sgn.py:76-81, 107-143).  spa1 and tem1 are input independent.  dif (sgn.py:73-75)
+ *   couples neighbouring frames of a clip: every frame writes dj (joint branch) and dd (dif branch) to the workspace and
+ *   dx[t] = dj[t] + dd[t] [t > 0] - dd[t + 1] [t + 1 < seg].  Padded joint rows and columns take part in nothing.
+ *   AGCN_ERR_WORKSPACE: ws_bytes < sgn_frames_bwd_workspace(N, seg, V).
+ *
+ * sgn_sample_bwd: the adjoint of sgn_sample's gather (feeders/loader.py:203-232, 302-358): win, r as there, dout
+ *   (N, S, seg, V*3) -> dwin (N, 3, T, V, 2), zeroed and then added to row by row in the order s major, k minor by the
+ *   thread that owns the feature column.  Padding rows and empty windows contribute nothing. */
+size_t agcn_sgn_frames_bwd_weights(int V);
+size_t agcn_sgn_clip_bwd_weights(int seg, int num_class);
+size_t agcn_sgn_frames_bwd_workspace(int N, int seg, int V);
+int agcn_sgn_clip_bwd(const float* feat, const float* w, size_t w_floats, const float* wt, size_t wt_floats,
+                      const float* dlogits, float* dfeat, int N, int seg, int num_class, void* stream);
+int agcn_sgn_frames_bwd(const float* x, const float* w, size_t w_floats, const float* wt, size_t wt_floats,
+                        const float* dfeat, float* dx, void* ws, size_t ws_bytes, int N, int seg, int V, void* stream);
+int agcn_sgn_sample_bwd(const float* win, const unsigned* r, const float* dout, float* dwin, int N, int T, int V, int K,
+                        int S, int seg, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
