@@ -127,6 +127,13 @@ SIGNATURES = {
     "agcn_sgn_clip_bwd": (_I, [_P, _P, _Z, _P, _Z, _P, _P, _I, _I, _I, _P]),
     "agcn_sgn_frames_bwd": (_I, [_P, _P, _Z, _P, _Z, _P, _P, _P, _Z, _I, _I, _I, _P]),
     "agcn_sgn_sample_bwd": (_I, [_P] * 4 + [_I] * 6 + [_P]),
+    "agcn_sgn_frames_tape_floats": (_Z, [_I, _I, _I]),
+    "agcn_sgn_clip_tape_floats": (_Z, [_I, _I, _I]),
+    "agcn_sgn_wgrad_workspace": (_Z, [_I] * 5),
+    "agcn_sgn_clip_bwd_tape": (_I, [_P, _P, _Z, _P, _Z, _P, _P, _I, _I, _I, _P, _Z, _P]),
+    "agcn_sgn_frames_bwd_tape": (_I, [_P, _P, _Z, _P, _Z, _P, _P, _P, _Z, _I, _I, _I, _P, _Z, _P]),
+    "agcn_sgn_frames_wgrad": (_I, [_P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _P]),
+    "agcn_sgn_clip_wgrad": (_I, [_P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _P]),
 }
 
 _lib = None

@@ -10,8 +10,14 @@ Three routes:
   images are cached under ``ops._cache_key`` and rebuilt after any parameter or running statistic changes.
 * the same launches in grad mode when x is the only tensor that asks for a gradient (every parameter frozen), behind
   ``ops.SGNInputGradFunction`` whose backward is ``ops.sgn_clip_bwd`` + ``ops.sgn_frames_bwd`` (csrc/sgn_bwd.hip);
-  ``input_gradient(x, cot)`` is that without autograd state.  Parameter gradients are not built in HIP.
-* everything else (grad mode with trainable parameters, ``train()``, a CPU tensor, ``step != seg``, ``AGCN_SGN_HIP=0``): the tensor-code
+  ``input_gradient(x, cot)`` is that without autograd state.
+* with ``fused_finetune = True`` (a plain attribute, off by default, not in the state_dict), eval mode, grad mode and
+  at least one trainable parameter: frozen-BatchNorm fine-tuning on the fused path.  ``ops.SGNFineTuneFunction`` runs the
+  fused forward; its backward tapes the two backward kernels and reduces the tapes to the gradients of the two folded
+  weight images (csrc/sgn_wgrad.hip), and torch autograd carries those through ``_folded()`` -- built in grad mode, fresh
+  per call -- to the parameters.  ``parameter_gradients(x, cot)`` is that without autograd state.  Train-mode BatchNorm
+  (batch statistics) is not built in HIP.
+* everything else (grad mode with trainable parameters and the flag off, ``train()``, a CPU tensor, ``step != seg``, ``AGCN_SGN_HIP=0``): the tensor-code
   composition below, channels last, ``F.linear`` / ``matmul`` on views and ``nn.BatchNorm`` modules.  It makes the class
   a complete ``nn.Module`` any torch optimiser can fine-tune and is the comparison of the fused path; it is NOT the hot
   path and is counted in ``ops.SGN_STATS['forward_tensor']``.
@@ -165,6 +171,7 @@ class SGN(nn.Module):
         for gcn in (self.gcn1, self.gcn2, self.gcn3):
             nn.init.constant_(gcn.w.cnn.weight, 0)
         self._infer_cache = {}
+        self.fused_finetune = False        # opt in: eval-mode backward() to the parameters on the HIP kernels
 
     # ---- the input-independent embeddings (reference sgn.py:78-79) ----
     def _spa1(self):
@@ -260,7 +267,26 @@ class SGN(nn.Module):
         return (torch.is_grad_enabled() and x.requires_grad and self._fusable(x)
                 and not any(p.requires_grad for p in self.parameters()))
 
+    def _fused_finetune(self, x):
+        """The flag, eval mode, grad mode, the kernels' domain and something to train."""
+        return (self.fused_finetune and torch.is_grad_enabled() and self._fusable(x)
+                and any(p.requires_grad for p in self.parameters()))
+
+    def _finetune_images(self):
+        """The four images for ``ops.SGNFineTuneFunction``: the forward ones in the CURRENT grad mode from a fresh fold (not
+        from ``_infer_cache``: they carry the autograd graph of this call), the transposed ones without grad from the
+        same folded tensors."""
+        frames, clip = self._folded()
+        wf = torch.cat([t.reshape(-1) for t in frames])
+        wc = torch.cat([t.reshape(-1) for t in clip])
+        with torch.no_grad():
+            wf_t = torch.cat([frames[i].t().reshape(-1) for i in (6, 10, 13, 15, 17, 19)]).contiguous()
+            wc_t = torch.cat([clip[1].transpose(1, 2).reshape(-1), clip[3].t().reshape(-1)]).contiguous()
+        return wf, wc, wf_t, wc_t
+
     def forward(self, x):
+        if self._fused_finetune(x):
+            return ops.SGNFineTuneFunction.apply(x, *self._finetune_images(), self.num_point, self.num_class)
         if self._fused_input_grad(x):
             with torch.no_grad():
                 images = self._images(transposed=True)
@@ -271,6 +297,35 @@ class SGN(nn.Module):
         wf, wc = self._images()
         feat, g = ops.sgn_frames(x.contiguous(), wf, self.num_point)
         return ops.sgn_clip(feat, wc, self.num_class), g
+
+    def parameter_gradients(self, x, cot, rows_per_split=0, max_tape_bytes=None):
+        """-> (logits, g, dx, {name: grad}) with the gradients of sum(logits * cot) in eval mode (BatchNorm on its running
+        statistics), for every parameter that requires grad.  Needs no prior autograd state and leaves every ``.grad``
+        alone.  On the GPU (fp32, step == seg, in_channels == 3, AGCN_SGN_HIP != 0) the batch dimension is all HIP: the
+        fused forward, the two taping backward kernels and the reductions of ``ops.sgn_image_gradients``; torch autograd
+        only takes the two image gradients through the fold.  Otherwise the composition with torch autograd (counted in
+        ``ops.SGN_STATS['forward_tensor']``).  ``rows_per_split`` / ``max_tape_bytes``: see ``ops.sgn_image_gradients``."""
+        if self.training:
+            raise ValueError("agcn_amd: SGN.parameter_gradients is the eval-mode gradient; call eval() first")
+        named = [(n, p) for n, p in self.named_parameters() if p.requires_grad]
+        params = [p for _, p in named]
+        if not self._fusable(x):
+            ops.SGN_STATS['forward_tensor'] += 1
+            with torch.enable_grad():
+                xg = x.detach().requires_grad_(True)
+                logits, g = self.forward_tensor(xg)
+                grads = torch.autograd.grad((logits * cot).sum(), [xg] + params, allow_unused=True)
+            dx, grads = grads[0], grads[1:]
+            logits, g = logits.detach(), g.detach()
+        else:
+            with torch.enable_grad():
+                wf, wc, wf_t, wc_t = self._finetune_images()
+            cap = ops.SGN_MAX_TAPE_BYTES if max_tape_bytes is None else max_tape_bytes
+            logits, g, dx, d_wf, d_wc = ops.sgn_image_gradients(x, wf.detach(), wc.detach(), wf_t, wc_t, cot,
+                                                                self.num_point, self.num_class, rows_per_split, cap)
+            grads = torch.autograd.grad([wf, wc], params, [d_wf, d_wc], allow_unused=True) if params else ()
+        out = {n: (torch.zeros_like(p) if gr is None else gr) for (n, p), gr in zip(named, grads)}
+        return logits, g, dx, out
 
     def input_gradient(self, x, cot):
         """-> (logits, g, dx) with dx = d sum(logits * cot) / dx, in eval mode.  Needs no autograd state and ignores the

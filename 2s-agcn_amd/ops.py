@@ -6,6 +6,7 @@ extension never allocates or keeps device memory.  Everything here launches on t
 
 Maths: SURVEY.md Appendix A (checked against the reference ``agcn.py:92-109`` by the oracle tests).
 """
+import math
 import os
 import weakref
 
@@ -1776,7 +1777,7 @@ def sgn_sample(win, r, seg):
 
 # ------------------------------------------------------------------------------------------------
 # base SGN, input gradients in eval mode (csrc/sgn_bwd.hip): the backward of the two launches above with respect to x,
-# and the adjoint of the sampler.  Parameter gradients are not built.
+# and the adjoint of the sampler.  The parameter gradients are further down (csrc/sgn_wgrad.hip).
 # ------------------------------------------------------------------------------------------------
 # diagnostic counters of the backward launches (a dict of its own: SGN_STATS is compared whole by its tests)
 SGN_GRAD_STATS = dict(clip_bwd=0, frames_bwd=0, sample_bwd=0)
@@ -1860,3 +1861,224 @@ class SGNInputGradFunction(torch.autograd.Function):
         x, feat, wf, wc, wf_t, wc_t = ctx.saved_tensors
         dfeat = sgn_clip_bwd(feat, wc, wc_t, dlogits.contiguous())
         return sgn_frames_bwd(x, wf, wf_t, dfeat, ctx.V), None, None, None, None, None, None
+
+
+# ------------------------------------------------------------------------------------------------
+# base SGN, parameter gradients in eval mode (csrc/sgn_wgrad.hip): frozen-BatchNorm fine-tuning.  The kernels give the
+# gradient with respect to the two folded weight images, in the images' layout; torch autograd takes it through the
+# fold (model/sgn.py::SGN._folded) to the parameters.  Train-mode BatchNorm is not built.
+# ------------------------------------------------------------------------------------------------
+# diagnostic counters of these launches (a dict of its own: SGN_STATS and SGN_GRAD_STATS are compared whole by their tests)
+SGN_WGRAD_STATS = dict(clip_bwd_tape=0, frames_bwd_tape=0, frames_wgrad=0, clip_wgrad=0)
+# a batch whose tapes would be larger is processed in chunks of whole clips
+SGN_MAX_TAPE_BYTES = 512 << 20
+
+
+def sgn_image_sections(V, seg, num_class):
+    """The sections of the two folded weight images in their order (csrc/sgn_plan.h: SgnFramesW, SgnClipW) ->
+    (frames, clip), each a list of (name, offset, shape)."""
+    def lay(items):
+        out, o = [], 0
+        for name, shape in items:
+            out.append((name, o, shape))
+            o += math.prod(shape)
+        return out
+    emb = lambda p: [(p + '1_w', (3, 64)), (p + '1_b', (64,)), (p + '2_w', (64, 64)), (p + '2_b', (64,))]  # noqa: E731
+    frames = lay([('aff', (4, V, 3))] + emb('je') + emb('de') + [('spa1', (V, 64)), ('g_w', (128, 512)), ('g_b', (512,)),
+                 ('c1_w', (256, 128)), ('c1_b', (128,)), ('c2_w', (256, 256)), ('c2_b', (256,)), ('c3_w', (512, 256)),
+                 ('c3_b', (256,))])
+    clip = lay([('tem1', (seg, 256)), ('t1_w', (768, 256)), ('t1_b', (256,)), ('t2_w', (256, 512)), ('t2_b', (512,)),
+                ('fc_w', (512, num_class)), ('fc_b', (num_class,))])
+    return frames, clip
+
+
+def sgn_image_forward_ref(x, wf, wc, V, seg, num_class):
+    """The tensor-code form of the fused SGN forward: x (N, seg, V*3) and the two flat folded images -> (logits, g),
+    differentiable in x, wf and wc.  The CPU route of SGNFineTuneFunction and the comparison of its image gradients."""
+    if x.dim() != 3 or x.shape[1] != seg or x.shape[2] != 3 * V:
+        raise ValueError(f"agcn_amd: sgn_image_forward_ref takes (N, {seg}, {3 * V}), got {tuple(x.shape)}")
+    fs, cs = sgn_image_sections(V, seg, num_class)
+    if wf.numel() != fs[-1][1] + math.prod(fs[-1][2]) or wc.numel() != cs[-1][1] + math.prod(cs[-1][2]):
+        raise ValueError("agcn_amd: sgn_image_forward_ref: the images do not have the sizes of csrc/sgn_plan.h")
+    f = {n: wf[o:o + math.prod(s)].reshape(s) for n, o, s in fs}
+    c = {n: wc[o:o + math.prod(s)].reshape(s) for n, o, s in cs}
+    relu = torch.relu
+    N = x.shape[0]
+    xr = x.reshape(N, seg, V, 3)
+    dif = torch.cat([xr.new_zeros(N, 1, V, 3), xr[:, 1:] - xr[:, :-1]], dim=1)
+
+    def emb(v, p):
+        return relu(relu(v @ f[p + '1_w'] + f[p + '1_b']) @ f[p + '2_w'] + f[p + '2_b'])
+
+    dy = emb(xr * f['aff'][0] + f['aff'][1], 'je') + emb(dif * f['aff'][2] + f['aff'][3], 'de')
+    h = torch.cat([dy, f['spa1'].expand(N, seg, V, 64)], dim=3)
+    gg = h @ f['g_w'] + f['g_b']
+    g = torch.softmax(gg[..., :256] @ gg[..., 256:].transpose(-1, -2), dim=-1)
+    for l in ('c1', 'c2', 'c3'):
+        h = relu(torch.cat([g @ h, h], dim=3) @ f[l + '_w'] + f[l + '_b'])
+    H = h.amax(2) + c['tem1']
+    Hp = torch.nn.functional.pad(H, (0, 0, 1, 1))
+    taps = torch.cat([Hp[:, dt:dt + seg] for dt in range(3)], dim=2)
+    y2 = relu(relu(taps @ c['t1_w'] + c['t1_b']) @ c['t2_w'] + c['t2_b'])
+    return y2.amax(1) @ c['fc_w'] + c['fc_b'], g
+
+
+def _tape(query, args, like, what):
+    n = query(*args)
+    if n == 0:
+        raise ValueError(f"agcn_amd: {what}: {args} is outside the kernels' domain")
+    return _empty((n,), like)
+
+
+def sgn_clip_bwd_tape(feat, wimg, wimg_t, dlogits):
+    """``sgn_clip_bwd`` (the same dfeat bits) that also writes the clip tape (csrc/sgn_wgrad_plan.h: SgnClipTape) ->
+    (dfeat, tape)."""
+    if feat.dim() != 3 or feat.shape[2] != 256:
+        raise ValueError(f"agcn_amd: sgn_clip_bwd_tape takes feat (N, seg, 256), got {tuple(feat.shape)}")
+    N, seg, _ = feat.shape
+    if dlogits.dim() != 2 or dlogits.shape[0] != N or dlogits.shape[1] < 1:
+        raise ValueError(f"agcn_amd: sgn_clip_bwd_tape takes dlogits ({N}, num_class), got {tuple(dlogits.shape)}")
+    nc = dlogits.shape[1]
+    tape = _tape(_L().agcn_sgn_clip_tape_floats, (N, seg, nc), feat, "sgn_clip_bwd_tape")
+    dfeat = _empty((N, seg, 256), feat)
+    rc = _L().agcn_sgn_clip_bwd_tape(_lib.ptr(feat), _lib.ptr(wimg), wimg.numel(), _lib.ptr(wimg_t), wimg_t.numel(),
+                                     _lib.ptr(dlogits), _lib.ptr(dfeat), N, seg, nc, _lib.ptr(tape), tape.numel(),
+                                     _lib.stream())
+    _lib.check(rc, "agcn_sgn_clip_bwd_tape")
+    SGN_WGRAD_STATS['clip_bwd_tape'] += 1
+    return dfeat, tape
+
+
+def sgn_frames_bwd_tape(x, wimg, wimg_t, dfeat, V):
+    """``sgn_frames_bwd`` (the same dx bits) that also writes the frames tape (SgnFramesTape) -> (dx, tape)."""
+    if x.dim() != 3 or x.shape[2] != 3 * V:
+        raise ValueError(f"agcn_amd: sgn_frames_bwd_tape takes (N, seg, {3 * V}), got {tuple(x.shape)}")
+    N, seg, _ = x.shape
+    if tuple(dfeat.shape) != (N, seg, 256):
+        raise ValueError(f"agcn_amd: sgn_frames_bwd_tape takes dfeat ({N}, {seg}, 256), got {tuple(dfeat.shape)}")
+    tape = _tape(_L().agcn_sgn_frames_tape_floats, (N, seg, V), x, "sgn_frames_bwd_tape")
+    dx = _empty((N, seg, 3 * V), x)
+    ws = _empty((max(1, _L().agcn_sgn_frames_bwd_workspace(N, seg, V) // 4),), x)
+    rc = _L().agcn_sgn_frames_bwd_tape(_lib.ptr(x), _lib.ptr(wimg), wimg.numel(), _lib.ptr(wimg_t), wimg_t.numel(),
+                                       _lib.ptr(dfeat), _lib.ptr(dx), ws.data_ptr(), ws.numel() * 4, N, seg, V,
+                                       _lib.ptr(tape), tape.numel(), _lib.stream())
+    _lib.check(rc, "agcn_sgn_frames_bwd_tape")
+    SGN_WGRAD_STATS['frames_bwd_tape'] += 1
+    return dx, tape
+
+
+def _sgn_wgrad_ws(N, seg, V, num_class, rows_per_split, like):
+    if rows_per_split < 0:
+        raise ValueError(f"agcn_amd: rows_per_split must be >= 0, got {rows_per_split}")
+    n = _L().agcn_sgn_wgrad_workspace(N, seg, V, num_class, rows_per_split)
+    if n == 0:
+        raise ValueError(f"agcn_amd: SGN parameter gradients: {(N, seg, V, num_class)} is outside the kernels' domain")
+    return _empty((n // 4,), like)
+
+
+def sgn_frames_wgrad(x, wimg, tape, V, num_class, rows_per_split=0):
+    """The frames tape -> the gradient of the frames image, in its layout."""
+    N, seg, _ = x.shape
+    if tape.numel() < _L().agcn_sgn_frames_tape_floats(N, seg, V) or x.shape[2] != 3 * V:
+        raise ValueError(f"agcn_amd: sgn_frames_wgrad: a tape of {tape.numel()} floats is not the tape of {tuple(x.shape)}")
+    ws = _sgn_wgrad_ws(N, seg, V, num_class, rows_per_split, x)
+    d_w = _empty((wimg.numel(),), x)
+    rc = _L().agcn_sgn_frames_wgrad(_lib.ptr(x), _lib.ptr(wimg), _lib.ptr(tape), _lib.ptr(d_w), ws.data_ptr(),
+                                    ws.numel() * 4, N, seg, V, rows_per_split, _lib.stream())
+    _lib.check(rc, "agcn_sgn_frames_wgrad")
+    SGN_WGRAD_STATS['frames_wgrad'] += 1
+    return d_w
+
+
+def sgn_clip_wgrad(tape, dfeat, dlogits, wimg, V, rows_per_split=0):
+    """The clip tape, dfeat and dlogits -> the gradient of the clip image, in its layout."""
+    N, seg, _ = dfeat.shape
+    nc = dlogits.shape[1]
+    if tape.numel() < _L().agcn_sgn_clip_tape_floats(N, seg, nc) or tuple(dlogits.shape) != (N, nc):
+        raise ValueError(f"agcn_amd: sgn_clip_wgrad: a tape of {tape.numel()} floats is not the tape of {tuple(dfeat.shape)}")
+    ws = _sgn_wgrad_ws(N, seg, V, nc, rows_per_split, dfeat)
+    d_w = _empty((wimg.numel(),), dfeat)
+    rc = _L().agcn_sgn_clip_wgrad(_lib.ptr(tape), _lib.ptr(dfeat), _lib.ptr(dlogits), _lib.ptr(d_w), ws.data_ptr(),
+                                  ws.numel() * 4, N, seg, nc, rows_per_split, _lib.stream())
+    _lib.check(rc, "agcn_sgn_clip_wgrad")
+    SGN_WGRAD_STATS['clip_wgrad'] += 1
+    return d_w
+
+
+def sgn_tape_chunk(N, seg, V, num_class, max_tape_bytes):
+    """Clips per chunk: as many whole clips as fit ``max_tape_bytes`` of tape (both tapes are linear in the clips), at
+    least one."""
+    per = 4 * (_L().agcn_sgn_frames_tape_floats(1, seg, V) + _L().agcn_sgn_clip_tape_floats(1, seg, num_class))
+    if per == 0:
+        raise ValueError(f"agcn_amd: SGN parameter gradients: {(seg, V, num_class)} is outside the kernels' domain")
+    return max(1, min(N, int(max_tape_bytes) // per))
+
+
+def _sgn_image_backward(x, feat, wf, wc, wf_t, wc_t, dlogits, V, rows_per_split, max_tape_bytes):
+    """-> (dx, d_wf, d_wc): chunks of whole clips, the chunks' image gradients added in chunk order."""
+    N, seg, _ = x.shape
+    nc = dlogits.shape[1]
+    chunk = sgn_tape_chunk(N, seg, V, nc, max_tape_bytes)
+    dxs, d_wf, d_wc = [], None, None
+    for n0 in range(0, N, chunk):
+        xs, fe, dl = x[n0:n0 + chunk], feat[n0:n0 + chunk], dlogits[n0:n0 + chunk]
+        dfeat, ctape = sgn_clip_bwd_tape(fe, wc, wc_t, dl)
+        dx, ftape = sgn_frames_bwd_tape(xs, wf, wf_t, dfeat, V)
+        gf = sgn_frames_wgrad(xs, wf, ftape, V, nc, rows_per_split)
+        gc = sgn_clip_wgrad(ctape, dfeat, dl, wc, V, rows_per_split)
+        del ftape, ctape
+        dxs.append(dx)
+        d_wf = gf if d_wf is None else d_wf + gf
+        d_wc = gc if d_wc is None else d_wc + gc
+    return (dxs[0] if len(dxs) == 1 else torch.cat(dxs)), d_wf, d_wc
+
+
+def sgn_image_gradients(x, wf, wc, wf_t, wc_t, cot, V, num_class, rows_per_split=0, max_tape_bytes=SGN_MAX_TAPE_BYTES):
+    """The fused eval forward and the gradient of sum(logits * cot) with respect to x and to the two folded images ->
+    (logits, g, dx, d_wf, d_wc); d_wf / d_wc have the layout of wf / wc."""
+    with torch.no_grad():
+        x = x.detach().contiguous()
+        feat, g = sgn_frames(x, wf, V)
+        logits = sgn_clip(feat, wc, num_class)
+        cot = cot.detach().to(logits).contiguous()
+        if tuple(cot.shape) != tuple(logits.shape):
+            raise ValueError(f"agcn_amd: sgn_image_gradients takes cot {tuple(logits.shape)}, got {tuple(cot.shape)}")
+        return (logits, g) + _sgn_image_backward(x, feat, wf, wc, wf_t, wc_t, cot, V, rows_per_split, max_tape_bytes)
+
+
+class SGNFineTuneFunction(torch.autograd.Function):
+    """SGN's eval forward as the two fused launches, differentiable with respect to x and the two folded weight images
+    (built in grad mode by model/sgn.py, so autograd continues through the fold to the parameters).  args: x, wf, wc,
+    wf_t, wc_t, V, num_class -> logits, g (g is not differentiable).  A CPU tensor runs ``sgn_image_forward_ref``."""
+
+    @staticmethod
+    def forward(ctx, x, wf, wc, wf_t, wc_t, V, num_class):
+        ctx.V = V
+        if not x.is_cuda:
+            with torch.enable_grad():
+                leaves = [t.detach().requires_grad_(True) for t in (x, wf, wc)]
+                logits, g = sgn_image_forward_ref(*leaves, V, x.shape[1], num_class)
+            ctx.ref = (leaves, logits)
+            g = g.detach()
+            ctx.mark_non_differentiable(g)
+            return logits.detach(), g
+        x = x.contiguous()
+        feat, g = sgn_frames(x, wf.detach(), V)
+        logits = sgn_clip(feat, wc.detach(), num_class)
+        ctx.ref = None
+        ctx.save_for_backward(x, feat, wf, wc, wf_t, wc_t)
+        ctx.mark_non_differentiable(g)
+        return logits, g
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dlogits, _dg):
+        if ctx.ref is not None:
+            leaves, logits = ctx.ref
+            with torch.enable_grad():
+                dx, d_wf, d_wc = torch.autograd.grad(logits, leaves, dlogits)
+        else:
+            x, feat, wf, wc, wf_t, wc_t = ctx.saved_tensors
+            dx, d_wf, d_wc = _sgn_image_backward(x, feat, wf, wc, wf_t, wc_t, dlogits.contiguous(), ctx.V, 0,
+                                                 SGN_MAX_TAPE_BYTES)
+        return (dx if ctx.needs_input_grad[0] else None), d_wf, d_wc, None, None, None, None

@@ -516,8 +516,8 @@ int agcn_sgn_sample(const float* win, const unsigned* r, float* out, int* L, int
                     void* stream);
 
 /* ---- base SGN, input gradients in eval mode (csrc/sgn_bwd.hip; geometry in csrc/sgn_bwd_plan.h) ----
- * What torch autograd does on the reference's eval forward (sgn.py:66-98) with respect to x; parameter gradients are not
- * built.  Same arithmetic rules as the forward: exact-f32 MFMA in every AGCN_GEMM mode, fixed summation orders, no
+ * What torch autograd does on the reference's eval forward (sgn.py:66-98) with respect to x (the parameter gradients
+ * follow further down).  Same arithmetic rules as the forward: exact-f32 MFMA in every AGCN_GEMM mode, fixed summation orders, no
  * atomics, no launch reads another clip's intermediates, so a clip's gradient is the same bits alone and in any batch.
  * Nothing of the forward is stored: each kernel recomputes what it needs from x / feat.  ReLU's derivative at 0 is 0; a
  * maximum routes to its lowest index (MaxPool's choice; ties only happen at 0, where nothing flows).  Checks as above.
@@ -551,6 +551,39 @@ int agcn_sgn_frames_bwd(const float* x, const float* w, size_t w_floats, const f
                         const float* dfeat, float* dx, void* ws, size_t ws_bytes, int N, int seg, int V, void* stream);
 int agcn_sgn_sample_bwd(const float* win, const unsigned* r, const float* dout, float* dwin, int N, int T, int V, int K,
                         int S, int seg, void* stream);
+
+/* ---- base SGN, parameter gradients in eval mode (csrc/sgn_wgrad.hip; geometry in csrc/sgn_wgrad_plan.h) ----
+ * Frozen-BatchNorm fine-tuning: the gradient of a loss on the logits with respect to the two folded weight images, each
+ * in its image's own layout (SgnFramesW / SgnClipW, the offsets of the forward image).  The caller takes them through
+ * the fold to the parameters (model/sgn.py).  Arithmetic rules as above: exact-f32 MFMA, fixed summation orders, no
+ * atomics.  Train-mode BatchNorm is not covered.
+ *
+ * sgn_frames_tape_floats / sgn_clip_tape_floats: floats of the caller-owned tapes (0 outside the domain).
+ * sgn_wgrad_workspace: bytes of the workspace both wgrad entries take (the largest partial: elements of a section times
+ *   the splits of its rows).  rows_per_split = 0 is the plan's default; tests pass small and odd values.
+ * sgn_clip_bwd_tape / sgn_frames_bwd_tape: sgn_clip_bwd / sgn_frames_bwd with the same results bit for bit, which also
+ *   copy every operand pair of a weight gradient to the tape (SgnClipTape / SgnFramesTape: the V real joint rows of a
+ *   frame only, H with the convolution's two zero rows per clip, columns 64..127 of d x0, d xn before the folded scale).
+ *   AGCN_ERR_WORKSPACE: tape_floats below the size query (or ws_bytes, as for sgn_frames_bwd).
+ * sgn_frames_wgrad: x, the frames tape -> d_w (sgn_frames_weights(V) floats, every float written).  w is the forward
+ *   image (not read at present: the tape holds every operand).  sgn_clip_wgrad: the clip tape, dfeat (N, seg, 256) as
+ *   sgn_clip_bwd_tape returned it, dlogits -> d_w (sgn_clip_weights(seg, num_class) floats).  Each section is a launch
+ *   over row splits that writes partials to ws and a launch that adds them in ascending split order.
+ *   AGCN_ERR_WORKSPACE: ws_bytes < sgn_wgrad_workspace(...).  AGCN_ERR_ARG: null pointers, V outside [2, 32],
+ *   num_class < 1, rows_per_split < 0. */
+size_t agcn_sgn_frames_tape_floats(int N, int seg, int V);
+size_t agcn_sgn_clip_tape_floats(int N, int seg, int num_class);
+size_t agcn_sgn_wgrad_workspace(int N, int seg, int V, int num_class, int rows_per_split);
+int agcn_sgn_clip_bwd_tape(const float* feat, const float* w, size_t w_floats, const float* wt, size_t wt_floats,
+                           const float* dlogits, float* dfeat, int N, int seg, int num_class, float* tape,
+                           size_t tape_floats, void* stream);
+int agcn_sgn_frames_bwd_tape(const float* x, const float* w, size_t w_floats, const float* wt, size_t wt_floats,
+                             const float* dfeat, float* dx, void* ws, size_t ws_bytes, int N, int seg, int V, float* tape,
+                             size_t tape_floats, void* stream);
+int agcn_sgn_frames_wgrad(const float* x, const float* w, const float* tape, float* d_w, void* ws, size_t ws_bytes, int N,
+                          int seg, int V, int rows_per_split, void* stream);
+int agcn_sgn_clip_wgrad(const float* tape, const float* dfeat, const float* dlogits, float* d_w, void* ws, size_t ws_bytes,
+                        int N, int seg, int num_class, int rows_per_split, void* stream);
 
 #ifdef __cplusplus
 }
