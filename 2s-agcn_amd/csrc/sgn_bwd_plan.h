@@ -93,12 +93,9 @@ static const SgnBwdLife SGN_BWD_LIVES[] = {
 // (into registers) before d g2 overwrites it.
 
 // ---- the dif coupling: frame f = n * seg + t writes dj[f] and dd[f] (V * 3 floats each) to the workspace, a second
-// kernel combines dx[t] = dj[t] + dd[t] [t > 0] - dd[t + 1] [t + 1 < seg].  The neighbours as guarded frame indices:
-// -1 = no such term, so that no index ever leaves the clip. ----
+// kernel combines dx[t] = dj[t] + dd[t] [t > 0] - dd[t + 1] [t + 1 < seg], with the guarded neighbours sgn_dif_* of
+// sgn_plan.h. ----
 SGN_HD size_t sgn_frames_bwd_ws_floats(long N, int seg, int V) { return (size_t)2 * (size_t)N * (size_t)seg * (size_t)(V * 3); }
-SGN_HD long sgn_dif_prev(long f, int seg) { return f % seg > 0 ? f - 1 : -1; }          // the frame dif[t] subtracts
-SGN_HD long sgn_dif_own(long f, int seg) { return f % seg > 0 ? f : -1; }               // dd[t] reaches x[t] iff t > 0
-SGN_HD long sgn_dif_next(long f, int seg) { return f % seg + 1 < seg ? f + 1 : -1; }    // dd[t + 1] reaches x[t]
 
 // ---- the sampler's adjoint: the kept row that pick (k, r) of a sequence of L rows reads, as an index into the kept-row
 // table (0 <= index < kept <= SGN_SAMPLE_MAX_ROWS), or -1 where the pick falls into the zero padding behind the kept rows
@@ -109,18 +106,9 @@ SGN_HD int sgn_pick_source(int k, int L, int seg, unsigned r, int kept) {
   return idx < kept ? idx : -1;
 }
 
-// ---- the clip kernel's tiles: tile k owns the frames [32 k, 32 k + rows).  Its conv gradient also reaches frame
+// ---- the clip kernel's tiles (sgn_plan.h: sgn_tile_rows, sgn_tile_frame).  A tile's conv gradient also reaches frame
 // 32 k - 1 (through tap 0 of its first frame) and frame 32 k + 32 (through tap 2 of its last): halo frames, owned by
 // the neighbouring tiles.  -1 = the halo is the conv's zero padding (or does not exist) and receives nothing. ----
-SGN_HD int sgn_tile_rows(int tile, int seg) {
-  const int left = seg - tile * SGN_VP;
-  return left < 0 ? 0 : left < SGN_VP ? left : SGN_VP;
-}
-// row 0..33 of a tile's H buffer holds frame 32 k - 1 + row, or the conv's zero padding (-1) outside the clip
-SGN_HD int sgn_tile_frame(int tile, int row, int seg) {
-  const int t = tile * SGN_VP - 1 + row;
-  return t >= 0 && t < seg ? t : -1;
-}
 SGN_HD int sgn_halo_lo(int tile, int seg) { return tile > 0 && tile * SGN_VP - 1 < seg ? tile * SGN_VP - 1 : -1; }
 SGN_HD int sgn_halo_hi(int tile, int seg) { return (tile + 1) * SGN_VP < seg ? (tile + 1) * SGN_VP : -1; }
 // LDS of agcn_sgn_clip_bwd: the forward's H / Y / maximum, where d Y1 (with a zero row on either side) takes the place

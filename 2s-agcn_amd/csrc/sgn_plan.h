@@ -82,6 +82,12 @@ SGN_HD SgnFramesW sgn_frames_w(int V) {
 #define SGN_FRAMES_LDS_FLOATS (SGN_LDS_XIN + 2 * SGN_VP * 4)
 static_assert(SGN_FRAMES_LDS_FLOATS * 4 <= SGN_LDS_LIMIT, "agcn_sgn_frames: LDS");
 
+// ---- dif[t] = x[t] - x[t - 1] inside a clip, zero at t = 0.  The neighbours of frame f = n * seg + t as guarded frame
+// indices: -1 = no such term, so that no index ever leaves the clip. ----
+SGN_HD long sgn_dif_prev(long f, int seg) { return f % seg > 0 ? f - 1 : -1; }          // the frame dif[t] subtracts
+SGN_HD long sgn_dif_own(long f, int seg) { return f % seg > 0 ? f : -1; }               // dd[t] reaches x[t] iff t > 0
+SGN_HD long sgn_dif_next(long f, int seg) { return f % seg + 1 < seg ? f + 1 : -1; }    // dd[t + 1] reaches x[t]
+
 // ---- folded weight image of agcn_sgn_clip ----
 struct SgnClipW {
   int tem1;                    // (seg, 256): tem_embed of the one-hot frames
@@ -112,6 +118,16 @@ SGN_HD SgnClipW sgn_clip_w(int seg, int num_class) {
 #define SGN_CLIP_LDS_FLOATS (SGN_CLIP_LDS_MAX + SGN_C4)
 static_assert(SGN_CLIP_LDS_FLOATS * 4 <= SGN_LDS_LIMIT, "agcn_sgn_clip: LDS");
 SGN_HD int sgn_clip_tiles(int seg) { return (seg + SGN_VP - 1) / SGN_VP; }
+// tile k owns the frames [32 k, 32 k + rows)
+SGN_HD int sgn_tile_rows(int tile, int seg) {
+  const int left = seg - tile * SGN_VP;
+  return left < 0 ? 0 : left < SGN_VP ? left : SGN_VP;
+}
+// row 0..33 of a tile's H buffer holds frame 32 k - 1 + row, or the conv's zero padding (-1) outside the clip
+SGN_HD int sgn_tile_frame(int tile, int row, int seg) {
+  const int t = tile * SGN_VP - 1 + row;
+  return t >= 0 && t < seg ? t : -1;
+}
 
 // ---- the sampler (reference feeders/loader.py:203-232, 302-358, equal-interval branch) ----
 #define SGN_SAMPLE_MAX_T 2048                  // = agcn_prenorm_max_frames()

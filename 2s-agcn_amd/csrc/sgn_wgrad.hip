@@ -1,9 +1,8 @@
 // Parameter gradients of the base SGN in eval mode (frozen-BatchNorm fine-tuning): the gradient of a loss on the logits
 // with respect to the two folded weight images of sgn.hip, each in its image's own layout (sgn_plan.h: SgnFramesW,
 // SgnClipW).  torch autograd carries them through the fold to the parameters (model/sgn.py::SGN._folded).
-//   sgn_frames_bwd_kernel<true>, sgn_clip_bwd_kernel<true>   the backward kernels of sgn_bwd_kernels.h, taping: same dx /
-//                           dfeat bits as the untaped instantiations, and every operand pair of a weight gradient copied
-//                           to a caller-owned tape (V real joint rows per frame; layout in sgn_wgrad_plan.h).
+// The operands come from the two tapes that the taping backward kernels of sgn_bwd.hip write (agcn_sgn_clip_bwd_tape,
+// agcn_sgn_frames_bwd_tape; V real joint rows per frame; layout in sgn_wgrad_plan.h).  The reduction kernels here:
 //   sgn_wgrad_gemm_kernel   dW (K, N) = X^T . Z over the rows of one split, one wave per 32 x (32..128) strip of dW,
 //                           exact-f32 MFMA (v_mfma_f32_32x32x2_f32), both operands read along their rows straight from
 //                           the tape; plain or grouped rows (the three taps of the temporal convolution).
@@ -15,7 +14,6 @@
 // same bits.  Geometry, splits, workspace and every guarded index: sgn_wgrad_plan.h.
 #include "agcn_common.h"
 #include "sgn_wgrad_plan.h"
-#include "sgn_bwd_kernels.h"
 
 struct SgnWgradGemm {
   const float* X;
@@ -225,41 +223,6 @@ extern "C" size_t agcn_sgn_clip_tape_floats(int N, int seg, int num_class) {
 extern "C" size_t agcn_sgn_wgrad_workspace(int N, int seg, int V, int num_class, int rows_per_split) {
   if (!sgn_wgrad_domain(N, seg, V, num_class) || rows_per_split < 0) return 0;
   return sgn_wgrad_ws_floats(N, seg, V, num_class, rows_per_split) * sizeof(float);
-}
-
-extern "C" int agcn_sgn_clip_bwd_tape(const float* feat, const float* w, size_t w_floats, const float* wt, size_t wt_floats,
-                                      const float* dlogits, float* dfeat, int N, int seg, int num_class, float* tape,
-                                      size_t tape_floats, void* stream) {
-  if (!feat || !w || !wt || !dlogits || !dfeat || !tape) return AGCN_ERR_ARG;
-  if (N < 1 || seg < 1 || num_class < 1) return AGCN_ERR_ARG;
-  if (!sgn_clip_domain(N, seg, num_class)) return AGCN_ERR_UNSUPPORTED;
-  if (w_floats != (size_t)sgn_clip_w(seg, num_class).total || wt_floats != (size_t)sgn_clip_wt().total) return AGCN_ERR_ARG;
-  if (tape_floats < sgn_clip_tape(N, seg).total) return AGCN_ERR_WORKSPACE;
-  AGCN_NOTE_KERNEL("sgn_clip_bwd_kernel<f32 mfma, tape> seg=%d clips=%d", seg, N);
-  return agcn_launch_big<sgn_clip_bwd_kernel<true>>(dim3((unsigned)N), dim3(SGN_THREADS), (size_t)SGN_CLIP_BWD_LDS_FLOATS * 4,
-                                                    (hipStream_t)stream, feat, w, wt, dlogits, dfeat, tape, seg, num_class);
-}
-
-extern "C" int agcn_sgn_frames_bwd_tape(const float* x, const float* w, size_t w_floats, const float* wt, size_t wt_floats,
-                                        const float* dfeat, float* dx, void* ws, size_t ws_bytes, int N, int seg, int V,
-                                        float* tape, size_t tape_floats, void* stream) {
-  if (!x || !w || !wt || !dfeat || !dx || !ws || !tape) return AGCN_ERR_ARG;
-  if (N < 1 || seg < 1 || V < 2 || V > SGN_MAX_V) return AGCN_ERR_ARG;
-  if (!sgn_frames_domain(N, seg, V)) return AGCN_ERR_UNSUPPORTED;
-  if (w_floats != (size_t)sgn_frames_w(V).total || wt_floats != (size_t)sgn_frames_wt().total) return AGCN_ERR_ARG;
-  if (ws_bytes < sgn_frames_bwd_ws_floats(N, seg, V) * sizeof(float)) return AGCN_ERR_WORKSPACE;
-  if (tape_floats < sgn_frames_tape_floats(N, seg, V)) return AGCN_ERR_WORKSPACE;
-  const long frames = (long)N * seg, total = frames * (V * 3);
-  float* dj = (float*)ws;
-  float* dd = dj + total;
-  AGCN_NOTE_KERNEL("sgn_frames_bwd_kernel<f32 mfma, tape> V=%d frames=%ld", V, frames);
-  int rc = agcn_launch_big<sgn_frames_bwd_kernel<true>>(dim3((unsigned)frames), dim3(SGN_THREADS),
-                                                        (size_t)SGN_FRAMES_BWD_LDS_FLOATS * 4, (hipStream_t)stream, x, w, wt,
-                                                        dfeat, dj, dd, tape, seg, V);
-  if (rc != AGCN_OK) return rc;
-  hipLaunchKernelGGL(sgn_dif_combine_kernel, dim3((unsigned)((total + SGN_THREADS - 1) / SGN_THREADS)), dim3(SGN_THREADS), 0,
-                     (hipStream_t)stream, (const float*)dj, (const float*)dd, dx, total, seg, V * 3);
-  return agcn_check_launch();
 }
 
 extern "C" int agcn_sgn_frames_wgrad(const float* x, const float* w, const float* tape, float* d_w, void* ws,

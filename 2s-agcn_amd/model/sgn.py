@@ -31,6 +31,9 @@ import torch.nn.functional as F
 
 from .. import ops
 
+# the names of the sections of the two weight images, in their order (they do not depend on the sizes)
+_FRAMES_SECTIONS, _CLIP_SECTIONS = ([n for n, _, _ in secs] for secs in ops.sgn_image_sections(2, 1, 1))
+
 
 def _cl_to_cf(x):
     """(bs, step, V, C) -> (bs, C, V, step): the layout the reference's BatchNorm / pooling modules see."""
@@ -230,27 +233,34 @@ class SGN(nn.Module):
                 self.fc.weight.t(), self.fc.bias]
         return frames, clip
 
+    @staticmethod
+    def _flatten(frames, clip):
+        """The two folded lists -> (frames image, clip image), each one flat tensor."""
+        return torch.cat([t.reshape(-1) for t in frames]), torch.cat([t.reshape(-1) for t in clip])
+
+    @staticmethod
+    def _transposed(frames, clip):
+        """The two folded lists -> the two images of the backward (csrc/sgn_bwd_plan.h: the same folded matrices stored
+        (N, K)): W^T of je2, de2, [g1 | g2], gcn1..3 of the frames image; of the three taps of cnn1 and of cnn2."""
+        f = dict(zip(_FRAMES_SECTIONS[1:], frames[4:]))      # 'aff' (4, V, 3) is the list's first four (V, 3) tensors
+        c = dict(zip(_CLIP_SECTIONS, clip))
+        wf_t = torch.cat([f[n].t().reshape(-1) for n in ('je2_w', 'de2_w', 'g_w', 'c1_w', 'c2_w', 'c3_w')])
+        wc_t = torch.cat([c['t1_w'].transpose(1, 2).reshape(-1), c['t2_w'].t().reshape(-1)])
+        return wf_t, wc_t
+
     def _images(self, transposed=False):
-        """-> (frames image, clip image); with ``transposed`` also the two images of the backward (csrc/sgn_bwd_plan.h: the
-        same folded matrices stored (N, K)).  Those are built on the first call that asks for them, under the same key:
-        a model that only predicts never builds them."""
+        """-> (frames image, clip image); with ``transposed`` also the two images of the backward.  Those are built on the
+        first call that asks for them, under the same key: a model that only predicts never builds them."""
         srcs = list(self.parameters()) + list(self.buffers())
         key = ops._cache_key(srcs)
         f = self._infer_cache.get('images')
         if f is None or f[0] != key:
-            frames, clip = self._folded()
-            wf = torch.cat([t.reshape(-1) for t in frames]).contiguous()
-            wc = torch.cat([t.reshape(-1) for t in clip]).contiguous()
-            f = self._infer_cache['images'] = (key, wf, wc)
+            f = self._infer_cache['images'] = (key,) + self._flatten(*self._folded())
         if not transposed:
             return f[1], f[2]
         t = self._infer_cache.get('images_t')
         if t is None or t[0] != key:
-            frames, clip = self._folded()
-            # W^T of je2, de2, [g1 | g2], gcn1..3 of the frames image; of the three taps of cnn1 and of cnn2
-            wf_t = torch.cat([frames[i].t().reshape(-1) for i in (6, 10, 13, 15, 17, 19)]).contiguous()
-            wc_t = torch.cat([clip[1].transpose(1, 2).reshape(-1), clip[3].t().reshape(-1)]).contiguous()
-            t = self._infer_cache['images_t'] = (key, wf_t, wc_t)
+            t = self._infer_cache['images_t'] = (key,) + self._transposed(*self._folded())
         return f[1], f[2], t[1], t[2]
 
     def _fusable(self, x):
@@ -277,11 +287,9 @@ class SGN(nn.Module):
         from ``_infer_cache``: they carry the autograd graph of this call), the transposed ones without grad from the
         same folded tensors."""
         frames, clip = self._folded()
-        wf = torch.cat([t.reshape(-1) for t in frames])
-        wc = torch.cat([t.reshape(-1) for t in clip])
+        wf, wc = self._flatten(frames, clip)
         with torch.no_grad():
-            wf_t = torch.cat([frames[i].t().reshape(-1) for i in (6, 10, 13, 15, 17, 19)]).contiguous()
-            wc_t = torch.cat([clip[1].transpose(1, 2).reshape(-1), clip[3].t().reshape(-1)]).contiguous()
+            wf_t, wc_t = self._transposed(frames, clip)
         return wf, wc, wf_t, wc_t
 
     def forward(self, x):

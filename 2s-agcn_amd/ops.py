@@ -1751,21 +1751,27 @@ def sgn_draws(N, S, seg, device):
     return torch.randint(0, 1 << 32, (N, S, seg), dtype=torch.int64, device=device).to(torch.int32)
 
 
+def _sgn_sample_args(name, win, r, seg):
+    """The window and draw checks of ``sgn_sample`` and ``sgn_sample_bwd`` (``name``: the one that was called) ->
+    (r as int32, N, T, V, K, S)."""
+    if win.dim() != 5 or win.shape[1] != 3:
+        raise ValueError(f"agcn_amd: {name} takes windows (N, 3, T, V, 2), got {tuple(win.shape)}")
+    N, _, T, V, K = win.shape
+    if K != 2:
+        raise ValueError(f"agcn_amd: {name} interleaves exactly two selected bodies, got {K}")
+    if r.dtype == torch.uint32:
+        r = r.view(torch.int32)
+    if r.dim() != 3 or r.shape[0] != N or r.shape[2] != seg or r.dtype != torch.int32:
+        raise ValueError(f"agcn_amd: {name} takes draws ({N}, S, {seg}) int32, got {r.dtype} {tuple(r.shape)}")
+    return r, N, T, V, K, r.shape[1]
+
+
 def sgn_sample(win, r, seg):
     """NTUDataLoaders.to_fix_length (equal-interval branch) on normalised windows win (N, 3, T, V, 2) in ``prenorm``'s
     output layout (agcn_sgn_sample): null rows dropped, the two bodies interleaved by frame, fewer than ``seg`` rows
     zero-padded, and one row per interval and draw.  r (N, S, seg): the draws as 32-bit patterns in an int32 (or uint32)
     tensor, read as unsigned.  Returns (out (N, S, seg, V*3), L (N,) int32 row counts), on the device."""
-    if win.dim() != 5 or win.shape[1] != 3:
-        raise ValueError(f"agcn_amd: sgn_sample takes windows (N, 3, T, V, 2), got {tuple(win.shape)}")
-    N, _, T, V, K = win.shape
-    if K != 2:
-        raise ValueError(f"agcn_amd: sgn_sample interleaves exactly two selected bodies, got {K}")
-    if r.dtype == torch.uint32:
-        r = r.view(torch.int32)
-    if r.dim() != 3 or r.shape[0] != N or r.shape[2] != seg or r.dtype != torch.int32:
-        raise ValueError(f"agcn_amd: sgn_sample takes draws ({N}, S, {seg}) int32, got {r.dtype} {tuple(r.shape)}")
-    S = r.shape[1]
+    r, N, T, V, K, S = _sgn_sample_args("sgn_sample", win, r, seg)
     out = _empty((N, S, seg, V * 3), win)
     L = torch.empty((N,), dtype=torch.int32, device=win.device)
     rc = _L().agcn_sgn_sample(_lib.ptr(win), _lib.ptr_bits(r), _lib.ptr(out), _lib.ptr_bits(L), N, T, V, K, S, seg,
@@ -1783,53 +1789,67 @@ def sgn_sample(win, r, seg):
 SGN_GRAD_STATS = dict(clip_bwd=0, frames_bwd=0, sample_bwd=0)
 
 
+def _sgn_clip_bwd(feat, wimg, wimg_t, dlogits, tape):
+    """``sgn_clip_bwd`` (tape=False) -> dfeat, or ``sgn_clip_bwd_tape`` (tape=True) -> (dfeat, tape)."""
+    name = "sgn_clip_bwd_tape" if tape else "sgn_clip_bwd"
+    if feat.dim() != 3 or feat.shape[2] != 256:
+        raise ValueError(f"agcn_amd: {name} takes feat (N, seg, 256), got {tuple(feat.shape)}")
+    N, seg, _ = feat.shape
+    if dlogits.dim() != 2 or dlogits.shape[0] != N or (tape and dlogits.shape[1] < 1):
+        raise ValueError(f"agcn_amd: {name} takes dlogits ({N}, num_class), got {tuple(dlogits.shape)}")
+    nc = dlogits.shape[1]
+    tp = _tape(_L().agcn_sgn_clip_tape_floats, (N, seg, nc), feat, name) if tape else None
+    dfeat = _empty((N, seg, 256), feat)
+    args = (_lib.ptr(feat), _lib.ptr(wimg), wimg.numel(), _lib.ptr(wimg_t), wimg_t.numel(), _lib.ptr(dlogits),
+            _lib.ptr(dfeat), N, seg, nc)
+    if tape:
+        rc = _L().agcn_sgn_clip_bwd_tape(*args, _lib.ptr(tp), tp.numel(), _lib.stream())
+    else:
+        rc = _L().agcn_sgn_clip_bwd(*args, _lib.stream())
+    _lib.check(rc, "agcn_" + name)
+    (SGN_WGRAD_STATS if tape else SGN_GRAD_STATS)[name[4:]] += 1
+    return (dfeat, tp) if tape else dfeat
+
+
+def _sgn_frames_bwd(x, wimg, wimg_t, dfeat, V, tape):
+    """``sgn_frames_bwd`` (tape=False) -> dx, or ``sgn_frames_bwd_tape`` (tape=True) -> (dx, tape)."""
+    name = "sgn_frames_bwd_tape" if tape else "sgn_frames_bwd"
+    if x.dim() != 3 or x.shape[2] != 3 * V:
+        raise ValueError(f"agcn_amd: {name} takes (N, seg, {3 * V}), got {tuple(x.shape)}")
+    N, seg, _ = x.shape
+    if tuple(dfeat.shape) != (N, seg, 256):
+        raise ValueError(f"agcn_amd: {name} takes dfeat ({N}, {seg}, 256), got {tuple(dfeat.shape)}")
+    tp = _tape(_L().agcn_sgn_frames_tape_floats, (N, seg, V), x, name) if tape else None
+    dx = _empty((N, seg, 3 * V), x)
+    ws = _empty((max(1, _L().agcn_sgn_frames_bwd_workspace(N, seg, V) // 4),), x)
+    args = (_lib.ptr(x), _lib.ptr(wimg), wimg.numel(), _lib.ptr(wimg_t), wimg_t.numel(), _lib.ptr(dfeat), _lib.ptr(dx),
+            ws.data_ptr(), ws.numel() * 4, N, seg, V)
+    if tape:
+        rc = _L().agcn_sgn_frames_bwd_tape(*args, _lib.ptr(tp), tp.numel(), _lib.stream())
+    else:
+        rc = _L().agcn_sgn_frames_bwd(*args, _lib.stream())
+    _lib.check(rc, "agcn_" + name)
+    (SGN_WGRAD_STATS if tape else SGN_GRAD_STATS)[name[4:]] += 1
+    return (dx, tp) if tape else dx
+
+
 def sgn_clip_bwd(feat, wimg, wimg_t, dlogits):
     """d logits (N, num_class) -> d feat (N, seg, 256) through fc, the maximum over the frames and the two convolutions
     of the frame-level module, recomputed from feat (N, seg, 256).  wimg: the forward image, wimg_t: the transposed one."""
-    if feat.dim() != 3 or feat.shape[2] != 256:
-        raise ValueError(f"agcn_amd: sgn_clip_bwd takes feat (N, seg, 256), got {tuple(feat.shape)}")
-    N, seg, _ = feat.shape
-    if dlogits.dim() != 2 or dlogits.shape[0] != N:
-        raise ValueError(f"agcn_amd: sgn_clip_bwd takes dlogits ({N}, num_class), got {tuple(dlogits.shape)}")
-    dfeat = _empty((N, seg, 256), feat)
-    rc = _L().agcn_sgn_clip_bwd(_lib.ptr(feat), _lib.ptr(wimg), wimg.numel(), _lib.ptr(wimg_t), wimg_t.numel(),
-                                _lib.ptr(dlogits), _lib.ptr(dfeat), N, seg, dlogits.shape[1], _lib.stream())
-    _lib.check(rc, "agcn_sgn_clip_bwd")
-    SGN_GRAD_STATS['clip_bwd'] += 1
-    return dfeat
+    return _sgn_clip_bwd(feat, wimg, wimg_t, dlogits, tape=False)
 
 
 def sgn_frames_bwd(x, wimg, wimg_t, dfeat, V):
     """d feat (N, seg, 256) -> dx (N, seg, V*3) through the joint-level module, recomputed from x, and the dif coupling
     between the frames of a clip."""
-    if x.dim() != 3 or x.shape[2] != 3 * V:
-        raise ValueError(f"agcn_amd: sgn_frames_bwd takes (N, seg, {3 * V}), got {tuple(x.shape)}")
-    N, seg, _ = x.shape
-    if tuple(dfeat.shape) != (N, seg, 256):
-        raise ValueError(f"agcn_amd: sgn_frames_bwd takes dfeat ({N}, {seg}, 256), got {tuple(dfeat.shape)}")
-    dx = _empty((N, seg, 3 * V), x)
-    ws = _empty((max(1, _L().agcn_sgn_frames_bwd_workspace(N, seg, V) // 4),), x)
-    rc = _L().agcn_sgn_frames_bwd(_lib.ptr(x), _lib.ptr(wimg), wimg.numel(), _lib.ptr(wimg_t), wimg_t.numel(),
-                                  _lib.ptr(dfeat), _lib.ptr(dx), ws.data_ptr(), ws.numel() * 4, N, seg, V, _lib.stream())
-    _lib.check(rc, "agcn_sgn_frames_bwd")
-    SGN_GRAD_STATS['frames_bwd'] += 1
-    return dx
+    return _sgn_frames_bwd(x, wimg, wimg_t, dfeat, V, tape=False)
 
 
 def sgn_sample_bwd(win, r, dout, seg):
     """The adjoint of ``sgn_sample``: dout (N, S, seg, V*3) -> dwin (N, 3, T, V, 2).  Every picked row's gradient is added
     to its source row of the window (a row picked by several draws accumulates, in the order s major, k minor); padding
     rows and empty windows contribute nothing."""
-    if win.dim() != 5 or win.shape[1] != 3:
-        raise ValueError(f"agcn_amd: sgn_sample_bwd takes windows (N, 3, T, V, 2), got {tuple(win.shape)}")
-    N, _, T, V, K = win.shape
-    if K != 2:
-        raise ValueError(f"agcn_amd: sgn_sample_bwd interleaves exactly two selected bodies, got {K}")
-    if r.dtype == torch.uint32:
-        r = r.view(torch.int32)
-    if r.dim() != 3 or r.shape[0] != N or r.shape[2] != seg or r.dtype != torch.int32:
-        raise ValueError(f"agcn_amd: sgn_sample_bwd takes draws ({N}, S, {seg}) int32, got {r.dtype} {tuple(r.shape)}")
-    S = r.shape[1]
+    r, N, T, V, K, S = _sgn_sample_args("sgn_sample_bwd", win, r, seg)
     if tuple(dout.shape) != (N, S, seg, V * 3):
         raise ValueError(f"agcn_amd: sgn_sample_bwd takes dout ({N}, {S}, {seg}, {V * 3}), got {tuple(dout.shape)}")
     dwin = _empty(tuple(win.shape), win)
@@ -1864,7 +1884,8 @@ class SGNInputGradFunction(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------
-# base SGN, parameter gradients in eval mode (csrc/sgn_wgrad.hip): frozen-BatchNorm fine-tuning.  The kernels give the
+# base SGN, parameter gradients in eval mode (the taping backward of csrc/sgn_bwd.hip and the reductions of
+# csrc/sgn_wgrad.hip): frozen-BatchNorm fine-tuning.  The kernels give the
 # gradient with respect to the two folded weight images, in the images' layout; torch autograd takes it through the
 # fold (model/sgn.py::SGN._folded) to the parameters.  Train-mode BatchNorm is not built.
 # ------------------------------------------------------------------------------------------------
@@ -1933,38 +1954,12 @@ def _tape(query, args, like, what):
 def sgn_clip_bwd_tape(feat, wimg, wimg_t, dlogits):
     """``sgn_clip_bwd`` (the same dfeat bits) that also writes the clip tape (csrc/sgn_wgrad_plan.h: SgnClipTape) ->
     (dfeat, tape)."""
-    if feat.dim() != 3 or feat.shape[2] != 256:
-        raise ValueError(f"agcn_amd: sgn_clip_bwd_tape takes feat (N, seg, 256), got {tuple(feat.shape)}")
-    N, seg, _ = feat.shape
-    if dlogits.dim() != 2 or dlogits.shape[0] != N or dlogits.shape[1] < 1:
-        raise ValueError(f"agcn_amd: sgn_clip_bwd_tape takes dlogits ({N}, num_class), got {tuple(dlogits.shape)}")
-    nc = dlogits.shape[1]
-    tape = _tape(_L().agcn_sgn_clip_tape_floats, (N, seg, nc), feat, "sgn_clip_bwd_tape")
-    dfeat = _empty((N, seg, 256), feat)
-    rc = _L().agcn_sgn_clip_bwd_tape(_lib.ptr(feat), _lib.ptr(wimg), wimg.numel(), _lib.ptr(wimg_t), wimg_t.numel(),
-                                     _lib.ptr(dlogits), _lib.ptr(dfeat), N, seg, nc, _lib.ptr(tape), tape.numel(),
-                                     _lib.stream())
-    _lib.check(rc, "agcn_sgn_clip_bwd_tape")
-    SGN_WGRAD_STATS['clip_bwd_tape'] += 1
-    return dfeat, tape
+    return _sgn_clip_bwd(feat, wimg, wimg_t, dlogits, tape=True)
 
 
 def sgn_frames_bwd_tape(x, wimg, wimg_t, dfeat, V):
     """``sgn_frames_bwd`` (the same dx bits) that also writes the frames tape (SgnFramesTape) -> (dx, tape)."""
-    if x.dim() != 3 or x.shape[2] != 3 * V:
-        raise ValueError(f"agcn_amd: sgn_frames_bwd_tape takes (N, seg, {3 * V}), got {tuple(x.shape)}")
-    N, seg, _ = x.shape
-    if tuple(dfeat.shape) != (N, seg, 256):
-        raise ValueError(f"agcn_amd: sgn_frames_bwd_tape takes dfeat ({N}, {seg}, 256), got {tuple(dfeat.shape)}")
-    tape = _tape(_L().agcn_sgn_frames_tape_floats, (N, seg, V), x, "sgn_frames_bwd_tape")
-    dx = _empty((N, seg, 3 * V), x)
-    ws = _empty((max(1, _L().agcn_sgn_frames_bwd_workspace(N, seg, V) // 4),), x)
-    rc = _L().agcn_sgn_frames_bwd_tape(_lib.ptr(x), _lib.ptr(wimg), wimg.numel(), _lib.ptr(wimg_t), wimg_t.numel(),
-                                       _lib.ptr(dfeat), _lib.ptr(dx), ws.data_ptr(), ws.numel() * 4, N, seg, V,
-                                       _lib.ptr(tape), tape.numel(), _lib.stream())
-    _lib.check(rc, "agcn_sgn_frames_bwd_tape")
-    SGN_WGRAD_STATS['frames_bwd_tape'] += 1
-    return dx, tape
+    return _sgn_frames_bwd(x, wimg, wimg_t, dfeat, V, tape=True)
 
 
 def _sgn_wgrad_ws(N, seg, V, num_class, rows_per_split, like):

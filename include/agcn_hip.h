@@ -515,7 +515,8 @@ int agcn_sgn_clip(const float* feat, const float* w, size_t w_floats, float* log
 int agcn_sgn_sample(const float* win, const unsigned* r, float* out, int* L, int N, int T, int V, int K, int S, int seg,
                     void* stream);
 
-/* ---- base SGN, input gradients in eval mode (csrc/sgn_bwd.hip; geometry in csrc/sgn_bwd_plan.h) ----
+/* ---- base SGN, input gradients in eval mode (csrc/sgn_bwd.hip; geometry in csrc/sgn_bwd_plan.h; the recomputed forward
+ * is the forward's own device code, csrc/sgn_device.h) ----
  * What torch autograd does on the reference's eval forward (sgn.py:66-98) with respect to x (the parameter gradients
  * follow further down).  Same arithmetic rules as the forward: exact-f32 MFMA in every AGCN_GEMM mode, fixed summation orders, no
  * atomics, no launch reads another clip's intermediates, so a clip's gradient is the same bits alone and in any batch.
@@ -552,7 +553,8 @@ int agcn_sgn_frames_bwd(const float* x, const float* w, size_t w_floats, const f
 int agcn_sgn_sample_bwd(const float* win, const unsigned* r, const float* dout, float* dwin, int N, int T, int V, int K,
                         int S, int seg, void* stream);
 
-/* ---- base SGN, parameter gradients in eval mode (csrc/sgn_wgrad.hip; geometry in csrc/sgn_wgrad_plan.h) ----
+/* ---- base SGN, parameter gradients in eval mode (the two taping backward entries: csrc/sgn_bwd.hip; the size queries
+ * and the reductions: csrc/sgn_wgrad.hip; geometry in csrc/sgn_wgrad_plan.h) ----
  * Frozen-BatchNorm fine-tuning: the gradient of a loss on the logits with respect to the two folded weight images, each
  * in its image's own layout (SgnFramesW / SgnClipW, the offsets of the forward image).  The caller takes them through
  * the fold to the parameters (model/sgn.py).  Arithmetic rules as above: exact-f32 MFMA, fixed summation orders, no

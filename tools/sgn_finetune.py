@@ -4,7 +4,7 @@ seg = 20), and what a step costs on the two routes of this commit:
     python tools/sgn_finetune.py --data windows.npy --labels labels.npy [--weights IN.pt] --out OUT.pt [--steps 100]
 A step: ``ops.prenorm`` -> ``ops.sgn_sample`` with fresh draws -> SGN in eval mode (BatchNorm on its running statistics)
 -> cross-entropy -> ``backward()`` -> ``torch.optim.Adam.step()``.  ``fused`` sets ``SGN.fused_finetune``: the fused
-forward, the taping backward kernels and the tape reductions of csrc/sgn_wgrad.hip, torch autograd only through the
+forward, the taping backward kernels (csrc/sgn_bwd.hip), the tape reductions of csrc/sgn_wgrad.hip, torch autograd only through the
 fold of the weight images.  ``tensor`` leaves the flag off: the tensor-code composition under torch autograd.  Model,
 windows, labels and draws come from fixed seeds, so both routes take the same steps and their losses are printed side by
 side.  Each repeat of each route runs in a fresh child process, alternating.
