@@ -103,6 +103,37 @@ __device__ __forceinline__ void rowmax(const f32x16 (&acc)[NB], const float* __r
   }
 }
 
+// The batch-statistics epilogue, on the accumulators like rowmax: per column the sum over the rows < nrows (>= 1) of
+// z = bias + acc and M2 = the sum of (z - sum / nrows)^2, in both lanes of the column; the tile is never stored.  Each
+// half-wave adds its rows in ascending j, and the two halves combine as (rows of h = 0) + (rows of h = 1) in either lane.
+template <int NB>
+__device__ __forceinline__ void colstats(const f32x16 (&acc)[NB], const float* __restrict__ bias, int nrows, float (&sum)[NB],
+                                         float (&m2)[NB]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = lane & 31, h = lane >> 5;
+#pragma unroll
+  for (int i = 0; i < NB; ++i) {
+    const float bv = bias[(wave + SGN_WAVES * i) * 32 + r];
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+      if (mfma_row(j, h) < nrows) s += acc[i][j] + bv;
+    const float so = __shfl_xor(s, 32);
+    s = h == 0 ? s + so : so + s;
+    const float mean = s / (float)nrows;
+    float q = 0.f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+      if (mfma_row(j, h) < nrows) {
+        const float d = acc[i][j] + bv - mean;
+        q = fmaf(d, d, q);
+      }
+    const float qo = __shfl_xor(q, 32);
+    sum[i] = s;
+    m2[i] = h == 0 ? q + qo : qo + q;
+  }
+}
+
 // rowmax with the index: best = the column's maximum of bv + acc over the rows < nrows where that is positive (else 0),
 // arg = its row (else -1), in both lanes of the column.  Rows ascend with j and a strict > keeps the lowest index; the
 // merge of the two half-waves keeps the lower row at a tie.

@@ -134,6 +134,13 @@ SIGNATURES = {
     "agcn_sgn_frames_bwd_tape": (_I, [_P, _P, _Z, _P, _Z, _P, _P, _P, _Z, _I, _I, _I, _P, _Z, _P]),
     "agcn_sgn_frames_wgrad": (_I, [_P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _P]),
     "agcn_sgn_clip_wgrad": (_I, [_P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _P]),
+    "agcn_sgn_stats_part_floats": (_Z, [_I] * 5),
+    "agcn_sgn_stats_channels": (_Z, [_I] * 3),
+    "agcn_sgn_input_stats": (_I, [_P, _P, _Z, _I, _I, _I, _P]),
+    "agcn_sgn_frames_stats": (_I, [_P, _P, _Z, _P, _Z, _I, _I, _I, _I, _P]),
+    "agcn_sgn_clip_stats": (_I, [_P, _P, _Z, _P, _Z, _I, _I, _I, _I, _P]),
+    "agcn_sgn_stats_finalize_workspace": (_Z, [_I] * 5),
+    "agcn_sgn_stats_finalize": (_I, [_P, _Z, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
 }
 
 _lib = None

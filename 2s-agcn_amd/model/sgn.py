@@ -15,8 +15,11 @@ Three routes:
   at least one trainable parameter: frozen-BatchNorm fine-tuning on the fused path.  ``ops.SGNFineTuneFunction`` runs the
   fused forward; its backward tapes the two backward kernels and reduces the tapes to the gradients of the two folded
   weight images (csrc/sgn_wgrad.hip), and torch autograd carries those through ``_folded()`` -- built in grad mode, fresh
-  per call -- to the parameters.  ``parameter_gradients(x, cot)`` is that without autograd state.  Train-mode BatchNorm
-  (batch statistics) is not built in HIP.
+  per call -- to the parameters.  ``parameter_gradients(x, cot)`` is that without autograd state.
+* ``batch_statistics(x)`` / ``recalibrate_bn(x)`` in any ``training`` state: the batch statistics of the seven BatchNorms
+  of x as one batch and the logits under them (the forward half of train-mode BatchNorm), as seven truncated passes of
+  the fused forward (csrc/sgn_stats.hip) on freshly folded images plus the two full-depth launches.  The backward of
+  batch-mode BatchNorm is not built in HIP.
 * everything else (grad mode with trainable parameters and the flag off, ``train()``, a CPU tensor, ``step != seg``, ``AGCN_SGN_HIP=0``): the tensor-code
   composition below, channels last, ``F.linear`` / ``matmul`` on views and ``nn.BatchNorm`` modules.  It makes the class
   a complete ``nn.Module`` any torch optimiser can fine-tune and is the comparison of the fused path; it is NOT the hot
@@ -200,11 +203,20 @@ class SGN(nn.Module):
         return self.fc(y.amax(1)), g
 
     # ---- folded weight images of the HIP path ----
-    def _folded(self):
-        """The folded tensors in the order of the weight images (csrc/sgn_plan.h): -> (frames list, clip list)."""
+    def _folded(self, override=None):
+        """The folded tensors in the order of the weight images (csrc/sgn_plan.h): -> (frames list, clip list).
+        ``override``: {BatchNorm module name: (mean, var)} folds that BatchNorm on the given statistics (in the module's
+        own feature order) instead of its running ones, {name: None} folds it as the identity (scale 1, shift 0): the
+        images of the batch-statistics passes.  Without it every BatchNorm is folded on its running statistics."""
         V, like = self.num_point, self.fc.weight
+        names = {m: n for n, m in self.named_modules()} if override else {}
 
         def fold(bn):
+            if override and names[bn] in override:
+                stats = override[names[bn]]
+                if stats is None:
+                    return torch.ones_like(bn.weight), torch.zeros_like(bn.bias)
+                return ops._fold((bn.weight, bn.bias, stats[0], stats[1]))
             return ops._fold((bn.weight, bn.bias, bn.running_mean, bn.running_var))
 
         def first(e, i):                       # the two 1x1 layers of an embedding: (w1, b1, w2, b2) images
@@ -263,11 +275,15 @@ class SGN(nn.Module):
             t = self._infer_cache['images_t'] = (key,) + self._transposed(*self._folded())
         return f[1], f[2], t[1], t[2]
 
-    def _fusable(self, x):
-        """What the kernels take, whatever the grad mode."""
-        return (not self.training and x.is_cuda and x.dtype == torch.float32
+    def _in_domain(self, x):
+        """What the kernels take, whatever the grad mode and the ``training`` state."""
+        return (x.is_cuda and x.dtype == torch.float32
                 and x.dim() == 3 and x.shape[1] == self.seg and self.in_channels == 3
                 and x.shape[2] == 3 * self.num_point and ops.sgn_hip_enabled())
+
+    def _fusable(self, x):
+        """What the eval-mode kernels take, whatever the grad mode."""
+        return not self.training and self._in_domain(x)
 
     def _fused(self, x):
         return not torch.is_grad_enabled() and self._fusable(x)
@@ -356,3 +372,129 @@ class SGN(nn.Module):
             logits = ops.sgn_clip(feat, wc, self.num_class)
             dfeat = ops.sgn_clip_bwd(feat, wc, wc_t, cot.detach().to(logits).contiguous())
             return logits, g, ops.sgn_frames_bwd(x, wf, wf_t, dfeat, self.num_point)
+
+    # ---- batch statistics: the forward half of train-mode BatchNorm ----
+    def _batch_images(self, known, identity):
+        """Fresh images (never cached) with the BatchNorms of ``known`` on those statistics and ``identity`` as it says:
+        the specification of ``_batch_folder``."""
+        override = dict(known)
+        if identity is not None:
+            override[identity] = None
+        return self._flatten(*self._folded(override))
+
+    def _batch_folder(self):
+        """-> fold(known, identity) for ``ops.sgn_batch_statistics``: ``_batch_images`` built incrementally.  One fold with
+        all seven BatchNorms as the identity gives the base images; a working copy takes the section of every BatchNorm
+        that enters ``known`` as base * scale (+ shift), the operations ``_folded`` applies to the same numbers, so the
+        sections a pass reads hold the bits of ``_batch_images(known, identity)``.  A pass never reads past the BatchNorm
+        it measures, and that one is still the identity in the working copy."""
+        V = self.num_point
+        base = self._flatten(*self._folded(dict.fromkeys(ops.SGN_BN_NAMES)))
+        work = [b.clone() for b in base]
+        secs = [{n: (o, s) for n, o, s in sec} for sec in ops.sgn_image_sections(V, self.seg, self.num_class)]
+        where = {'gcn1.bn': (0, 'c1'), 'gcn2.bn': (0, 'c2'), 'gcn3.bn': (0, 'c3'), 'cnn.bn1': (1, 't1'), 'cnn.bn2': (1, 't2')}
+        done = set()
+
+        def view(img, which, name):
+            o, shape = secs[which][name]
+            return img[which][o:o + math.prod(shape)].view(shape)
+
+        def fold(known, identity):
+            for name in known:
+                if name in done:
+                    continue
+                done.add(name)
+                bn = self.get_submodule(name)
+                s, sh = ops._fold((bn.weight, bn.bias, known[name][0], known[name][1]))
+                if name in where:
+                    which, p = where[name]
+                    torch.mul(view(base, which, p + '_w'), s[None, :], out=view(work, which, p + '_w'))
+                    view(work, which, p + '_b').copy_(view(base, which, p + '_b') * s + sh)
+                else:                                  # norm_data: BatchNorm feature c*V + v -> aff rows [v*3 + c]
+                    row = 0 if name == ops.SGN_BN_NAMES[0] else 2
+                    aff = view(work, 0, 'aff')
+                    aff[row].copy_(s.reshape(3, V).t())
+                    aff[row + 1].copy_(sh.reshape(3, V).t())
+            assert identity is None or identity not in done
+            return work[0], work[1]
+
+        return fold
+
+    def _batch_statistics_tensor(self, x):
+        """The composition with every BatchNorm in batch mode and dropout off.  Only Python flags are flipped for the
+        duration of the call (a BatchNorm that does not track statistics touches no buffer); hooks read the inputs."""
+        bns = {n: self.get_submodule(n) for n in ops.SGN_BN_NAMES}
+        mods = list(bns.values()) + [self.cnn.dropout]
+        flags = [(m.training, getattr(m, 'track_running_stats', None)) for m in mods]
+        seen, hooks = {}, []
+
+        def reader(name):
+            def hook(_m, args):
+                a = args[0]
+                dims = [d for d in range(a.dim()) if d != 1]
+                var, mean = torch.var_mean(a, dim=dims, unbiased=False)
+                seen[name] = (mean, var, a.numel() // a.shape[1])
+            return hook
+
+        try:
+            for n, m in bns.items():
+                m.training, m.track_running_stats = True, False
+                hooks.append(m.register_forward_pre_hook(reader(n)))
+            self.cnn.dropout.training = False
+            logits, g = self.forward_tensor(x)
+        finally:
+            for h in hooks:
+                h.remove()
+            for m, (tr, track) in zip(mods, flags):
+                m.training = tr
+                if track is not None:
+                    m.track_running_stats = track
+        return logits, g, {n: seen[n] for n in ops.SGN_BN_NAMES}
+
+    def batch_statistics(self, x, max_part_bytes=None):
+        """-> (logits, g, stats): what ONE train-mode forward of x (N, seg, 3V) as one batch computes with dropout off (the
+        reference's sgn.py in train() with cnn.dropout.p = 0).  ``stats`` = {BatchNorm module name: (mean, biased var,
+        count)} for the seven BatchNorms in dependency order (``ops.SGN_BN_NAMES``), each in its module's feature order;
+        BatchNorm k sees activations normalised by the batch statistics of the BatchNorms before it.  Mutates nothing and
+        works in any ``training`` state.  On the GPU (fp32, step == seg, in_channels == 3, AGCN_SGN_HIP != 0):
+        ``ops.sgn_batch_statistics``, seven truncated passes of the fused forward (csrc/sgn_stats.hip) chunked under
+        ``max_part_bytes`` and the two full-depth launches; otherwise the composition under ``no_grad`` (counted in
+        ``ops.SGN_STATS['forward_tensor']``)."""
+        if x.dim() != 3:
+            raise ValueError(f"agcn_amd: SGN.batch_statistics takes (N, seg, 3 V), got {tuple(x.shape)}")
+        N, seg = x.shape[0], x.shape[1]
+        if N * seg < 2:
+            raise ValueError(f"agcn_amd: SGN.batch_statistics needs more than one value per channel, got {N} x {seg} frames")
+        V = self.num_point
+        with torch.no_grad():
+            if not self._in_domain(x):
+                ops.SGN_STATS['forward_tensor'] += 1
+                return self._batch_statistics_tensor(x)
+            cap = ops.SGN_MAX_STATS_BYTES if max_part_bytes is None else max_part_bytes
+            logits, g, raw = ops.sgn_batch_statistics(x, self._batch_folder(), V, self.num_class, cap)
+            counts = dict(zip(ops.SGN_BN_NAMES, [N * seg] * 2 + [N * seg * V] * 3 + [N * seg] * 2))
+            stats = {}
+            for i, name in enumerate(ops.SGN_BN_NAMES):
+                mean, var = raw[name]
+                if i < 2:                              # the kernels' [v*3 + c] -> the module's c*V + v
+                    mean, var = (t.view(V, 3).t().reshape(-1) for t in (mean, var))
+                stats[name] = (mean, var, counts[name])
+            return logits, g, stats
+
+    def recalibrate_bn(self, x, momentum=None, reset=True, max_part_bytes=None):
+        """Re-estimate the seven BatchNorms on x (AdaBN): ``batch_statistics(x)``, then ``running_mean``, ``running_var``
+        (unbiased, n / (n - 1)) and ``num_batches_tracked`` are updated in place exactly as one train-mode forward of x
+        would.  ``momentum=None``: the cumulative average (after ``reset`` the running statistics ARE the batch's), a
+        float: the exponential one.  ``reset=True`` calls ``reset_running_stats()`` first.  -> stats.  The in-place writes
+        bump the buffers' versions: the next prediction rebuilds the cached weight images."""
+        _, _, stats = self.batch_statistics(x, max_part_bytes)
+        with torch.no_grad():
+            for name, (mean, var, count) in stats.items():
+                bn = self.get_submodule(name)
+                if reset:
+                    bn.reset_running_stats()
+                bn.num_batches_tracked.add_(1)
+                f = 1.0 / float(bn.num_batches_tracked) if momentum is None else float(momentum)
+                bn.running_mean.mul_(1.0 - f).add_(mean.to(bn.running_mean), alpha=f)
+                bn.running_var.mul_(1.0 - f).add_(var.to(bn.running_var) * (count / (count - 1)), alpha=f)
+        return stats

@@ -1887,7 +1887,7 @@ class SGNInputGradFunction(torch.autograd.Function):
 # base SGN, parameter gradients in eval mode (the taping backward of csrc/sgn_bwd.hip and the reductions of
 # csrc/sgn_wgrad.hip): frozen-BatchNorm fine-tuning.  The kernels give the
 # gradient with respect to the two folded weight images, in the images' layout; torch autograd takes it through the
-# fold (model/sgn.py::SGN._folded) to the parameters.  Train-mode BatchNorm is not built.
+# fold (model/sgn.py::SGN._folded) to the parameters.  Batch statistics: further down (csrc/sgn_stats.hip).
 # ------------------------------------------------------------------------------------------------
 # diagnostic counters of these launches (a dict of its own: SGN_STATS and SGN_GRAD_STATS are compared whole by their tests)
 SGN_WGRAD_STATS = dict(clip_bwd_tape=0, frames_bwd_tape=0, frames_wgrad=0, clip_wgrad=0)
@@ -2077,3 +2077,142 @@ class SGNFineTuneFunction(torch.autograd.Function):
             dx, d_wf, d_wc = _sgn_image_backward(x, feat, wf, wc, wf_t, wc_t, dlogits.contiguous(), ctx.V, 0,
                                                  SGN_MAX_TAPE_BYTES)
         return (dx if ctx.needs_input_grad[0] else None), d_wf, d_wc, None, None, None, None
+
+
+# ------------------------------------------------------------------------------------------------
+# base SGN, batch statistics of its seven BatchNorms (csrc/sgn_stats.hip): the forward half of train-mode BatchNorm.
+# BatchNorm k sees activations normalised by the batch statistics of the BatchNorms in front of it, so the statistics come
+# from sequential passes, each the fused forward cut off at one BatchNorm, on a freshly folded image.
+# ------------------------------------------------------------------------------------------------
+# the BatchNorm modules of model/sgn.py::SGN in dependency order, and the (kind, layer) of the pass that measures each
+SGN_BN_NAMES = ('joint_embed.cnn.0.bn', 'dif_embed.cnn.0.bn', 'gcn1.bn', 'gcn2.bn', 'gcn3.bn', 'cnn.bn1', 'cnn.bn2')
+SGN_STATS_INPUT, SGN_STATS_FRAMES, SGN_STATS_CLIP = 0, 1, 2
+
+# diagnostic counters of these launches (a dict of its own, like SGN_WGRAD_STATS)
+SGN_BNSTATS_STATS = dict(input_stats=0, frames_stats=0, clip_stats=0, stats_finalize=0)
+
+SGN_MAX_STATS_BYTES = 64 << 20
+
+
+def _sgn_stats_part(kind, layer, N, seg, V, like):
+    n = _L().agcn_sgn_stats_part_floats(kind, layer, N, seg, V)
+    if n == 0:
+        raise ValueError(f"agcn_amd: SGN batch statistics: pass {(kind, layer)} of {(N, seg, V)} is outside the kernels' domain")
+    return _empty((n,), like)
+
+
+def sgn_input_stats(x, V):
+    """Per clip and feature the (sum, M2 about the clip's mean) of x and of dif over the seg frames: x (N, seg, V*3) ->
+    part (N, 2, 2 * 3V), features [x | dif] each in [v*3 + c] order."""
+    if x.dim() != 3 or x.shape[2] != 3 * V:
+        raise ValueError(f"agcn_amd: sgn_input_stats takes (N, seg, {3 * V}), got {tuple(x.shape)}")
+    N, seg, _ = x.shape
+    part = _sgn_stats_part(SGN_STATS_INPUT, 0, N, seg, V, x)
+    rc = _L().agcn_sgn_input_stats(_lib.ptr(x), _lib.ptr(part), part.numel(), N, seg, V, _lib.stream())
+    _lib.check(rc, "agcn_sgn_input_stats")
+    SGN_BNSTATS_STATS['input_stats'] += 1
+    return part.view(N, 2, 6 * V)
+
+
+def sgn_frames_stats(x, wimg, layer, V):
+    """``sgn_frames`` cut off at gcn<layer>'s product, on an image whose gcn<layer> BatchNorm is folded as the identity ->
+    part (N * seg, 2, C): per frame and channel the sum over the V joints and M2 about the frame's mean."""
+    if x.dim() != 3 or x.shape[2] != 3 * V:
+        raise ValueError(f"agcn_amd: sgn_frames_stats takes (N, seg, {3 * V}), got {tuple(x.shape)}")
+    N, seg, _ = x.shape
+    part = _sgn_stats_part(SGN_STATS_FRAMES, layer, N, seg, V, x)
+    rc = _L().agcn_sgn_frames_stats(_lib.ptr(x), _lib.ptr(wimg), wimg.numel(), _lib.ptr(part), part.numel(), layer, N, seg,
+                                    V, _lib.stream())
+    _lib.check(rc, "agcn_sgn_frames_stats")
+    SGN_BNSTATS_STATS['frames_stats'] += 1
+    return part.view(N * seg, 2, -1)
+
+
+def sgn_clip_stats(feat, wimg, layer, num_class):
+    """``sgn_clip`` cut off at cnn<layer>'s output, on an image whose bn<layer> is folded as the identity -> part
+    (N * tiles, 2, C): per (clip, 32-frame tile) and channel the sum over the tile's valid frames and M2 about their mean."""
+    if feat.dim() != 3 or feat.shape[2] != 256:
+        raise ValueError(f"agcn_amd: sgn_clip_stats takes feat (N, seg, 256), got {tuple(feat.shape)}")
+    N, seg, _ = feat.shape
+    part = _sgn_stats_part(SGN_STATS_CLIP, layer, N, seg, 2, feat)
+    rc = _L().agcn_sgn_clip_stats(_lib.ptr(feat), _lib.ptr(wimg), wimg.numel(), _lib.ptr(part), part.numel(), layer, N, seg,
+                                  num_class, _lib.stream())
+    _lib.check(rc, "agcn_sgn_clip_stats")
+    SGN_BNSTATS_STATS['clip_stats'] += 1
+    return part.view(-1, 2, part.numel() // (2 * N * ((seg + 31) // 32)))
+
+
+def sgn_stats_finalize(part, kind, layer, N, seg, V, carry=None, want_carry=False):
+    """Merge the groups of ``part`` (pairwise update, fp64 state: the groups of a clip in ascending index, then the clips
+    in ascending index) on top of the optional ``carry`` ((3, C) float64: count, mean, M2) -> (mean (C,), biased var
+    (C,), carry_out or None)."""
+    C = _L().agcn_sgn_stats_channels(kind, layer, V)
+    if C == 0 or (carry is not None and (carry.dtype != torch.float64 or tuple(carry.shape) != (3, C)
+                                         or not carry.is_contiguous() or carry.device != part.device)):
+        raise ValueError(f"agcn_amd: sgn_stats_finalize: pass {(kind, layer)} takes a carry (3, {C}) float64")
+    mean, var = _empty((C,), part), _empty((C,), part)
+    out = torch.empty((3, C), dtype=torch.float64, device=part.device) if want_carry else None
+    nbytes = _L().agcn_sgn_stats_finalize_workspace(kind, layer, N, seg, V)
+    ws = torch.empty((max(1, nbytes // 8),), dtype=torch.float64, device=part.device)
+    rc = _L().agcn_sgn_stats_finalize(_lib.ptr(part.view(-1)), part.numel(), kind, layer, N, seg, V,
+                                      None if carry is None else carry.data_ptr(), None if out is None else out.data_ptr(),
+                                      _lib.ptr(mean), _lib.ptr(var), ws.data_ptr(), nbytes, _lib.stream())
+    _lib.check(rc, "agcn_sgn_stats_finalize")
+    SGN_BNSTATS_STATS['stats_finalize'] += 1
+    return mean, var, out
+
+
+def sgn_stats_clip_bytes(seg, V):
+    """Bytes of the largest partial buffer of a pass per clip (every partial buffer is linear in the clips)."""
+    per = 4 * max(_L().agcn_sgn_stats_part_floats(k, l, 1, seg, V)
+                  for k, l in ((SGN_STATS_INPUT, 0), (SGN_STATS_FRAMES, 3), (SGN_STATS_CLIP, 2)))
+    if per == 0:
+        raise ValueError(f"agcn_amd: SGN batch statistics: {(seg, V)} is outside the kernels' domain")
+    return per
+
+
+def sgn_stats_chunk(N, seg, V, max_part_bytes):
+    """Clips per chunk: as many whole clips as keep every partial buffer under ``max_part_bytes``, at least one."""
+    return max(1, min(N, int(max_part_bytes) // sgn_stats_clip_bytes(seg, V)))
+
+
+def sgn_batch_statistics(x, fold, V, num_class, max_part_bytes=SGN_MAX_STATS_BYTES):
+    """The batch statistics of SGN's seven BatchNorms on x (N, seg, V*3) as ONE batch, and the forward under them ->
+    (logits, g, {name: (mean, biased var)}) with the names of ``SGN_BN_NAMES``; the two input BatchNorms in the kernels'
+    feature order [v*3 + c].  ``fold(known, identity)`` -> (frames image, clip image): the caller's fold with the
+    BatchNorms in the dict ``known`` {name: (mean, var)} on those statistics and the BatchNorm ``identity`` (a name or
+    None) as scale 1, shift 0 (model/sgn.py::SGN._batch_images or the incremental ``_batch_folder``, the same bits);
+    ``known`` only grows between calls and holds the two input BatchNorms in their module's order c*V + v.  Seven passes in dependency order, each chunked by whole clips under ``max_part_bytes`` with the
+    finalize's carry state, so the chunking does not change a bit; then the existing full-depth launches on the final
+    images."""
+    if x.dim() != 3 or x.shape[2] != 3 * V:
+        raise ValueError(f"agcn_amd: sgn_batch_statistics takes (N, seg, {3 * V}), got {tuple(x.shape)}")
+    x = x.detach().contiguous()
+    N, seg, _ = x.shape
+    chunk = sgn_stats_chunk(N, seg, V, max_part_bytes)
+
+    def run(kind, layer, src, launch):
+        carry = None
+        for n0 in range(0, N, chunk):
+            part = launch(src[n0:n0 + chunk])
+            n = min(chunk, N - n0)
+            mean, var, carry = sgn_stats_finalize(part, kind, layer, n, seg, V, carry, want_carry=n0 + chunk < N)
+        return mean, var
+
+    known, out = {}, {}
+    mean, var = run(SGN_STATS_INPUT, 0, x, lambda xs: sgn_input_stats(xs, V))
+    for i, name in enumerate(SGN_BN_NAMES[:2]):
+        out[name] = (mean[i * 3 * V:(i + 1) * 3 * V], var[i * 3 * V:(i + 1) * 3 * V])
+        known[name] = tuple(t.view(V, 3).t().reshape(-1) for t in out[name])
+    for layer in (1, 2, 3):
+        name = SGN_BN_NAMES[1 + layer]
+        wf, _ = fold(known, name)
+        known[name] = out[name] = run(SGN_STATS_FRAMES, layer, x, lambda xs: sgn_frames_stats(xs, wf, layer, V))
+    wf, _ = fold(known, None)
+    feat, g = sgn_frames(x, wf, V)
+    for layer in (1, 2):
+        name = SGN_BN_NAMES[4 + layer]
+        _, wc = fold(known, name)
+        known[name] = out[name] = run(SGN_STATS_CLIP, layer, feat, lambda fs: sgn_clip_stats(fs, wc, layer, num_class))
+    _, wc = fold(known, None)
+    return sgn_clip(feat, wc, num_class), g, out

@@ -587,6 +587,45 @@ int agcn_sgn_frames_wgrad(const float* x, const float* w, const float* tape, flo
 int agcn_sgn_clip_wgrad(const float* tape, const float* dfeat, const float* dlogits, float* d_w, void* ws, size_t ws_bytes,
                         int N, int seg, int num_class, int rows_per_split, void* stream);
 
+/* ---- base SGN, batch statistics of its seven BatchNorms (csrc/sgn_stats.hip; geometry in csrc/sgn_stats_plan.h) ----
+ * The forward half of train-mode BatchNorm: what nn.BatchNorm1d / 2d measure in training mode in norm_data
+ * (sgn.py:110-117), gcn_spa (sgn.py:183-194) and local (sgn.py:161-175) during one forward of the whole batch.
+ * BatchNorm k sees activations normalised by the batch statistics of every BatchNorm in front of it, so the caller runs
+ * the passes in dependency order, each on a folded weight image (sgn_frames_weights / sgn_clip_weights floats) in which
+ * the earlier BatchNorms carry their batch statistics and the BatchNorm under measurement is folded as the identity
+ * (scale 1, shift 0); the later sections of the image are not read.  A pass writes per group (a clip, a frame, a row
+ * tile of a clip) and channel the sum and M2 = the sum of squares about the group's own mean to `part`
+ * ((groups, 2, C) floats); sgn_stats_finalize merges the groups.  Arithmetic rules as above: exact-f32 MFMA, fixed
+ * orders, no atomics; a group's partials do not depend on the batch around it.
+ *
+ * kind: 0 = input (layer 0), 1 = frames (layer 1..3 = gcn1..3.bn), 2 = clip (layer 1..2 = cnn.bn1, cnn.bn2; V ignored).
+ * sgn_stats_part_floats: floats of `part` for a launch of N clips (0 outside the domain).  sgn_stats_channels: C.
+ * sgn_input_stats: x (N, seg, V*3) -> C = 2 * 3V channels: x[:, e], then dif[:, e] (sgn.py:73-75, zero at t = 0, which
+ *   counts as a sample), e = v*3 + c; one group per clip, seg samples each.
+ * sgn_frames_stats: sgn_frames cut off at gcn<layer>'s product (sgn.py:192, the input of the bn of sgn.py:193): C = 128, 256, 256; one
+ *   group per frame, the V real joint rows each.  Checks as sgn_frames, AGCN_ERR_ARG for layer outside 1..3.
+ * sgn_clip_stats: sgn_clip cut off at cnn1's (layer 1, sgn.py:169) or cnn2's (layer 2, sgn.py:173) output: C = 256, 512;
+ *   one group per (clip, 32-frame tile), the tile's valid frames each.  Checks as sgn_clip, AGCN_ERR_ARG for layer
+ *   outside 1..2.
+ * sgn_stats_finalize: (count, sum, M2) of the groups of `part` merged by the pairwise update (Chan et al.) with the state
+ *   in fp64 -> mean, biased variance (C floats each; both may be NULL when carry_out is given).  Two launches: one thread
+ *   per (clip, channel) merges the clip's groups in ascending group index into ws ((N, 3, C) doubles), then one thread
+ *   per channel merges the clips in ascending clip index: the order is a function of the group index alone.  carry_in /
+ *   carry_out: optional (3, C) doubles (count, mean, M2) under / after the clips, so that a batch processed in chunks of
+ *   whole clips merges in the order of one launch and gives the same bits.  sgn_stats_finalize_workspace: bytes of ws.
+ *   AGCN_ERR_WORKSPACE: part_floats or ws_bytes below their size queries. */
+size_t agcn_sgn_stats_part_floats(int kind, int layer, int N, int seg, int V);
+size_t agcn_sgn_stats_channels(int kind, int layer, int V);
+int agcn_sgn_input_stats(const float* x, float* part, size_t part_floats, int N, int seg, int V, void* stream);
+int agcn_sgn_frames_stats(const float* x, const float* w, size_t w_floats, float* part, size_t part_floats, int layer,
+                          int N, int seg, int V, void* stream);
+int agcn_sgn_clip_stats(const float* feat, const float* w, size_t w_floats, float* part, size_t part_floats, int layer,
+                        int N, int seg, int num_class, void* stream);
+size_t agcn_sgn_stats_finalize_workspace(int kind, int layer, int N, int seg, int V);
+int agcn_sgn_stats_finalize(const float* part, size_t part_floats, int kind, int layer, int N, int seg, int V,
+                            const double* carry_in, double* carry_out, float* mean, float* var, void* ws, size_t ws_bytes,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif
