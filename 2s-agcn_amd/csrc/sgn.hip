@@ -1,11 +1,13 @@
 // Fused eval-mode inference of the base SGN (reference model/architecture/sgn/archiv/sgn.py) and the sampler in front
-// of it (reference feeders/loader.py::NTUDataLoaders.to_fix_length, equal-interval branch).  Three kernels:
+// of it (reference feeders/loader.py::NTUDataLoaders.to_fix_length, equal-interval branch).  Four kernels:
 //   sgn_frames_kernel   joint-level module, one workgroup per frame: dif, the two embeddings + spa1, the adaptive
 //                       adjacency g = softmax(g1(x)^T g2(x)), three gcn_spa layers with their BatchNorm folded, the
 //                       maximum over joints.  Activations stay in LDS, weights stream from global / L2.
 //   sgn_clip_kernel     frame-level module + classifier, one workgroup per clip: + tem1, k = 3 temporal conv, 1x1 conv,
 //                       maximum over frames, fc.
 //   sgn_sample_kernel   null-row removal, two-body interleave, padding and the S interval draws as one gather.
+//   sgn_collate_kernel  the same gather by sample index from a device-resident dataset, with the subject flags and the
+//                       training rotation (reference feeders/loader.py::collate_fn_fix_{train,val,test}).
 // All products are exact-f32 MFMA (v_mfma_f32_32x32x2_f32) in every AGCN_GEMM mode: the work is launch- and latency-
 // bound, the split modes would add range-scaling passes and buy nothing.  Every sum has a fixed order and no launch
 // reads another frame's or clip's intermediate, so the outputs are bitwise reproducible and independent of the batch.
@@ -131,6 +133,56 @@ __global__ __launch_bounds__(SGN_THREADS) void sgn_sample_kernel(const float* __
   }
 }
 
+// The training / evaluation collate: sgn_sample_kernel's gather on sample index[n] of a device-resident pool, with the
+// subject flag of every picked row and one rotation per sample.  A thread owns whole joints, so that it holds the
+// (x, y, z) the rotation mixes.  Without angles no arithmetic touches the values: the same bits as sgn_sample_kernel.
+__global__ __launch_bounds__(SGN_THREADS) void sgn_collate_kernel(const float* __restrict__ pool,
+                                                                  const long long* __restrict__ index,
+                                                                  const unsigned* __restrict__ r,
+                                                                  const float* __restrict__ angles,
+                                                                  float* __restrict__ out, float* __restrict__ subj,
+                                                                  int* __restrict__ Lout, long P, int T, int V, int S,
+                                                                  int seg) {
+  __shared__ unsigned short rows[SGN_SAMPLE_MAX_ROWS];
+  __shared__ int scan[SGN_THREADS];
+  __shared__ unsigned char flag[SGN_SAMPLE_MAX_ROWS];
+  __shared__ float R[9];
+  const long n = blockIdx.x;
+  const int tid = threadIdx.x;
+  const long src = sgn_collate_source(index, n, P);       // the same for every thread: the branch below is uniform
+  const int kept = src >= 0 ? sgn_kept_rows(pool, src, T, V, flag, scan, rows) : 0;
+  const int L = kept > 0 ? sgn_sample_rows(kept, seg) : 0;
+  if (tid == 0) {
+    Lout[n] = L;
+    if (angles) sgn_rotation(angles + n * 3, R);
+  }
+  __syncthreads();
+  const long total = (long)S * seg * V;
+  for (long e = tid; e < total; e += SGN_THREADS) {
+    const int v = (int)(e % V), k = (int)(e / V % seg), s = (int)(e / V / seg);
+    float x = 0.f, y = 0.f, z = 0.f, body = 0.f;
+    if (L > 0) {
+      const int idx = sgn_pick(k, L, seg, r[(n * S + s) * seg + k]);
+      if (idx < kept) {                           // rows from `kept` on are the zero padding
+        const int row = rows[idx], t = row >> 1, m = row & 1;
+        x = pool[sgn_win_index(src, 0, t, v, m, T, V)];
+        y = pool[sgn_win_index(src, 1, t, v, m, T, V)];
+        z = pool[sgn_win_index(src, 2, t, v, m, T, V)];
+        body = (float)m;
+        if (angles) {
+          const float rx = sgn_rotate(R, 0, x, y, z), ry = sgn_rotate(R, 1, x, y, z), rz = sgn_rotate(R, 2, x, y, z);
+          x = rx, y = ry, z = rz;
+        }
+      }
+    }
+    const long o = sgn_sample_out_index(n, s, k, v * 3, S, seg, V);
+    out[o] = x;
+    out[o + 1] = y;
+    out[o + 2] = z;
+    if (subj && v == 0) subj[sgn_subject_index(n, s, k, S, seg)] = body;
+  }
+}
+
 extern "C" size_t agcn_sgn_frames_weights(int V) { return V >= 2 && V <= SGN_MAX_V ? (size_t)sgn_frames_w(V).total : 0; }
 extern "C" size_t agcn_sgn_clip_weights(int seg, int num_class) {
   return sgn_clip_domain(1, seg, num_class) ? (size_t)sgn_clip_w(seg, num_class).total : 0;
@@ -164,5 +216,16 @@ extern "C" int agcn_sgn_sample(const float* win, const unsigned* r, float* out, 
   if (!sgn_sample_domain(N, T, V, K, S, seg)) return AGCN_ERR_ARG;
   hipLaunchKernelGGL(sgn_sample_kernel, dim3((unsigned)N), dim3(SGN_THREADS), 0, (hipStream_t)stream, win, r, out, L, T,
                      V, S, seg);
+  return agcn_check_launch();
+}
+
+extern "C" int agcn_sgn_collate(const float* pool, const long long* index, const unsigned* r, const float* angles,
+                                float* out, float* subj, int* L, long P, int N, int T, int V, int K, int S, int seg,
+                                void* stream) {
+  if (!pool || !r || !out || !L) return AGCN_ERR_ARG;
+  if (!sgn_collate_domain(P, N, T, V, K, S, seg)) return AGCN_ERR_ARG;
+  if (!index && N > P) return AGCN_ERR_ARG;
+  hipLaunchKernelGGL(sgn_collate_kernel, dim3((unsigned)N), dim3(SGN_THREADS), 0, (hipStream_t)stream, pool, index, r,
+                     angles, out, subj, L, P, T, V, S, seg);
   return agcn_check_launch();
 }

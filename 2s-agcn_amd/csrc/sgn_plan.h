@@ -158,3 +158,36 @@ SGN_HD long sgn_win_index(long n, int c, int t, int v, int m, int T, int V) {
 SGN_HD long sgn_sample_out_index(long n, int s, int k, int f, int S, int seg, int V) {
   return ((n * S + s) * seg + k) * (long)(V * 3) + f;
 }
+
+// ---- the collate (reference feeders/loader.py:109-201: collate_fn_fix_{train,val,test}; feeders/tools.py:278-314) ----
+// the sampler's domain on a pool of P samples; N clips are collated per launch
+SGN_HD bool sgn_collate_domain(long P, long N, int T, int V, int K, long S, int seg) {
+  return P >= 1 && P <= 0x7fffffffL && sgn_sample_domain(N, T, V, K, S, seg);
+}
+// the pool sample workgroup n collates, or -1: an index outside [0, P) selects nothing (an all-zero clip, L = 0)
+SGN_HD long sgn_collate_source(const long long* index, long n, long P) {
+  const long long i = index ? index[n] : (long long)n;
+  return i >= 0 && i < (long long)P ? (long)i : -1;
+}
+// c = a . b, 3 x 3 row-major, each element summed in column order
+SGN_HD void sgn_mat3_mul(const float* a, const float* b, float* c) {
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) c[i * 3 + j] = a[i * 3] * b[j] + a[i * 3 + 1] * b[3 + j] + a[i * 3 + 2] * b[6 + j];
+}
+// R = (Rz . Ry) . Rx of the angles a = (ax, ay, az) in radians, row-major, in fp32: the reference's _rot with its sign
+// convention (the transposes of the usual right-handed matrices) and its association
+SGN_HD void sgn_rotation(const float* a, float* R) {
+  const float cx = cosf(a[0]), sx = sinf(a[0]), cy = cosf(a[1]), sy = sinf(a[1]), cz = cosf(a[2]), sz = sinf(a[2]);
+  const float rx[9] = {1.f, 0.f, 0.f, 0.f, cx, sx, 0.f, -sx, cx};
+  const float ry[9] = {cy, 0.f, -sy, 0.f, 1.f, 0.f, sy, 0.f, cy};
+  const float rz[9] = {cz, sz, 0.f, -sz, cz, 0.f, 0.f, 0.f, 1.f};
+  float zy[9];
+  sgn_mat3_mul(rz, ry, zy);
+  sgn_mat3_mul(zy, rx, R);
+}
+// component i of R . p
+SGN_HD float sgn_rotate(const float* R, int i, float x, float y, float z) {
+  return R[i * 3] * x + R[i * 3 + 1] * y + R[i * 3 + 2] * z;
+}
+// subject flags (N, S, seg)
+SGN_HD long sgn_subject_index(long n, int s, int k, int S, int seg) { return (n * S + s) * seg + k; }

@@ -3,3 +3,4 @@ consumes ~700+ clips/s needs on top of it -- batched on-device augmentation and 
 ring (``device.py``)."""
 from .feeder import Feeder  # noqa: F401
 from .device import DeviceAugment, DeviceLoader  # noqa: F401
+from .sgn import SGNBatches  # noqa: F401

@@ -1,7 +1,9 @@
 """``Feeder``: the reference's skeleton dataset (``feeders/feeder.py:35-227``, the AGCN/AAGCN branch: ``.npy`` clips
 ``(N, C, T, V, M)`` memory-mapped + a ``(sample_name, label)`` pickle, ``data_gen/ntu_gendata.py:158-173``), same
 constructor flags, same order of the per-sample transforms in ``__getitem__`` (:182-221), ``top_k`` (:224-227).
-The SGN-specific branches (pickled SGN arrays, ``joint_15`` remapping) are out of this path's scope.
+With ``'SGN'`` in ``dataset`` and a ``.pkl`` data path it loads the SGN pickles instead (:92-136): ``(N, T, 2*V*3)`` arrays
+and a label array, a ``train`` path joined with its ``val`` sibling, transposed to ``(N, 3, T, V, 2)``, sample names
+``arange`` -- the dataset ``feeders.sgn.SGNBatches`` collates.  The ``joint_15`` remapping is not built.
 
 With ``device_augment=True`` the random transforms are NOT applied per sample on the host: ``__getitem__`` returns the
 raw clip and ``DeviceAugment.from_feeder(feeder)`` applies the same transforms to whole batches on the GPU."""
@@ -17,7 +19,9 @@ class Feeder(Dataset):
     def __init__(self, data_path, label_path, dataset='NTU60-CV', random_choose=False, random_shift=False,
                  random_move=False, window_size=-1, normalization=False, random_zaxis_flip=False,
                  random_xaxis_scale=False, random_yaxis_scale=False, random_subsample=None, random_rotation=False,
-                 stretch=False, debug=False, use_mmap=True, device_augment=False, **_):
+                 stretch=False, debug=False, use_mmap=True, device_augment=False, joint_15=False, **_):
+        if joint_15:
+            raise ValueError("agcn_amd.Feeder: the joint_15 remapping (reference feeders/feeder.py:110-116) is not built")
         self.data_path, self.label_path, self.dataset = data_path, label_path, dataset
         self.random_choose, self.random_shift, self.random_move = random_choose, random_shift, random_move
         self.window_size, self.normalization = window_size, normalization
@@ -29,7 +33,25 @@ class Feeder(Dataset):
         if normalization:
             self.get_mean_map()
 
+    def load_sgn_data(self):
+        """reference feeder.py:92-136: pickled (N, T, 2*V*3) rows [body 0 | body 1], joints of (x, y, z) -> (N, 3, T, V, 2)"""
+        def read(path):
+            with open(path, 'rb') as f:                  # the user's own dataset files
+                return np.asarray(pickle.load(f))
+        paths = [(self.data_path, self.label_path)]
+        if 'train' in self.data_path:
+            paths.append((self.data_path.replace('train', 'val'), self.label_path.replace('train', 'val')))
+        data = np.concatenate([read(d) for d, _ in paths], axis=0)
+        self.label = np.concatenate([read(lab) for _, lab in paths], axis=0)
+        if data.ndim != 3 or data.shape[2] % 6:
+            raise ValueError(f"agcn_amd.Feeder: SGN data is (N, T, 2*V*3), got {data.shape}")
+        data = data.reshape(data.shape[0], data.shape[1], 2, data.shape[2] // 6, 3)
+        self.data = np.ascontiguousarray(data.transpose((0, 4, 1, 3, 2)), dtype=np.float32)
+        self.sample_name = np.arange(self.label.shape[0], dtype=self.label.dtype)
+
     def load_data(self):
+        if 'SGN' in self.dataset and self.data_path.endswith('.pkl'):
+            return self.load_sgn_data()
         if self.label_path.endswith('.npy'):
             self.label = np.load(self.label_path).astype(np.int64)
             self.sample_name = np.arange(len(self.label))

@@ -121,6 +121,7 @@ SIGNATURES = {
     "agcn_sgn_frames": (_I, [_P, _P, _Z, _P, _P, _I, _I, _I, _P]),
     "agcn_sgn_clip": (_I, [_P, _P, _Z, _P, _I, _I, _I, _P]),
     "agcn_sgn_sample": (_I, [_P] * 4 + [_I] * 6 + [_P]),
+    "agcn_sgn_collate": (_I, [_P] * 7 + [ctypes.c_long] + [_I] * 6 + [_P]),
     "agcn_sgn_frames_bwd_weights": (_Z, [_I]),
     "agcn_sgn_clip_bwd_weights": (_Z, [_I, _I]),
     "agcn_sgn_frames_bwd_workspace": (_Z, [_I, _I, _I]),

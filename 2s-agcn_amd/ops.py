@@ -10,6 +10,7 @@ import math
 import os
 import weakref
 
+import numpy as np
 import torch
 
 from . import lib as _lib
@@ -1745,10 +1746,11 @@ def sgn_clip(feat, wimg, num_class):
     return logits
 
 
-def sgn_draws(N, S, seg, device):
+def sgn_draws(N, S, seg, device, generator=None):
     """(N, S, seg) random 32-bit patterns for ``sgn_sample``, drawn on the device (no sync).  The sampler reduces them
-    modulo an interval width of at most a few hundred rows: the bias of that at 32 bits is below 1e-7."""
-    return torch.randint(0, 1 << 32, (N, S, seg), dtype=torch.int64, device=device).to(torch.int32)
+    modulo an interval width of at most a few hundred rows: the bias of that at 32 bits is below 1e-7.  ``generator``: a
+    torch.Generator of that device instead of its default one."""
+    return torch.randint(0, 1 << 32, (N, S, seg), dtype=torch.int64, device=device, generator=generator).to(torch.int32)
 
 
 def _sgn_sample_args(name, win, r, seg):
@@ -1779,6 +1781,125 @@ def sgn_sample(win, r, seg):
     _lib.check(rc, "agcn_sgn_sample")
     SGN_STATS['sample_hip'] += 1
     return out, L
+
+
+# ------------------------------------------------------------------------------------------------
+# base SGN, the training / evaluation collate (csrc/sgn.hip::sgn_collate_kernel): the reference's three collates
+# (feeders/loader.py:109-201) on a dataset that lives on the device
+# ------------------------------------------------------------------------------------------------
+# diagnostic counters (a dict of its own: SGN_STATS is compared whole by its tests)
+SGN_COLLATE_STATS = dict(collate_hip=0, collate_ref=0)
+
+
+def sgn_rotation_angles(N, theta, device, generator=None):
+    """(N, 3) rotation angles in radians, uniform in [-theta, theta), from the device's generator (no sync): the
+    counterpart of ``sgn_draws`` for the rotation of ``sgn_collate`` (reference feeders/tools.py::torch_transform)."""
+    return torch.empty((N, 3), dtype=torch.float32, device=device).uniform_(-float(theta), float(theta),
+                                                                            generator=generator)
+
+
+def sgn_rotation_ref(angles):
+    """angles (N, 3) -> R (N, 3, 3) fp32 numpy, R = (Rz . Ry) . Rx with the reference's matrices
+    (feeders/tools.py::_rot: the transposes of the usual right-handed ones) -- what ``sgn_rotation`` in sgn_plan.h builds."""
+    a = np.asarray(angles.detach().cpu().numpy() if torch.is_tensor(angles) else angles, dtype=np.float32).reshape(-1, 3)
+    c, s = np.cos(a), np.sin(a)
+    R = np.zeros((3, a.shape[0], 3, 3), dtype=np.float32)
+    R[:, :, 0, 0] = R[:, :, 1, 1] = R[:, :, 2, 2] = 1.0
+    rx, ry, rz = R
+    rx[:, 1, 1], rx[:, 1, 2], rx[:, 2, 1], rx[:, 2, 2] = c[:, 0], s[:, 0], -s[:, 0], c[:, 0]
+    ry[:, 0, 0], ry[:, 0, 2], ry[:, 2, 0], ry[:, 2, 2] = c[:, 1], -s[:, 1], s[:, 1], c[:, 1]
+    rz[:, 0, 0], rz[:, 0, 1], rz[:, 1, 0], rz[:, 1, 1] = c[:, 2], s[:, 2], -s[:, 2], c[:, 2]
+    return np.matmul(np.matmul(rz, ry), rx)
+
+
+def _sgn_collate_args(pool, r, seg, index, angles):
+    """The checks of ``sgn_collate`` and ``sgn_collate_ref`` -> (r as int32, N, S)."""
+    if pool.dim() != 5 or pool.shape[1] != 3 or pool.shape[4] != 2 or pool.shape[0] < 1:
+        raise ValueError(f"agcn_amd: sgn_collate takes a pool (P, 3, T, V, 2), got {tuple(pool.shape)}")
+    if r.dtype == torch.uint32:
+        r = r.view(torch.int32)
+    if r.dim() != 3 or r.shape[0] < 1 or r.shape[1] < 1 or r.shape[2] != seg or r.dtype != torch.int32:
+        raise ValueError(f"agcn_amd: sgn_collate takes draws (N, S, {seg}) int32, got {r.dtype} {tuple(r.shape)}")
+    N, S = r.shape[0], r.shape[1]
+    if index is None:
+        if N > pool.shape[0]:
+            raise ValueError(f"agcn_amd: sgn_collate without an index collates the first N samples: N = {N} > P = "
+                             f"{pool.shape[0]}")
+    elif index.dtype != torch.int64 or tuple(index.shape) != (N,):
+        raise ValueError(f"agcn_amd: sgn_collate takes index ({N},) int64, got {index.dtype} {tuple(index.shape)}")
+    if angles is not None and (angles.dtype != torch.float32 or tuple(angles.shape) != (N, 3)):
+        raise ValueError(f"agcn_amd: sgn_collate takes angles ({N}, 3) fp32, got {angles.dtype} {tuple(angles.shape)}")
+    P, _, T, V, _ = pool.shape
+    if not (T <= 2048 and 2 <= V <= 32 and S * seg <= (1 << 20)):
+        raise ValueError(f"agcn_amd: sgn_collate: T = {T}, V = {V}, S * seg = {S * seg} outside the sampler's domain "
+                         f"(T <= 2048, 2 <= V <= 32, S * seg <= 2^20)")
+    return r, N, S
+
+
+def sgn_collate_ref(pool, r, seg, index=None, angles=None, want_subject=False):
+    """The specification of ``sgn_collate`` as numpy on the host (and its route for CPU tensors and AGCN_SGN_HIP=0):
+    same arguments, same results, returned on ``pool``'s device.  Per clip n: sample ``index[n]`` (n without an index;
+    outside [0, P): zeros, L = 0); row (t, m) is kept iff body m's frame t is not all zero, rows in (t, m) order; fewer
+    than ``seg`` rows are followed by zero rows; b_k = rint(k * (L / seg)) in fp64; draw s takes row
+    b_k + r[n, s, k] % (b_{k+1} - b_k); the subject flag is the body m of that row (0 for a padding row); with angles
+    every joint of a picked row becomes R_n . p (``sgn_rotation_ref``), in fp32."""
+    r, N, S = _sgn_collate_args(pool, r, seg, index, angles)
+    pn = pool.detach().cpu().numpy()
+    rn = r.detach().cpu().numpy().view(np.uint32).astype(np.int64)
+    idx = np.arange(N) if index is None else index.detach().cpu().numpy()
+    P, _, T, V, _ = pn.shape
+    out = np.zeros((N, S, seg, V * 3), dtype=np.float32)
+    subj = np.zeros((N, S, seg), dtype=np.float32)
+    Ls = np.zeros((N,), dtype=np.int32)
+    bodies = np.arange(2 * T) & 1
+    for n in range(N):
+        if not 0 <= idx[n] < P:
+            continue
+        rows = np.transpose(pn[idx[n]], (1, 3, 2, 0)).reshape(T * 2, V * 3)        # (t, m) major, (v, c) minor
+        keep = (rows != 0).any(1)
+        kept = int(keep.sum())
+        if kept == 0:
+            continue
+        L = max(kept, seg)
+        rows = np.concatenate([rows[keep], np.zeros((L - kept, V * 3), dtype=np.float32)])
+        body = np.concatenate([bodies[keep], np.zeros((L - kept,), dtype=np.int64)]).astype(np.float32)
+        b = np.rint(np.arange(seg + 1, dtype=np.float64) * (float(L) / float(seg))).astype(np.int64)
+        pick = np.clip(b[:-1] + rn[n] % np.maximum(b[1:] - b[:-1], 1), 0, L - 1)    # (S, seg)
+        out[n], subj[n], Ls[n] = rows[pick], body[pick], L
+    if angles is not None:
+        R = sgn_rotation_ref(angles)[:, None, None, None]                           # (N, 1, 1, 1, 3, 3)
+        p = out.reshape(N, S, seg, V, 3)
+        x, y, z = p[..., 0:1], p[..., 1:2], p[..., 2:3]
+        out = (R[..., 0] * x + R[..., 1] * y + R[..., 2] * z).astype(np.float32).reshape(N, S, seg, V * 3)
+    SGN_COLLATE_STATS['collate_ref'] += 1
+    dev = pool.device
+    return (torch.from_numpy(out).to(dev), torch.from_numpy(Ls).to(dev),
+            torch.from_numpy(subj).to(dev) if want_subject else None)
+
+
+def sgn_collate(pool, r, seg, index=None, angles=None, want_subject=False):
+    """The reference's SGN collates (feeders/loader.py::collate_fn_fix_train / _val / _test) as one launch
+    (agcn_sgn_collate) on a dataset ``pool`` (P, 3, T, V, 2) that lives on the device.  r (N, S, seg): the draws, as for
+    ``sgn_sample``.  index (N,) int64 on the device: the samples to collate (None: the first N); an index outside
+    [0, P) gives a zero clip and L = 0.  angles (N, 3) radians: the training rotation, shared by a sample's S draws
+    (None: none, and then the values are ``sgn_sample``'s bits).  Returns (x (N, S, seg, V*3), L (N,) int32, subject
+    flags (N, S, seg) or None).  A CPU pool, or AGCN_SGN_HIP=0, runs ``sgn_collate_ref``."""
+    if not (pool.is_cuda and sgn_hip_enabled()):
+        return sgn_collate_ref(pool, r, seg, index, angles, want_subject)
+    r, N, S = _sgn_collate_args(pool, r, seg, index, angles)
+    P, _, T, V, K = pool.shape
+    for name, t in (('r', r), ('index', index), ('angles', angles)):
+        if t is not None and not (t.device == pool.device and t.is_contiguous()):
+            raise ValueError(f"agcn_amd: sgn_collate takes a contiguous {name} on {pool.device}")
+    out = _empty((N, S, seg, V * 3), pool)
+    L = torch.empty((N,), dtype=torch.int32, device=pool.device)
+    subj = _empty((N, S, seg), pool) if want_subject else None
+    rc = _L().agcn_sgn_collate(_lib.ptr(pool), None if index is None else index.data_ptr(), _lib.ptr_bits(r),
+                               _lib.ptr(angles), _lib.ptr(out), _lib.ptr(subj), _lib.ptr_bits(L), P, N, T, V, K, S, seg,
+                               _lib.stream())
+    _lib.check(rc, "agcn_sgn_collate")
+    SGN_COLLATE_STATS['collate_hip'] += 1
+    return out, L, subj
 
 
 # ------------------------------------------------------------------------------------------------

@@ -9,8 +9,9 @@ paths resolved by ``import_class``, state_dict checkpoints named ``<work_dir>/we
 per-epoch LR rule, mean-CE loss, clip 1.0, SGD.  What differs (MI355X-first): one process per GPU, flat
 parameter/gradient buffers, one RCCL all-reduce and one fused clip+SGD launch chain per step (trainer.py), tensor
 or tuple model outputs both accepted, unknown config keys warn instead of assert, and a
-built-in synthetic feeder so the loop runs without a dataset.  Out of scope here: SAM/Adam/LLRD optimizers,
-TensorBoard, the SGN feeders.
+built-in synthetic feeder so the loop runs without a dataset.  Out of scope here: SAM/LLRD optimizers and TensorBoard.
+``Processor`` itself stays SGD-only; with ``use_sgn_dataloader`` ``main.py`` runs ``sgn_processor.SGNProcessor`` instead:
+``model.sgn.SGN`` on the SGN collate (``feeders.sgn.SGNBatches``) with Adam or SGD and the label-smoothing loss.
 """
 import argparse
 import importlib
@@ -83,6 +84,12 @@ def get_parser():
                    help='apply the feeder\'s random transforms to whole batches on the GPU (feeders.DeviceAugment) '
                         'instead of per sample on the host; only feeders that support it (feeders.feeder.Feeder)')
     p.add_argument('--prefetch-depth', type=int, default=2, help='batches staged ahead through pinned host buffers')
+    p.add_argument('--use-sgn-dataloader', type=str2bool, default=False,
+                   help='train / evaluate model.sgn.SGN on the SGN collate (sgn_processor.SGNProcessor, feeders.sgn.SGNBatches)')
+    p.add_argument('--train-dataloader-args', default=dict(), help='SGN collate: dataset, seg, multi_test, aug')
+    p.add_argument('--test-dataloader-args', default=dict(), help='SGN collate: dataset, seg, multi_test')
+    p.add_argument('--label-smoothing', type=float, default=0.0,
+                   help='SGNProcessor: 1 - eps on the target, eps / (C - 1) on every other class (0 = cross-entropy)')
     return p
 
 
@@ -385,6 +392,13 @@ class Processor:
             score = full[:n]                            # the wrap-around padding of the shards is dropped again
             loss_sum = _dp.allreduce_scalar(loss_sum, self.world, self.device)
             seen = _dp.allreduce_scalar(seen, self.world, self.device)
+        return self._report(epoch, loader_name, score, loss_sum, seen, save_score)
+
+    def _report(self, epoch, loader_name, score, loss_sum, seen, save_score=None):
+        """Top-k through the dataset's labels, the mean loss, the log lines and the optional score pickle of an eval
+        (shared with ``sgn_processor.SGNProcessor``)."""
+        ds = self.datasets[loader_name]
+        n = len(ds)
         labels = np.asarray(ds.label)[:n]
         res = {}
         for k in self.arg.show_topk:

@@ -515,6 +515,22 @@ int agcn_sgn_clip(const float* feat, const float* w, size_t w_floats, float* log
 int agcn_sgn_sample(const float* win, const unsigned* r, float* out, int* L, int N, int T, int V, int K, int S, int seg,
                     void* stream);
 
+/* ---- base SGN, the training / evaluation collate (csrc/sgn.hip; plan and rotation in csrc/sgn_plan.h) ----
+ * The reference's NTUDataLoaders.collate_fn_fix_train / _val / _test (feeders/loader.py:109-201) as one launch on a
+ * dataset that lives on the device, one workgroup per clip, no atomics.
+ *
+ * sgn_collate: pool (P, 3, T, V, K = 2), a dataset in Feeder.__getitem__'s layout.  Workgroup n collates sample
+ *   index[n] (int64), or sample n when index is null (then N <= P).  An index outside [0, P) gives an all-zero clip and
+ *   L = 0, never a read outside the pool.  Sampling is sgn_sample's: r (N, S, seg) uint32 -> out (N, S, seg, V*3) and
+ *   L (N) int32, the same rows, the same interval plan, the same bits.  subj (N, S, seg), may be null: the body
+ *   (0.0 / 1.0) the picked row came from, 0.0 for a padding row (subject_seq after pad_to_segment_length).  angles
+ *   (N, 3) radians, may be null: every joint p = (x, y, z) of every picked row of clip (n, s) becomes R_n . p with
+ *   R = (Rz . Ry) . Rx in fp32 (feeders/tools.py::_rot, its sign convention, this association: sgn_rotation in
+ *   sgn_plan.h); the S draws of a sample share R_n; padding rows stay exactly zero.
+ *   AGCN_ERR_ARG: null pool / r / out / L, P < 1, index null and N > P, or outside sgn_sample's domain. */
+int agcn_sgn_collate(const float* pool, const long long* index, const unsigned* r, const float* angles, float* out,
+                     float* subj, int* L, long P, int N, int T, int V, int K, int S, int seg, void* stream);
+
 /* ---- base SGN, input gradients in eval mode (csrc/sgn_bwd.hip; geometry in csrc/sgn_bwd_plan.h; the recomputed forward
  * is the forward's own device code, csrc/sgn_device.h) ----
  * What torch autograd does on the reference's eval forward (sgn.py:66-98) with respect to x (the parameter gradients

@@ -3,7 +3,8 @@
 
 Single GPU: runs in-process.  ``--ddp True --world-size N`` (or the yaml keys): one process per GPU is spawned
 (reference main.py:55 ``mp.spawn``), each calls ``init_process_group("nccl")`` = RCCL over xGMI.  Also works under
-``python -m torch.distributed.run`` (RANK/WORLD_SIZE already set)."""
+``python -m torch.distributed.run`` (RANK/WORLD_SIZE already set).  ``use_sgn_dataloader: true`` trains / evaluates SGN
+(``agcn_amd.sgn_processor.SGNProcessor``), in one process."""
 import os
 import sys
 
@@ -20,7 +21,12 @@ def _run(rank, world_size, argv):
         os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world_size))
         os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
         os.environ.setdefault('MASTER_PORT', '8020')
-    Processor(load_args(argv)).start()
+    arg = load_args(argv)
+    if arg.use_sgn_dataloader:                   # model.sgn.SGN on the SGN collate, Adam or SGD (single process)
+        from agcn_amd.sgn_processor import SGNProcessor
+        SGNProcessor(arg).start()
+    else:
+        Processor(arg).start()
 
 
 def main(argv=None):
