@@ -450,10 +450,6 @@ size_t agcn_adjacency_fused_workspace(int C, int Ci) {
   return own > ws ? own : ws;
 }
 
-int agcn_adjacency_fused_fwd_ex(const float* x, const float* wab, const float* bab, const float* A, const float* PA,
-                                const float* alpha, float* tp_out, float* spart, float* P, float* adj, float* x_absmax_out,
-                                const float* x_absmax_in, void* workspace, size_t workspace_bytes, int N, int C, int Ci, int T,
-                                int V, void* stream);
 int agcn_adjacency_fused_fwd(const float* x, const float* wab, const float* bab, const float* A, const float* PA,
                              const float* alpha, float* tp_out, float* spart, float* P, float* adj, void* workspace,
                              size_t workspace_bytes, int N, int C, int Ci, int T, int V, void* stream) {

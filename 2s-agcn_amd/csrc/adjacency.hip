@@ -599,8 +599,6 @@ int agcn_adjacency_bwd_softmax(const float* dadj_part, const float* P, const flo
 }
 
 // dtp: (N,6Ci,T*V) ; dbpart: (N*ntiles, 6Ci) scratch ; scratch: agcn_colsum_scratch_bytes(6Ci) ; db: (6Ci)
-int agcn_adjacency_bwd_scores_ex(const float* tp, const float* dS, float* dtp, float* dbpart, void* scratch, float* db,
-                                 float* dtp_absmax_out, int N, int Ci, int T, int V, void* stream);
 int agcn_adjacency_bwd_scores(const float* tp, const float* dS, float* dtp, float* dbpart, void* scratch, float* db,
                               int N, int Ci, int T, int V, void* stream) {
   return agcn_adjacency_bwd_scores_ex(tp, dS, dtp, dbpart, scratch, db, nullptr, N, Ci, T, V, stream);

@@ -5,14 +5,12 @@
 #include <stdlib.h>
 #include <string.h>
 #include "knobs.h"
+// the C ABI: every exported prototype and the AGCN_OK / AGCN_ERR_* codes.  Each definition is compiled against its
+// declaration, so a definition that drifts from the header is a "conflicting types" error, not a wild pointer at run time.
+#include "../../include/agcn_hip.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-#define AGCN_OK 0
-#define AGCN_ERR_ARG (-1)
-#define AGCN_ERR_WORKSPACE (-2)
-#define AGCN_ERR_UNSUPPORTED (-3)
 
 // exact-f32 matrix core op: D(32x32) += A(32x2) * B(2x32); lane l holds A[l&31][l>>5], B[l>>5][l&31];
 // D register j of lane l is D[row = (j&3) + 8*(j>>2) + 4*(l>>5)][col = l&31].
@@ -47,9 +45,6 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   const int base = (x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q;
   return base + k;
 }
-
-extern "C" size_t agcn_colsum_scratch_bytes(int W);
-extern "C" int agcn_colsum(const float* X, int nslots, int W, void* scratch, float* out, void* stream);
 
 // adjacency.hip: slab sum + 1/K + column softmax + graph terms (also the tail of adj_fused.hip's forward)
 int agcn_adj_finalize(const float* spart, const float* A, const float* PA, const float* alpha, float* P, float* adj,

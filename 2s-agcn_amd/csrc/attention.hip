@@ -160,8 +160,6 @@ int agcn_stc_row_reduce(const float* y, const float* g, const float* wv, const f
 }
 
 // out = y * a_s[n,v] * a_t[n,t] * a_c[n,c]      (a_* = 1 + sigmoid gate); N*C*T*V % 4 == 0
-int agcn_stc_apply_ex(const float* y, const float* a_s, const float* a_t, const float* a_c, float* out, float* absmax_out,
-                      int N, int C, int T, int V, void* stream);
 int agcn_stc_apply(const float* y, const float* a_s, const float* a_t, const float* a_c, float* out, int N, int C, int T,
                    int V, void* stream) {
   return agcn_stc_apply_ex(y, a_s, a_t, a_c, out, nullptr, N, C, T, V, stream);

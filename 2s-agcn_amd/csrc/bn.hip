@@ -353,9 +353,6 @@ int agcn_bn_eval_coeff(const float* gamma, const float* beta, const float* runni
 }
 
 // res_mode: 0 none, 1 identity residual r, 2 BN'd residual branch scale2*r+shift2 ; total = N*C*P must be %4
-int agcn_bn_act_fwd_ex(const float* y1, const float* scale1, const float* shift1, const float* r, const float* scale2,
-                       const float* shift2, float* out, unsigned* sign_bits, float* absmax_out, int N, int C, int P,
-                       int res_mode, int relu, void* stream);
 int agcn_bn_act_fwd(const float* y1, const float* scale1, const float* shift1, const float* r, const float* scale2,
                     const float* shift2, float* out, unsigned* sign_bits, int N, int C, int P, int res_mode, int relu,
                     void* stream) {
@@ -405,11 +402,6 @@ int agcn_bn_bwd_reduce(const float* dout, const void* mask, int mask_bits, const
   return agcn_check_launch();
 }
 
-int agcn_bn_bwd_apply_ex(const float* part, int nrows, double count, float param_grad_scale, const float* dout,
-                         const void* mask, int mask_bits, const float* y1, const float* gamma1, const float* mean1,
-                         const float* invstd1, const float* y2, const float* gamma2, const float* mean2,
-                         const float* invstd2, float* coef, float* dy1, float* dgamma1, float* dbeta1, float* dy2,
-                         float* dgamma2, float* dbeta2, float* absmax1_out, int N, int C, int P, void* stream);
 int agcn_bn_bwd_apply(const float* part, int nrows, double count, float param_grad_scale, const float* dout,
                       const void* mask, int mask_bits, const float* y1, const float* gamma1, const float* mean1, const float* invstd1,
                       const float* y2, const float* gamma2, const float* mean2, const float* invstd2, float* coef,

@@ -940,9 +940,6 @@ int agcn_gcn_stats_slots(int N, int C, int Cout, int T, int V) {
   return (int)d.slab_slots;
 }
 
-int agcn_conv_fwd_ex(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* workspace,
-                     size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride,
-                     const float* x_absmax, void* stream);
 int agcn_conv_fwd(const float* x, const float* w, const float* bias, float* y, float* stats_part, void* workspace,
                   size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride,
                   void* stream) {
@@ -961,10 +958,6 @@ int agcn_conv_fwd_ex(const float* x, const float* w, const float* bias, float* y
                          (taps - 1) / 2, x_absmax, (hipStream_t)stream, nullptr);
 }
 
-int agcn_conv_bwd_data_ex(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
-                          const float* mask1, const float* add2, const float* mask2, void* workspace,
-                          size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride,
-                          const float* dy_absmax, void* stream);
 int agcn_conv_bwd_data(const float* dy, const float* w, float* dx, int accumulate, const float* add1,
                        const float* mask1, const float* add2, const float* mask2, void* workspace,
                        size_t workspace_bytes, int N, int Cin, int Cout, int T, int V, int taps, int stride,
@@ -984,9 +977,6 @@ int agcn_conv_bwd_data_ex(const float* dy, const float* w, float* dx, int accumu
                               V, taps, stride, (taps - 1) / 2, dy_absmax, (hipStream_t)stream, nullptr);
 }
 
-int agcn_gcn_aggregate_project_fwd_ex(const float* x, const float* adj, const float* wcat, const float* bias, float* y,
-                                      float* stats_part, void* workspace, size_t workspace_bytes, int N, int C, int Cout,
-                                      int T, int V, const float* x_absmax, void* stream);
 int agcn_gcn_aggregate_project_fwd(const float* x, const float* adj, const float* wcat, const float* bias, float* y,
                                    float* stats_part, void* workspace, size_t workspace_bytes, int N, int C, int Cout,
                                    int T, int V, void* stream) {
@@ -1036,12 +1026,6 @@ int agcn_conv9_infer(const float* x, const float* w, const float* bias, const fl
                              agcn_gemm_precision(), (hipStream_t)stream, res, relu, nullptr, nullptr, nullptr);
 }
 
-int agcn_gcn_bwd_data_fused_supported(int C, int Cout, int V);
-int agcn_gcn_aggregate_project_bwd_data_ex(const float* dy, const float* adj, const float* wcat, const float* dtp,
-                                           const float* w2, int K2, float* dx, int accumulate, const float* add1,
-                                           const float* mask1, const float* add2, const float* mask2, int mask_bits,
-                                           void* workspace, size_t workspace_bytes, int N, int C, int Cout, int T, int V,
-                                           const float* dy_absmax, const float* dtp_absmax, void* stream);
 int agcn_gcn_aggregate_project_bwd_data(const float* dy, const float* adj, const float* wcat, float* dx,
                                         int accumulate, const float* add1, const float* mask1, const float* add2,
                                         const float* mask2, int mask_bits, void* workspace, size_t workspace_bytes,
@@ -1081,9 +1065,6 @@ int agcn_gcn_aggregate_project_bwd_data_fused(const float* dy, const float* adj,
                                                 stream);
 }
 
-int agcn_gcn_dadj_ex(const float* dy, const float* wcat, const float* x, float* dadj_part, void* workspace,
-                     size_t workspace_bytes, int N, int C, int Cout, int T, int V, const float* dy_absmax,
-                     const float* x_absmax, void* stream);
 int agcn_gcn_dadj(const float* dy, const float* wcat, const float* x, float* dadj_part, void* workspace,
                   size_t workspace_bytes, int N, int C, int Cout, int T, int V, void* stream) {
   return agcn_gcn_dadj_ex(dy, wcat, x, dadj_part, workspace, workspace_bytes, N, C, Cout, T, V, nullptr, nullptr, stream);

@@ -485,9 +485,6 @@ size_t agcn_gcn_project_bwd_weight_workspace(int N, int C, int Cout, int T, int 
   return d.ws_bytes;
 }
 
-int agcn_conv_bwd_weight_ex(const float* dy, const float* x, float* dw, void* workspace, size_t workspace_bytes, int N,
-                            int Cin, int Cout, int T, int V, int taps, int stride, const float* dy_absmax,
-                            const float* x_absmax, void* stream);
 int agcn_conv_bwd_weight(const float* dy, const float* x, float* dw, void* workspace, size_t workspace_bytes, int N,
                          int Cin, int Cout, int T, int V, int taps, int stride, void* stream) {
   return agcn_conv_bwd_weight_ex(dy, x, dw, workspace, workspace_bytes, N, Cin, Cout, T, V, taps, stride, nullptr, nullptr,
@@ -504,9 +501,6 @@ int agcn_conv_bwd_weight_ex(const float* dy, const float* x, float* dw, void* wo
                            x_absmax, (hipStream_t)stream, nullptr);
 }
 
-int agcn_gcn_project_bwd_weight_ex(const float* dy, const float* x, const float* adj, float* dwcat, void* workspace,
-                                   size_t workspace_bytes, int N, int C, int Cout, int T, int V, const float* dy_absmax,
-                                   const float* x_absmax, void* stream);
 int agcn_gcn_project_bwd_weight(const float* dy, const float* x, const float* adj, float* dwcat, void* workspace,
                                 size_t workspace_bytes, int N, int C, int Cout, int T, int V, void* stream) {
   return agcn_gcn_project_bwd_weight_ex(dy, x, adj, dwcat, workspace, workspace_bytes, N, C, Cout, T, V, nullptr, nullptr,

@@ -6,7 +6,7 @@
 #include <type_traits>
 
 #ifndef AGCN_ERR_UNSUPPORTED
-#define AGCN_ERR_UNSUPPORTED (-3)        // as in agcn_common.h
+#define AGCN_ERR_UNSUPPORTED (-3)        // as in include/agcn_hip.h, for the host-only check that includes this file alone
 #endif
 
 // the supported domain (agcn_tconv_*), and the shapes the agcn_conv_* entry points cover: rows of the same plan that keep

@@ -1,4 +1,15 @@
-"""ctypes binding of the C-ABI shared library ``libagcn_hip.so`` (declared in ``include/agcn_hip.h``).
+"""ctypes binding of the C-ABI shared library ``libagcn_hip.so``, derived from its one declaration.
+
+``include/agcn_hip.h`` is the only place an entry point is written out: the sources under ``csrc/`` include it (a
+definition that drifts is a compile error) and this module parses its text at import (``parse_header``) into
+``DECLARATIONS``, the ctypes table ``SIGNATURES`` and the ``AGCN_ERR_*`` codes.  Importing needs the header, not the
+library.
+
+``call(name, *args)`` / ``status(name, *args)`` are the checked way in: tensors are passed as they are and converted by
+the DECLARED parameter types (a wrong device, layout or element type raises before the foreign call), the trailing
+``void* stream`` is the current stream, and ``call`` turns a non-zero status into a ``RuntimeError`` that names the entry
+point.  ``load()`` returns the bare handle for size queries and for callers that pass addresses themselves (``ptr``,
+``ptr_bits``, ``stream``, ``check``).
 
 The library is built in-tree by ``__graft_entry__.build()`` (``hipcc --offload-arch=gfx950``).  There is NO
 fallback: if the library is missing or a call fails, a ``RuntimeError`` is raised (the product path never
@@ -6,143 +17,104 @@ routes through the CPU oracle or stock PyTorch operators for the hot path).
 """
 import ctypes
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libagcn_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "agcn_hip.h")
 
-_P = ctypes.c_void_p
-_I = ctypes.c_int
-_F = ctypes.c_float
-_D = ctypes.c_double
-_Z = ctypes.c_size_t
+# the closed set of types the header may use; anything else is an error of parse_header
+_RETURNS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char*": ctypes.c_char_p}
+_SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "size_t": ctypes.c_size_t, "float": ctypes.c_float,
+            "double": ctypes.c_double}
+_FP32, _FP64, _INT32 = ("fp32", (torch.float32,)), ("float64", (torch.float64,)), ("int32", (torch.int32,))
+_BITS32, _ANY = ("int32", (torch.int32, torch.uint32)), ("", None)
+# pointer type -> (the element kind in words, the dtypes a tensor argument may have; None: any)
+_POINTERS = {"float*": _FP32, "const float*": _FP32, "double*": _FP64, "const double*": _FP64,
+             "int*": _INT32, "const int*": _INT32, "unsigned*": _BITS32, "const unsigned*": _BITS32,
+             "const long long*": ("int64", (torch.int64,)), "const unsigned char*": ("uint8", (torch.uint8,)),
+             "void*": _ANY, "const void*": _ANY}
+_TYPE_WORDS = {"const", "void", "char", "int", "long", "unsigned", "signed", "short", "float", "double", "size_t"}
 
-# name -> (restype, argtypes); mirrors include/agcn_hip.h one to one
-SIGNATURES = {
-    "agcn_version": (_I, []),
-    "agcn_arch": (ctypes.c_char_p, []),
-    "agcn_last_kernel": (ctypes.c_char_p, []),
-    "agcn_gemm_mode": (ctypes.c_char_p, []),
-    "agcn_chain_mode": (ctypes.c_char_p, []),
-    "agcn_conv_tile_frames": (_I, [_I, _I]),
-    "agcn_conv_num_tiles": (_I, [_I, _I]),
-    "agcn_conv_stats_tiles": (_I, [_I, _I, _I, _I, _I, _I]),
-    "agcn_dadj_num_slots": (_I, [_I, _I, _I]),
-    "agcn_scores_num_tiles": (_I, [_I, _I]),
-    "agcn_conv_workspace": (_Z, [_I, _I, _I, _I, _I, _I]),
-    "agcn_gcn_workspace": (_Z, [_I, _I, _I, _I]),
-    "agcn_gcn_stats_tiles": (_I, [_I, _I, _I, _I]),
-    "agcn_gcn_stats_slots": (_I, [_I, _I, _I, _I, _I]),
-    "agcn_conv_fwd": (_I, [_P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "agcn_conv_bwd_data": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "agcn_conv_bwd_weight_workspace": (_Z, [_I, _I, _I, _I, _I, _I, _I]),
-    "agcn_conv_bwd_weight": (_I, [_P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "agcn_gcn_aggregate_project_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _P]),
-    "agcn_gcn_aggregate_project_fwd_ex": (_I, [_P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _P, _P]),
-    "agcn_gcn_aggregate_project_bwd_data_ex": (_I, [_P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _Z, _I, _I, _I, _I, _I, _P, _P, _P]),
-    "agcn_gcn_dadj_ex": (_I, [_P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _P, _P, _P]),
-    "agcn_adjacency_bwd_scores_ex": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "agcn_conv_bwd_weight_ex": (_I, [_P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
-    "agcn_gcn_project_bwd_weight_ex": (_I, [_P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _P, _P, _P]),
-    "agcn_absmax": (_I, [_P, ctypes.c_long, _P, _P]),
-    "agcn_tconv_workspace": (_Z, [_I] * 7),
-    "agcn_tconv_stats_tiles": (_I, [_I] * 7),
-    "agcn_tconv_fwd": (_I, [_P] * 6 + [_Z] + [_I] * 8 + [_P, _P]),
-    "agcn_tconv_bwd_data": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _Z] + [_I] * 8 + [_P, _P]),
-    "agcn_tconv_bwd_weight_workspace": (_Z, [_I] * 8),
-    "agcn_tconv_bwd_weight": (_I, [_P] * 4 + [_Z] + [_I] * 8 + [_P] * 3),
-    "agcn_bn_act_fwd_ex": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "agcn_bn_bwd_apply_ex": (_I, [_P, _I, _D, _F, _P, _P, _I] + [_P] * 16 + [_I, _I, _I, _P]),
-    "agcn_conv_fwd_ex": (_I, [_P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "agcn_conv_bwd_data_ex": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "agcn_gcn_first_supported": (_I, [_I, _I, _I]),
-    "agcn_gcn_first_tiles": (_I, [_I, _I]),
-    "agcn_gcn_first_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "agcn_gcn_unit_infer_workspace": (_Z, [_I, _I, _I, _I, _I]),
-    "agcn_gcn_unit_infer": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _Z, _I, _I, _I, _I, _I, _P]),
-    "agcn_conv9_infer": (_I, [_P, _P, _P, _P, _I, _P, _P, _Z, _I, _I, _I, _I, _I, _I, _P]),
-    "agcn_tconv_infer": (_I, [_P] * 7 + [_I, _P, _P, _Z] + [_I] * 8 + [_P, _P]),
-    "agcn_gcn_aggregate_project_bwd_data": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _Z, _I, _I, _I, _I, _I, _P]),
-    "agcn_gcn_bwd_data_fused_supported": (_I, [_I, _I, _I]),
-    "agcn_gcn_aggregate_project_bwd_data_fused": (_I, [_P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _Z, _I, _I, _I, _I, _I, _P]),
-    "agcn_gcn_dadj": (_I, [_P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _P]),
-    "agcn_gcn_project_bwd_weight_workspace": (_Z, [_I, _I, _I, _I, _I]),
-    "agcn_gcn_project_bwd_weight": (_I, [_P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _P]),
-    "agcn_adjacency_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "agcn_adjacency_fused_supported": (_I, [_I, _I, _I, _I]),
-    "agcn_adjacency_fused_workspace": (_Z, [_I, _I]),
-    "agcn_adjacency_fused_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _P]),
-    "agcn_adjacency_fused_fwd_ex": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _P]),
-    "agcn_adjacency_fused_bwd_scores": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _P]),
-    "agcn_adjacency_bwd_softmax": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "agcn_adjacency_bwd_scores": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "agcn_colsum_scratch_bytes": (_Z, [_I]),
-    "agcn_colsum": (_I, [_P, _I, _I, _P, _P, _P]),
-    "agcn_bn_stats_finalize": (_I, [_P, _I, _I, _D, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P]),
-    "agcn_bn_eval_coeff": (_I, [_P, _P, _P, _P, _F, _I, _P, _P, _P]),
-    "agcn_bn_act_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "agcn_bn_bwd": (_I, [_P, _P, _I] + [_P] * 16 + [_I, _I, _I, _P]),
-    "agcn_bn_bwd_reduce": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
-    "agcn_bn_bwd_apply": (_I, [_P, _I, _D, _F, _P, _P, _I] + [_P] * 15 + [_I, _I, _I, _P]),
-    "agcn_bn_eval_coeff_ex": (_I, [_P, _P, _P, _P, _F, _I, _P, _P, _P, _P, _P]),
-    "agcn_bn_bwd_eval": (_I, [_P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "agcn_bn_bwd_eval_finalize": (_I, [_P, _I, _I] + [_P] * 13),
-    "agcn_stc_row_reduce": (_I, [_P, _P, _P, _P, _I, _P, _P, _F, _F, _I, _I, _I, _I, _P]),
-    "agcn_stc_apply": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "agcn_stc_apply_ex": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "agcn_stc_bwd_apply": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "agcn_data_bn_stats": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
-    "agcn_data_bn_apply": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "agcn_data_bn_bwd_reduce": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "agcn_data_bn_bwd_apply": (_I, [_P, _P, _P, _P, _P, _P, _D, _P, _I, _I, _I, _I, _I, _P]),
-    "agcn_pool_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
-    "agcn_pool_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P]),
-    "agcn_linear_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "agcn_linear_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "agcn_gate_conv_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "agcn_gate_conv_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "agcn_sgd_step_workspace": (_Z, [ctypes.c_long]),
-    "agcn_sgd_step": (_I, [_P, _P, _P, ctypes.c_long, _F, _F, _F, _I, _F, _F, _I, _P, _Z, _P, _P]),
-    "agcn_prenorm_max_frames": (_I, []),
-    "agcn_skel_append": (_I, [_P, _P] + [_I] * 6 + [_P]),
-    "agcn_prenorm": (_I, [_P] * 4 + [_I] * 16 + [_P]),
-    "agcn_prenorm_windows": (_I, [_P] * 7 + [_I] * 16 + [_P]),
-    "agcn_skel_smooth": (_I, [_P, _P] + [_I] * 4 + [_P]),
-    "agcn_skel_append_many": (_I, [_P] * 4 + [_I] * 5 + [_P]),
-    "agcn_tokens_fwd": (_I, [_P, _P, _P, _I, _P] + [_I] * 5 + [_P]),
-    "agcn_tokens_bwd": (_I, [_P] * 4 + [_I] * 7 + [_P]),
-    "agcn_mha_fwd": (_I, [_P, _P, _I, _P, _F, _P, _P, _P] + [_I] * 4 + [_P]),
-    "agcn_mha_bwd": (_I, [_P] * 4 + [_F, _P, _P, _Z] + [_I] * 4 + [_P]),
-    "agcn_ln_fwd": (_I, [_P] * 4 + [_F, _P, _P, _P, ctypes.c_long, _I, _P]),
-    "agcn_ln_bwd": (_I, [_P] * 9 + [_P, _Z, ctypes.c_long, _I, _P]),
-    "agcn_sgn_frames_weights": (_Z, [_I]),
-    "agcn_sgn_clip_weights": (_Z, [_I, _I]),
-    "agcn_sgn_frames": (_I, [_P, _P, _Z, _P, _P, _I, _I, _I, _P]),
-    "agcn_sgn_clip": (_I, [_P, _P, _Z, _P, _I, _I, _I, _P]),
-    "agcn_sgn_sample": (_I, [_P] * 4 + [_I] * 6 + [_P]),
-    "agcn_sgn_collate": (_I, [_P] * 7 + [ctypes.c_long] + [_I] * 6 + [_P]),
-    "agcn_sgn_frames_bwd_weights": (_Z, [_I]),
-    "agcn_sgn_clip_bwd_weights": (_Z, [_I, _I]),
-    "agcn_sgn_frames_bwd_workspace": (_Z, [_I, _I, _I]),
-    "agcn_sgn_clip_bwd": (_I, [_P, _P, _Z, _P, _Z, _P, _P, _I, _I, _I, _P]),
-    "agcn_sgn_frames_bwd": (_I, [_P, _P, _Z, _P, _Z, _P, _P, _P, _Z, _I, _I, _I, _P]),
-    "agcn_sgn_sample_bwd": (_I, [_P] * 4 + [_I] * 6 + [_P]),
-    "agcn_sgn_frames_tape_floats": (_Z, [_I, _I, _I]),
-    "agcn_sgn_clip_tape_floats": (_Z, [_I, _I, _I]),
-    "agcn_sgn_wgrad_workspace": (_Z, [_I] * 5),
-    "agcn_sgn_clip_bwd_tape": (_I, [_P, _P, _Z, _P, _Z, _P, _P, _I, _I, _I, _P, _Z, _P]),
-    "agcn_sgn_frames_bwd_tape": (_I, [_P, _P, _Z, _P, _Z, _P, _P, _P, _Z, _I, _I, _I, _P, _Z, _P]),
-    "agcn_sgn_frames_wgrad": (_I, [_P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _P]),
-    "agcn_sgn_clip_wgrad": (_I, [_P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _P]),
-    "agcn_sgn_stats_part_floats": (_Z, [_I] * 5),
-    "agcn_sgn_stats_channels": (_Z, [_I] * 3),
-    "agcn_sgn_input_stats": (_I, [_P, _P, _Z, _I, _I, _I, _P]),
-    "agcn_sgn_frames_stats": (_I, [_P, _P, _Z, _P, _Z, _I, _I, _I, _I, _P]),
-    "agcn_sgn_clip_stats": (_I, [_P, _P, _Z, _P, _Z, _I, _I, _I, _I, _P]),
-    "agcn_sgn_stats_finalize_workspace": (_Z, [_I] * 5),
-    "agcn_sgn_stats_finalize": (_I, [_P, _Z, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
-}
+
+def _c_type(tokens):
+    return " ".join(tokens).replace(" *", "*")
+
+
+def parse_header(text):
+    """The header's text -> ({name: (return type, [(C type, parameter name), ...])}, {AGCN_* code: value}).  Strict: a
+    declaration that does not read as ``type name(type name, ...)``, a parameter without a name or a type outside the
+    closed set above raises RuntimeError naming the declaration."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)      # the prose holds parentheses and semicolons
+    codes = {m.group(1): int(m.group(2))
+             for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(AGCN_\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", text, flags=re.M)}
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{', " ", text)
+    decls = {}
+    for chunk in text.split(";"):
+        decl = " ".join(chunk.split())
+        if decl in ("", "}"):
+            continue
+        m = re.fullmatch(r"([\w\s*]+?)\b(\w+) ?\(([^()]*)\)", decl)
+        if m is None:
+            raise RuntimeError(f"agcn_amd: cannot read the declaration `{decl}` of the C ABI header")
+        ret, name = _c_type(m.group(1).replace("*", " * ").split()), m.group(2)
+        if ret not in _RETURNS:
+            raise RuntimeError(f"agcn_amd: return type `{ret}` outside the binding's set in `{decl}`")
+        params = []
+        for p in ([] if m.group(3).strip() in ("", "void") else m.group(3).split(",")):
+            tokens = p.replace("*", " * ").split()
+            if len(tokens) < 2 or tokens[-1] == "*" or tokens[-1] in _TYPE_WORDS:
+                raise RuntimeError(f"agcn_amd: parameter `{p.strip()}` has no name in `{decl}`")
+            ctype = _c_type(tokens[:-1])
+            if ctype not in _SCALARS and ctype not in _POINTERS:
+                raise RuntimeError(f"agcn_amd: parameter type `{ctype}` outside the binding's set in `{decl}`")
+            params.append((ctype, tokens[-1]))
+        decls[name] = (ret, params)
+    return decls, codes
+
+
+def _read_header():
+    try:
+        with open(HEADER_PATH) as f:
+            return f.read()
+    except OSError as e:
+        raise RuntimeError(f"agcn_amd: the C ABI header {HEADER_PATH} is missing ({e}); the binding is derived from "
+                           f"it") from e
+
+
+def _pointer_converter(ctype, where):
+    """Tensor -> device address for one pointer parameter: None is NULL, a Python int is an address the caller vouches
+    for, a tensor must be contiguous on a GPU and of the declared element type."""
+    kind, dtypes = _POINTERS[ctype]
+    want = f"{where}: expected a contiguous {kind + ' ' if kind else ''}GPU tensor"
+
+    def convert(t):
+        if t is None or type(t) is int:
+            return t
+        if not (t.is_cuda and t.is_contiguous() and (dtypes is None or t.dtype in dtypes)):
+            raise RuntimeError(f"agcn_amd: {want}, got {t.dtype} {tuple(t.shape)} on {t.device} "
+                               f"contiguous={t.is_contiguous()}")
+        return t.data_ptr()
+    return convert
+
+
+DECLARATIONS, _CODES = parse_header(_read_header())
+ERR_ARG, ERR_WORKSPACE, ERR_UNSUPPORTED = (_CODES[k] for k in ("AGCN_ERR_ARG", "AGCN_ERR_WORKSPACE",
+                                                                "AGCN_ERR_UNSUPPORTED"))
+# name -> (restype, argtypes): plain ctypes types, c_void_p for every pointer
+SIGNATURES = {name: (_RETURNS[ret], [_SCALARS.get(t, ctypes.c_void_p) for t, _ in params])
+              for name, (ret, params) in DECLARATIONS.items()}
+# name -> one converter per parameter in front of the stream (None: a scalar, passed as it is), for every entry point
+# that enqueues work: it returns a status and ends in `void* stream`, which status() supplies
+_CONVERTERS = {}
+for _name, (_ret, _params) in DECLARATIONS.items():
+    if any(t in _POINTERS for t, _ in _params):
+        assert _ret == "int" and _params[-1] == ("void*", "stream"), f"{_name}: not `int {_name}(..., void* stream)`"
+        _CONVERTERS[_name] = tuple(_pointer_converter(t, f"{_name}({p})") if t in _POINTERS else None
+                                   for t, p in _params[:-1])
 
 _lib = None
 
@@ -165,23 +137,10 @@ def load():
     return lib
 
 
-def ptr_bits(t):
-    """Device pointer of an int32 sign-bit-mask tensor (None -> NULL)."""
-    if t is None:
-        return None
-    if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.int32):
-        raise RuntimeError(f"agcn_amd: expected a contiguous int32 GPU tensor, got {t.dtype} on {t.device}")
-    return t.data_ptr()
-
-
-def ptr(t):
-    """Device pointer of a tensor (None -> NULL).  The tensor must be contiguous fp32 on a GPU."""
-    if t is None:
-        return None
-    if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32):
-        raise RuntimeError(f"agcn_amd: expected a contiguous fp32 GPU tensor, got {t.dtype} "
-                           f"{tuple(t.shape)} on {t.device} contiguous={t.is_contiguous()}")
-    return t.data_ptr()
+ptr = _pointer_converter("const float*", "ptr")
+ptr.__doc__ = "Device pointer of a tensor (None -> NULL).  The tensor must be contiguous fp32 on a GPU."
+ptr_bits = _pointer_converter("const int*", "ptr_bits")
+ptr_bits.__doc__ = "Device pointer of an int32 sign-bit-mask tensor (None -> NULL)."
 
 
 def stream():
@@ -191,3 +150,19 @@ def stream():
 def check(rc, what):
     if rc != 0:
         raise RuntimeError(f"agcn_amd: {what} failed with code {rc}")
+
+
+def status(name, *args):
+    """Enqueue entry point ``name`` on the current stream and return its status code.  ``args``: everything in front of
+    the stream, tensors as they are (converted by the declared parameter types, see _pointer_converter)."""
+    convert = _CONVERTERS.get(name)
+    if convert is None:
+        raise RuntimeError(f"agcn_amd: {name} is not a stream entry point of include/agcn_hip.h")
+    if len(args) != len(convert):
+        raise RuntimeError(f"agcn_amd: {name} takes {len(convert)} arguments in front of the stream, got {len(args)}")
+    return getattr(_lib or load(), name)(*[a if c is None else c(a) for c, a in zip(convert, args)], stream())
+
+
+def call(name, *args):
+    """``status`` that raises RuntimeError, naming the entry point, on a non-zero code."""
+    check(status(name, *args), name)

@@ -147,9 +147,7 @@ def conv_fwd(x, w, b, stride=1, want_stats=False, x_amax=None, pad=None):
     ws, nb = _conv_ws(Cin, Cout, T, V, taps, stride, x, pad)
     # x_amax: 1-element tensor with max |x| left by bn_act_fwd(..., want_amax=True): the split-fp16 temporal convolution
     # then skips its own pass over x
-    _lib.check(_L().agcn_tconv_fwd(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(y), _lib.ptr(stats), ws.data_ptr(),
-                                   nb, N, Cin, Cout, T, V, taps, stride, pad, _lib.ptr(x_amax), _lib.stream()),
-               "agcn_tconv_fwd")
+    _lib.call("agcn_tconv_fwd", x, w, b, y, stats, ws, nb, N, Cin, Cout, T, V, taps, stride, pad, x_amax)
     return y, stats
 
 
@@ -160,10 +158,8 @@ def conv_bwd_data(dy, w, x_shape, stride=1, out=None, accumulate=False, add1=Non
     pad = (taps - 1) // 2 if pad is None else pad
     dx = out if out is not None else _empty(x_shape, dy)
     ws, nb = _conv_ws(Cin, Cout, T, V, taps, stride, dy, pad)
-    _lib.check(_L().agcn_tconv_bwd_data(_lib.ptr(dy), _lib.ptr(w), _lib.ptr(dx), int(accumulate), _lib.ptr(add1),
-                                        _lib.ptr(mask1), _lib.ptr(add2), _lib.ptr(mask2), ws.data_ptr(), nb, N, Cin,
-                                        Cout, T, V, taps, stride, pad, _lib.ptr(dy_amax), _lib.stream()),
-               "agcn_tconv_bwd_data")
+    _lib.call("agcn_tconv_bwd_data", dy, w, dx, int(accumulate), add1, mask1, add2, mask2, ws, nb, N, Cin, Cout, T, V,
+              taps, stride, pad, dy_amax)
     return dx
 
 
@@ -176,9 +172,7 @@ def conv_bwd_weight(dy, x, w_shape, stride=1, dy_amax=None, x_amax=None, pad=Non
     nbytes = _L().agcn_tconv_bwd_weight_workspace(N, Cin, Cout, T, V, taps, stride, pad)
     ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x.device)
     dw = _empty(tuple(w_shape), x)
-    _lib.check(_L().agcn_tconv_bwd_weight(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(dw), _lib.ptr(ws), nbytes, N, Cin, Cout,
-                                          T, V, taps, stride, pad, _lib.ptr(dy_amax), _lib.ptr(x_amax), _lib.stream()),
-               "agcn_tconv_bwd_weight")
+    _lib.call("agcn_tconv_bwd_weight", dy, x, dw, ws, nbytes, N, Cin, Cout, T, V, taps, stride, pad, dy_amax, x_amax)
     return dw
 
 
@@ -190,8 +184,7 @@ def adjacency_fwd(tp, A, PA, alpha=None):
     spart = _empty((N, 3, nt, V, V), tp)
     P = _empty((N, 3, V, V), tp)
     adj = _empty((N, 3, V, V), tp)
-    _lib.check(_L().agcn_adjacency_fwd(_lib.ptr(tp), _lib.ptr(A), _lib.ptr(PA), _lib.ptr(alpha), _lib.ptr(spart),
-                                       _lib.ptr(P), _lib.ptr(adj), N, Ci, T, V, _lib.stream()), "agcn_adjacency_fwd")
+    _lib.call("agcn_adjacency_fwd", tp, A, PA, alpha, spart, P, adj, N, Ci, T, V)
     return P, adj
 
 
@@ -220,10 +213,8 @@ def adjacency_fused_fwd(x, wab, bab, A, PA, alpha=None, keep_tp=False, x_amax_ou
     adj = _empty((N, 3, V, V), x)
     nb = _L().agcn_adjacency_fused_workspace(C, Ci)
     ws = _ws(nb, x)
-    _lib.check(_L().agcn_adjacency_fused_fwd_ex(_lib.ptr(x), _lib.ptr(wab.reshape(6 * Ci, C)), _lib.ptr(bab), _lib.ptr(A),
-                                                _lib.ptr(PA), _lib.ptr(alpha), _lib.ptr(tp), _lib.ptr(spart), _lib.ptr(P),
-                                                _lib.ptr(adj), _lib.ptr(x_amax_out), _lib.ptr(x_amax), ws.data_ptr(), nb, N,
-                                                C, Ci, T, V, _lib.stream()), "agcn_adjacency_fused_fwd")
+    _lib.call("agcn_adjacency_fused_fwd_ex", x, wab.reshape(6 * Ci, C), bab, A, PA, alpha, tp, spart, P, adj,
+              x_amax_out, x_amax, ws, nb, N, C, Ci, T, V)
     return (P, adj, tp) if keep_tp else (P, adj)
 
 
@@ -243,9 +234,7 @@ def gcn_first_fwd(x, adj, wcat, bias, wdown, bdown, want_stats=False):
         nt = _L().agcn_gcn_first_tiles(T, V)
         st, st2 = _empty((N * nt, 2, Cout), x), _empty((N * nt, 2, Cout), x)
     wdown2 = wdown.reshape(Cout, C).contiguous()
-    _lib.check(_L().agcn_gcn_first_fwd(_lib.ptr(x), _lib.ptr(adj), _lib.ptr(wcat), _lib.ptr(bias), _lib.ptr(wdown2),
-                                       _lib.ptr(bdown), _lib.ptr(ypre), _lib.ptr(st), _lib.ptr(dpre), _lib.ptr(st2),
-                                       N, C, Cout, T, V, _lib.stream()), "agcn_gcn_first_fwd")
+    _lib.call("agcn_gcn_first_fwd", x, adj, wcat, bias, wdown2, bdown, ypre, st, dpre, st2, N, C, Cout, T, V)
     return ypre, st, dpre, st2
 
 
@@ -258,10 +247,7 @@ def aggregate_project_fwd(x, adj, wcat, bias, want_stats=False, x_amax=None):
     if want_stats:
         stats = _empty((_L().agcn_gcn_stats_slots(N, C, Cout, T, V), 2, Cout), x)
     ws, nb = _gcn_ws(C, Cout, T, V, x)
-    _lib.check(_L().agcn_gcn_aggregate_project_fwd_ex(_lib.ptr(x), _lib.ptr(adj), _lib.ptr(wcat), _lib.ptr(bias),
-                                                      _lib.ptr(y), _lib.ptr(stats), ws.data_ptr(), nb, N, C, Cout, T, V,
-                                                      _lib.ptr(x_amax), _lib.stream()),
-               "agcn_gcn_aggregate_project_fwd")
+    _lib.call("agcn_gcn_aggregate_project_fwd_ex", x, adj, wcat, bias, y, stats, ws, nb, N, C, Cout, T, V, x_amax)
     return y, stats
 
 
@@ -278,18 +264,16 @@ def aggregate_project_bwd_data(dy, adj, wcat, x_shape, out=None, accumulate=Fals
     if len(kinds) > 1:
         raise RuntimeError("agcn_amd: mask1 and mask2 must be of one kind (fp32 tensors or int32 sign bit masks)")
     mbits = int(torch.int32 in kinds)
+    # the masks are declared const float* and hold either kind under mask_bits: checked here, passed as addresses
     mp = _lib.ptr_bits if mbits else _lib.ptr
+    K2, w2 = 0, None
     if dtp is not None:
         K2 = dtp.shape[1]
-        _lib.check(_L().agcn_gcn_aggregate_project_bwd_data_ex(
-            _lib.ptr(dy), _lib.ptr(adj), _lib.ptr(wcat), _lib.ptr(dtp), _lib.ptr(wab.reshape(K2, C)), K2, _lib.ptr(dx),
-            int(accumulate), _lib.ptr(add1), mp(mask1), _lib.ptr(add2), mp(mask2), mbits, ws.data_ptr(), nb, N, C, Cout,
-            T, V, _lib.ptr(dy_amax), _lib.ptr(dtp_amax), _lib.stream()), "agcn_gcn_aggregate_project_bwd_data_fused")
-        return dx
-    _lib.check(_L().agcn_gcn_aggregate_project_bwd_data_ex(
-        _lib.ptr(dy), _lib.ptr(adj), _lib.ptr(wcat), None, None, 0, _lib.ptr(dx), int(accumulate), _lib.ptr(add1),
-        mp(mask1), _lib.ptr(add2), mp(mask2), mbits, ws.data_ptr(), nb, N, C, Cout, T, V, _lib.ptr(dy_amax), None,
-        _lib.stream()), "agcn_gcn_aggregate_project_bwd_data")
+        w2 = wab.reshape(K2, C)
+    else:
+        dtp_amax = None
+    _lib.call("agcn_gcn_aggregate_project_bwd_data_ex", dy, adj, wcat, dtp, w2, K2, dx, int(accumulate), add1,
+              mp(mask1), add2, mp(mask2), mbits, ws, nb, N, C, Cout, T, V, dy_amax, dtp_amax)
     return dx
 
 
@@ -302,10 +286,7 @@ def project_bwd_weight(dy, x, adj, Cout, dy_amax=None, x_amax=None):
     nbytes = _L().agcn_gcn_project_bwd_weight_workspace(N, C, Cout, T, V)
     ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x.device)
     dw = _empty((Cout, 3 * C), x)
-    _lib.check(_L().agcn_gcn_project_bwd_weight_ex(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(adj), _lib.ptr(dw), _lib.ptr(ws),
-                                                   nbytes, N, C, Cout, T, V, _lib.ptr(dy_amax), _lib.ptr(x_amax),
-                                                   _lib.stream()),
-               "agcn_gcn_project_bwd_weight")
+    _lib.call("agcn_gcn_project_bwd_weight_ex", dy, x, adj, dw, ws, nbytes, N, C, Cout, T, V, dy_amax, x_amax)
     return dw
 
 
@@ -319,15 +300,12 @@ def adjacency_bwd(dy, wcat, x, tp, P, alpha=None, wab=None, bab=None, dy_amax=No
     nslots = _L().agcn_dadj_num_slots(C, V, T)
     dpart = _empty((N, 3, nslots, V, V), x)
     ws, nb = _gcn_ws(C, Cout, T, V, x)
-    _lib.check(_L().agcn_gcn_dadj_ex(_lib.ptr(dy), _lib.ptr(wcat), _lib.ptr(x), _lib.ptr(dpart), ws.data_ptr(), nb, N, C,
-                                     Cout, T, V, _lib.ptr(dy_amax), _lib.ptr(x_amax), _lib.stream()), "agcn_gcn_dadj")
+    _lib.call("agcn_gcn_dadj_ex", dy, wcat, x, dpart, ws, nb, N, C, Cout, T, V, dy_amax, x_amax)
     dadj = _empty((N, 3, V, V), x)
     dS = _empty((N, 3, V, V), x)
     dPA = _empty((3, V, V), x)
     dal_part = _empty((N * 3,), x) if alpha is not None else None
-    _lib.check(_L().agcn_adjacency_bwd_softmax(_lib.ptr(dpart), _lib.ptr(P), _lib.ptr(alpha), _lib.ptr(dadj),
-                                               _lib.ptr(dS), _lib.ptr(dPA), _lib.ptr(dal_part), N, Ci, T, V, nslots,
-                                               _lib.stream()), "agcn_adjacency_bwd_softmax")
+    _lib.call("agcn_adjacency_bwd_softmax", dpart, P, alpha, dadj, dS, dPA, dal_part, N, Ci, T, V, nslots)
     nt = _L().agcn_scores_num_tiles(V, T)
     dtp = _empty((N, 6 * Ci, T, V), x)
     dbpart = _empty((N * nt, 6 * Ci), x)
@@ -337,16 +315,11 @@ def adjacency_bwd(dy, wcat, x, tp, P, alpha=None, wab=None, bab=None, dy_amax=No
     if tp is None:
         nb = _L().agcn_adjacency_fused_workspace(C, Ci)
         ws = _ws(nb, x)
-        _lib.check(_L().agcn_adjacency_fused_bwd_scores(
-            _lib.ptr(x), _lib.ptr(wab.reshape(6 * Ci, C)), _lib.ptr(bab), _lib.ptr(dS), _lib.ptr(dtp), _lib.ptr(dbpart),
-            scratch.data_ptr(), _lib.ptr(dbab), ws.data_ptr(), nb, N, C, Ci, T, V, _lib.stream()),
-            "agcn_adjacency_fused_bwd_scores")
+        _lib.call("agcn_adjacency_fused_bwd_scores", x, wab.reshape(6 * Ci, C), bab, dS, dtp, dbpart, scratch, dbab, ws,
+                  nb, N, C, Ci, T, V)
     else:
         dtp_amax = _empty((1,), x) if fused_amax_enabled() else None
-        _lib.check(_L().agcn_adjacency_bwd_scores_ex(_lib.ptr(tp), _lib.ptr(dS), _lib.ptr(dtp), _lib.ptr(dbpart),
-                                                     scratch.data_ptr(), _lib.ptr(dbab), _lib.ptr(dtp_amax), N, Ci, T, V,
-                                                     _lib.stream()),
-                   "agcn_adjacency_bwd_scores")
+        _lib.call("agcn_adjacency_bwd_scores_ex", tp, dS, dtp, dbpart, scratch, dbab, dtp_amax, N, Ci, T, V)
     dalpha = dal_part.sum() if dal_part is not None else None
     return dPA, dtp, dbab, dalpha, dadj, dtp_amax
 
@@ -358,9 +331,7 @@ def stc_row_reduce(y, g=None, wv=None, wt=None, want_t=False, want_v=False, scal
     out_t = _empty((N, C, T), y) if want_t else None
     out_v = _empty((N, C, V), y) if want_v else None
     per_row = int(wt is not None and wt.dim() == 3)
-    _lib.check(_L().agcn_stc_row_reduce(_lib.ptr(y), _lib.ptr(g), _lib.ptr(wv), _lib.ptr(wt), per_row, _lib.ptr(out_t),
-                                        _lib.ptr(out_v), float(scale_t), float(scale_v), N, C, T, V, _lib.stream()),
-               "agcn_stc_row_reduce")
+    _lib.call("agcn_stc_row_reduce", y, g, wv, wt, per_row, out_t, out_v, float(scale_t), float(scale_v), N, C, T, V)
     return out_t, out_v
 
 
@@ -370,8 +341,7 @@ def linear_fwd(x, w, b, act=0):
     N, K = x.shape
     O = w.shape[0]
     out = _empty((N, O), x)
-    _lib.check(_L().agcn_linear_fwd(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(out), N, K, O, int(act),
-                                    _lib.stream()), "agcn_linear_fwd")
+    _lib.call("agcn_linear_fwd", x, w, b, out, N, K, O, int(act))
     return out
 
 
@@ -382,9 +352,7 @@ def linear_bwd(dout, out, x, w, act=0, need_din=True):
     dpre = _empty((N, O), x)
     din = _empty((N, K), x) if need_din else None
     dw, db = _empty((O, K), x), _empty((O,), x)
-    _lib.check(_L().agcn_linear_bwd(_lib.ptr(dout), _lib.ptr(out), _lib.ptr(x), _lib.ptr(w), _lib.ptr(dpre),
-                                    _lib.ptr(din), _lib.ptr(dw), _lib.ptr(db), N, K, O, int(act), _lib.stream()),
-               "agcn_linear_bwd")
+    _lib.call("agcn_linear_bwd", dout, out, x, w, dpre, din, dw, db, N, K, O, int(act))
     return din, dw, db
 
 
@@ -393,8 +361,7 @@ def gate_conv_fwd(x, w, b):
     N, C, L = x.shape
     Ks = w.shape[-1]
     a = _empty((N, L), x)
-    _lib.check(_L().agcn_gate_conv_fwd(_lib.ptr(x), _lib.ptr(w.reshape(C, Ks)), _lib.ptr(b), _lib.ptr(a), N, C, L, Ks,
-                                       _lib.stream()), "agcn_gate_conv_fwd")
+    _lib.call("agcn_gate_conv_fwd", x, w.reshape(C, Ks), b, a, N, C, L, Ks)
     return a
 
 
@@ -404,9 +371,7 @@ def gate_conv_bwd(da, a, x, w):
     Ks = w.shape[-1]
     dpre = _empty((N, L), x)
     dx, dw, db = _empty((N, C, L), x), _empty((1, C, Ks), x), _empty((1,), x)
-    _lib.check(_L().agcn_gate_conv_bwd(_lib.ptr(da), _lib.ptr(a), _lib.ptr(x), _lib.ptr(w.reshape(C, Ks)),
-                                       _lib.ptr(dpre), _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db), N, C, L, Ks,
-                                       _lib.stream()), "agcn_gate_conv_bwd")
+    _lib.call("agcn_gate_conv_bwd", da, a, x, w.reshape(C, Ks), dpre, dx, dw, db, N, C, L, Ks)
     return dx, dw, db
 
 
@@ -420,17 +385,14 @@ class DataBNFunction(torch.autograd.Function):
         x = x.contiguous()
         N, C, T, V, M = x.shape
         CH = C * V * M
-        L = _L()
         if training:
             part = _empty((N, 2, CH), x)
-            _lib.check(L.agcn_data_bn_stats(_lib.ptr(x), _lib.ptr(part), N, C, T, V, M, _lib.stream()),
-                       "agcn_data_bn_stats")
+            _lib.call("agcn_data_bn_stats", x, part, N, C, T, V, M)
             (st,), gcount = _bn_coeffs(True, [part], N * T, [(w, b, rm, rv)], sync, N)
         else:
             (st,), gcount = _bn_coeffs(False, [None], N * T, [(w, b, rm, rv)], None, N)
         out = _empty((N * M, C, T, V), x)
-        _lib.check(L.agcn_data_bn_apply(_lib.ptr(x), _lib.ptr(st.scale), _lib.ptr(st.shift), _lib.ptr(out), N, C, T, V, M,
-                                        _lib.stream()), "agcn_data_bn_apply")
+        _lib.call("agcn_data_bn_apply", x, st.scale, st.shift, out, N, C, T, V, M)
         ctx.st, ctx.sync, ctx.gcount, ctx.training = st, sync, gcount, training
         ctx.save_for_backward(x, w)
         return out
@@ -442,7 +404,6 @@ class DataBNFunction(torch.autograd.Function):
         dy = dy.contiguous()
         N, C, T, V, M = x.shape
         CH = C * V * M
-        L = _L()
         # the reduce stage feeds the statistics' correction terms of dx (train) and dgamma / dbeta; with frozen statistics
         # (eval) dx = gamma*invstd_run*dy is the apply stage with the two sums at zero (exactly: its correction terms are
         # products with 0) and the sums, taken at the running mean / invstd, are needed for dgamma / dbeta only
@@ -450,8 +411,7 @@ class DataBNFunction(torch.autograd.Function):
         sums = None
         if ctx.training or ng[1] or ng[2]:
             part = _empty((N, 2, CH), x)
-            _lib.check(L.agcn_data_bn_bwd_reduce(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(st.mean), _lib.ptr(st.invstd),
-                                                 _lib.ptr(part), N, C, T, V, M, _lib.stream()), "agcn_data_bn_bwd_reduce")
+            _lib.call("agcn_data_bn_bwd_reduce", dy, x, st.mean, st.invstd, part, N, C, T, V, M)
             sums = _colsum(part, N, 2 * CH)
         scale = 1.0
         if ctx.training and sync is not None:
@@ -461,9 +421,8 @@ class DataBNFunction(torch.autograd.Function):
         if ng[0]:
             dx = torch.empty_like(x)
             corr = sums if ctx.training else torch.zeros(2 * CH, dtype=torch.float32, device=x.device)
-            _lib.check(L.agcn_data_bn_bwd_apply(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(w), _lib.ptr(st.mean),
-                                                _lib.ptr(st.invstd), _lib.ptr(corr), float(ctx.gcount), _lib.ptr(dx), N, C,
-                                                T, V, M, _lib.stream()), "agcn_data_bn_bwd_apply")
+            _lib.call("agcn_data_bn_bwd_apply", dy, x, w, st.mean, st.invstd, corr, float(ctx.gcount), dx, N, C, T, V,
+                      M)
         if sums is not None:
             dbeta, dgamma = sums[:CH], sums[CH:]
             if scale != 1.0:
@@ -486,8 +445,7 @@ class PoolFCFunction(torch.autograd.Function):
         NM, C, T, V = x.shape
         N = NM // M
         rowmean, pooled = _empty((NM, C), x), _empty((N, C), x)
-        _lib.check(_L().agcn_pool_fwd(_lib.ptr(x), _lib.ptr(rowmean), _lib.ptr(pooled), N, M, C, T * V, _lib.stream()),
-                   "agcn_pool_fwd")
+        _lib.call("agcn_pool_fwd", x, rowmean, pooled, N, M, C, T * V)
         logits = linear_fwd(pooled, w, b, 0)
         ctx.save_for_backward(pooled, logits, w)
         ctx.shape, ctx.M = (NM, C, T, V), M
@@ -502,8 +460,7 @@ class PoolFCFunction(torch.autograd.Function):
         dx = None
         if ctx.needs_input_grad[0]:
             dx = _empty((NM, C, T, V), pooled)
-            _lib.check(_L().agcn_pool_bwd(_lib.ptr(dpooled), _lib.ptr(dx), NM // M, M, C, T * V, _lib.stream()),
-                       "agcn_pool_bwd")
+            _lib.call("agcn_pool_bwd", dpooled, dx, NM // M, M, C, T * V)
         return dx, dw, db, None
 
 
@@ -544,8 +501,7 @@ class STCAttentionFunction(torch.autograd.Function):
         # the gated tensor feeds the f16x3 temporal convolution (and its weight gradient): leave its maximum behind
         o_amax = _empty((1,), y) if fused_amax_enabled() else None
         INFER_STATS['stc_apply'] += 1
-        _lib.check(_L().agcn_stc_apply_ex(_lib.ptr(y), _lib.ptr(a_s), _lib.ptr(a_t), _lib.ptr(a_c), _lib.ptr(out),
-                                          _lib.ptr(o_amax), N, C, T, V, _lib.stream()), "agcn_stc_apply")
+        _lib.call("agcn_stc_apply_ex", y, a_s, a_t, a_c, out, o_amax, N, C, T, V)
         _note_out_amax(out, o_amax)
         ctx.save_for_backward(y, m_s, mv1, a_s, a_t, a_c, m_c, h, *par)
         return out
@@ -576,9 +532,7 @@ class STCAttentionFunction(torch.autograd.Function):
         dm_s, dsa_w, dsa_b = gate_conv_bwd(da_s, a_s, m_s, sa_w)
         dms = (dm_s / T).contiguous()
         dy = torch.empty_like(y)
-        _lib.check(_L().agcn_stc_bwd_apply(_lib.ptr(dout), _lib.ptr(a_s), _lib.ptr(a_t), _lib.ptr(a_c), _lib.ptr(dmv1),
-                                           _lib.ptr(dms), _lib.ptr(dy), N, C, T, V, _lib.stream()),
-                   "agcn_stc_bwd_apply")
+        _lib.call("agcn_stc_bwd_apply", dout, a_s, a_t, a_c, dmv1, dms, dy, N, C, T, V)
         return dy, dsa_w, dsa_b, dta_w, dta_b, df1w, df1b, df2w, df2b
 
 
@@ -625,8 +579,7 @@ def sync_of(bn_module):
 def _colsum(slab, nslots, width):
     out = _empty((width,), slab)
     scratch = _scratch(width, slab)
-    _lib.check(_L().agcn_colsum(_lib.ptr(slab), int(nslots), int(width), scratch.data_ptr(), _lib.ptr(out),
-                                _lib.stream()), "agcn_colsum")
+    _lib.call("agcn_colsum", slab, int(nslots), int(width), scratch, out)
     return out
 
 
@@ -664,12 +617,8 @@ def bn_train_coeffs(stats_part, count, gamma, beta, running_mean, running_var, m
     st.scale, st.shift = _empty((C,), gamma), _empty((C,), gamma)
     nslots = stats_part.shape[0]
     scratch = _scratch(2 * C, gamma)
-    _lib.check(_L().agcn_bn_stats_finalize(_lib.ptr(stats_part), nslots, C, float(count), _lib.ptr(gamma),
-                                           _lib.ptr(beta), _lib.ptr(running_mean), _lib.ptr(running_var),
-                                           float(momentum), float(eps), scratch.data_ptr(), _lib.ptr(st.mean),
-                                           _lib.ptr(st.invstd),
-                                           _lib.ptr(st.scale), _lib.ptr(st.shift), _lib.stream()),
-               "agcn_bn_stats_finalize")
+    _lib.call("agcn_bn_stats_finalize", stats_part, nslots, C, float(count), gamma, beta, running_mean, running_var,
+              float(momentum), float(eps), scratch, st.mean, st.invstd, st.scale, st.shift)
     return st
 
 
@@ -679,10 +628,8 @@ def bn_eval_coeffs(gamma, beta, running_mean, running_var, eps=BN_EPS):
     st.eval = True
     st.scale, st.shift = _empty((C,), gamma), _empty((C,), gamma)
     st.mean, st.invstd = _empty((C,), gamma), _empty((C,), gamma)     # frozen statistics, for the eval-mode backward
-    _lib.check(_L().agcn_bn_eval_coeff_ex(_lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(running_mean),
-                                          _lib.ptr(running_var), float(eps), C, _lib.ptr(st.scale), _lib.ptr(st.shift),
-                                          _lib.ptr(st.mean), _lib.ptr(st.invstd), _lib.stream()),
-               "agcn_bn_eval_coeff_ex")
+    _lib.call("agcn_bn_eval_coeff_ex", gamma, beta, running_mean, running_var, float(eps), C, st.scale, st.shift,
+              st.mean, st.invstd)
     return st
 
 
@@ -696,15 +643,19 @@ def bn_act_fwd(y1, st1, r=None, st2=None, relu=True, want_bits=False, amax_out=N
     bits = torch.empty((y1.numel() + 31) // 32, dtype=torch.int32, device=y1.device) if want_bits else None
     mode = 0 if r is None else (1 if st2 is None else 2)
     # amax_out: optional 1-element tensor that receives max |out| (for the split-fp16 kernels that read `out` next)
-    _lib.check(_L().agcn_bn_act_fwd_ex(_lib.ptr(y1), _lib.ptr(st1.scale), _lib.ptr(st1.shift), _lib.ptr(r),
-                                       _lib.ptr(st2.scale) if st2 else None, _lib.ptr(st2.shift) if st2 else None,
-                                       _lib.ptr(out), _lib.ptr_bits(bits), _lib.ptr(amax_out), N, C, T * V, mode,
-                                       int(relu), _lib.stream()),
-               "agcn_bn_act_fwd")
+    _lib.call("agcn_bn_act_fwd_ex", y1, st1.scale, st1.shift, r, st2.scale if st2 else None, st2.shift if st2 else None,
+              out, bits, amax_out, N, C, T * V, mode, int(relu))
     return (out, bits) if want_bits else out
 
 
 EVAL_BWD_STATS = {'sums': 0, 'nosums': 0}     # diagnostic: agcn_bn_bwd_eval launches with / without the row partials
+
+
+def _mask_arg(mask):
+    """(address, mask_bits) of a ReLU mask: the fp32 activation tensor (0) or its int32 sign bit words (1).  One C
+    parameter takes either kind under the flag, so the kind is checked here and the address is what travels."""
+    mbits = int(mask is not None and mask.dtype == torch.int32)
+    return (_lib.ptr_bits(mask) if mbits else _lib.ptr(mask)), mbits
 
 
 def bn_bwd_eval(dout, mask, y1, st1, y2=None, st2=None, want_sums=True, amax_out=None):
@@ -719,43 +670,36 @@ def bn_bwd_eval(dout, mask, y1, st1, y2=None, st2=None, want_sums=True, amax_out
     dy1 = torch.empty_like(dout)
     dy2 = torch.empty_like(dout) if two else None
     part = _empty((N * C * 3,), dout) if want_sums else None
-    mbits = int(mask is not None and mask.dtype == torch.int32)
-    mptr = _lib.ptr_bits(mask) if mbits else _lib.ptr(mask)
+    mptr, mbits = _mask_arg(mask)
     EVAL_BWD_STATS['sums' if want_sums else 'nosums'] += 1
-    _lib.check(_L().agcn_bn_bwd_eval(_lib.ptr(dout), mptr, mbits, _lib.ptr(y1) if want_sums else None,
-                                     _lib.ptr(st1.scale), _lib.ptr(y2) if (want_sums and two) else None,
-                                     _lib.ptr(st2.scale) if two else None, int(want_sums), _lib.ptr(part),
-                                     _lib.ptr(dy1), _lib.ptr(dy2), _lib.ptr(amax_out), N, C, T * V, _lib.stream()),
-               "agcn_bn_bwd_eval")
+    _lib.call("agcn_bn_bwd_eval", dout, mptr, mbits, y1 if want_sums else None, st1.scale,
+              y2 if (want_sums and two) else None, st2.scale if two else None, int(want_sums), part, dy1, dy2, amax_out,
+              N, C, T * V)
     if not want_sums:
         return dy1, None, None, None, dy2, None, None, None
     dg1, db1, dc1 = _empty((C,), dout), _empty((C,), dout), _empty((C,), dout)
     dg2 = db2 = dc2 = None
     if two:
         dg2, db2, dc2 = _empty((C,), dout), _empty((C,), dout), _empty((C,), dout)
-    _lib.check(_L().agcn_bn_bwd_eval_finalize(
-        _lib.ptr(part), N, C, _lib.ptr(st1.scale), _lib.ptr(st1.mean), _lib.ptr(st1.invstd),
-        _lib.ptr(st2.scale) if two else None, _lib.ptr(st2.mean) if two else None,
-        _lib.ptr(st2.invstd) if two else None, _lib.ptr(dg1), _lib.ptr(db1), _lib.ptr(dc1), _lib.ptr(dg2),
-        _lib.ptr(db2), _lib.ptr(dc2), _lib.stream()), "agcn_bn_bwd_eval_finalize")
+    _lib.call("agcn_bn_bwd_eval_finalize", part, N, C, st1.scale, st1.mean, st1.invstd, st2.scale if two else None,
+              st2.mean if two else None, st2.invstd if two else None, dg1, db1, dc1, dg2, db2, dc2)
     return dy1, dg1, db1, dc1, dy2, dg2, db2, dc2
 
 
 def _bn_bwd_two_stage(grad, ins, outs, part, coef, amax_out, N, C, TV, sync, gcount):
     """The train-mode BatchNorm backward as reduce + apply instead of the fused ``agcn_bn_bwd``: where the apply stage
     also leaves max |dy1| behind (``amax_out``, for the split-fp16 kernels that read dy1 next) and / or the per-channel
-    sums are all-reduced in between (``sync``).  grad = (dout, mask, mask_bits), ins / outs: bn_bwd's pointer tuples."""
+    sums are all-reduced in between (``sync``).  grad = (dout, mask address, mask_bits), ins / outs: bn_bwd's tuples."""
     dout, mptr, mbits = grad
-    _lib.check(_L().agcn_bn_bwd_reduce(dout, mptr, mbits, ins[0], ins[4], _lib.ptr(part), N, C, TV, _lib.stream()),
-               "agcn_bn_bwd_reduce")
+    _lib.call("agcn_bn_bwd_reduce", dout, mptr, mbits, ins[0], ins[4], part, N, C, TV)
     sums, nslots, total, scale = part, N, float(N) * float(TV), 1.0
     if sync is not None:
         # one collective for both branches; dgamma/dbeta come out as GLOBAL sums, scaled by 1/world so that the
         # gradient average of the data-parallel step restores them (every rank holds the same value)
         sums, nslots, scale = _allreduce_sum(_colsum(part, N, 3 * C), sync), 1, 1.0 / sync.world
         total = float(gcount) if gcount is not None else total * sync.world
-    _lib.check(_L().agcn_bn_bwd_apply_ex(_lib.ptr(sums), nslots, total, scale, dout, mptr, mbits, *ins, _lib.ptr(coef),
-                                         *outs, _lib.ptr(amax_out), N, C, TV, _lib.stream()), "agcn_bn_bwd_apply")
+    _lib.call("agcn_bn_bwd_apply_ex", sums, nslots, total, scale, dout, mptr, mbits, *ins, coef, *outs, amax_out, N, C,
+              TV)
 
 
 def bn_bwd(dout, mask, y1, gamma1, st1, y2=None, gamma2=None, st2=None, sync=None, gcount=None, amax_out=None,
@@ -786,14 +730,11 @@ def bn_bwd(dout, mask, y1, gamma1, st1, y2=None, gamma2=None, st2=None, sync=Non
     if y2 is not None:
         dy2 = torch.empty_like(y2)
         dg2, db2 = _empty((C,), y1), _empty((C,), y1)
-    mbits = int(mask is not None and mask.dtype == torch.int32)
-    grad = (_lib.ptr(dout), _lib.ptr_bits(mask) if mbits else _lib.ptr(mask), mbits)
-    ins = (_lib.ptr(y1), _lib.ptr(gamma1), _lib.ptr(st1.mean), _lib.ptr(st1.invstd), _lib.ptr(y2), _lib.ptr(gamma2),
-           _lib.ptr(st2.mean) if st2 else None, _lib.ptr(st2.invstd) if st2 else None)
-    outs = (_lib.ptr(dy1), _lib.ptr(dg1), _lib.ptr(db1), _lib.ptr(dy2), _lib.ptr(dg2), _lib.ptr(db2))
+    grad = (dout, *_mask_arg(mask))
+    ins = (y1, gamma1, st1.mean, st1.invstd, y2, gamma2, st2.mean if st2 else None, st2.invstd if st2 else None)
+    outs = (dy1, dg1, db1, dy2, dg2, db2)
     if sync is None and amax_out is None:
-        _lib.check(_L().agcn_bn_bwd(*grad, *ins, _lib.ptr(part), _lib.ptr(coef), *outs, N, C, T * V, _lib.stream()),
-                   "agcn_bn_bwd")
+        _lib.call("agcn_bn_bwd", *grad, *ins, part, coef, *outs, N, C, T * V)
     else:
         _bn_bwd_two_stage(grad, ins, outs, part, coef, amax_out, N, C, T * V, sync, gcount)
     if S > 1:                          # the weight / bias are shared by the S virtual sub-batches
@@ -1030,7 +971,16 @@ def tcn_backward(s, dout, join=True, want_sums=True):
 
 
 # ---- BN-folded inference (eval mode under no_grad): adjacency + two kernels per TCN_GCN_unit ----------------------
-ERR_UNSUPPORTED = -3
+ERR_UNSUPPORTED = _lib.ERR_UNSUPPORTED
+
+
+def _launched(name, *args):
+    """``_lib.call`` for the entry points a caller may fall back from: False where the library reports the shape
+    unsupported (nothing was launched), True when the work is enqueued; every other status raises."""
+    rc = _lib.status(name, *args)
+    if rc != ERR_UNSUPPORTED:
+        _lib.check(rc, name)
+    return rc != ERR_UNSUPPORTED
 
 # Parameters and BatchNorm running statistics are written through RAW POINTERS by the training path (agcn_sgd_step on the
 # flat buffer, agcn_bn_stats_finalize), which moves neither data_ptr nor the tensors' version counters.  Everything that
@@ -1078,13 +1028,9 @@ def gcn_unit_infer(x, adj, wcat, bias, res=None, x2=None, w2=None, relu=True):
     nbytes = _L().agcn_gcn_unit_infer_workspace(C, Cout, K2, T, V)
     ws = _ws(nbytes, x)
     y = _empty((N, Cout, T, V), x)
-    rc = _L().agcn_gcn_unit_infer(_lib.ptr(x), _lib.ptr(adj), _lib.ptr(wcat), _lib.ptr(bias), _lib.ptr(res),
-                                  _lib.ptr(x2), _lib.ptr(w2), K2, 1 if relu else 0, _lib.ptr(y), ws.data_ptr(), nbytes,
-                                  N, C, Cout, T, V, _lib.stream())
-    if rc == ERR_UNSUPPORTED:
-        return None
-    _lib.check(rc, "agcn_gcn_unit_infer")
-    return y
+    ok = _launched("agcn_gcn_unit_infer", x, adj, wcat, bias, res, x2, w2, K2, 1 if relu else 0, y, ws, nbytes, N, C, Cout,
+                   T, V)
+    return y if ok else None
 
 
 def conv9_infer(x, w, b, res=None, relu=True, stride=1):
@@ -1094,12 +1040,8 @@ def conv9_infer(x, w, b, res=None, relu=True, stride=1):
     To = conv_out_frames(T, 9, stride)
     ws, nbytes = _conv_ws(Cin, Cout, T, V, 9, stride, x)
     y = _empty((N, Cout, To, V), x)
-    rc = _L().agcn_conv9_infer(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(res), 1 if relu else 0, _lib.ptr(y),
-                               ws.data_ptr(), nbytes, N, Cin, Cout, T, V, stride, _lib.stream())
-    if rc == ERR_UNSUPPORTED:
-        return None
-    _lib.check(rc, "agcn_conv9_infer")
-    return y
+    ok = _launched("agcn_conv9_infer", x, w, b, res, 1 if relu else 0, y, ws, nbytes, N, Cin, Cout, T, V, stride)
+    return y if ok else None
 
 
 def tconv_infer(x, w, b, a_s=None, a_t=None, a_c=None, res=None, relu=True, stride=1, pad=None, x_amax=None):
@@ -1115,12 +1057,9 @@ def tconv_infer(x, w, b, a_s=None, a_t=None, a_c=None, res=None, relu=True, stri
         raise ValueError(f"agcn_amd: a {taps}-frame kernel with padding {pad} does not fit {T} frames")
     ws, nbytes = _conv_ws(Cin, Cout, T, V, taps, stride, x, pad)
     y = _empty((N, Cout, To, V), x)
-    rc = _L().agcn_tconv_infer(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(a_s), _lib.ptr(a_t), _lib.ptr(a_c),
-                               _lib.ptr(res), 1 if relu else 0, _lib.ptr(y), ws.data_ptr(), nbytes, N, Cin, Cout, T, V,
-                               taps, stride, pad, _lib.ptr(x_amax), _lib.stream())
-    if rc == ERR_UNSUPPORTED:
+    if not _launched("agcn_tconv_infer", x, w, b, a_s, a_t, a_c, res, 1 if relu else 0, y, ws, nbytes, N, Cin, Cout, T,
+                     V, taps, stride, pad, x_amax):
         return None
-    _lib.check(rc, "agcn_tconv_infer")
     INFER_STATS['tconv_infer'] += 1
     return y
 
@@ -1264,9 +1203,7 @@ def skel_append(ring, frame, slot, count, moving_avg=1):
     Mmax, Tmax, V, C = ring.shape
     if C != 3 or tuple(frame.shape) != (Mmax, V, 3):
         raise ValueError(f"agcn_amd: skel_append takes a ({Mmax}, {V}, 3) frame for this ring, got {tuple(frame.shape)}")
-    rc = _L().agcn_skel_append(_lib.ptr(frame), _lib.ptr(ring), Mmax, Tmax, V, int(slot), int(count), int(moving_avg),
-                               _lib.stream())
-    _lib.check(rc, "agcn_skel_append")
+    _lib.call("agcn_skel_append", frame, ring, Mmax, Tmax, V, int(slot), int(count), int(moving_avg))
 
 
 def prenorm(x, num_select=None, origin=0, frames=None, zaxis=(0, 1), zaxis2=None, xaxis=(8, 4), pad=True, center=True,
@@ -1290,10 +1227,8 @@ def prenorm(x, num_select=None, origin=0, frames=None, zaxis=(0, 1), zaxis2=None
     sel = torch.empty((N, K), dtype=torch.int32, device=x.device)
     energy = _empty((N, M), x) if select else None
     (z0, z1), (x0, x1), (zz0, zz1) = _axis(zaxis), _axis(xaxis), _axis(zaxis2)
-    rc = _L().agcn_prenorm(_lib.ptr(x), _lib.ptr(out), _lib.ptr_bits(sel), _lib.ptr(energy), N, M, K, T, Tmax, int(origin),
-                           V, 1 if select else 0, 1 if pad else 0, 1 if center else (2 if center_firstframe else 0),
-                           z0, z1, x0, x1, zz0, zz1, _lib.stream())
-    _lib.check(rc, "agcn_prenorm")
+    _lib.call("agcn_prenorm", x, out, sel, energy, N, M, K, T, Tmax, int(origin), V, 1 if select else 0,
+              1 if pad else 0, 1 if center else (2 if center_firstframe else 0), z0, z1, x0, x1, zz0, zz1)
     return out, sel, energy
 
 
@@ -1333,12 +1268,9 @@ def prenorm_windows(pool, start, length, block=None, frames=None, num_select=Non
     sel = torch.empty((N, K), dtype=torch.int32, device=pool.device)
     energy = _empty((N, M), pool) if select else None
     (z0, z1), (x0, x1), (zz0, zz1) = _axis(zaxis), _axis(xaxis), _axis(zaxis2)
-    rc = _L().agcn_prenorm_windows(_lib.ptr(pool), _lib.ptr(out), _lib.ptr_bits(sel), _lib.ptr(energy),
-                                   _lib.ptr_bits(block), _lib.ptr_bits(start), _lib.ptr_bits(length), N, nblocks, M, K,
-                                   T, Tmax, V, 1 if select else 0, 1 if pad else 0,
-                                   1 if center else (2 if center_firstframe else 0), z0, z1, x0, x1, zz0, zz1,
-                                   _lib.stream())
-    _lib.check(rc, "agcn_prenorm_windows")
+    _lib.call("agcn_prenorm_windows", pool, out, sel, energy, block, start, length, N, nblocks, M, K, T, Tmax, V,
+              1 if select else 0, 1 if pad else 0, 1 if center else (2 if center_firstframe else 0), z0, z1, x0, x1,
+              zz0, zz1)
     return out, sel, energy
 
 
@@ -1352,8 +1284,7 @@ def skel_smooth(raw, moving_avg=1):
     if not 1 <= int(moving_avg) <= L:
         raise ValueError(f"agcn_amd: skel_smooth needs 1 <= moving_avg <= L = {L}, got {moving_avg}")
     out = _empty((Mmax, L, V, 3), raw)
-    rc = _L().agcn_skel_smooth(_lib.ptr(raw), _lib.ptr(out), Mmax, L, V, int(moving_avg), _lib.stream())
-    _lib.check(rc, "agcn_skel_smooth")
+    _lib.call("agcn_skel_smooth", raw, out, Mmax, L, V, int(moving_avg))
     return out
 
 
@@ -1369,9 +1300,7 @@ def skel_append_many(rings, frames, slot, count, moving_avg=1):
                          f"{tuple(frames.shape)}")
     _plan(slot, S, 'slot')
     _plan(count, S, 'count')
-    rc = _L().agcn_skel_append_many(_lib.ptr(frames), _lib.ptr(rings), _lib.ptr_bits(slot), _lib.ptr_bits(count), S, Mmax,
-                                    Tmax, V, int(moving_avg), _lib.stream())
-    _lib.check(rc, "agcn_skel_append_many")
+    _lib.call("agcn_skel_append_many", frames, rings, slot, count, S, Mmax, Tmax, V, int(moving_avg))
 
 
 # ---- the autograd nodes ---------------------------------------------------------------------------------------------------
@@ -1555,14 +1484,6 @@ def encoder_hip_enabled():
 ENCODER_STATS = {'layers_hip': 0, 'layers_tensor': 0}
 
 
-def _ptr_u8(t):
-    if t is None:
-        return None
-    if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.uint8):
-        raise RuntimeError(f"agcn_amd: expected a contiguous uint8 GPU tensor, got {t.dtype} on {t.device}")
-    return t.data_ptr()
-
-
 class TokensFunction(torch.autograd.Function):
     """x (N*M, C, T', V), cls (1, 1, D) or None, pe (1, rows >= L, D) or None -> tok (N, L, D): token cls + m*T' + t,
     feature v*C + c, plus the positional rows (reference aagcn_v17.py:290-299).  args: x, cls, pe, M"""
@@ -1576,8 +1497,7 @@ class TokensFunction(torch.autograd.Function):
         cls_ = None if cls is None else cls.contiguous()
         pe_ = None if pe is None else pe.contiguous()
         tok = _empty((N, L, D), x)
-        _lib.check(_L().agcn_tokens_fwd(_lib.ptr(x), _lib.ptr(cls_), _lib.ptr(pe_), 0 if pe is None else pe.shape[-2],
-                                        _lib.ptr(tok), N, M, C, Tp, V, _lib.stream()), "agcn_tokens_fwd")
+        _lib.call("agcn_tokens_fwd", x, cls_, pe_, 0 if pe is None else pe.shape[-2], tok, N, M, C, Tp, V)
         ctx.dims = (N, M, C, Tp, V, cls is not None, None if pe is None else tuple(pe.shape))
         return tok
 
@@ -1589,9 +1509,8 @@ class TokensFunction(torch.autograd.Function):
         dx = _empty((N * M, C, Tp, V), dtok) if ng[0] else None
         dcls = _empty((1, 1, V * C), dtok) if (has_cls and ng[1]) else None
         dpe = _empty(pe_shape, dtok) if (pe_shape is not None and ng[2]) else None
-        _lib.check(_L().agcn_tokens_bwd(_lib.ptr(dtok), _lib.ptr(dx), _lib.ptr(dcls), _lib.ptr(dpe), int(has_cls),
-                                        0 if dpe is None else pe_shape[-2], N, M, C, Tp, V, _lib.stream()),
-                   "agcn_tokens_bwd")
+        _lib.call("agcn_tokens_bwd", dtok, dx, dcls, dpe, int(has_cls), 0 if dpe is None else pe_shape[-2], N, M, C, Tp,
+                  V)
         return dx, dcls, dpe, None
 
 
@@ -1622,9 +1541,7 @@ class MHAFunction(torch.autograd.Function):
         need_bwd = ctx.needs_input_grad[0]
         prob = _empty((N, H, L, L), qkv) if need_bwd else None
         avg = _empty((N, L, L), qkv) if need_avg else None
-        _lib.check(_L().agcn_mha_fwd(_lib.ptr(qkv), _ptr_u8(null_tok), int(causal), _ptr_u8(keep), float(keep_scale),
-                                     _lib.ptr(out), _lib.ptr(prob), _lib.ptr(avg), N, L, H, dh, _lib.stream()),
-                   "agcn_mha_fwd")
+        _lib.call("agcn_mha_fwd", qkv, null_tok, int(causal), keep, float(keep_scale), out, prob, avg, N, L, H, dh)
         if need_bwd:
             ctx.save_for_backward(qkv, prob, keep)
         ctx.dims, ctx.keep_scale = (N, L, H, dh), float(keep_scale)
@@ -1639,9 +1556,7 @@ class MHAFunction(torch.autograd.Function):
         dout = dout.contiguous()
         dqkv = torch.empty_like(qkv)
         ws = _empty((N, H, L, L), qkv)
-        _lib.check(_L().agcn_mha_bwd(_lib.ptr(dout), _lib.ptr(qkv), _lib.ptr(prob), _ptr_u8(keep), ctx.keep_scale,
-                                     _lib.ptr(dqkv), ws.data_ptr(), ws.numel() * 4, N, L, H, dh, _lib.stream()),
-                   "agcn_mha_bwd")
+        _lib.call("agcn_mha_bwd", dout, qkv, prob, keep, ctx.keep_scale, dqkv, ws, ws.numel() * 4, N, L, H, dh)
         return dqkv, None, None, None, None, None, None
 
 
@@ -1679,8 +1594,7 @@ class AddLayerNormFunction(torch.autograd.Function):
         R = a.numel() // D
         out = torch.empty_like(a)
         mean, rstd = _empty((R,), a), _empty((R,), a)
-        _lib.check(_L().agcn_ln_fwd(_lib.ptr(a), _lib.ptr(b), _lib.ptr(weight), _lib.ptr(bias), float(eps), _lib.ptr(out),
-                                    _lib.ptr(mean), _lib.ptr(rstd), R, D, _lib.stream()), "agcn_ln_fwd")
+        _lib.call("agcn_ln_fwd", a, b, weight, bias, float(eps), out, mean, rstd, R, D)
         ctx.save_for_backward(a, b, weight, mean, rstd)
         return out
 
@@ -1693,9 +1607,7 @@ class AddLayerNormFunction(torch.autograd.Function):
         dx = torch.empty_like(a)
         dg, db = _empty((D,), a), _empty((D,), a)
         ws = _empty(((min(R, 1024) + 3) * 2 * D,), a)      # one (dgamma, dbeta) row per wave: encoder_plan.h
-        _lib.check(_L().agcn_ln_bwd(_lib.ptr(dout), _lib.ptr(a), _lib.ptr(b), _lib.ptr(weight), _lib.ptr(mean),
-                                    _lib.ptr(rstd), _lib.ptr(dx), _lib.ptr(dg), _lib.ptr(db), ws.data_ptr(),
-                                    ws.numel() * 4, R, D, _lib.stream()), "agcn_ln_bwd")
+        _lib.call("agcn_ln_bwd", dout, a, b, weight, mean, rstd, dx, dg, db, ws, ws.numel() * 4, R, D)
         return dx, (dx if b is not None else None), dg, db, None
 
 
@@ -1726,9 +1638,7 @@ def sgn_frames(x, wimg, V, want_g=True):
     N, seg, _ = x.shape
     feat = _empty((N, seg, 256), x)
     g = _empty((N, seg, V, V), x) if want_g else None
-    rc = _L().agcn_sgn_frames(_lib.ptr(x), _lib.ptr(wimg), wimg.numel(), _lib.ptr(feat), _lib.ptr(g), N, seg, V,
-                              _lib.stream())
-    _lib.check(rc, "agcn_sgn_frames")
+    _lib.call("agcn_sgn_frames", x, wimg, wimg.numel(), feat, g, N, seg, V)
     SGN_STATS['frames_hip'] += 1
     return feat, g
 
@@ -1739,9 +1649,7 @@ def sgn_clip(feat, wimg, num_class):
     if C != 256:
         raise ValueError(f"agcn_amd: sgn_clip takes (N, seg, 256), got {tuple(feat.shape)}")
     logits = _empty((N, num_class), feat)
-    rc = _L().agcn_sgn_clip(_lib.ptr(feat), _lib.ptr(wimg), wimg.numel(), _lib.ptr(logits), N, seg, num_class,
-                            _lib.stream())
-    _lib.check(rc, "agcn_sgn_clip")
+    _lib.call("agcn_sgn_clip", feat, wimg, wimg.numel(), logits, N, seg, num_class)
     SGN_STATS['clip_hip'] += 1
     return logits
 
@@ -1776,9 +1684,7 @@ def sgn_sample(win, r, seg):
     r, N, T, V, K, S = _sgn_sample_args("sgn_sample", win, r, seg)
     out = _empty((N, S, seg, V * 3), win)
     L = torch.empty((N,), dtype=torch.int32, device=win.device)
-    rc = _L().agcn_sgn_sample(_lib.ptr(win), _lib.ptr_bits(r), _lib.ptr(out), _lib.ptr_bits(L), N, T, V, K, S, seg,
-                              _lib.stream())
-    _lib.check(rc, "agcn_sgn_sample")
+    _lib.call("agcn_sgn_sample", win, r, out, L, N, T, V, K, S, seg)
     SGN_STATS['sample_hip'] += 1
     return out, L
 
@@ -1894,10 +1800,7 @@ def sgn_collate(pool, r, seg, index=None, angles=None, want_subject=False):
     out = _empty((N, S, seg, V * 3), pool)
     L = torch.empty((N,), dtype=torch.int32, device=pool.device)
     subj = _empty((N, S, seg), pool) if want_subject else None
-    rc = _L().agcn_sgn_collate(_lib.ptr(pool), None if index is None else index.data_ptr(), _lib.ptr_bits(r),
-                               _lib.ptr(angles), _lib.ptr(out), _lib.ptr(subj), _lib.ptr_bits(L), P, N, T, V, K, S, seg,
-                               _lib.stream())
-    _lib.check(rc, "agcn_sgn_collate")
+    _lib.call("agcn_sgn_collate", pool, index, r, angles, out, subj, L, P, N, T, V, K, S, seg)
     SGN_COLLATE_STATS['collate_hip'] += 1
     return out, L, subj
 
@@ -1921,13 +1824,11 @@ def _sgn_clip_bwd(feat, wimg, wimg_t, dlogits, tape):
     nc = dlogits.shape[1]
     tp = _tape(_L().agcn_sgn_clip_tape_floats, (N, seg, nc), feat, name) if tape else None
     dfeat = _empty((N, seg, 256), feat)
-    args = (_lib.ptr(feat), _lib.ptr(wimg), wimg.numel(), _lib.ptr(wimg_t), wimg_t.numel(), _lib.ptr(dlogits),
-            _lib.ptr(dfeat), N, seg, nc)
+    args = (feat, wimg, wimg.numel(), wimg_t, wimg_t.numel(), dlogits, dfeat, N, seg, nc)
     if tape:
-        rc = _L().agcn_sgn_clip_bwd_tape(*args, _lib.ptr(tp), tp.numel(), _lib.stream())
+        _lib.call("agcn_sgn_clip_bwd_tape", *args, tp, tp.numel())
     else:
-        rc = _L().agcn_sgn_clip_bwd(*args, _lib.stream())
-    _lib.check(rc, "agcn_" + name)
+        _lib.call("agcn_sgn_clip_bwd", *args)
     (SGN_WGRAD_STATS if tape else SGN_GRAD_STATS)[name[4:]] += 1
     return (dfeat, tp) if tape else dfeat
 
@@ -1943,13 +1844,11 @@ def _sgn_frames_bwd(x, wimg, wimg_t, dfeat, V, tape):
     tp = _tape(_L().agcn_sgn_frames_tape_floats, (N, seg, V), x, name) if tape else None
     dx = _empty((N, seg, 3 * V), x)
     ws = _empty((max(1, _L().agcn_sgn_frames_bwd_workspace(N, seg, V) // 4),), x)
-    args = (_lib.ptr(x), _lib.ptr(wimg), wimg.numel(), _lib.ptr(wimg_t), wimg_t.numel(), _lib.ptr(dfeat), _lib.ptr(dx),
-            ws.data_ptr(), ws.numel() * 4, N, seg, V)
+    args = (x, wimg, wimg.numel(), wimg_t, wimg_t.numel(), dfeat, dx, ws, ws.numel() * 4, N, seg, V)
     if tape:
-        rc = _L().agcn_sgn_frames_bwd_tape(*args, _lib.ptr(tp), tp.numel(), _lib.stream())
+        _lib.call("agcn_sgn_frames_bwd_tape", *args, tp, tp.numel())
     else:
-        rc = _L().agcn_sgn_frames_bwd(*args, _lib.stream())
-    _lib.check(rc, "agcn_" + name)
+        _lib.call("agcn_sgn_frames_bwd", *args)
     (SGN_WGRAD_STATS if tape else SGN_GRAD_STATS)[name[4:]] += 1
     return (dx, tp) if tape else dx
 
@@ -1974,9 +1873,7 @@ def sgn_sample_bwd(win, r, dout, seg):
     if tuple(dout.shape) != (N, S, seg, V * 3):
         raise ValueError(f"agcn_amd: sgn_sample_bwd takes dout ({N}, {S}, {seg}, {V * 3}), got {tuple(dout.shape)}")
     dwin = _empty(tuple(win.shape), win)
-    rc = _L().agcn_sgn_sample_bwd(_lib.ptr(win), _lib.ptr_bits(r), _lib.ptr(dout), _lib.ptr(dwin), N, T, V, K, S, seg,
-                                  _lib.stream())
-    _lib.check(rc, "agcn_sgn_sample_bwd")
+    _lib.call("agcn_sgn_sample_bwd", win, r, dout, dwin, N, T, V, K, S, seg)
     SGN_GRAD_STATS['sample_bwd'] += 1
     return dwin
 
@@ -2099,9 +1996,7 @@ def sgn_frames_wgrad(x, wimg, tape, V, num_class, rows_per_split=0):
         raise ValueError(f"agcn_amd: sgn_frames_wgrad: a tape of {tape.numel()} floats is not the tape of {tuple(x.shape)}")
     ws = _sgn_wgrad_ws(N, seg, V, num_class, rows_per_split, x)
     d_w = _empty((wimg.numel(),), x)
-    rc = _L().agcn_sgn_frames_wgrad(_lib.ptr(x), _lib.ptr(wimg), _lib.ptr(tape), _lib.ptr(d_w), ws.data_ptr(),
-                                    ws.numel() * 4, N, seg, V, rows_per_split, _lib.stream())
-    _lib.check(rc, "agcn_sgn_frames_wgrad")
+    _lib.call("agcn_sgn_frames_wgrad", x, wimg, tape, d_w, ws, ws.numel() * 4, N, seg, V, rows_per_split)
     SGN_WGRAD_STATS['frames_wgrad'] += 1
     return d_w
 
@@ -2114,9 +2009,7 @@ def sgn_clip_wgrad(tape, dfeat, dlogits, wimg, V, rows_per_split=0):
         raise ValueError(f"agcn_amd: sgn_clip_wgrad: a tape of {tape.numel()} floats is not the tape of {tuple(dfeat.shape)}")
     ws = _sgn_wgrad_ws(N, seg, V, nc, rows_per_split, dfeat)
     d_w = _empty((wimg.numel(),), dfeat)
-    rc = _L().agcn_sgn_clip_wgrad(_lib.ptr(tape), _lib.ptr(dfeat), _lib.ptr(dlogits), _lib.ptr(d_w), ws.data_ptr(),
-                                  ws.numel() * 4, N, seg, nc, rows_per_split, _lib.stream())
-    _lib.check(rc, "agcn_sgn_clip_wgrad")
+    _lib.call("agcn_sgn_clip_wgrad", tape, dfeat, dlogits, d_w, ws, ws.numel() * 4, N, seg, nc, rows_per_split)
     SGN_WGRAD_STATS['clip_wgrad'] += 1
     return d_w
 
@@ -2229,8 +2122,7 @@ def sgn_input_stats(x, V):
         raise ValueError(f"agcn_amd: sgn_input_stats takes (N, seg, {3 * V}), got {tuple(x.shape)}")
     N, seg, _ = x.shape
     part = _sgn_stats_part(SGN_STATS_INPUT, 0, N, seg, V, x)
-    rc = _L().agcn_sgn_input_stats(_lib.ptr(x), _lib.ptr(part), part.numel(), N, seg, V, _lib.stream())
-    _lib.check(rc, "agcn_sgn_input_stats")
+    _lib.call("agcn_sgn_input_stats", x, part, part.numel(), N, seg, V)
     SGN_BNSTATS_STATS['input_stats'] += 1
     return part.view(N, 2, 6 * V)
 
@@ -2242,9 +2134,7 @@ def sgn_frames_stats(x, wimg, layer, V):
         raise ValueError(f"agcn_amd: sgn_frames_stats takes (N, seg, {3 * V}), got {tuple(x.shape)}")
     N, seg, _ = x.shape
     part = _sgn_stats_part(SGN_STATS_FRAMES, layer, N, seg, V, x)
-    rc = _L().agcn_sgn_frames_stats(_lib.ptr(x), _lib.ptr(wimg), wimg.numel(), _lib.ptr(part), part.numel(), layer, N, seg,
-                                    V, _lib.stream())
-    _lib.check(rc, "agcn_sgn_frames_stats")
+    _lib.call("agcn_sgn_frames_stats", x, wimg, wimg.numel(), part, part.numel(), layer, N, seg, V)
     SGN_BNSTATS_STATS['frames_stats'] += 1
     return part.view(N * seg, 2, -1)
 
@@ -2256,9 +2146,7 @@ def sgn_clip_stats(feat, wimg, layer, num_class):
         raise ValueError(f"agcn_amd: sgn_clip_stats takes feat (N, seg, 256), got {tuple(feat.shape)}")
     N, seg, _ = feat.shape
     part = _sgn_stats_part(SGN_STATS_CLIP, layer, N, seg, 2, feat)
-    rc = _L().agcn_sgn_clip_stats(_lib.ptr(feat), _lib.ptr(wimg), wimg.numel(), _lib.ptr(part), part.numel(), layer, N, seg,
-                                  num_class, _lib.stream())
-    _lib.check(rc, "agcn_sgn_clip_stats")
+    _lib.call("agcn_sgn_clip_stats", feat, wimg, wimg.numel(), part, part.numel(), layer, N, seg, num_class)
     SGN_BNSTATS_STATS['clip_stats'] += 1
     return part.view(-1, 2, part.numel() // (2 * N * ((seg + 31) // 32)))
 
@@ -2275,10 +2163,8 @@ def sgn_stats_finalize(part, kind, layer, N, seg, V, carry=None, want_carry=Fals
     out = torch.empty((3, C), dtype=torch.float64, device=part.device) if want_carry else None
     nbytes = _L().agcn_sgn_stats_finalize_workspace(kind, layer, N, seg, V)
     ws = torch.empty((max(1, nbytes // 8),), dtype=torch.float64, device=part.device)
-    rc = _L().agcn_sgn_stats_finalize(_lib.ptr(part.view(-1)), part.numel(), kind, layer, N, seg, V,
-                                      None if carry is None else carry.data_ptr(), None if out is None else out.data_ptr(),
-                                      _lib.ptr(mean), _lib.ptr(var), ws.data_ptr(), nbytes, _lib.stream())
-    _lib.check(rc, "agcn_sgn_stats_finalize")
+    _lib.call("agcn_sgn_stats_finalize", part.view(-1), part.numel(), kind, layer, N, seg, V, carry, out, mean, var, ws,
+              nbytes)
     SGN_BNSTATS_STATS['stats_finalize'] += 1
     return mean, var, out
 

@@ -208,12 +208,9 @@ class TrainEngine:
     def apply_update(self):
         """Fused global-norm clip + SGD(momentum, nesterov, weight decay) over the flat buffers (``agcn_sgd_step``);
         the flat gradient holds the SUM over ranks, 1/world_size is applied inside."""
-        L = _lib.load()
-        _lib.check(L.agcn_sgd_step(self.fp.flat.data_ptr(), self.fp.grad.data_ptr(), self.fp.momentum.data_ptr(),
-                                   self.fp.total, float(self.lr), float(self.momentum), float(self.weight_decay),
-                                   int(self.nesterov), float(self.max_grad_norm), 1.0 / self.world_size,
-                                   int(self.steps_done == 0), self.ws.data_ptr(), self.ws.numel() * 4,
-                                   self.norm.data_ptr(), _lib.stream()), "agcn_sgd_step")
+        _lib.call("agcn_sgd_step", self.fp.flat, self.fp.grad, self.fp.momentum, self.fp.total, float(self.lr),
+                  float(self.momentum), float(self.weight_decay), int(self.nesterov), float(self.max_grad_norm),
+                  1.0 / self.world_size, int(self.steps_done == 0), self.ws, self.ws.numel() * 4, self.norm)
         self.steps_done += 1
         from . import ops as _ops
         _ops.note_params_changed()        # raw-pointer update: invalidates caches derived from the parameters
