@@ -1,0 +1,495 @@
+"""SGN v15, the attention SGN (reference model/architecture/sgn/sgn_v15.py): the base SGN's input side -- two DataNorm +
+1x1 embeddings of position and velocity, the one-hot joint and frame embeddings, maximum over joints, maximum over frames,
+fc -- with one pre-norm multi-head-attention block (reference model/layers/attention/crossattention.py::Transformer) over
+the joints of a frame in place of the three adaptive graph convolutions and the same block over the frames of a clip in
+place of the temporal CNN.  Constructor arguments, module tree and state_dict keys are the reference's, so a trained
+``sgn-*.pt`` loads as it is; the class constructs without a GPU and needs neither einops nor torchinfo.
+
+Two routes:
+
+* eval mode under ``no_grad`` on the GPU in the structure of the reference's experiment yaml (``_fusable``): two HIP
+  launches (csrc/sgn_v15.hip) on weight images with every BatchNorm folded -- ``ops.sgn15_frames`` (input side + the
+  spatial block + maximum over joints) and ``ops.sgn15_clip`` (+ tem_emb, the temporal block, maximum over frames, fc).
+  The images are cached under ``ops._cache_key`` and rebuilt after any parameter or running statistic changes; a batch
+  of more than ``ops.SGN15_MAX_CLIPS`` clips goes through in chunks of whole clips with the same bits.  With
+  ``fused_attention = True`` (a plain attribute, off by default, not in the state_dict) the kernels also store the
+  attention maps.
+* everything else (grad mode, ``train()``, a CPU tensor, any other supported configuration, ``AGCN_SGN_HIP=0``): the
+  tensor-code composition ``forward_tensor``, channels last, a complete ``nn.Module`` in every mode.  It is the
+  comparison of the fused path, NOT the hot path, and is counted in ``ops.SGN_STATS['forward_tensor']``.
+
+One block, with n_a, n_f the two per-channel BatchNorms: a = softmax_j((n_a(x) Wq)(n_a(x) Wk)^T d_head^-1/2) per head,
+x1 = concat_h(a . n_a(x) Wv) Wo + bo + res_a(x), y = relu(n_f(x1) W1 + b1) W2 + b2 + res_f(x1): both residuals take the
+un-normalised input, and a residual is a Linear where the widths differ (crossattention.py:297-304)."""
+import math
+from collections import OrderedDict
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from .. import ops
+
+_EMB_MODES = (0, 1)
+
+
+def _unsupported(what):
+    raise NotImplementedError(f"agcn_amd.sgn_v15: {what}")
+
+
+class DataNorm(nn.Module):
+    """BatchNorm1d over the C*V features of a frame, feature c*V + v (reference blocks/semantic.py:21-31), on
+    channels-last x (bs, step, V, C)."""
+
+    def __init__(self, dim):
+        super().__init__()
+        self.bn = nn.BatchNorm1d(dim)
+
+    def forward(self, x):
+        bs, step, V, C = x.shape
+        y = self.bn(x.permute(0, 3, 2, 1).reshape(bs, C * V, step))
+        return y.reshape(bs, C, V, step).permute(0, 3, 2, 1)
+
+
+class _Conv1x1(nn.Module):
+    """reference block.py::Conv1xN at kernel size 1: the Conv2d holds the parameters, applied as a linear map."""
+
+    def __init__(self, cin, cout, bias):
+        super().__init__()
+        self.conv = nn.Conv2d(cin, cout, kernel_size=(1, 1), bias=bool(bias))
+
+    def forward(self, x):
+        return F.linear(x, self.conv.weight.flatten(1), self.conv.bias)
+
+
+class Conv(nn.Module):
+    """reference block.py::Conv as Embedding builds it: conv + activation under ``block``."""
+
+    def __init__(self, cin, cout, bias):
+        super().__init__()
+        self.block = nn.Sequential(OrderedDict(conv=_Conv1x1(cin, cout, bias), act=nn.ReLU()))
+
+    def forward(self, x):
+        return self.block(x)
+
+
+class Embedding(nn.Module):
+    """Mode 1 of the reference's Embedding (blocks/semantic.py:34-125): [DataNorm,] two 1x1 convs with ReLU."""
+
+    def __init__(self, in_channels, out_channels, bias, num_point, in_norm):
+        super().__init__()
+        self.norm = DataNorm(in_channels * num_point) if in_norm else nn.Identity()
+        self.cnn1 = Conv(in_channels, out_channels, bias)
+        self.cnn2 = Conv(out_channels, out_channels, bias)
+
+    def forward(self, x):
+        return self.cnn2(self.cnn1(self.norm(x)))
+
+
+class FeatureExtractor(nn.Module):
+    def __init__(self, in_pos, in_vel, in_channels, out_channels, bias, num_point, fusion):
+        super().__init__()
+        self.fusion, self.in_pos, self.in_vel = fusion, in_pos, in_vel
+        if in_pos > 0:
+            self.pos_embed = Embedding(in_channels, out_channels, bias, num_point, True)
+        if in_vel > 0:
+            self.vel_embed = Embedding(in_channels, out_channels, bias, num_point, True)
+        if in_pos == 0 and in_vel == 0:
+            raise ValueError("Input args are faulty...")
+
+    def forward(self, x):
+        """x (bs, step, V, C); velocity is x[t] - x[t - 1] with a zero at t = 0."""
+        if self.in_vel > 0:
+            dif = torch.cat([x.new_zeros(x.shape[0], 1, *x.shape[2:]), x[:, 1:] - x[:, :-1]], dim=1)
+        if self.in_pos > 0 and self.in_vel > 0:
+            pos, vel = self.pos_embed(x), self.vel_embed(dif)
+            return torch.cat([pos, vel], dim=3) if self.fusion == 0 else pos + vel
+        return self.pos_embed(x) if self.in_pos > 0 else self.vel_embed(dif)
+
+
+class OneHotTensor(nn.Module):
+    """The reference's persistent one-hot buffer, in its shape: mode 0 (1, V, V, seg) one-hot over the joint, mode 1
+    (1, seg, V, seg) one-hot over the frame (blocks/semantic.py:128-146)."""
+
+    def __init__(self, dim_eye, dim_length, mode):
+        super().__init__()
+        eye = torch.eye(dim_eye)[None, None].repeat(1, dim_length, 1, 1)
+        self.register_buffer('onehot', (eye.permute(0, 3, 2, 1) if mode == 0 else eye.permute(0, 3, 1, 2)).contiguous())
+
+
+class SemanticEmbedding(nn.Module):
+    def __init__(self, num_point, num_segment, sem_spa, sem_tem, spa_out, tem_out, bias):
+        super().__init__()
+        self.sem_spa, self.sem_tem = sem_spa, sem_tem
+        if sem_spa > 0:
+            self.spa_onehot = OneHotTensor(num_point, num_segment, 0)
+            self.spa_embedding = Embedding(num_point, spa_out, bias, num_point, False)
+        if sem_tem > 0:
+            self.tem_onehot = OneHotTensor(num_segment, num_point, 1)
+            self.tem_embedding = Embedding(num_segment, tem_out, bias, num_point, False)
+
+    def spa(self):
+        """(V, C): the input-independent joint embedding, or None."""
+        return self.spa_embedding(self.spa_onehot.onehot[0, :, :, 0].t()) if self.sem_spa > 0 else None
+
+    def tem(self):
+        """(seg, C): the input-independent frame embedding, or None."""
+        return self.tem_embedding(self.tem_onehot.onehot[0, :, 0, :].t()) if self.sem_tem > 0 else None
+
+
+class Normalize(nn.Module):
+    """BatchNorm1d over the channels of (b, n, c) tokens (crossattention.py:37-43)."""
+
+    def __init__(self, fn):
+        super().__init__()
+        self.fn = fn
+
+    def forward(self, x):
+        return self.fn(x.transpose(1, 2)).transpose(1, 2)
+
+
+class PreNorm(nn.Module):
+    def __init__(self, dim, fn):
+        super().__init__()
+        self.norm = Normalize(nn.BatchNorm1d(dim))
+        self.fn = fn
+
+    def forward(self, x):
+        return self.fn(self.norm(x))
+
+
+def _residual(dim, output_dim, force=False):
+    return nn.Linear(dim, output_dim) if force or dim != output_dim else nn.Identity()
+
+
+class Attention(nn.Module):
+    def __init__(self, dim, heads, dim_head, dropout, res_proj, output_dim):
+        super().__init__()
+        inner = dim_head * heads
+        self.heads, self.dim_head, self.scale = heads, dim_head, dim_head ** -0.5
+        self.to_q = nn.Linear(dim, inner, bias=False)
+        self.to_k = nn.Linear(dim, inner, bias=False)
+        self.to_v = nn.Linear(dim, inner, bias=False)
+        self.to_out = nn.Sequential(OrderedDict(linear=nn.Linear(inner, output_dim), dropout=nn.Dropout(dropout)))
+        self.residual = _residual(dim, output_dim, res_proj)
+
+    def forward(self, x):
+        b, n, _ = x.shape
+        q, k, v = (t(x).reshape(b, n, self.heads, self.dim_head).transpose(1, 2) for t in (self.to_q, self.to_k, self.to_v))
+        attn = torch.softmax(q.matmul(k.transpose(-1, -2)) * self.scale, dim=-1)
+        out = attn.matmul(v).transpose(1, 2).reshape(b, n, self.heads * self.dim_head)
+        return self.to_out(out), attn
+
+
+class FeedForward(nn.Module):
+    def __init__(self, dim, hidden_dim, dropout, output_dim):
+        super().__init__()
+        output_dim = output_dim or dim
+        self.net = nn.Sequential(OrderedDict(linear1=nn.Linear(dim, hidden_dim), relu=nn.ReLU(), dropout1=nn.Dropout(dropout),
+                                             linear2=nn.Linear(hidden_dim, output_dim), dropout2=nn.Dropout(dropout)))
+        self.residual = _residual(dim, output_dim)
+
+    def forward(self, x):
+        return self.net(x)
+
+
+def _per_layer(v, depth, kind):
+    v = [v] * depth if isinstance(v, kind) else v
+    assert isinstance(v, list) and len(v) >= depth
+    return v
+
+
+class Transformer(nn.Module):
+    """The pre-norm BatchNorm / relu branch of crossattention.py::Transformer."""
+
+    def __init__(self, dim, depth, heads, dim_head, mlp_dim, dropout, mlp_out_dim, global_norm, d_out=None, res_proj=False):
+        super().__init__()
+        dim, heads, dim_head, mlp_dim, mlp_out_dim = (_per_layer(v, depth, int) for v in (dim, heads, dim_head, mlp_dim,
+                                                                                            mlp_out_dim))
+        dropout = _per_layer(float(dropout) if isinstance(dropout, (int, float)) else dropout, depth, float)
+        d_out = dim if d_out is None else _per_layer(d_out, depth, int)
+        self.layers = nn.ModuleDict()
+        for i in range(depth):
+            attn = Attention(dim[i], heads[i], dim_head[i], dropout[i], res_proj, d_out[i])
+            ffn = FeedForward(d_out[i], mlp_dim[i], dropout[i], mlp_out_dim[i])
+            self.layers[f'l{i + 1}'] = nn.ModuleDict(OrderedDict(attn=PreNorm(dim[i], attn), ffn=PreNorm(d_out[i], ffn)))
+        self.norm = Normalize(nn.BatchNorm1d(mlp_out_dim[-1] or dim[-1])) if global_norm else nn.Identity()
+
+    def forward(self, x):
+        attn_list = []
+        for layer in self.layers.values():
+            x1, attn = layer['attn'](x)
+            x = x1 + layer['attn'].fn.residual(x)
+            x = layer['ffn'](x) + layer['ffn'].fn.residual(x)
+            attn_list.append(attn)
+        return self.norm(x), attn_list
+
+
+class MHA(nn.Module):
+    def __init__(self, name, kwargs):
+        super().__init__()
+        kw = dict(kwargs or {})
+        if 'norm' not in kw:
+            _unsupported(f"{name} without 'norm' selects the reference's nn.TransformerEncoderLayer branch")
+        if kw.get('post_norm', False):
+            _unsupported(f"{name}: post_norm")
+        if 'bn' not in str(kw['norm']):
+            _unsupported(f"{name}: norm {kw['norm']!r} (only 'bn')")
+        if kw.get('activation', 'gelu') != 'relu':
+            _unsupported(f"{name}: activation {kw.get('activation', 'gelu')!r} (only 'relu')")
+        self.transformer = Transformer(dim=kw['d_model'], depth=kw['num_layers'], heads=kw['nhead'], dim_head=kw['d_head'],
+                                       mlp_dim=kw['dim_feedforward'], dropout=kw['dropout'],
+                                       mlp_out_dim=kw['dim_feedforward_output'], global_norm=kw['global_norm'],
+                                       d_out=kw.get('d_out'), res_proj=kw.get('res_proj', False))
+
+    def forward(self, x):
+        """x (bs, step, V, C) -> (y, [attn per layer]): tokens are the joints of a frame (spatial) or the frames of a clip
+        with the joints' channels side by side (temporal)."""
+        raise NotImplementedError
+
+
+class SpatialMHA(MHA):
+    def forward(self, x):
+        bs, step, V, C = x.shape
+        y, attn = self.transformer(x.reshape(bs * step, V, C))
+        return y.reshape(bs, step, V, -1), attn
+
+
+class TemporalMHA(MHA):
+    def forward(self, x):
+        bs, step, V, C = x.shape
+        y, attn = self.transformer(x.reshape(bs, step, V * C))
+        return y.reshape(bs, step, V, -1), attn
+
+
+def _cf(x):
+    """(bs, step, V, C) -> the reference's (bs, C, V, step), as a view."""
+    return x.permute(0, 3, 2, 1)
+
+
+def _t(w):
+    """Conv / linear weight (Cout, Cin, ...) -> the (Cin, Cout) row-major image the kernels read."""
+    return w.flatten(1).t()
+
+
+class SGN(nn.Module):
+    def __init__(self, num_class=60, num_point=25, num_segment=20, in_channels=3, bias=1, dropout=0.0, dropout2d=0.0,
+                 c_multiplier=1, norm_type='bn-pre', act_type='relu', input_position=1, input_velocity=1, semantic_joint=1,
+                 semantic_frame=1, semantic_class=0, input_emb_fusion=1, semantic_joint_fusion=0, semantic_frame_fusion=1,
+                 semantic_frame_location=0, spatial_maxpool=1, temporal_maxpool=1, spatial_mha_kwargs=None,
+                 temporal_mha_kwargs=None):
+        super().__init__()
+        for name, mode in (('input_position', input_position), ('input_velocity', input_velocity),
+                           ('semantic_joint', semantic_joint), ('semantic_frame', semantic_frame)):
+            if mode not in _EMB_MODES:
+                _unsupported(f"{name} = {mode}: only the embedding modes 0 and 1 are built")
+        if semantic_class != 0:
+            _unsupported(f"semantic_class = {semantic_class}")
+        if 'bn' not in str(norm_type):
+            _unsupported(f"norm_type {norm_type!r} (only 'bn')")
+        if act_type != 'relu':
+            _unsupported(f"act_type {act_type!r} (only 'relu')")
+        for name, v in (('spatial_maxpool', spatial_maxpool), ('temporal_maxpool', temporal_maxpool)):
+            if v not in (0, 1):
+                _unsupported(f"{name} = {v}")
+        for name, v in (('input_emb_fusion', input_emb_fusion), ('semantic_joint_fusion', semantic_joint_fusion)):
+            if v not in (0, 1):
+                raise ValueError(f"agcn_amd.sgn_v15: {name} must be 0 (concat) or 1 (sum)")
+        if input_position == 0 and semantic_joint > 0:
+            raise ValueError("input_position is 0 but semantic_joint is not")
+        assert semantic_frame_location in (0, 1)
+        if isinstance(c_multiplier, (int, float)):
+            c_multiplier = [c_multiplier] * 4
+        elif not isinstance(c_multiplier, list):
+            raise ValueError("Unknown c_multiplier type")
+        self.c1, self.c2, self.c3, self.c4 = (int(c * m) for c, m in zip((64, 128, 256, 512), c_multiplier))
+        self.num_class, self.num_point, self.num_segment, self.in_channels = num_class, num_point, num_segment, in_channels
+        self.bias = bias
+        self.input_position, self.input_velocity = input_position, input_velocity
+        self.semantic_joint, self.semantic_frame, self.semantic_class = semantic_joint, semantic_frame, semantic_class
+        self.input_emb_fusion, self.semantic_joint_fusion = input_emb_fusion, semantic_joint_fusion
+        self.semantic_frame_fusion, self.semantic_frame_location = semantic_frame_fusion, semantic_frame_location
+        self.spatial_maxpool, self.temporal_maxpool = spatial_maxpool, temporal_maxpool
+        self.fc_dropout = nn.Dropout(dropout)
+
+        self.feature_extractor = FeatureExtractor(input_position, input_velocity, in_channels, self.c1, bias, num_point,
+                                                  input_emb_fusion)
+        sem_out = self.c2 if input_emb_fusion == 0 else self.c1
+        self.semantic_embedding = SemanticEmbedding(num_point, num_segment, semantic_joint, semantic_frame, sem_out,
+                                                    self.c3, bias)
+        self.spatial_mha = SpatialMHA('spatial_mha_kwargs', spatial_mha_kwargs)
+        self.temporal_mha = TemporalMHA('temporal_mha_kwargs', temporal_mha_kwargs)
+        self._mha_args = tuple({k: kw.get(k) for k in ('d_model', 'nhead', 'd_head', 'dim_feedforward', 'num_layers',
+                                                       'dim_feedforward_output', 'global_norm', 'd_out', 'res_proj')}
+                               for kw in (spatial_mha_kwargs, temporal_mha_kwargs))
+
+        fc_in = self.c4                    # the reference's arithmetic (sgn_v15.py:234-238)
+        if spatial_maxpool == 0 and temporal_maxpool == 0:
+            fc_in = fc_in * num_segment * num_point
+        if temporal_maxpool == 0:
+            fc_in = fc_in * num_segment
+        self.fc = nn.Linear(fc_in, num_class)
+
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                n = m.kernel_size[0] * m.kernel_size[1] * m.out_channels
+                m.weight.data.normal_(0, math.sqrt(2. / n))
+        self._infer_cache = {}
+        self.fused_attention = False       # opt in: the fused route also stores and returns the attention maps
+
+    @property
+    def seg(self):
+        """The name the base SGN and the online recognisers use for ``num_segment``."""
+        return self.num_segment
+
+    # ---- tensor-code composition ----
+    def _forward_tensor(self, x):
+        """-> (logits, aux, feat): feat is the input of the temporal block (bs, step, V or 1, C)."""
+        bs, step, dim = x.shape
+        V = dim // self.in_channels
+        x = x.reshape(bs, step, V, self.in_channels)
+        h = self.feature_extractor(x)
+        spa, tem = self.semantic_embedding.spa(), self.semantic_embedding.tem()
+        if spa is not None:
+            spa_x = spa[None, None].expand(bs, step, V, spa.shape[1])
+            h = torch.cat([h, spa_x], dim=3) if self.semantic_joint_fusion == 0 else h + spa_x
+        if tem is not None and self.semantic_frame_location == 1:
+            h = h + tem[None, :, None, :]
+        spatial, spatial_attn = self.spatial_mha(h)
+        h = spatial
+        if tem is not None and self.semantic_frame_location == 0:
+            h = h + tem[None, :, None, :]
+        if self.spatial_maxpool == 1:                          # plain maxima: no ReLU in front
+            h = h.amax(2, keepdim=True)
+        feat = h
+        temporal, temporal_attn = self.temporal_mha(h)
+        y = temporal.amax((1, 2), keepdim=True) if self.temporal_maxpool == 1 else temporal
+        y = self.fc(self.fc_dropout(_cf(y).flatten(1)))
+        aux = dict(tem_emb=None if tem is None else tem.t()[None, :, None, :].expand(bs, tem.shape[1], V, step),
+                   spa_emb=None if spa is None else spa.t()[None, :, :, None].expand(bs, spa.shape[1], V, step),
+                   spatial_attn_list=spatial_attn, temporal_attn_list=temporal_attn,
+                   spatial_featuremap=_cf(spatial), temporal_featuremap=_cf(temporal))
+        return y, aux, feat
+
+    def forward_tensor(self, x):
+        logits, aux, _ = self._forward_tensor(x)
+        return logits, aux
+
+    # ---- folded weight images of the HIP path ----
+    def _structure_fused(self):
+        """The structure of the reference's experiment yaml at sizes inside the kernels' domain."""
+        s, t = self._mha_args
+        if not (self.input_position == self.input_velocity == self.semantic_joint == self.semantic_frame == 1
+                and self.input_emb_fusion == 1 and self.semantic_joint_fusion == 0 and self.semantic_frame_location == 0
+                and self.spatial_maxpool == self.temporal_maxpool == 1 and self.in_channels == 3
+                and (self.c1, self.c2, self.c3, self.c4) == (64, 128, 256, 512)):
+            return False
+        for a, din, dout in ((s, 128, 256), (t, 256, 512)):
+            one = lambda v: v[0] if isinstance(v, list) else v      # noqa: E731
+            if (a['num_layers'] != 1 or a['global_norm'] or a['res_proj'] or one(a['d_model']) != din
+                    or one(a['dim_feedforward_output']) != dout or (a['d_out'] is not None and one(a['d_out']) != din)):
+                return False
+        return True
+
+    def _geometry(self):
+        """((heads, d_head, ff) of the spatial block, of the temporal block)."""
+        out = []
+        for m in (self.spatial_mha, self.temporal_mha):
+            l1 = m.transformer.layers['l1']
+            out.append((l1['attn'].fn.heads, l1['attn'].fn.dim_head, l1['ffn'].fn.net.linear1.out_features))
+        return tuple(out)
+
+    @staticmethod
+    def _fold_block(layer):
+        """One block's sections in the order of csrc/sgn_v15_plan.h::Sgn15BlockW."""
+        a, f = layer['attn'], layer['ffn']
+        att, ffn = a.fn, f.fn
+        sa, sha = ops._fold((a.norm.fn.weight, a.norm.fn.bias, a.norm.fn.running_mean, a.norm.fn.running_var))
+        sf, shf = ops._fold((f.norm.fn.weight, f.norm.fn.bias, f.norm.fn.running_mean, f.norm.fn.running_var))
+        wqkv = torch.cat([att.to_q.weight.t() * att.scale, att.to_k.weight.t(), att.to_v.weight.t()], dim=1)   # (DIN, 3 inner)
+        w1 = ffn.net.linear1.weight.t()                                                                         # (DIN, ff)
+        return [wqkv * sa[:, None], sha @ wqkv,
+                att.to_out.linear.weight.t(), att.to_out.linear.bias,
+                w1 * sf[:, None], shf @ w1 + ffn.net.linear1.bias,
+                torch.cat([ffn.net.linear2.weight.t(), ffn.residual.weight.t()]), ffn.net.linear2.bias + ffn.residual.bias]
+
+    def _folded(self):
+        """The folded tensors in the order of the two weight images -> (frames list, clip list)."""
+        V, like = self.num_point, self.fc.weight
+        fe = self.feature_extractor
+
+        def emb(e):
+            a, b = e.cnn1.block.conv.conv, e.cnn2.block.conv.conv
+            bias = lambda c: c.bias if c.bias is not None else like.new_zeros(c.out_channels)      # noqa: E731
+            return [_t(a.weight), bias(a), _t(b.weight), bias(b)]
+
+        aff = []
+        for e in (fe.pos_embed, fe.vel_embed):              # BatchNorm feature c*V + v -> [v*3 + c]
+            bn = e.norm.bn
+            aff += [c.reshape(3, V).t() for c in ops._fold((bn.weight, bn.bias, bn.running_mean, bn.running_var))]
+        frames = (aff + emb(fe.pos_embed) + emb(fe.vel_embed) + [self.semantic_embedding.spa()]
+                  + self._fold_block(self.spatial_mha.transformer.layers['l1']))
+        clip = ([self.semantic_embedding.tem()] + self._fold_block(self.temporal_mha.transformer.layers['l1'])
+                + [self.fc.weight.t(), self.fc.bias])
+        return frames, clip
+
+    def _images(self):
+        """-> (frames image, clip image, spa table (V, 64), tem table (seg, 256)), cached."""
+        key = ops._cache_key(list(self.parameters()) + list(self.buffers()))
+        f = self._infer_cache.get('images')
+        if f is None or f[0] != key:
+            frames, clip = self._folded()
+            secs = {n: (o, s) for n, o, s in ops.sgn15_image_sections(self.num_point, self.num_segment, self.num_class,
+                                                                      *self._geometry())[0]}
+            wf = torch.cat([t.reshape(-1) for t in frames])
+            wc = torch.cat([t.reshape(-1) for t in clip])
+            o, s = secs['spa']
+            f = self._infer_cache['images'] = (key, wf, wc, wf[o:o + math.prod(s)].view(s),
+                                               wc[:self.num_segment * 256].view(self.num_segment, 256))
+        return f[1:]
+
+    def _fusable(self, x):
+        """What the eval-mode kernels take, whatever the grad mode."""
+        if self.training or not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()):
+            return False
+        if x.shape[1] != self.num_segment or x.shape[2] != 3 * self.num_point or x.shape[0] < 1:
+            return False
+        if not (ops.sgn_hip_enabled() and self._structure_fused()):
+            return False
+        sp, tp = self._geometry()
+        return (ops.sgn15_weights_floats(self.num_point, self.num_segment, self.num_class, sp, tp) is not None)
+
+    def forward(self, x):
+        if torch.is_grad_enabled() or not self._fusable(x):
+            ops.SGN_STATS['forward_tensor'] += 1
+            return self.forward_tensor(x)
+        wf, wc, spa, tem = self._images()
+        sp, tp = self._geometry()
+        N, seg, V = x.shape[0], self.num_segment, self.num_point
+        parts = []
+        for lo in range(0, N, ops.SGN15_MAX_CLIPS):        # one pair of launches unless the batch exceeds their limit
+            xs = x[lo:lo + ops.SGN15_MAX_CLIPS]
+            feat, sa = ops.sgn15_frames(xs, wf, V, *sp, want_attn=self.fused_attention)
+            parts.append((sa,) + ops.sgn15_clip(feat, wc, self.num_class, *tp, want_attn=self.fused_attention))
+        sa, logits, ta = parts[0] if len(parts) == 1 else (
+            None if p[0] is None else torch.cat(p) for p in zip(*parts))
+        aux = dict(tem_emb=tem.t()[None, :, None, :].expand(N, 256, V, seg),
+                   spa_emb=spa.t()[None, :, :, None].expand(N, 64, V, seg),
+                   spatial_attn_list=[sa] if self.fused_attention else None,
+                   temporal_attn_list=[ta] if self.fused_attention else None)
+        return logits, aux
+
+    def input_gradient(self, x, cot):
+        """-> (logits, aux, dx) with dx = d sum(logits * cot) / dx in eval mode, through the composition and torch
+        autograd (no HIP backward is built for v15; counted in ``ops.SGN_STATS['forward_tensor']``).  Needs no autograd
+        state and ignores the parameters' requires_grad."""
+        if self.training:
+            raise ValueError("agcn_amd: SGN.input_gradient is the eval-mode gradient; call eval() first")
+        ops.SGN_STATS['forward_tensor'] += 1
+        with torch.enable_grad():
+            xg = x.detach().requires_grad_(True)
+            logits, aux = self.forward_tensor(xg)
+            dx, = torch.autograd.grad((logits * cot.detach().to(logits)).sum(), xg)
+        aux = {k: ([a.detach() for a in v] if isinstance(v, list) else None if v is None else v.detach())
+               for k, v in aux.items()}
+        return logits.detach(), aux, dx

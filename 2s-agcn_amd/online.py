@@ -10,7 +10,8 @@ scores and the label, which is the only synchronisation.
 ``RecordingRecognition`` labels a whole recording and ``MultiStreamRecognition`` serves several streams: both normalise
 many windows in one launch (``ops.prenorm_windows``) and run them through the model as one batch.
 
-With ``sgn_preprocess=True`` the recognisers run the reference's deployed SGN (``model.sgn.SGN``) as its
+With ``sgn_preprocess=True`` the recognisers run the reference's deployed SGN (``model.sgn.SGN``, or the attention SGN
+``model.sgn_v15.SGN`` of its newer ``inference_221012.py``) as its
 ``inference.py:102-107, 148-150`` does: the normalised window goes through ``ops.sgn_sample`` (``NTUDataLoaders.to_fix_length``:
 ``multi_test`` random subsamples of ``model.seg`` rows), the model runs on the subsamples and their logits are averaged.
 

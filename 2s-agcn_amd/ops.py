@@ -2223,3 +2223,109 @@ def sgn_batch_statistics(x, fold, V, num_class, max_part_bytes=SGN_MAX_STATS_BYT
         known[name] = out[name] = run(SGN_STATS_CLIP, layer, feat, lambda fs: sgn_clip_stats(fs, wc, layer, num_class))
     _, wc = fold(known, None)
     return sgn_clip(feat, wc, num_class), g, out
+
+
+# ------------------------------------------------------------------------------------------------
+# SGN v15, the attention SGN: eval-mode inference (csrc/sgn_v15.hip; layouts in csrc/sgn_v15_plan.h)
+# ------------------------------------------------------------------------------------------------
+# diagnostic counters of the two launches (a dict of its own: SGN_STATS is compared whole by its tests)
+SGN15_STATS = dict(frames_hip=0, clip_hip=0)
+# clips per pair of launches: a larger batch goes through in chunks of whole clips (model/sgn_v15.py), with the same bits
+# (a clip's result does not depend on its batch).  At seg <= 32 this stays inside the entries' limits (about 2M frames
+# for agcn_sgn15_frames, 524 287 clips for agcn_sgn15_clip: csrc/sgn_v15_plan.h).
+SGN15_MAX_CLIPS = 1 << 15
+
+
+def sgn15_weights_floats(V, seg, num_class, spatial, temporal):
+    """(floats of the frames image, of the clip image) for the blocks ``spatial`` / ``temporal`` = (heads, d_head, ff),
+    or None outside the kernels' domain (csrc/sgn_v15_plan.h)."""
+    nf = _L().agcn_sgn15_frames_weights(V, *spatial)
+    nc = _L().agcn_sgn15_clip_weights(seg, num_class, *temporal)
+    return (nf, nc) if nf and nc else None
+
+
+def sgn15_image_sections(V, seg, num_class, spatial, temporal):
+    """The sections of the two folded weight images of SGN v15 in their order (csrc/sgn_v15_plan.h) -> (frames, clip),
+    each a list of (name, offset, shape).  ``spatial`` / ``temporal``: (heads, d_head, ff) of the two blocks.  A block
+    (din -> dout) is qkv_w (din, 3 inner) = [Wq d_head^-1/2 | Wk | Wv] with the attention BatchNorm folded, qkv_b, o_w
+    (inner, din), o_b, f1_w (din, ff) with the feed-forward BatchNorm folded, f1_b, f2_w = [W2 ; Wr] (ff + din, dout),
+    f2_b = b2 + br."""
+    def lay(items):
+        out, o = [], 0
+        for name, shape in items:
+            out.append((name, o, shape))
+            o += math.prod(shape)
+        return out
+
+    def block(p, din, dout, heads, d_head, ff):
+        inner = heads * d_head
+        return [(p + 'qkv_w', (din, 3 * inner)), (p + 'qkv_b', (3 * inner,)), (p + 'o_w', (inner, din)), (p + 'o_b', (din,)),
+                (p + 'f1_w', (din, ff)), (p + 'f1_b', (ff,)), (p + 'f2_w', (ff + din, dout)), (p + 'f2_b', (dout,))]
+
+    emb = lambda p: [(p + '1_w', (3, 64)), (p + '1_b', (64,)), (p + '2_w', (64, 64)), (p + '2_b', (64,))]  # noqa: E731
+    frames = lay([('aff', (4, V, 3))] + emb('pe') + emb('ve') + [('spa', (V, 64))] + block('s_', 128, 256, *spatial))
+    clip = lay([('tem', (seg, 256))] + block('t_', 256, 512, *temporal) + [('fc_w', (512, num_class)), ('fc_b', (num_class,))])
+    return frames, clip
+
+
+def sgn15_frames(x, wimg, V, heads, d_head, ff, want_attn=False):
+    """The joint-level module of SGN v15 on x (N, seg, V*3) with the folded frames image -> (feat (N, seg, 256), the
+    maximum over the joints of the spatial block's output WITHOUT tem_emb (``sgn15_clip`` adds it), attn (N*seg, heads,
+    V, V) or None)."""
+    if x.dim() != 3 or x.shape[2] != 3 * V:
+        raise ValueError(f"agcn_amd: sgn15_frames takes (N, seg, {3 * V}), got {tuple(x.shape)}")
+    N, seg, _ = x.shape
+    feat = _empty((N, seg, 256), x)
+    attn = _empty((N * seg, heads, V, V), x) if want_attn else None
+    _lib.call("agcn_sgn15_frames", x, wimg, wimg.numel(), feat, attn, N, seg, V, heads, d_head, ff)
+    SGN15_STATS['frames_hip'] += 1
+    return feat, attn
+
+
+def sgn15_clip(feat, wimg, num_class, heads, d_head, ff, want_attn=False):
+    """The frame-level module and the classifier of SGN v15 on feat (N, seg, 256) -> (logits (N, num_class), attn (N,
+    heads, seg, seg) or None)."""
+    if feat.dim() != 3 or feat.shape[2] != 256:
+        raise ValueError(f"agcn_amd: sgn15_clip takes (N, seg, 256), got {tuple(feat.shape)}")
+    N, seg, _ = feat.shape
+    logits = _empty((N, num_class), feat)
+    attn = _empty((N, heads, seg, seg), feat) if want_attn else None
+    _lib.call("agcn_sgn15_clip", feat, wimg, wimg.numel(), logits, attn, N, seg, num_class, heads, d_head, ff)
+    SGN15_STATS['clip_hip'] += 1
+    return logits, attn
+
+
+def sgn15_forward_ref(x, wf, wc, V, seg, num_class, spatial, temporal):
+    """The tensor-code form of the fused SGN v15 forward, reading ONLY the two flat folded images: the CPU-checkable
+    specification of the fold and the layout.  x (N, seg, V*3) -> (logits, feat (N, seg, 256) as ``sgn15_frames`` returns
+    it, spatial attn (N*seg, heads, V, V), temporal attn (N, heads, seg, seg))."""
+    if x.dim() != 3 or x.shape[1] != seg or x.shape[2] != 3 * V:
+        raise ValueError(f"agcn_amd: sgn15_forward_ref takes (N, {seg}, {3 * V}), got {tuple(x.shape)}")
+    fs, cs = sgn15_image_sections(V, seg, num_class, spatial, temporal)
+    if wf.numel() != fs[-1][1] + math.prod(fs[-1][2]) or wc.numel() != cs[-1][1] + math.prod(cs[-1][2]):
+        raise ValueError("agcn_amd: sgn15_forward_ref: the images do not have the sizes of csrc/sgn_v15_plan.h")
+    f = {n: wf[o:o + math.prod(s)].reshape(s) for n, o, s in fs}
+    c = {n: wc[o:o + math.prod(s)].reshape(s) for n, o, s in cs}
+    relu = torch.relu
+    N = x.shape[0]
+    xr = x.reshape(N, seg, V, 3)
+    dif = torch.cat([xr.new_zeros(N, 1, V, 3), xr[:, 1:] - xr[:, :-1]], dim=1)
+
+    def emb(v, p):
+        return relu(relu(v @ f[p + '1_w'] + f[p + '1_b']) @ f[p + '2_w'] + f[p + '2_b'])
+
+    def block(t, w, p, heads, d_head):
+        """t (B, R, din)"""
+        B, R, _ = t.shape
+        q, k, v = ((t @ w[p + 'qkv_w'] + w[p + 'qkv_b']).reshape(B, R, 3, heads, d_head).permute(2, 0, 3, 1, 4))
+        a = torch.softmax(q @ k.transpose(-1, -2), dim=-1)                       # d_head^-1/2 is folded into q
+        t1 = (a @ v).transpose(1, 2).reshape(B, R, heads * d_head) @ w[p + 'o_w'] + w[p + 'o_b'] + t
+        hid = relu(t1 @ w[p + 'f1_w'] + w[p + 'f1_b'])
+        return torch.cat([hid, t1], dim=2) @ w[p + 'f2_w'] + w[p + 'f2_b'], a
+
+    h = torch.cat([emb(xr * f['aff'][0] + f['aff'][1], 'pe') + emb(dif * f['aff'][2] + f['aff'][3], 've'),
+                   f['spa'].expand(N, seg, V, 64)], dim=3)
+    y, sa = block(h.reshape(N * seg, V, 128), f, 's_', spatial[0], spatial[1])
+    feat = y.reshape(N, seg, V, 256).amax(2)
+    z, ta = block(feat + c['tem'], c, 't_', temporal[0], temporal[1])
+    return z.amax(1) @ c['fc_w'] + c['fc_b'], feat, sa, ta

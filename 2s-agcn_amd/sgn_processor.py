@@ -1,4 +1,5 @@
-"""``SGNProcessor``: training and evaluating ``model.sgn.SGN`` through ``main.py`` (``use_sgn_dataloader: true``), the
+"""``SGNProcessor``: training and evaluating ``model.sgn.SGN`` or ``model.sgn_v15.SGN`` through ``main.py``
+(``use_sgn_dataloader: true``), the
 counterpart of the reference's SGN route (utils/processor.py: load_data :479-520 with ``FeederDataLoader``, the Adam
 branch of load_optimizer, ``LabelSmoothingLoss``, train :604-778 with clip_grad_norm_ 1.0 at :698, eval :784-914 with the
 mean over ``multi_test`` draws).
@@ -17,6 +18,7 @@ import torch
 
 from .feeders.sgn import SGNBatches
 from .model.sgn import SGN
+from .model.sgn_v15 import SGN as SGN15
 from .processor import Processor, import_class
 from .trainer import learning_rate
 
@@ -45,8 +47,9 @@ class SGNProcessor(Processor):
         np.random.seed(arg.seed)
         os.makedirs(os.path.join(arg.work_dir, 'weight'), exist_ok=True)
         self.global_step = 0
-        if import_class(arg.model) is not SGN:
-            raise ValueError(f"agcn_amd.SGNProcessor: use_sgn_dataloader trains model.sgn.SGN only, got {arg.model!r}")
+        if import_class(arg.model) not in (SGN, SGN15):
+            raise ValueError("agcn_amd.SGNProcessor: use_sgn_dataloader trains model.sgn.SGN or model.sgn_v15.SGN only, got "
+                             f"{arg.model!r}")
         self.load_model()
         self.load_data()
         self.load_optimizer()

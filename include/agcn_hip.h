@@ -642,6 +642,31 @@ int agcn_sgn_stats_finalize(const float* part, size_t part_floats, int kind, int
                             const double* carry_in, double* carry_out, float* mean, float* var, void* ws, size_t ws_bytes,
                             void* stream);
 
+/* ---- SGN v15, the attention SGN: eval-mode inference (csrc/sgn_v15.hip; the block: csrc/sgn_v15_device.h; geometry and
+ * weight-image layouts: csrc/sgn_v15_plan.h) ----
+ * reference model/architecture/sgn/sgn_v15.py in the structure of config/nturgbd-cross-view/train_sgn_v15.yaml: the base
+ * SGN's input side, one pre-norm multi-head-attention block (model/layers/attention/crossattention.py::Transformer, one
+ * layer, BatchNorm, relu) 128 -> 256 over the joints of a frame, and the same block 256 -> 512 over the frames of a clip.
+ * heads, d_head, ff describe the block of the entry they are passed to.  Arithmetic rules as for the base SGN: exact-f32
+ * MFMA in every AGCN_GEMM mode, fixed summation orders, no atomics; a clip's result does not depend on its batch.
+ * Domain: N * seg <= 2097151 frames (sgn15_frames, as sgn_frames), N <= 524287 clips (sgn15_clip), 2 <= V <= 32,
+ *   1 <= seg <= 32 (sgn15_clip; one row tile), heads * d_head and ff multiples of 128 up to 1024,
+ *   d_head 16, 32, 64 or a multiple of 128.
+ * sgn15_frames_weights / sgn15_clip_weights: floats of the folded weight images (0 outside the domain), built by the
+ *   caller (model/sgn_v15.py::SGN._images) in the order of sgn_v15_plan.h.
+ * sgn15_frames: x (N, seg, V*3) -> feat (N, seg, 256), the maximum over the real joints of the block's output (no ReLU
+ *   in front: it may be negative); tem_emb is added by sgn15_clip, which gives the reference's bits (max_v(y + tem) =
+ *   max_v(y) + tem).  attn (N*seg, heads, V, V) is stored unless NULL.
+ * sgn15_clip: feat (N, seg, 256) -> logits (N, num_class): + tem_emb, the block, the maximum over the real frames, fc.
+ *   attn (N, heads, seg, seg) is stored unless NULL.
+ * AGCN_ERR_ARG: a null x / feat / w / logits, sizes outside the domain, w_floats different from the size query. */
+size_t agcn_sgn15_frames_weights(int V, int heads, int d_head, int ff);
+size_t agcn_sgn15_clip_weights(int seg, int num_class, int heads, int d_head, int ff);
+int agcn_sgn15_frames(const float* x, const float* w, size_t w_floats, float* feat, float* attn, int N, int seg, int V,
+                      int heads, int d_head, int ff, void* stream);
+int agcn_sgn15_clip(const float* feat, const float* w, size_t w_floats, float* logits, float* attn, int N, int seg,
+                    int num_class, int heads, int d_head, int ff, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
