@@ -19,6 +19,8 @@ CASES = {
     'j25_yaml': (25, 20, 3, 1, (1, 512, 512), (1, 1024, 1024)),
     'j32_seg32': (32, 32, 1, 1, (4, 32, 256), (2, 64, 384)),
     'j7_seg12_nobias': (7, 12, 4, 0, (8, 16, 128), (8, 32, 256)),
+    'j9_seg7_h2x256': (9, 7, 2, 1, (2, 256, 128), (2, 256, 384)),            # two sliced heads per block
+    'j16_seg17_h16x16': (16, 17, 2, 1, (16, 16, 256), (8, 16, 384)),         # two groups of 16-wide heads; 16-wide heads in the clip block
 }
 TENSORS = ('logits', 'spatial_attn', 'temporal_attn', 'spa_emb', 'tem_emb', 'feat', 'pooled')
 

@@ -78,7 +78,7 @@ def test_fused_eval_matches_reference(case):
     assert all(v < 1e-4 for v in errs.values()), errs
 
 
-@pytest.mark.parametrize('case', ['j3_seg2', 'j15_deployed', 'j25_yaml'])
+@pytest.mark.parametrize('case', ['j3_seg2', 'j15_deployed', 'j25_yaml', 'j9_seg7_h2x256', 'j16_seg17_h16x16'])
 def test_attention_flag_and_batch_do_not_change_the_bits(case):
     c, m = _model(case)
     x = torch.from_numpy(c['x']).to(DEV)
