@@ -1,10 +1,12 @@
 // The attention block of SGN v15, written once as a device function template over (input width, output width): the
 // joint-level kernel calls it at 128 -> 256 over the joints of a frame, the frame-level kernel at 256 -> 512 over the
 // frames of a clip (sgn_v15.hip).  Geometry, walks and the LDS carve: sgn_v15_plan.h; the MFMA helpers: sgn_device.h.
+// Behind it its backward, sgn15_block_bwd (sgn_v15_bwd.hip; formulas and carve: sgn_v15_bwd_plan.h).
 // Everything is exact-f32 MFMA with a fixed summation order; no atomics.
 #pragma once
 #include "sgn_device.h"
 #include "sgn_v15_plan.h"
+#include "sgn_v15_bwd_plan.h"
 
 // mma_w with the column step between a wave's blocks as a parameter: block i of the wave sits cstep columns after
 // block i - 1 (the q, k and v sections of one group are `inner` columns apart in [Wq | Wk | Wv]).  As there, 16 weight
@@ -75,10 +77,12 @@ __device__ __forceinline__ void sgn15_qkv(const float* X, const float* __restric
 // index carried into the store the compiler put a full vmcnt(0) wait behind every batch of weight loads of the product
 // loops (measured: 1.76 instead of 1.21 ms for one window with 1 x 1024 heads).
 // Barriers inside; the caller puts one in front (X complete) and needs none behind for m.
+// sgn15_block_y is the block up to the accumulators of y (without b2 + br), which the backward takes the arg-max rows
+// from; it leaves x1 in X and a barrier behind the last read of QKV and P.  sgn15_block adds the maximum.
 template <int DIN, int DOUT>
-__device__ __forceinline__ void sgn15_block(float* X, float* QKV, float* P, const float* __restrict__ w,
-                                            const Sgn15BlockW& o, int rows, int heads, int d_head, int ff,
-                                            float* __restrict__ attn, float (&m)[DOUT / SGN15_GROUP]) {
+__device__ __forceinline__ void sgn15_block_y(float* X, float* QKV, float* P, const float* __restrict__ w,
+                                              const Sgn15BlockW& o, int rows, int heads, int d_head, int ff,
+                                              float* __restrict__ attn, f32x16 (&accY)[DOUT / SGN15_GROUP]) {
   constexpr int XS = SGN15_X_STRIDE(DIN), QS = SGN15_QKV_STRIDE, NBO = DIN / SGN15_GROUP, NBY = DOUT / SGN15_GROUP;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
   const int inner = heads * d_head, groups = sgn15_groups(heads, d_head);
@@ -172,7 +176,8 @@ __device__ __forceinline__ void sgn15_block(float* X, float* QKV, float* P, cons
   __syncthreads();
 
   // y = [relu(x1 W1 + b1) | x1] . [W2 ; Wr] + (b2 + br): the hidden tile in chunks of 128 columns, ascending, then x1
-  f32x16 accY[NBY] = {};
+#pragma unroll
+  for (int i = 0; i < NBY; ++i) accY[i] = f32x16{};
   for (int c = 0; c < sgn15_chunks(ff); ++c) {
     const int col = sgn15_chunk_col(c) + wave * 32 + r;
     f32x16 hid[1] = {};
@@ -185,6 +190,16 @@ __device__ __forceinline__ void sgn15_block(float* X, float* QKV, float* P, cons
     __syncthreads();
   }
   mma_w<NBY>(X + r * XS + h, w + o.f2_w + (long)(ff + h) * DOUT + wave * 32 + r, DOUT, DIN, accY);
+}
+
+template <int DIN, int DOUT>
+__device__ __forceinline__ void sgn15_block(float* X, float* QKV, float* P, const float* __restrict__ w,
+                                            const Sgn15BlockW& o, int rows, int heads, int d_head, int ff,
+                                            float* __restrict__ attn, float (&m)[DOUT / SGN15_GROUP]) {
+  constexpr int NBY = DOUT / SGN15_GROUP;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+  f32x16 accY[NBY];
+  sgn15_block_y<DIN, DOUT>(X, QKV, P, w, o, rows, heads, d_head, ff, attn, accY);
 #pragma unroll
   for (int i = 0; i < NBY; ++i) {
     const float bv = w[o.f2_b + (wave + SGN_WAVES * i) * 32 + r];
@@ -193,5 +208,252 @@ __device__ __forceinline__ void sgn15_block(float* X, float* QKV, float* P, cons
     for (int j = 0; j < 16; ++j)
       if (mfma_row(j, h) < rows) v = fmaxf(v, accY[i][j] + bv);
     m[i] = fmaxf(v, __shfl_xor(v, 32));
+  }
+}
+
+// ---- the backward of the block (sgn_v15_bwd_plan.h: the formulas, the carve, where it can go wrong) ----
+
+// The arg-max row of acc + bv over the rows < nrows of the lane's column, in both lanes of the column.  Unlike col_argmax
+// it starts from -inf: there is no ReLU in front of v15's maxima, so a maximum may be negative and always has a row.
+// Rows ascend with j and a strict > keeps the lowest index; the merge of the two half-waves keeps the lower row at a tie.
+__device__ __forceinline__ int sgn15_col_argmax(const f32x16& acc, float bv, int nrows) {
+  const int h = (threadIdx.x & 63) >> 5;
+  float best = -INFINITY;
+  int arg = -1;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const int row = mfma_row(j, h);
+    const float v = acc[j] + bv;
+    if (row < nrows && (arg < 0 || v > best)) {
+      best = v;
+      arg = row;
+    }
+  }
+  const float ob = __shfl_xor(best, 32);
+  const int oa = __shfl_xor(arg, 32);
+  if (oa >= 0 && (arg < 0 || ob > best || (ob == best && oa < arg))) arg = oa;
+  return arg;
+}
+
+// an accumulator tile -> 32 columns of an LDS band from column `col` on
+__device__ __forceinline__ void sgn15_store_tile(const f32x16& a, float* band, int stride, int col) {
+  const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) band[mfma_row(j, h) * stride + col + r] = a[j];
+}
+// ... -> the wave's own 32-column block of a 128-column band
+__device__ __forceinline__ void sgn15_store_block(const f32x16& a, float* band, int stride) {
+  sgn15_store_tile(a, band, stride, (threadIdx.x >> 6) * 32);
+}
+
+// dS = P * (dP - rowsum(dP * P)) of one head, dP in the accumulator layout, P in its slot -> dS in registers.  The row sum
+// runs over the 32 lanes of the half-wave that holds the row; P is zero in padded rows and columns, and so is dS.
+__device__ __forceinline__ f32x16 sgn15_softmax_bwd(const f32x16& dp, const float* Pslot) {
+  const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+  f32x16 ds;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const float p = Pslot[mfma_row(j, h) * SGN15_P_STRIDE + r];
+    const float rs = half_sum(dp[j] * p);
+    ds[j] = p * (dp[j] - rs);
+  }
+  return ds;
+}
+
+// X holds the `rows` real token rows x (as for sgn15_block, one barrier in front).  d[i]: the gradient of the pooled
+// column (wave + SGN_WAVES * i) * 32 + r, which goes to the column's arg-max row.  reload(): writes x into X again (the
+// forward leaves x1 there).  -> dX[i]: d x of the column blocks wave + SGN_WAVES * i, all 32 rows (padded rows: zero).
+// w / o the forward image, wt / ot the transposed one.  Barriers inside, the last one behind every read of LDS.
+template <int DIN, int DOUT, class Reload>
+__device__ __forceinline__ void sgn15_block_bwd(float* X, float* QKV, float* DO, float* P, const float* __restrict__ w,
+                                                const Sgn15BlockW& o, const float* __restrict__ wt, const Sgn15BlockWT& ot,
+                                                int rows, int heads, int d_head, int ff,
+                                                const float (&d)[DOUT / SGN15_GROUP], Reload reload,
+                                                f32x16 (&dX)[DIN / SGN15_GROUP]) {
+  constexpr int XS = SGN15_X_STRIDE(DIN), QS = SGN15_QKV_STRIDE, DS = SGN15_BWD_DO_STRIDE, PS = SGN15_P_STRIDE;
+  constexpr int DYS = SGN15_BWD_DY_STRIDE(DOUT), NBO = DIN / SGN15_GROUP, NBY = DOUT / SGN15_GROUP;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+  const int inner = heads * d_head, groups = sgn15_groups(heads, d_head);
+  const int Kp = (rows + 1) & ~1;
+  float* Q = QKV;
+  float* Kk = QKV + SGN15_GROUP;
+  float* Vv = QKV + 2 * SGN15_GROUP;
+  float* DY = QKV;                                 // (32, DOUT + 1) over QKV and DO
+  float* DH = P;                                   // (32, 129)
+
+  // ---- the forward and the arg-max row of every column; dy dense, one non-zero per column ----
+  {
+    f32x16 accY[NBY];
+    sgn15_block_y<DIN, DOUT>(X, QKV, P, w, o, rows, heads, d_head, ff, nullptr, accY);
+#pragma unroll
+    for (int i = 0; i < NBY; ++i) {
+      const int col = (wave + SGN_WAVES * i) * 32 + r;
+      const int arg = sgn15_col_argmax(accY[i], w[o.f2_b + col], rows);
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const int row = mfma_row(j, h);
+        DY[row * DYS + col] = row == arg ? d[i] : 0.f;
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- the feed-forward: dx1 = dy Wr^T + sum_c (dy W2_c^T * [hidden_c > 0]) W1_c^T, in registers ----
+  const int ldf2 = ff + DIN;
+  f32x16 dx1[NBO] = {};
+  mma_w<NBO>(DY + r * DYS + h, wt + ot.f2 + (long)h * ldf2 + ff + wave * 32 + r, ldf2, DOUT, dx1);
+  for (int c = 0; c < sgn15_chunks(ff); ++c) {
+    const int col = sgn15_chunk_col(c) + wave * 32 + r;
+    f32x16 hid[1] = {};
+    mma_ws<1>(X + r * XS + h, w + o.f1_w + (long)h * ff + col, ff, 0, DIN, hid);      // the forward's sequence
+    f32x16 dh[1] = {};
+    mma_w<1>(DY + r * DYS + h, wt + ot.f2 + (long)h * ldf2 + col, ldf2, DOUT, dh);
+    const float bv = w[o.f1_b + col];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) DH[mfma_row(j, h) * DS + wave * 32 + r] = hid[0][j] + bv > 0.f ? dh[0][j] : 0.f;
+    __syncthreads();
+    mma_w<NBO>(DH + r * DS + h, wt + ot.f1 + (long)(sgn15_chunk_col(c) + h) * DIN + wave * 32 + r, DIN, SGN15_GROUP, dx1);
+    __syncthreads();
+  }
+  reload();
+#pragma unroll
+  for (int i = 0; i < NBO; ++i) dX[i] = dx1[i];    // the attention residual
+  __syncthreads();
+
+  // do = dx1 Wo_g^T into DO: each 128-column half of dx1 is staged through DO from the registers that hold it
+  auto make_do = [&](int g) {
+    f32x16 a[1] = {};
+#pragma unroll
+    for (int i = 0; i < NBO; ++i) {
+      sgn15_store_block(dx1[i], DO, DS);
+      __syncthreads();
+      mma_w<1>(DO + r * DS + h, wt + ot.o + (long)(i * SGN15_GROUP + h) * inner + sgn15_group_col(g) + wave * 32 + r, inner,
+               SGN15_GROUP, a);
+      __syncthreads();
+    }
+    sgn15_store_block(a[0], DO, DS);
+    __syncthreads();
+  };
+  // [dq | dk | dv] of group g over [q | k | v], then dX += [dq | dk | dv] (Wqkv_g)^T; a barrier in front and behind
+  auto finish = [&](int g, const f32x16& dq, const f32x16& dk, const f32x16& dv) {
+    __syncthreads();
+    sgn15_store_block(dq, Q, QS);
+    sgn15_store_block(dk, Kk, QS);
+    sgn15_store_block(dv, Vv, QS);
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < 3; ++s)
+      mma_w<NBO>(QKV + s * SGN15_GROUP + r * QS + h,
+                 wt + ot.qkv + ((long)s * inner + sgn15_group_col(g) + h) * DIN + wave * 32 + r, DIN, SGN15_GROUP, dX);
+    __syncthreads();
+  };
+
+  if (!sgn15_sliced(d_head)) {
+    const int hg = sgn15_group_heads(d_head);
+    const int lh0 = wave * 32 / d_head;            // the (first) head of the wave's 32-column block
+    const bool pair = d_head == SGN15_MIN_HEAD;
+    for (int g = 0; g < groups; ++g) {
+      sgn15_qkv<DIN, 3>(X, w, o, inner, g, 0, QKV);
+      make_do(g);
+      for (int lh = wave; lh < hg; lh += SGN_WAVES) {
+        const f32x16 s = mma_l(Q + lh * d_head, QS, 1, Kk + lh * d_head, 1, QS, d_head, f32x16{});
+        sgn15_softmax_store(s, rows, P + lh * SGN15_P_SLOT, nullptr);
+      }
+      __syncthreads();
+      // dv = P^T do of the wave's block; dP = do_h v_h^T and dS of the wave's heads
+      f32x16 dv = mma_l(P + lh0 * SGN15_P_SLOT, 1, PS, DO + wave * 32, DS, 1, Kp, f32x16{});
+      if (pair) {
+        const f32x16 dv1 = mma_l(P + (lh0 + 1) * SGN15_P_SLOT, 1, PS, DO + wave * 32, DS, 1, Kp, f32x16{});
+        if (r >= 16) dv = dv1;
+      }
+      f32x16 ds[2];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int lh = wave + SGN_WAVES * u;
+        if (lh < hg) {
+          const f32x16 dp = mma_l(DO + lh * d_head, DS, 1, Vv + lh * d_head, 1, QS, d_head, f32x16{});
+          ds[u] = sgn15_softmax_bwd(dp, P + lh * SGN15_P_SLOT);
+        }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int lh = wave + SGN_WAVES * u;
+        if (lh < hg) {
+#pragma unroll
+          for (int j = 0; j < 16; ++j) P[lh * SGN15_P_SLOT + mfma_row(j, h) * PS + r] = ds[u][j];
+        }
+      }
+      __syncthreads();
+      // dq = dS k, dk = dS^T q of the wave's block
+      f32x16 dq = mma_l(P + lh0 * SGN15_P_SLOT, PS, 1, Kk + wave * 32, QS, 1, Kp, f32x16{});
+      f32x16 dk = mma_l(P + lh0 * SGN15_P_SLOT, 1, PS, Q + wave * 32, QS, 1, Kp, f32x16{});
+      if (pair) {
+        const f32x16 dq1 = mma_l(P + (lh0 + 1) * SGN15_P_SLOT, PS, 1, Kk + wave * 32, QS, 1, Kp, f32x16{});
+        const f32x16 dk1 = mma_l(P + (lh0 + 1) * SGN15_P_SLOT, 1, PS, Q + wave * 32, QS, 1, Kp, f32x16{});
+        if (r >= 16) {
+          dq = dq1;
+          dk = dk1;
+        }
+      }
+      finish(g, dq, dk, dv);
+    }
+  } else {
+    const int hs = sgn15_head_groups(d_head);
+    float* dS = P + SGN15_BWD_DS_SLOT * SGN15_P_SLOT;
+    for (int head = 0; head < heads; ++head) {
+      // pass 1: the scores and P, the forward's sequence
+      f32x16 s = {};
+      for (int sl = 0; sl < hs; ++sl) {
+        sgn15_qkv<DIN, 2>(X, w, o, inner, head * hs + sl, 0, QKV);
+        __syncthreads();
+        s = mma_l(Q + wave * 32, QS, 1, Kk + wave * 32, 1, QS, 32, s);
+        __syncthreads();
+      }
+      sgn15_store_tile(s, P + (1 + wave) * SGN15_P_SLOT, PS, 0);
+      __syncthreads();
+      if (wave == 0) {
+        f32x16 t;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          const int e = mfma_row(j, h) * PS + r;
+          t[j] = ((P[SGN15_P_SLOT + e] + P[2 * SGN15_P_SLOT + e]) + P[3 * SGN15_P_SLOT + e]) + P[4 * SGN15_P_SLOT + e];
+        }
+        sgn15_softmax_store(t, rows, P, nullptr);
+      }
+      __syncthreads();
+      // pass 2: dP = sum over the slices of do_s v_s^T, K split over the waves, partials added in wave order; dS
+      f32x16 dp = {};
+      for (int sl = 0; sl < hs; ++sl) {
+        sgn15_qkv<DIN, 1>(X, w, o, inner, head * hs + sl, 2, QKV);
+        make_do(head * hs + sl);
+        dp = mma_l(DO + wave * 32, DS, 1, Vv + wave * 32, 1, QS, 32, dp);
+        __syncthreads();
+      }
+      sgn15_store_tile(dp, P + (1 + wave) * SGN15_P_SLOT, PS, 0);
+      __syncthreads();
+      if (wave == 0) {
+        f32x16 t;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          const int e = mfma_row(j, h) * PS + r;
+          t[j] = ((P[SGN15_P_SLOT + e] + P[2 * SGN15_P_SLOT + e]) + P[3 * SGN15_P_SLOT + e]) + P[4 * SGN15_P_SLOT + e];
+        }
+        const f32x16 v = sgn15_softmax_bwd(t, P);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) dS[mfma_row(j, h) * PS + r] = v[j];
+      }
+      __syncthreads();
+      // pass 3: dq_s, dk_s, dv_s slice by slice
+      for (int sl = 0; sl < hs; ++sl) {
+        const int g = head * hs + sl;
+        sgn15_qkv<DIN, 3>(X, w, o, inner, g, 0, QKV);
+        make_do(g);
+        const f32x16 dv = mma_l(P, 1, PS, DO + wave * 32, DS, 1, Kp, f32x16{});
+        const f32x16 dq = mma_l(dS, PS, 1, Kk + wave * 32, QS, 1, Kp, f32x16{});
+        const f32x16 dk = mma_l(dS, 1, PS, Q + wave * 32, QS, 1, Kp, f32x16{});
+        finish(g, dq, dk, dv);
+      }
+    }
   }
 }

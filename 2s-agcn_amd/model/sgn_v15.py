@@ -18,6 +18,11 @@ Two routes:
   tensor-code composition ``forward_tensor``, channels last, a complete ``nn.Module`` in every mode.  It is the
   comparison of the fused path, NOT the hot path, and is counted in ``ops.SGN_STATS['forward_tensor']``.
 
+``input_gradient`` (what ``explain()`` of an online recogniser asks for) has the same two routes: with
+``fused_input_gradient = True`` (a plain attribute, off by default, not in the state_dict) the fused forward followed by
+``ops.sgn15_clip_bwd`` and ``ops.sgn15_frames_bwd`` (csrc/sgn_v15_bwd.hip) on transposed weight images cached with the
+forward ones, otherwise torch autograd on the composition.
+
 One block, with n_a, n_f the two per-channel BatchNorms: a = softmax_j((n_a(x) Wq)(n_a(x) Wk)^T d_head^-1/2) per head,
 x1 = concat_h(a . n_a(x) Wv) Wo + bo + res_a(x), y = relu(n_f(x1) W1 + b1) W2 + b2 + res_f(x1): both residuals take the
 un-normalised input, and a residual is a Linear where the widths differ (crossattention.py:297-304)."""
@@ -336,6 +341,7 @@ class SGN(nn.Module):
                 m.weight.data.normal_(0, math.sqrt(2. / n))
         self._infer_cache = {}
         self.fused_attention = False       # opt in: the fused route also stores and returns the attention maps
+        self.fused_input_gradient = False  # opt in: input_gradient through the HIP backward (csrc/sgn_v15_bwd.hip)
 
     @property
     def seg(self):
@@ -438,15 +444,24 @@ class SGN(nn.Module):
         key = ops._cache_key(list(self.parameters()) + list(self.buffers()))
         f = self._infer_cache.get('images')
         if f is None or f[0] != key:
-            frames, clip = self._folded()
-            secs = {n: (o, s) for n, o, s in ops.sgn15_image_sections(self.num_point, self.num_segment, self.num_class,
-                                                                      *self._geometry())[0]}
-            wf = torch.cat([t.reshape(-1) for t in frames])
-            wc = torch.cat([t.reshape(-1) for t in clip])
-            o, s = secs['spa']
-            f = self._infer_cache['images'] = (key, wf, wc, wf[o:o + math.prod(s)].view(s),
-                                               wc[:self.num_segment * 256].view(self.num_segment, 256))
-        return f[1:]
+            with torch.no_grad():          # whatever the caller's grad mode: the cache holds leaves without a graph
+                frames, clip = self._folded()
+                secs = {n: (o, s) for n, o, s in ops.sgn15_image_sections(self.num_point, self.num_segment, self.num_class,
+                                                                          *self._geometry())[0]}
+                wf = torch.cat([t.reshape(-1) for t in frames])
+                wc = torch.cat([t.reshape(-1) for t in clip])
+                o, s = secs['spa']
+                wf_t, wc_t = ops.sgn15_transpose_images(wf, wc, self.num_point, self.num_segment, self.num_class,
+                                                        *self._geometry())
+                f = self._infer_cache['images'] = (key, wf, wc, wf[o:o + math.prod(s)].view(s),
+                                                   wc[:self.num_segment * 256].view(self.num_segment, 256), wf_t, wc_t)
+        return f[1:5]
+
+    def _images_t(self):
+        """-> (transposed frames image, transposed clip image) of the input-gradient kernels, cached with ``_images``
+        under the same key and rebuilt with them."""
+        self._images()
+        return self._infer_cache['images'][5:]
 
     def _fusable(self, x):
         """What the eval-mode kernels take, whatever the grad mode."""
@@ -463,28 +478,64 @@ class SGN(nn.Module):
         if torch.is_grad_enabled() or not self._fusable(x):
             ops.SGN_STATS['forward_tensor'] += 1
             return self.forward_tensor(x)
-        wf, wc, spa, tem = self._images()
+        parts = self._fused_forward(x)
+        sa, logits, ta = (parts[0][i] if len(parts) == 1 or parts[0][i] is None else torch.cat([p[i] for p in parts])
+                          for i in (2, 3, 4))
+        return logits, self._fused_aux(x.shape[0], sa, ta)
+
+    def _fused_forward(self, x):
+        """The two forward launches per chunk of at most ``ops.SGN15_MAX_CLIPS`` clips -> [(lo, feat, spatial attn, logits,
+        temporal attn)]."""
+        wf, wc, _, _ = self._images()
         sp, tp = self._geometry()
-        N, seg, V = x.shape[0], self.num_segment, self.num_point
         parts = []
-        for lo in range(0, N, ops.SGN15_MAX_CLIPS):        # one pair of launches unless the batch exceeds their limit
+        for lo in range(0, x.shape[0], ops.SGN15_MAX_CLIPS):        # one pair of launches unless the batch exceeds their limit
             xs = x[lo:lo + ops.SGN15_MAX_CLIPS]
-            feat, sa = ops.sgn15_frames(xs, wf, V, *sp, want_attn=self.fused_attention)
-            parts.append((sa,) + ops.sgn15_clip(feat, wc, self.num_class, *tp, want_attn=self.fused_attention))
-        sa, logits, ta = parts[0] if len(parts) == 1 else (
-            None if p[0] is None else torch.cat(p) for p in zip(*parts))
-        aux = dict(tem_emb=tem.t()[None, :, None, :].expand(N, 256, V, seg),
-                   spa_emb=spa.t()[None, :, :, None].expand(N, 64, V, seg),
-                   spatial_attn_list=[sa] if self.fused_attention else None,
-                   temporal_attn_list=[ta] if self.fused_attention else None)
-        return logits, aux
+            feat, sa = ops.sgn15_frames(xs, wf, self.num_point, *sp, want_attn=self.fused_attention)
+            parts.append((lo, feat, sa) + ops.sgn15_clip(feat, wc, self.num_class, *tp, want_attn=self.fused_attention))
+        return parts
+
+    def _fused_aux(self, N, sa, ta):
+        _, _, spa, tem = self._images()
+        seg, V = self.num_segment, self.num_point
+        return dict(tem_emb=tem.t()[None, :, None, :].expand(N, 256, V, seg),
+                    spa_emb=spa.t()[None, :, :, None].expand(N, 64, V, seg),
+                    spatial_attn_list=[sa] if self.fused_attention else None,
+                    temporal_attn_list=[ta] if self.fused_attention else None)
+
+    def _fused_gradient(self, x):
+        """Whether ``input_gradient`` takes the HIP route for x: opted in, the forward's conditions, and both transposed
+        images inside the backward's domain."""
+        return (self.fused_input_gradient and self._fusable(x)
+                and ops.sgn15_bwd_weights_floats(self.num_point, self.num_segment, self.num_class, *self._geometry())
+                is not None)
 
     def input_gradient(self, x, cot):
-        """-> (logits, aux, dx) with dx = d sum(logits * cot) / dx in eval mode, through the composition and torch
-        autograd (no HIP backward is built for v15; counted in ``ops.SGN_STATS['forward_tensor']``).  Needs no autograd
-        state and ignores the parameters' requires_grad."""
+        """-> (logits, aux, dx) with dx = d sum(logits * cot) / dx in eval mode.  Needs no autograd state and ignores the
+        parameters' requires_grad.  Two routes:
+
+        * ``fused_input_gradient = True`` (a plain attribute, off by default, not in the state_dict) on what the fused
+          forward takes: the two forward launches, then ``ops.sgn15_clip_bwd`` and ``ops.sgn15_frames_bwd``
+          (csrc/sgn_v15_bwd.hip), which store nothing of the forward, sum in fixed orders and give a clip the same bits
+          alone and in any batch; counted in ``ops.SGN15_STATS`` and ``ops.SGN15_BWD_STATS``.
+        * otherwise the composition and torch autograd, counted in ``ops.SGN_STATS['forward_tensor']``."""
         if self.training:
             raise ValueError("agcn_amd: SGN.input_gradient is the eval-mode gradient; call eval() first")
+        if self._fused_gradient(x):
+            # no_grad around the whole route, the folds included: the cached images must stay leaves without a graph
+            with torch.no_grad():
+                x = x.detach()
+                wf, wc, _, _ = self._images()
+                wf_t, wc_t = self._images_t()
+                sp, tp = self._geometry()
+                cot = cot.detach().to(x).contiguous()
+                parts, dxs = self._fused_forward(x), []
+                for lo, feat, _, _, _ in parts:
+                    n = feat.shape[0]
+                    dfeat = ops.sgn15_clip_bwd(feat, wc, wc_t, cot[lo:lo + n], *tp)
+                    dxs.append(ops.sgn15_frames_bwd(x[lo:lo + n], wf, wf_t, dfeat, self.num_point, *sp))
+                cat = lambda i: parts[0][i] if len(parts) == 1 or parts[0][i] is None else torch.cat([p[i] for p in parts])  # noqa: E731
+                return cat(3), self._fused_aux(x.shape[0], cat(2), cat(4)), dxs[0] if len(dxs) == 1 else torch.cat(dxs)
         ops.SGN_STATS['forward_tensor'] += 1
         with torch.enable_grad():
             xg = x.detach().requires_grad_(True)

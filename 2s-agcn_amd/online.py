@@ -74,6 +74,9 @@ class _Recogniser:
         self.device = torch.device(device)
         if isinstance(model, str):
             model = load_model(model, model_args, weights)
+            from .model.sgn_v15 import SGN as SGN15
+            if isinstance(model, SGN15):
+                model.fused_input_gradient = True      # explain() through the HIP backward (csrc/sgn_v15_bwd.hip)
         self.model = model.to(self.device).eval()
         self.max_frame, self.max_person, self.num_select = int(max_frame), int(max_num_skeleton), int(max_num_skeleton_true)
         self.num_joint, self.moving_avg = int(num_joint), int(moving_avg)

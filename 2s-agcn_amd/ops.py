@@ -2295,6 +2295,81 @@ def sgn15_clip(feat, wimg, num_class, heads, d_head, ff, want_attn=False):
     return logits, attn
 
 
+# diagnostic counters of the input-gradient launches (again a dict of its own: SGN15_STATS is compared whole)
+SGN15_BWD_STATS = dict(clip_bwd=0, frames_bwd=0)
+
+
+def sgn15_bwd_weights_floats(V, seg, num_class, spatial, temporal):
+    """(floats of the transposed frames image, of the transposed clip image), or None outside the kernels' domain
+    (csrc/sgn_v15_bwd_plan.h)."""
+    nf = _L().agcn_sgn15_frames_bwd_weights(V, *spatial)
+    nc = _L().agcn_sgn15_clip_bwd_weights(seg, num_class, *temporal)
+    return (nf, nc) if nf and nc else None
+
+
+def sgn15_bwd_image_sections(spatial, temporal):
+    """The sections of the two TRANSPOSED weight images of the SGN v15 input gradient in their order
+    (csrc/sgn_v15_bwd_plan.h: Sgn15FramesWT, Sgn15ClipWT) -> (frames, clip), each a list of (name, offset, shape, source):
+    the section is the transpose of section ``source`` of the forward image (``sgn15_image_sections``)."""
+    def lay(items):
+        out, o = [], 0
+        for src, shape in items:
+            out.append((src + '_t', o, shape, src))
+            o += math.prod(shape)
+        return out
+
+    def block(p, din, dout, heads, d_head, ff):
+        inner = heads * d_head
+        return [(p + 'qkv_w', (3 * inner, din)), (p + 'o_w', (din, inner)), (p + 'f1_w', (ff, din)),
+                (p + 'f2_w', (dout, ff + din))]
+
+    return (lay([('pe2_w', (64, 64)), ('ve2_w', (64, 64))] + block('s_', 128, 256, *spatial)),
+            lay(block('t_', 256, 512, *temporal)))
+
+
+def sgn15_transpose_images(wf, wc, V, seg, num_class, spatial, temporal):
+    """The two transposed images from the two forward images."""
+    out = []
+    for img, fwd, bwd in zip((wf, wc), sgn15_image_sections(V, seg, num_class, spatial, temporal),
+                             sgn15_bwd_image_sections(spatial, temporal)):
+        at = {n: (o, s) for n, o, s in fwd}
+        out.append(torch.cat([img[at[src][0]:at[src][0] + math.prod(at[src][1])].view(at[src][1]).t().reshape(-1)
+                              for _, _, _, src in bwd]))
+    return tuple(out)
+
+
+def sgn15_clip_bwd(feat, wimg, wimg_t, dlogits, heads, d_head, ff):
+    """d logits (N, num_class) -> d feat (N, seg, 256) through fc, the maximum over the frames and the temporal block of
+    SGN v15, recomputed from feat (N, seg, 256) as ``sgn15_frames`` returns it.  wimg: the forward clip image, wimg_t: the
+    transposed one."""
+    if feat.dim() != 3 or feat.shape[2] != 256:
+        raise ValueError(f"agcn_amd: sgn15_clip_bwd takes (N, seg, 256), got {tuple(feat.shape)}")
+    N, seg, _ = feat.shape
+    if dlogits.dim() != 2 or dlogits.shape[0] != N:
+        raise ValueError(f"agcn_amd: sgn15_clip_bwd takes dlogits ({N}, num_class), got {tuple(dlogits.shape)}")
+    dfeat = _empty((N, seg, 256), feat)
+    _lib.call("agcn_sgn15_clip_bwd", feat, wimg, wimg.numel(), wimg_t, wimg_t.numel(), dlogits, dfeat, N, seg,
+              dlogits.shape[1], heads, d_head, ff)
+    SGN15_BWD_STATS['clip_bwd'] += 1
+    return dfeat
+
+
+def sgn15_frames_bwd(x, wimg, wimg_t, dfeat, V, heads, d_head, ff):
+    """d feat (N, seg, 256) -> dx (N, seg, V*3) through the maximum over the joints, the spatial block and the input side
+    of SGN v15, recomputed from x, and the velocity's coupling between the frames of a clip."""
+    if x.dim() != 3 or x.shape[2] != 3 * V:
+        raise ValueError(f"agcn_amd: sgn15_frames_bwd takes (N, seg, {3 * V}), got {tuple(x.shape)}")
+    N, seg, _ = x.shape
+    if tuple(dfeat.shape) != (N, seg, 256):
+        raise ValueError(f"agcn_amd: sgn15_frames_bwd takes dfeat ({N}, {seg}, 256), got {tuple(dfeat.shape)}")
+    dx = _empty((N, seg, 3 * V), x)
+    ws = _empty((max(1, _L().agcn_sgn15_frames_bwd_workspace(N, seg, V) // 4),), x)
+    _lib.call("agcn_sgn15_frames_bwd", x, wimg, wimg.numel(), wimg_t, wimg_t.numel(), dfeat, dx, ws, ws.numel() * 4, N,
+              seg, V, heads, d_head, ff)
+    SGN15_BWD_STATS['frames_bwd'] += 1
+    return dx
+
+
 def sgn15_forward_ref(x, wf, wc, V, seg, num_class, spatial, temporal):
     """The tensor-code form of the fused SGN v15 forward, reading ONLY the two flat folded images: the CPU-checkable
     specification of the fold and the layout.  x (N, seg, V*3) -> (logits, feat (N, seg, 256) as ``sgn15_frames`` returns

@@ -667,6 +667,35 @@ int agcn_sgn15_frames(const float* x, const float* w, size_t w_floats, float* fe
 int agcn_sgn15_clip(const float* feat, const float* w, size_t w_floats, float* logits, float* attn, int N, int seg,
                     int num_class, int heads, int d_head, int ff, void* stream);
 
+/* ---- SGN v15: input gradients in eval mode (csrc/sgn_v15_bwd.hip; the block backward: csrc/sgn_v15_device.h; geometry,
+ * the transposed images and the LDS lifetimes: csrc/sgn_v15_bwd_plan.h) ----
+ * The backward of sgn15_clip and sgn15_frames, in that order: dx = d sum(logits * dlogits) / dx.  Nothing of the forward is
+ * stored: each kernel recomputes what it needs from x / feat with the forward's device code.  ReLU's derivative at 0 is 0;
+ * a maximum (no ReLU in front of it: it may be negative) routes to its lowest index.  Arithmetic rules and domain as for
+ * the forward; a clip's gradient does not depend on its batch.
+ * sgn15_frames_bwd_weights / sgn15_clip_bwd_weights: floats of the TRANSPOSED weight images (0 outside the domain), built
+ *   by the caller next to the forward images (model/sgn_v15.py::SGN._images) in the order of Sgn15FramesWT / Sgn15ClipWT:
+ *   every matrix (N, K) row-major -- the second embedding layers (frames) and qkv_w, o_w, f1_w, f2_w of the block.  The
+ *   kernels read the forward image as well (biases, 3 -> 64 layers, aff, tem, fc).
+ * sgn15_frames_bwd_workspace: bytes of the caller-owned workspace of sgn15_frames_bwd (dj and dd, below).
+ * sgn15_clip_bwd: feat (N, seg, 256) as sgn15_frames returns it, dlogits (N, num_class) -> dfeat (N, seg, 256), one
+ *   workgroup per clip: fc, the maximum over the real frames, the block; tem_emb is a constant.
+ * sgn15_frames_bwd: x (N, seg, V*3), dfeat -> dx (N, seg, V*3), one workgroup per frame and a combining launch: the
+ *   maximum over the real joints, the block (its spa columns go nowhere), the two embeddings and their DataNorm.  The
+ *   velocity couples neighbouring frames of a clip: every frame writes dj (position branch) and dd (velocity branch) to
+ *   the workspace and dx[t] = dj[t] + dd[t] [t > 0] - dd[t + 1] [t + 1 < seg].
+ * AGCN_ERR_ARG: a null pointer, sizes outside the domain, w_floats / wt_floats / ws_bytes different from the size
+ *   queries. */
+size_t agcn_sgn15_frames_bwd_weights(int V, int heads, int d_head, int ff);
+size_t agcn_sgn15_clip_bwd_weights(int seg, int num_class, int heads, int d_head, int ff);
+size_t agcn_sgn15_frames_bwd_workspace(int N, int seg, int V);
+int agcn_sgn15_clip_bwd(const float* feat, const float* w, size_t w_floats, const float* wt, size_t wt_floats,
+                        const float* dlogits, float* dfeat, int N, int seg, int num_class, int heads, int d_head, int ff,
+                        void* stream);
+int agcn_sgn15_frames_bwd(const float* x, const float* w, size_t w_floats, const float* wt, size_t wt_floats,
+                          const float* dfeat, float* dx, void* ws, size_t ws_bytes, int N, int seg, int V, int heads,
+                          int d_head, int ff, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
