@@ -7,6 +7,7 @@
 #include "sgn_device.h"
 #include "sgn_v15_plan.h"
 #include "sgn_v15_bwd_plan.h"
+#include "sgn_v15_wgrad_plan.h"
 
 // mma_w with the column step between a wave's blocks as a parameter: block i of the wave sits cstep columns after
 // block i - 1 (the q, k and v sections of one group are `inner` columns apart in [Wq | Wk | Wv]).  As there, 16 weight
@@ -246,6 +247,26 @@ __device__ __forceinline__ void sgn15_store_block(const f32x16& a, float* band, 
   sgn15_store_tile(a, band, stride, (threadIdx.x >> 6) * 32);
 }
 
+// ---- the taping instantiations (sgn_v15_wgrad_plan.h): global stores only, from the lanes that hold the values; trow is
+// row 0 of this token set in the tape, TC the tape's row stride.  Lanes of padded rows store nothing. ----
+// the real rows of an accumulator tile -> 32 columns of the tape from column `col` on
+__device__ __forceinline__ void sgn15_tape_tile(const f32x16& a, int rows, float* trow, size_t TC, int col) {
+  const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const int row = mfma_row(j, h);
+    if (row < rows) trow[(size_t)row * TC + col + r] = a[j];
+  }
+}
+// rows [0, nrows) x width columns of an LDS band -> the tape, consecutive threads on consecutive columns.  Only reads LDS:
+// it may run next to readers of the band, between the barrier behind its producer and the one in front of its next writer.
+__device__ __forceinline__ void sgn15_tape_band(const float* band, int stride, int nrows, int width, float* dst, size_t ld) {
+  for (int i = threadIdx.x; i < nrows * width; i += SGN_THREADS) {
+    const int row = i / width, c = i - row * width;
+    dst[(size_t)row * ld + c] = band[row * stride + c];
+  }
+}
+
 // dS = P * (dP - rowsum(dP * P)) of one head, dP in the accumulator layout, P in its slot -> dS in registers.  The row sum
 // runs over the 32 lanes of the half-wave that holds the row; P is zero in padded rows and columns, and so is dS.
 __device__ __forceinline__ f32x16 sgn15_softmax_bwd(const f32x16& dp, const float* Pslot) {
@@ -264,12 +285,17 @@ __device__ __forceinline__ f32x16 sgn15_softmax_bwd(const f32x16& dp, const floa
 // column (wave + SGN_WAVES * i) * 32 + r, which goes to the column's arg-max row.  reload(): writes x into X again (the
 // forward leaves x1 there).  -> dX[i]: d x of the column blocks wave + SGN_WAVES * i, all 32 rows (padded rows: zero).
 // w / o the forward image, wt / ot the transposed one.  Barriers inside, the last one behind every read of LDS.
-template <int DIN, int DOUT, class Reload>
+// TAPE: the same arithmetic in the same order (dX is the same bits), and every operand pair of the block's weight
+// gradients copied to the tape rows trow (sections bt, row stride TC) at the step it is live; o = concat_h(P v), which only
+// the forward holds, is formed again in the group walk while P and v are live.  ymax, unless null: the pooled maxima of
+// the DOUT columns, the forward's values.  With TAPE off trow, TC, bt and ymax are not read.
+template <int DIN, int DOUT, bool TAPE, class Reload>
 __device__ __forceinline__ void sgn15_block_bwd(float* X, float* QKV, float* DO, float* P, const float* __restrict__ w,
                                                 const Sgn15BlockW& o, const float* __restrict__ wt, const Sgn15BlockWT& ot,
                                                 int rows, int heads, int d_head, int ff,
                                                 const float (&d)[DOUT / SGN15_GROUP], Reload reload,
-                                                f32x16 (&dX)[DIN / SGN15_GROUP]) {
+                                                f32x16 (&dX)[DIN / SGN15_GROUP], float* __restrict__ trow, size_t TC,
+                                                const Sgn15BlockTape& bt, float* __restrict__ ymax) {
   constexpr int XS = SGN15_X_STRIDE(DIN), QS = SGN15_QKV_STRIDE, DS = SGN15_BWD_DO_STRIDE, PS = SGN15_P_STRIDE;
   constexpr int DYS = SGN15_BWD_DY_STRIDE(DOUT), NBO = DIN / SGN15_GROUP, NBY = DOUT / SGN15_GROUP;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
@@ -293,10 +319,23 @@ __device__ __forceinline__ void sgn15_block_bwd(float* X, float* QKV, float* DO,
       for (int j = 0; j < 16; ++j) {
         const int row = mfma_row(j, h);
         DY[row * DYS + col] = row == arg ? d[i] : 0.f;
+        if constexpr (TAPE)
+          if (row < rows) trow[(size_t)row * TC + bt.dy + col] = row == arg ? d[i] : 0.f;
       }
+      if constexpr (TAPE)
+        if (ymax) {                                // the maximum as sgn15_block forms it
+          const float bv = w[o.f2_b + col];
+          float v = -INFINITY;
+#pragma unroll
+          for (int j = 0; j < 16; ++j)
+            if (mfma_row(j, h) < rows) v = fmaxf(v, accY[i][j] + bv);
+          v = fmaxf(v, __shfl_xor(v, 32));
+          if (h == 0) ymax[col] = v;
+        }
     }
   }
   __syncthreads();
+  if constexpr (TAPE) sgn15_tape_band(X, XS, rows, DIN, trow + bt.x1, TC);       // x1: X is not written before reload()
 
   // ---- the feed-forward: dx1 = dy Wr^T + sum_c (dy W2_c^T * [hidden_c > 0]) W1_c^T, in registers ----
   const int ldf2 = ff + DIN;
@@ -311,6 +350,16 @@ __device__ __forceinline__ void sgn15_block_bwd(float* X, float* QKV, float* DO,
     const float bv = w[o.f1_b + col];
 #pragma unroll
     for (int j = 0; j < 16; ++j) DH[mfma_row(j, h) * DS + wave * 32 + r] = hid[0][j] + bv > 0.f ? dh[0][j] : 0.f;
+    if constexpr (TAPE) {
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const int row = mfma_row(j, h);
+        if (row < rows) {
+          trow[(size_t)row * TC + bt.hid + col] = fmaxf(hid[0][j] + bv, 0.f);
+          trow[(size_t)row * TC + bt.dhid + col] = hid[0][j] + bv > 0.f ? dh[0][j] : 0.f;
+        }
+      }
+    }
     __syncthreads();
     mma_w<NBO>(DH + r * DS + h, wt + ot.f1 + (long)(sgn15_chunk_col(c) + h) * DIN + wave * 32 + r, DIN, SGN15_GROUP, dx1);
     __syncthreads();
@@ -319,6 +368,13 @@ __device__ __forceinline__ void sgn15_block_bwd(float* X, float* QKV, float* DO,
 #pragma unroll
   for (int i = 0; i < NBO; ++i) dX[i] = dx1[i];    // the attention residual
   __syncthreads();
+  if constexpr (TAPE) {
+#pragma unroll
+    for (int i = 0; i < NBO; ++i) sgn15_tape_tile(dx1[i], rows, trow, TC, bt.dx1 + (wave + SGN_WAVES * i) * 32);
+    sgn15_tape_band(X, XS, rows, DIN, trow + bt.x, TC);                           // x again: only read from here on
+  }
+  // o of group g = P v (both live), the forward's product: the taping instantiation only
+  auto tape_o = [&](int g, const f32x16& av) { sgn15_tape_tile(av, rows, trow, TC, bt.o + sgn15_group_col(g) + wave * 32); };
 
   // do = dx1 Wo_g^T into DO: each 128-column half of dx1 is staged through DO from the registers that hold it
   auto make_do = [&](int g) {
@@ -340,6 +396,12 @@ __device__ __forceinline__ void sgn15_block_bwd(float* X, float* QKV, float* DO,
     sgn15_store_block(dq, Q, QS);
     sgn15_store_block(dk, Kk, QS);
     sgn15_store_block(dv, Vv, QS);
+    if constexpr (TAPE) {                          // behind the pair select, once per group
+      const int col = bt.dqkv + sgn15_group_col(g) + wave * 32;
+      sgn15_tape_tile(dq, rows, trow, TC, col);
+      sgn15_tape_tile(dk, rows, trow, TC, col + inner);
+      sgn15_tape_tile(dv, rows, trow, TC, col + 2 * inner);
+    }
     __syncthreads();
 #pragma unroll
     for (int s = 0; s < 3; ++s)
@@ -360,6 +422,14 @@ __device__ __forceinline__ void sgn15_block_bwd(float* X, float* QKV, float* DO,
         sgn15_softmax_store(s, rows, P + lh * SGN15_P_SLOT, nullptr);
       }
       __syncthreads();
+      if constexpr (TAPE) {
+        f32x16 av = mma_l(P + lh0 * SGN15_P_SLOT, PS, 1, Vv + wave * 32, QS, 1, Kp, f32x16{});
+        if (pair) {
+          const f32x16 av1 = mma_l(P + (lh0 + 1) * SGN15_P_SLOT, PS, 1, Vv + wave * 32, QS, 1, Kp, f32x16{});
+          if (r >= 16) av = av1;
+        }
+        tape_o(g, av);
+      }
       // dv = P^T do of the wave's block; dP = do_h v_h^T and dS of the wave's heads
       f32x16 dv = mma_l(P + lh0 * SGN15_P_SLOT, 1, PS, DO + wave * 32, DS, 1, Kp, f32x16{});
       if (pair) {
@@ -449,6 +519,7 @@ __device__ __forceinline__ void sgn15_block_bwd(float* X, float* QKV, float* DO,
         const int g = head * hs + sl;
         sgn15_qkv<DIN, 3>(X, w, o, inner, g, 0, QKV);
         make_do(g);
+        if constexpr (TAPE) tape_o(g, mma_l(P, PS, 1, Vv + wave * 32, QS, 1, Kp, f32x16{}));
         const f32x16 dv = mma_l(P, 1, PS, DO + wave * 32, DS, 1, Kp, f32x16{});
         const f32x16 dq = mma_l(dS, PS, 1, Kk + wave * 32, QS, 1, Kp, f32x16{});
         const f32x16 dk = mma_l(dS, 1, PS, Q + wave * 32, QS, 1, Kp, f32x16{});

@@ -23,6 +23,13 @@ Two routes:
 ``ops.sgn15_clip_bwd`` and ``ops.sgn15_frames_bwd`` (csrc/sgn_v15_bwd.hip) on transposed weight images cached with the
 forward ones, otherwise torch autograd on the composition.
 
+Frozen-BatchNorm fine-tuning: with ``fused_finetune = True`` (a plain attribute, off by default, not in the state_dict),
+eval mode, grad mode and some parameter that requires grad, ``forward`` is ``ops.SGN15FineTuneFunction``: the two forward
+launches, and in ``backward()`` the two taping backward launches and the fixed-order reductions of
+csrc/sgn_v15_wgrad.hip, which give the gradients of the two folded images; torch autograd takes them through the fold
+(``_finetune_images``, a fresh fold per call) to the parameters.  ``parameter_gradients`` is the same route without
+autograd state.  Nothing of the forward is stored but feat; the tapes are capped by ``ops.SGN_MAX_TAPE_BYTES``.
+
 One block, with n_a, n_f the two per-channel BatchNorms: a = softmax_j((n_a(x) Wq)(n_a(x) Wk)^T d_head^-1/2) per head,
 x1 = concat_h(a . n_a(x) Wv) Wo + bo + res_a(x), y = relu(n_f(x1) W1 + b1) W2 + b2 + res_f(x1): both residuals take the
 un-normalised input, and a residual is a Linear where the widths differ (crossattention.py:297-304)."""
@@ -342,6 +349,7 @@ class SGN(nn.Module):
         self._infer_cache = {}
         self.fused_attention = False       # opt in: the fused route also stores and returns the attention maps
         self.fused_input_gradient = False  # opt in: input_gradient through the HIP backward (csrc/sgn_v15_bwd.hip)
+        self.fused_finetune = False        # opt in: eval-mode backward() to the parameters on the HIP kernels
 
     @property
     def seg(self):
@@ -474,7 +482,38 @@ class SGN(nn.Module):
         sp, tp = self._geometry()
         return (ops.sgn15_weights_floats(self.num_point, self.num_segment, self.num_class, sp, tp) is not None)
 
+    def _bwd_domain(self):
+        return ops.sgn15_bwd_weights_floats(self.num_point, self.num_segment, self.num_class, *self._geometry()) is not None
+
+    def _fused_finetune(self, x):
+        """The flag, eval mode, grad mode, the forward's and the backward's domain, and something to train."""
+        return (self.fused_finetune and torch.is_grad_enabled() and self._fusable(x) and self._bwd_domain()
+                and any(p.requires_grad for p in self.parameters()))
+
+    def _finetune_images(self):
+        """The four images for ``ops.SGN15FineTuneFunction``: the forward ones in the CURRENT grad mode from a fresh fold
+        (never from ``_infer_cache``: they carry the autograd graph of this call), the transposed ones without grad from
+        the same numbers."""
+        frames, clip = self._folded()
+        wf = torch.cat([t.reshape(-1) for t in frames])
+        wc = torch.cat([t.reshape(-1) for t in clip])
+        with torch.no_grad():
+            wf_t, wc_t = ops.sgn15_transpose_images(wf.detach(), wc.detach(), self.num_point, self.num_segment,
+                                                    self.num_class, *self._geometry())
+        return wf, wc, wf_t, wc_t
+
+    def _finetune_aux(self, N):
+        """The embeddings' tables, as the fused forward returns them; the taping route stores no attention maps."""
+        with torch.no_grad():
+            aux = self._fused_aux(N, None, None)
+        aux['spatial_attn_list'] = aux['temporal_attn_list'] = None
+        return aux
+
     def forward(self, x):
+        if self._fused_finetune(x):
+            logits = ops.SGN15FineTuneFunction.apply(x, *self._finetune_images(), self.num_point, self.num_class,
+                                                     *self._geometry())
+            return logits, self._finetune_aux(x.shape[0])
         if torch.is_grad_enabled() or not self._fusable(x):
             ops.SGN_STATS['forward_tensor'] += 1
             return self.forward_tensor(x)
@@ -506,9 +545,43 @@ class SGN(nn.Module):
     def _fused_gradient(self, x):
         """Whether ``input_gradient`` takes the HIP route for x: opted in, the forward's conditions, and both transposed
         images inside the backward's domain."""
-        return (self.fused_input_gradient and self._fusable(x)
-                and ops.sgn15_bwd_weights_floats(self.num_point, self.num_segment, self.num_class, *self._geometry())
-                is not None)
+        return self.fused_input_gradient and self._fusable(x) and self._bwd_domain()
+
+    def parameter_gradients(self, x, cot, rows_per_split=0, max_tape_bytes=None):
+        """-> (logits, aux, dx, {name: grad}) with the gradients of sum(logits * cot) in eval mode (BatchNorm on its running
+        statistics), for every parameter that requires grad.  Needs no prior autograd state and leaves every ``.grad``
+        alone.  On what the fused forward and the HIP backward take, the batch dimension is all HIP: the two forward
+        launches, the two taping backward launches and the reductions of ``ops.sgn15_image_gradients`` (counted in
+        ``ops.SGN15_STATS`` and ``ops.SGN15_WGRAD_STATS``); torch autograd only takes the two image gradients through the
+        fold.  Otherwise the composition with torch autograd (counted in ``ops.SGN_STATS['forward_tensor']``).
+        ``rows_per_split`` / ``max_tape_bytes``: see ``ops.sgn15_image_gradients``."""
+        if self.training:
+            raise ValueError("agcn_amd: SGN.parameter_gradients is the eval-mode gradient; call eval() first")
+        named = [(n, p) for n, p in self.named_parameters() if p.requires_grad]
+        params = [p for _, p in named]
+        if not (self._fusable(x) and self._bwd_domain()):
+            ops.SGN_STATS['forward_tensor'] += 1
+            with torch.enable_grad():
+                xg = x.detach().requires_grad_(True)
+                logits, aux = self.forward_tensor(xg)
+                grads = torch.autograd.grad((logits * cot.detach().to(logits)).sum(), [xg] + params, allow_unused=True)
+            dx, grads = grads[0], grads[1:]
+            aux = {k: ([a.detach() for a in v] if isinstance(v, list) else None if v is None else v.detach())
+                   for k, v in aux.items()}
+            logits = logits.detach()
+        else:
+            with torch.enable_grad():
+                wf, wc, wf_t, wc_t = self._finetune_images()
+            cap = ops.SGN_MAX_TAPE_BYTES if max_tape_bytes is None else max_tape_bytes
+            logits, dx, d_wf, d_wc = ops.sgn15_image_gradients(x, wf.detach(), wc.detach(), wf_t, wc_t, cot, self.num_point,
+                                                               self.num_class, *self._geometry(), rows_per_split, cap)
+            # an image none of whose parameters asks for a gradient (head-only fine-tuning) carries no graph
+            live = [(w, g) for w, g in ((wf, d_wf), (wc, d_wc)) if w.requires_grad]
+            grads = (torch.autograd.grad([w for w, _ in live], params, [g for _, g in live], allow_unused=True)
+                     if live else (None,) * len(params))
+            aux = self._finetune_aux(x.shape[0])
+        out = {n: (torch.zeros_like(p) if gr is None else gr) for (n, p), gr in zip(named, grads)}
+        return logits, aux, dx, out
 
     def input_gradient(self, x, cot):
         """-> (logits, aux, dx) with dx = d sum(logits * cot) / dx in eval mode.  Needs no autograd state and ignores the

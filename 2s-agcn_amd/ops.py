@@ -2404,3 +2404,178 @@ def sgn15_forward_ref(x, wf, wc, V, seg, num_class, spatial, temporal):
     feat = y.reshape(N, seg, V, 256).amax(2)
     z, ta = block(feat + c['tem'], c, 't_', temporal[0], temporal[1])
     return z.amax(1) @ c['fc_w'] + c['fc_b'], feat, sa, ta
+
+
+# ------------------------------------------------------------------------------------------------
+# SGN v15, parameter gradients in eval mode (the taping backward of csrc/sgn_v15_bwd.hip and the reductions of
+# csrc/sgn_v15_wgrad.hip): frozen-BatchNorm fine-tuning.  The kernels give the gradient with respect to the two folded
+# weight images, in the images' layout; torch autograd takes it through the fold (model/sgn_v15.py::SGN._folded) to the
+# parameters.  ``spatial`` / ``temporal`` are (heads, d_head, ff) of the two blocks.
+# ------------------------------------------------------------------------------------------------
+# diagnostic counters of these launches (a dict of its own, like SGN_WGRAD_STATS)
+SGN15_WGRAD_STATS = dict(clip_bwd_tape=0, frames_bwd_tape=0, frames_wgrad=0, clip_wgrad=0)
+# None, or a callable(label) that tools/sgn_v15_finetune.py sets to record a device event behind the taping launches
+# ('tape') and behind the reductions ('reduce') of every chunk
+SGN15_WGRAD_MARK = None
+
+
+def sgn15_clip_bwd_tape(feat, wimg, wimg_t, dlogits, heads, d_head, ff):
+    """``sgn15_clip_bwd`` (the same dfeat bits) that also writes the clip tape (csrc/sgn_v15_wgrad_plan.h: Sgn15ClipTape)
+    -> (dfeat, tape)."""
+    if feat.dim() != 3 or feat.shape[2] != 256:
+        raise ValueError(f"agcn_amd: sgn15_clip_bwd_tape takes (N, seg, 256), got {tuple(feat.shape)}")
+    N, seg, _ = feat.shape
+    if dlogits.dim() != 2 or dlogits.shape[0] != N or dlogits.shape[1] < 1:
+        raise ValueError(f"agcn_amd: sgn15_clip_bwd_tape takes dlogits ({N}, num_class), got {tuple(dlogits.shape)}")
+    nc = dlogits.shape[1]
+    tp = _tape(_L().agcn_sgn15_clip_tape_floats, (N, seg, nc, heads, d_head, ff), feat, "sgn15_clip_bwd_tape")
+    dfeat = _empty((N, seg, 256), feat)
+    _lib.call("agcn_sgn15_clip_bwd_tape", feat, wimg, wimg.numel(), wimg_t, wimg_t.numel(), dlogits, dfeat, N, seg, nc,
+              heads, d_head, ff, tp, tp.numel())
+    SGN15_WGRAD_STATS['clip_bwd_tape'] += 1
+    return dfeat, tp
+
+
+def sgn15_frames_bwd_tape(x, wimg, wimg_t, dfeat, V, heads, d_head, ff):
+    """``sgn15_frames_bwd`` (the same dx bits) that also writes the frames tape (Sgn15FramesTape) -> (dx, tape)."""
+    if x.dim() != 3 or x.shape[2] != 3 * V:
+        raise ValueError(f"agcn_amd: sgn15_frames_bwd_tape takes (N, seg, {3 * V}), got {tuple(x.shape)}")
+    N, seg, _ = x.shape
+    if tuple(dfeat.shape) != (N, seg, 256):
+        raise ValueError(f"agcn_amd: sgn15_frames_bwd_tape takes dfeat ({N}, {seg}, 256), got {tuple(dfeat.shape)}")
+    tp = _tape(_L().agcn_sgn15_frames_tape_floats, (N, seg, V, heads, d_head, ff), x, "sgn15_frames_bwd_tape")
+    dx = _empty((N, seg, 3 * V), x)
+    ws = _empty((max(1, _L().agcn_sgn15_frames_bwd_workspace(N, seg, V) // 4),), x)
+    _lib.call("agcn_sgn15_frames_bwd_tape", x, wimg, wimg.numel(), wimg_t, wimg_t.numel(), dfeat, dx, ws, ws.numel() * 4, N,
+              seg, V, heads, d_head, ff, tp, tp.numel())
+    SGN15_WGRAD_STATS['frames_bwd_tape'] += 1
+    return dx, tp
+
+
+def _sgn15_wgrad_ws(args, rows_per_split, like):
+    if rows_per_split < 0:
+        raise ValueError(f"agcn_amd: rows_per_split must be >= 0, got {rows_per_split}")
+    n = _L().agcn_sgn15_wgrad_workspace(*args, rows_per_split)
+    if n == 0:
+        raise ValueError(f"agcn_amd: SGN v15 parameter gradients: {args} is outside the kernels' domain")
+    return _empty((n // 4,), like)
+
+
+def sgn15_frames_wgrad(x, wimg, tape, V, heads, d_head, ff, rows_per_split=0):
+    """x and the frames tape -> the gradient of the frames image ``wimg``, in its layout."""
+    N, seg, _ = x.shape
+    if x.shape[2] != 3 * V or tape.numel() < _L().agcn_sgn15_frames_tape_floats(N, seg, V, heads, d_head, ff):
+        raise ValueError(f"agcn_amd: sgn15_frames_wgrad: a tape of {tape.numel()} floats is not the tape of {tuple(x.shape)}")
+    ws = _sgn15_wgrad_ws((N, seg, V, 0, heads, d_head, ff), rows_per_split, x)
+    d_w = _empty((wimg.numel(),), x)
+    _lib.call("agcn_sgn15_frames_wgrad", x, tape, tape.numel(), d_w, d_w.numel(), ws, ws.numel() * 4, N, seg, V, heads,
+              d_head, ff, rows_per_split)
+    SGN15_WGRAD_STATS['frames_wgrad'] += 1
+    return d_w
+
+
+def sgn15_clip_wgrad(tape, dlogits, wimg, seg, heads, d_head, ff, rows_per_split=0):
+    """The clip tape and dlogits (N, num_class) -> the gradient of the clip image ``wimg``, in its layout."""
+    N, nc = dlogits.shape
+    if tape.numel() < _L().agcn_sgn15_clip_tape_floats(N, seg, nc, heads, d_head, ff):
+        raise ValueError(f"agcn_amd: sgn15_clip_wgrad: a tape of {tape.numel()} floats is not the tape of {(N, seg, nc)}")
+    ws = _sgn15_wgrad_ws((N, seg, 0, nc, heads, d_head, ff), rows_per_split, dlogits)
+    d_w = _empty((wimg.numel(),), dlogits)
+    _lib.call("agcn_sgn15_clip_wgrad", tape, tape.numel(), dlogits, d_w, d_w.numel(), ws, ws.numel() * 4, N, seg, nc, heads,
+              d_head, ff, rows_per_split)
+    SGN15_WGRAD_STATS['clip_wgrad'] += 1
+    return d_w
+
+
+def sgn15_tape_chunk(N, seg, V, num_class, spatial, temporal, max_tape_bytes):
+    """Clips per chunk: as many whole clips as fit ``max_tape_bytes`` of tape (both tapes are linear in the clips), at
+    least one and at most ``SGN15_MAX_CLIPS``."""
+    nf = _L().agcn_sgn15_frames_tape_floats(1, seg, V, *spatial)
+    nc = _L().agcn_sgn15_clip_tape_floats(1, seg, num_class, *temporal)
+    per = 4 * (nf + nc)
+    if nf == 0 or nc == 0:
+        raise ValueError(f"agcn_amd: SGN v15 parameter gradients: {(seg, V, num_class, spatial, temporal)} is outside the "
+                         f"kernels' domain")
+    return max(1, min(N, SGN15_MAX_CLIPS, int(max_tape_bytes) // per))
+
+
+def _sgn15_image_backward(x, feat, wf, wc, wf_t, wc_t, dlogits, V, spatial, temporal, rows_per_split, max_tape_bytes):
+    """-> (dx, d_wf, d_wc): chunks of whole clips, the chunks' image gradients added in ascending chunk order."""
+    N, seg, _ = x.shape
+    chunk = sgn15_tape_chunk(N, seg, V, dlogits.shape[1], spatial, temporal, max_tape_bytes)
+    dxs, d_wf, d_wc = [], None, None
+    for n0 in range(0, N, chunk):
+        xs, fe, dl = x[n0:n0 + chunk], feat[n0:n0 + chunk], dlogits[n0:n0 + chunk]
+        dfeat, ctape = sgn15_clip_bwd_tape(fe, wc, wc_t, dl, *temporal)
+        dx, ftape = sgn15_frames_bwd_tape(xs, wf, wf_t, dfeat, V, *spatial)
+        if SGN15_WGRAD_MARK:
+            SGN15_WGRAD_MARK('tape')
+        gf = sgn15_frames_wgrad(xs, wf, ftape, V, *spatial, rows_per_split=rows_per_split)
+        gc = sgn15_clip_wgrad(ctape, dl, wc, seg, *temporal, rows_per_split=rows_per_split)
+        if SGN15_WGRAD_MARK:
+            SGN15_WGRAD_MARK('reduce')
+        del ftape, ctape
+        dxs.append(dx)
+        d_wf = gf if d_wf is None else d_wf + gf
+        d_wc = gc if d_wc is None else d_wc + gc
+    return (dxs[0] if len(dxs) == 1 else torch.cat(dxs)), d_wf, d_wc
+
+
+def _sgn15_fused_forward(x, wf, wc, V, num_class, spatial, temporal):
+    """The two forward launches per chunk of at most ``SGN15_MAX_CLIPS`` clips -> (logits, feat)."""
+    feats, logits = [], []
+    for lo in range(0, x.shape[0], SGN15_MAX_CLIPS):
+        feat, _ = sgn15_frames(x[lo:lo + SGN15_MAX_CLIPS], wf, V, *spatial)
+        feats.append(feat)
+        logits.append(sgn15_clip(feat, wc, num_class, *temporal)[0])
+    return (logits[0], feats[0]) if len(feats) == 1 else (torch.cat(logits), torch.cat(feats))
+
+
+def sgn15_image_gradients(x, wf, wc, wf_t, wc_t, cot, V, num_class, spatial, temporal, rows_per_split=0,
+                          max_tape_bytes=SGN_MAX_TAPE_BYTES):
+    """The fused eval forward of SGN v15 and the gradient of sum(logits * cot) with respect to x and to the two folded
+    images -> (logits, dx, d_wf, d_wc); d_wf / d_wc have the layout of wf / wc.  The batch goes through in chunks of
+    whole clips under both ``max_tape_bytes`` of tape and ``SGN15_MAX_CLIPS``."""
+    with torch.no_grad():
+        x = x.detach().contiguous()
+        logits, feat = _sgn15_fused_forward(x, wf, wc, V, num_class, spatial, temporal)
+        cot = cot.detach().to(logits).contiguous()
+        if tuple(cot.shape) != tuple(logits.shape):
+            raise ValueError(f"agcn_amd: sgn15_image_gradients takes cot {tuple(logits.shape)}, got {tuple(cot.shape)}")
+        return (logits,) + _sgn15_image_backward(x, feat, wf, wc, wf_t, wc_t, cot, V, spatial, temporal, rows_per_split,
+                                                 max_tape_bytes)
+
+
+class SGN15FineTuneFunction(torch.autograd.Function):
+    """SGN v15's eval forward as the two fused launches, differentiable with respect to x and the two folded weight
+    images (built in grad mode by model/sgn_v15.py, so autograd continues through the fold to the parameters).  args: x,
+    wf, wc, wf_t, wc_t, V, num_class, spatial, temporal -> logits.  A CPU tensor runs ``sgn15_forward_ref``."""
+
+    @staticmethod
+    def forward(ctx, x, wf, wc, wf_t, wc_t, V, num_class, spatial, temporal):
+        ctx.geometry = (V, spatial, temporal)
+        if not x.is_cuda:
+            with torch.enable_grad():
+                leaves = [t.detach().requires_grad_(True) for t in (x, wf, wc)]
+                logits = sgn15_forward_ref(*leaves, V, x.shape[1], num_class, spatial, temporal)[0]
+            ctx.ref = (leaves, logits)
+            return logits.detach()
+        x = x.contiguous()
+        logits, feat = _sgn15_fused_forward(x, wf.detach(), wc.detach(), V, num_class, spatial, temporal)
+        ctx.ref = None
+        ctx.save_for_backward(x, feat, wf, wc, wf_t, wc_t)
+        return logits
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dlogits):
+        if ctx.ref is not None:
+            leaves, logits = ctx.ref
+            with torch.enable_grad():
+                dx, d_wf, d_wc = torch.autograd.grad(logits, leaves, dlogits)
+        else:
+            x, feat, wf, wc, wf_t, wc_t = ctx.saved_tensors
+            V, spatial, temporal = ctx.geometry
+            dx, d_wf, d_wc = _sgn15_image_backward(x, feat, wf, wc, wf_t, wc_t, dlogits.contiguous(), V, spatial, temporal,
+                                                   0, SGN_MAX_TAPE_BYTES)
+        return (dx if ctx.needs_input_grad[0] else None), d_wf, d_wc, None, None, None, None, None, None

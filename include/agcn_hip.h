@@ -696,6 +696,46 @@ int agcn_sgn15_frames_bwd(const float* x, const float* w, size_t w_floats, const
                           const float* dfeat, float* dx, void* ws, size_t ws_bytes, int N, int seg, int V, int heads,
                           int d_head, int ff, void* stream);
 
+/* ---- SGN v15: parameter gradients in eval mode (the two taping backward entries: csrc/sgn_v15_bwd.hip; the size queries
+ * and the reductions: csrc/sgn_v15_wgrad.hip on the kernels of csrc/sgn_wgrad_device.h; tapes and workspace:
+ * csrc/sgn_v15_wgrad_plan.h) ----
+ * Frozen-BatchNorm fine-tuning of the attention SGN: the gradient of a loss on the logits with respect to the two folded
+ * weight images, each in its image's own layout (the offsets of sgn15_frames_weights / sgn15_clip_weights).  The caller
+ * takes them through the fold to the parameters (model/sgn_v15.py).  Arithmetic rules and domain as above: exact-f32 MFMA,
+ * fixed summation orders, no atomics.  heads, d_head, ff describe the block of the entry they are passed to.
+ *
+ * sgn15_frames_tape_floats / sgn15_clip_tape_floats: floats of the caller-owned tapes (0 outside the domain).
+ * sgn15_wgrad_workspace: bytes of the workspace of ONE wgrad entry (the largest partial: elements of a section times the
+ *   splits of its rows).  V > 0: sgn15_frames_wgrad with the spatial block's heads, d_head, ff (num_class is not read);
+ *   V = 0: sgn15_clip_wgrad with the temporal block's.  rows_per_split = 0 is the plan's default; tests pass small and odd
+ *   values.  0 outside the domain or for rows_per_split < 0.
+ * sgn15_clip_bwd_tape / sgn15_frames_bwd_tape: sgn15_clip_bwd / sgn15_frames_bwd with the same results bit for bit, which
+ *   also copy every operand pair of a weight gradient to the tape (Sgn15ClipTape / Sgn15FramesTape: one row per real frame
+ *   of a clip / real joint of a frame with x, [dq | dk | dv], o, dx1, [relu(hidden) | x1], d hidden and dy of the block; the
+ *   clip tape also the block's dX and the pooled maxima (N, 512), the frames tape the embeddings' operands, columns
+ *   64..127 of the block's dX and d xn before the folded scale).  Checks as the untaped entries; AGCN_ERR_ARG for a null
+ *   tape, AGCN_ERR_WORKSPACE for tape_floats below the size query.
+ * sgn15_frames_wgrad: x, the frames tape -> d_w (sgn15_frames_weights floats, every float written).
+ * sgn15_clip_wgrad: the clip tape, dlogits (N, num_class) -> d_w (sgn15_clip_weights floats, every float written).  Each
+ *   section is a launch over row splits that writes partials to ws and a launch that adds them in ascending split order.
+ *   AGCN_ERR_ARG: a null pointer, sizes outside the domain, rows_per_split < 0, d_w_floats different from the size query.
+ *   AGCN_ERR_WORKSPACE: tape_floats or ws_bytes below their size queries.  Nothing is launched on an error. */
+size_t agcn_sgn15_frames_tape_floats(int N, int seg, int V, int heads, int d_head, int ff);
+size_t agcn_sgn15_clip_tape_floats(int N, int seg, int num_class, int heads, int d_head, int ff);
+size_t agcn_sgn15_wgrad_workspace(int N, int seg, int V, int num_class, int heads, int d_head, int ff, int rows_per_split);
+int agcn_sgn15_clip_bwd_tape(const float* feat, const float* w, size_t w_floats, const float* wt, size_t wt_floats,
+                             const float* dlogits, float* dfeat, int N, int seg, int num_class, int heads, int d_head,
+                             int ff, float* tape, size_t tape_floats, void* stream);
+int agcn_sgn15_frames_bwd_tape(const float* x, const float* w, size_t w_floats, const float* wt, size_t wt_floats,
+                               const float* dfeat, float* dx, void* ws, size_t ws_bytes, int N, int seg, int V, int heads,
+                               int d_head, int ff, float* tape, size_t tape_floats, void* stream);
+int agcn_sgn15_frames_wgrad(const float* x, const float* tape, size_t tape_floats, float* d_w, size_t d_w_floats, void* ws,
+                            size_t ws_bytes, int N, int seg, int V, int heads, int d_head, int ff, int rows_per_split,
+                            void* stream);
+int agcn_sgn15_clip_wgrad(const float* tape, size_t tape_floats, const float* dlogits, float* d_w, size_t d_w_floats,
+                          void* ws, size_t ws_bytes, int N, int seg, int num_class, int heads, int d_head, int ff,
+                          int rows_per_split, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
