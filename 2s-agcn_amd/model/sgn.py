@@ -137,9 +137,7 @@ class compute_g_spa(nn.Module):
         return self.softmax(self.g1(x1).matmul(self.g2(x1).transpose(-1, -2)))
 
 
-def _t(w):
-    """Conv / linear weight (Cout, Cin, ...) -> the (Cin, Cout) row-major image the kernels read."""
-    return w.flatten(1).t()
+_t = ops._sgn_t
 
 
 def _bias(conv, n, like):
@@ -332,24 +330,16 @@ class SGN(nn.Module):
         if self.training:
             raise ValueError("agcn_amd: SGN.parameter_gradients is the eval-mode gradient; call eval() first")
         named = [(n, p) for n, p in self.named_parameters() if p.requires_grad]
-        params = [p for _, p in named]
         if not self._fusable(x):
             ops.SGN_STATS['forward_tensor'] += 1
-            with torch.enable_grad():
-                xg = x.detach().requires_grad_(True)
-                logits, g = self.forward_tensor(xg)
-                grads = torch.autograd.grad((logits * cot).sum(), [xg] + params, allow_unused=True)
-            dx, grads = grads[0], grads[1:]
-            logits, g = logits.detach(), g.detach()
-        else:
-            with torch.enable_grad():
-                wf, wc, wf_t, wc_t = self._finetune_images()
-            cap = ops.SGN_MAX_TAPE_BYTES if max_tape_bytes is None else max_tape_bytes
-            logits, g, dx, d_wf, d_wc = ops.sgn_image_gradients(x, wf.detach(), wc.detach(), wf_t, wc_t, cot,
-                                                                self.num_point, self.num_class, rows_per_split, cap)
-            grads = torch.autograd.grad([wf, wc], params, [d_wf, d_wc], allow_unused=True) if params else ()
-        out = {n: (torch.zeros_like(p) if gr is None else gr) for (n, p), gr in zip(named, grads)}
-        return logits, g, dx, out
+            logits, g, dx, grads = ops.sgn_composition_gradients(self.forward_tensor, x, cot, [p for _, p in named])
+            return logits, g, dx, ops.sgn_named_gradients(named, grads)
+        with torch.enable_grad():
+            wf, wc, wf_t, wc_t = self._finetune_images()
+        cap = ops.SGN_MAX_TAPE_BYTES if max_tape_bytes is None else max_tape_bytes
+        logits, g, dx, d_wf, d_wc = ops.sgn_image_gradients(x, wf.detach(), wc.detach(), wf_t, wc_t, cot, self.num_point,
+                                                            self.num_class, rows_per_split, cap)
+        return logits, g, dx, ops.sgn_fold_gradients((wf, wc), (d_wf, d_wc), named)
 
     def input_gradient(self, x, cot):
         """-> (logits, g, dx) with dx = d sum(logits * cot) / dx, in eval mode.  Needs no autograd state and ignores the
@@ -360,18 +350,10 @@ class SGN(nn.Module):
             raise ValueError("agcn_amd: SGN.input_gradient is the eval-mode gradient; call eval() first")
         if not self._fusable(x):
             ops.SGN_STATS['forward_tensor'] += 1
-            with torch.enable_grad():
-                xg = x.detach().requires_grad_(True)
-                logits, g = self.forward_tensor(xg)
-                dx, = torch.autograd.grad((logits * cot).sum(), xg)
-            return logits.detach(), g.detach(), dx
+            return ops.sgn_composition_gradients(self.forward_tensor, x, cot)[:3]
         with torch.no_grad():
-            wf, wc, wf_t, wc_t = self._images(transposed=True)
-            x = x.detach().contiguous()
-            feat, g = ops.sgn_frames(x, wf, self.num_point)
-            logits = ops.sgn_clip(feat, wc, self.num_class)
-            dfeat = ops.sgn_clip_bwd(feat, wc, wc_t, cot.detach().to(logits).contiguous())
-            return logits, g, ops.sgn_frames_bwd(x, wf, wf_t, dfeat, self.num_point)
+            images = self._images(transposed=True)
+        return ops.sgn_input_gradient(x, *images, cot, self.num_point, self.num_class)
 
     # ---- batch statistics: the forward half of train-mode BatchNorm ----
     def _batch_images(self, known, identity):

@@ -279,9 +279,7 @@ def _cf(x):
     return x.permute(0, 3, 2, 1)
 
 
-def _t(w):
-    """Conv / linear weight (Cout, Cin, ...) -> the (Cin, Cout) row-major image the kernels read."""
-    return w.flatten(1).t()
+_t = ops._sgn_t
 
 
 class SGN(nn.Module):
@@ -517,22 +515,10 @@ class SGN(nn.Module):
         if torch.is_grad_enabled() or not self._fusable(x):
             ops.SGN_STATS['forward_tensor'] += 1
             return self.forward_tensor(x)
-        parts = self._fused_forward(x)
-        sa, logits, ta = (parts[0][i] if len(parts) == 1 or parts[0][i] is None else torch.cat([p[i] for p in parts])
-                          for i in (2, 3, 4))
-        return logits, self._fused_aux(x.shape[0], sa, ta)
-
-    def _fused_forward(self, x):
-        """The two forward launches per chunk of at most ``ops.SGN15_MAX_CLIPS`` clips -> [(lo, feat, spatial attn, logits,
-        temporal attn)]."""
         wf, wc, _, _ = self._images()
-        sp, tp = self._geometry()
-        parts = []
-        for lo in range(0, x.shape[0], ops.SGN15_MAX_CLIPS):        # one pair of launches unless the batch exceeds their limit
-            xs = x[lo:lo + ops.SGN15_MAX_CLIPS]
-            feat, sa = ops.sgn15_frames(xs, wf, self.num_point, *sp, want_attn=self.fused_attention)
-            parts.append((lo, feat, sa) + ops.sgn15_clip(feat, wc, self.num_class, *tp, want_attn=self.fused_attention))
-        return parts
+        logits, _, sa, ta = ops.sgn15_fused_forward(x, wf, wc, self.num_point, self.num_class, *self._geometry(),
+                                                    want_attn=self.fused_attention)
+        return logits, self._fused_aux(x.shape[0], sa, ta)
 
     def _fused_aux(self, N, sa, ta):
         _, _, spa, tem = self._images()
@@ -558,30 +544,17 @@ class SGN(nn.Module):
         if self.training:
             raise ValueError("agcn_amd: SGN.parameter_gradients is the eval-mode gradient; call eval() first")
         named = [(n, p) for n, p in self.named_parameters() if p.requires_grad]
-        params = [p for _, p in named]
         if not (self._fusable(x) and self._bwd_domain()):
             ops.SGN_STATS['forward_tensor'] += 1
-            with torch.enable_grad():
-                xg = x.detach().requires_grad_(True)
-                logits, aux = self.forward_tensor(xg)
-                grads = torch.autograd.grad((logits * cot.detach().to(logits)).sum(), [xg] + params, allow_unused=True)
-            dx, grads = grads[0], grads[1:]
-            aux = {k: ([a.detach() for a in v] if isinstance(v, list) else None if v is None else v.detach())
-                   for k, v in aux.items()}
-            logits = logits.detach()
-        else:
-            with torch.enable_grad():
-                wf, wc, wf_t, wc_t = self._finetune_images()
-            cap = ops.SGN_MAX_TAPE_BYTES if max_tape_bytes is None else max_tape_bytes
-            logits, dx, d_wf, d_wc = ops.sgn15_image_gradients(x, wf.detach(), wc.detach(), wf_t, wc_t, cot, self.num_point,
-                                                               self.num_class, *self._geometry(), rows_per_split, cap)
-            # an image none of whose parameters asks for a gradient (head-only fine-tuning) carries no graph
-            live = [(w, g) for w, g in ((wf, d_wf), (wc, d_wc)) if w.requires_grad]
-            grads = (torch.autograd.grad([w for w, _ in live], params, [g for _, g in live], allow_unused=True)
-                     if live else (None,) * len(params))
-            aux = self._finetune_aux(x.shape[0])
-        out = {n: (torch.zeros_like(p) if gr is None else gr) for (n, p), gr in zip(named, grads)}
-        return logits, aux, dx, out
+            logits, aux, dx, grads = ops.sgn_composition_gradients(self.forward_tensor, x, cot, [p for _, p in named])
+            return logits, aux, dx, ops.sgn_named_gradients(named, grads)
+        with torch.enable_grad():
+            wf, wc, wf_t, wc_t = self._finetune_images()
+        cap = ops.SGN_MAX_TAPE_BYTES if max_tape_bytes is None else max_tape_bytes
+        logits, dx, d_wf, d_wc = ops.sgn15_image_gradients(x, wf.detach(), wc.detach(), wf_t, wc_t, cot, self.num_point,
+                                                           self.num_class, *self._geometry(), rows_per_split, cap)
+        grads = ops.sgn_fold_gradients((wf, wc), (d_wf, d_wc), named)
+        return logits, self._finetune_aux(x.shape[0]), dx, grads
 
     def input_gradient(self, x, cot):
         """-> (logits, aux, dx) with dx = d sum(logits * cot) / dx in eval mode.  Needs no autograd state and ignores the
@@ -597,23 +570,10 @@ class SGN(nn.Module):
         if self._fused_gradient(x):
             # no_grad around the whole route, the folds included: the cached images must stay leaves without a graph
             with torch.no_grad():
-                x = x.detach()
                 wf, wc, _, _ = self._images()
-                wf_t, wc_t = self._images_t()
-                sp, tp = self._geometry()
-                cot = cot.detach().to(x).contiguous()
-                parts, dxs = self._fused_forward(x), []
-                for lo, feat, _, _, _ in parts:
-                    n = feat.shape[0]
-                    dfeat = ops.sgn15_clip_bwd(feat, wc, wc_t, cot[lo:lo + n], *tp)
-                    dxs.append(ops.sgn15_frames_bwd(x[lo:lo + n], wf, wf_t, dfeat, self.num_point, *sp))
-                cat = lambda i: parts[0][i] if len(parts) == 1 or parts[0][i] is None else torch.cat([p[i] for p in parts])  # noqa: E731
-                return cat(3), self._fused_aux(x.shape[0], cat(2), cat(4)), dxs[0] if len(dxs) == 1 else torch.cat(dxs)
+                logits, sa, ta, dx = ops.sgn15_input_gradient(x, wf, wc, *self._images_t(), cot, self.num_point,
+                                                              self.num_class, *self._geometry(),
+                                                              want_attn=self.fused_attention)
+                return logits, self._fused_aux(x.shape[0], sa, ta), dx
         ops.SGN_STATS['forward_tensor'] += 1
-        with torch.enable_grad():
-            xg = x.detach().requires_grad_(True)
-            logits, aux = self.forward_tensor(xg)
-            dx, = torch.autograd.grad((logits * cot.detach().to(logits)).sum(), xg)
-        aux = {k: ([a.detach() for a in v] if isinstance(v, list) else None if v is None else v.detach())
-               for k, v in aux.items()}
-        return logits.detach(), aux, dx
+        return ops.sgn_composition_gradients(self.forward_tensor, x, cot)[:3]

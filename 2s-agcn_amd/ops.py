@@ -6,6 +6,7 @@ extension never allocates or keeps device memory.  Everything here launches on t
 
 Maths: SURVEY.md Appendix A (checked against the reference ``agcn.py:92-109`` by the oracle tests).
 """
+import collections
 import math
 import os
 import weakref
@@ -1813,56 +1814,52 @@ def sgn_collate(pool, r, seg, index=None, angles=None, want_subject=False):
 SGN_GRAD_STATS = dict(clip_bwd=0, frames_bwd=0, sample_bwd=0)
 
 
-def _sgn_clip_bwd(feat, wimg, wimg_t, dlogits, tape):
-    """``sgn_clip_bwd`` (tape=False) -> dfeat, or ``sgn_clip_bwd_tape`` (tape=True) -> (dfeat, tape)."""
-    name = "sgn_clip_bwd_tape" if tape else "sgn_clip_bwd"
+def _sgn_clip_bwd(fam, feat, wimg, wimg_t, dlogits, block, tape):
+    """The clip backward of the family ``fam`` (``_SGN`` / ``_SGN15``; ``block``: () / (heads, d_head, ff)) -> dfeat, or
+    with ``tape`` the taping instantiation (the same dfeat bits) -> (dfeat, tape)."""
+    name = fam.prefix + ("_clip_bwd_tape" if tape else "_clip_bwd")
     if feat.dim() != 3 or feat.shape[2] != 256:
         raise ValueError(f"agcn_amd: {name} takes feat (N, seg, 256), got {tuple(feat.shape)}")
     N, seg, _ = feat.shape
     if dlogits.dim() != 2 or dlogits.shape[0] != N or (tape and dlogits.shape[1] < 1):
         raise ValueError(f"agcn_amd: {name} takes dlogits ({N}, num_class), got {tuple(dlogits.shape)}")
     nc = dlogits.shape[1]
-    tp = _tape(_L().agcn_sgn_clip_tape_floats, (N, seg, nc), feat, name) if tape else None
+    tp = _tape(getattr(_L(), f"agcn_{fam.prefix}_clip_tape_floats"), (N, seg, nc) + block, feat, name) if tape else None
     dfeat = _empty((N, seg, 256), feat)
-    args = (feat, wimg, wimg.numel(), wimg_t, wimg_t.numel(), dlogits, dfeat, N, seg, nc)
-    if tape:
-        _lib.call("agcn_sgn_clip_bwd_tape", *args, tp, tp.numel())
-    else:
-        _lib.call("agcn_sgn_clip_bwd", *args)
-    (SGN_WGRAD_STATS if tape else SGN_GRAD_STATS)[name[4:]] += 1
+    _lib.call("agcn_" + name, feat, wimg, wimg.numel(), wimg_t, wimg_t.numel(), dlogits, dfeat, N, seg, nc, *block,
+              *((tp, tp.numel()) if tape else ()))
+    (fam.wgrad_stats if tape else fam.bwd_stats)["clip_bwd_tape" if tape else "clip_bwd"] += 1
     return (dfeat, tp) if tape else dfeat
 
 
-def _sgn_frames_bwd(x, wimg, wimg_t, dfeat, V, tape):
-    """``sgn_frames_bwd`` (tape=False) -> dx, or ``sgn_frames_bwd_tape`` (tape=True) -> (dx, tape)."""
-    name = "sgn_frames_bwd_tape" if tape else "sgn_frames_bwd"
+def _sgn_frames_bwd(fam, x, wimg, wimg_t, dfeat, V, block, tape):
+    """The frames backward of the family ``fam`` -> dx, or with ``tape`` the taping instantiation (the same dx bits) ->
+    (dx, tape)."""
+    name = fam.prefix + ("_frames_bwd_tape" if tape else "_frames_bwd")
     if x.dim() != 3 or x.shape[2] != 3 * V:
         raise ValueError(f"agcn_amd: {name} takes (N, seg, {3 * V}), got {tuple(x.shape)}")
     N, seg, _ = x.shape
     if tuple(dfeat.shape) != (N, seg, 256):
         raise ValueError(f"agcn_amd: {name} takes dfeat ({N}, {seg}, 256), got {tuple(dfeat.shape)}")
-    tp = _tape(_L().agcn_sgn_frames_tape_floats, (N, seg, V), x, name) if tape else None
+    tp = _tape(getattr(_L(), f"agcn_{fam.prefix}_frames_tape_floats"), (N, seg, V) + block, x, name) if tape else None
     dx = _empty((N, seg, 3 * V), x)
-    ws = _empty((max(1, _L().agcn_sgn_frames_bwd_workspace(N, seg, V) // 4),), x)
-    args = (x, wimg, wimg.numel(), wimg_t, wimg_t.numel(), dfeat, dx, ws, ws.numel() * 4, N, seg, V)
-    if tape:
-        _lib.call("agcn_sgn_frames_bwd_tape", *args, tp, tp.numel())
-    else:
-        _lib.call("agcn_sgn_frames_bwd", *args)
-    (SGN_WGRAD_STATS if tape else SGN_GRAD_STATS)[name[4:]] += 1
+    ws = _empty((max(1, getattr(_L(), f"agcn_{fam.prefix}_frames_bwd_workspace")(N, seg, V) // 4),), x)
+    _lib.call("agcn_" + name, x, wimg, wimg.numel(), wimg_t, wimg_t.numel(), dfeat, dx, ws, ws.numel() * 4, N, seg, V,
+              *block, *((tp, tp.numel()) if tape else ()))
+    (fam.wgrad_stats if tape else fam.bwd_stats)["frames_bwd_tape" if tape else "frames_bwd"] += 1
     return (dx, tp) if tape else dx
 
 
 def sgn_clip_bwd(feat, wimg, wimg_t, dlogits):
     """d logits (N, num_class) -> d feat (N, seg, 256) through fc, the maximum over the frames and the two convolutions
     of the frame-level module, recomputed from feat (N, seg, 256).  wimg: the forward image, wimg_t: the transposed one."""
-    return _sgn_clip_bwd(feat, wimg, wimg_t, dlogits, tape=False)
+    return _sgn_clip_bwd(_SGN, feat, wimg, wimg_t, dlogits, (), tape=False)
 
 
 def sgn_frames_bwd(x, wimg, wimg_t, dfeat, V):
     """d feat (N, seg, 256) -> dx (N, seg, V*3) through the joint-level module, recomputed from x, and the dif coupling
     between the frames of a clip."""
-    return _sgn_frames_bwd(x, wimg, wimg_t, dfeat, V, tape=False)
+    return _sgn_frames_bwd(_SGN, x, wimg, wimg_t, dfeat, V, (), tape=False)
 
 
 def sgn_sample_bwd(win, r, dout, seg):
@@ -1912,35 +1909,54 @@ SGN_WGRAD_STATS = dict(clip_bwd_tape=0, frames_bwd_tape=0, frames_wgrad=0, clip_
 # a batch whose tapes would be larger is processed in chunks of whole clips
 SGN_MAX_TAPE_BYTES = 512 << 20
 
+# What tells the two models of the family apart in the host code they share (the backward launches, the chunked image
+# backward, the fine-tuning Functions): the prefix of the C entries, the name in messages, and the counter dicts of the
+# plain and of the taping backward launches.  ``_SGN15`` stands with its counters further down.
+_SgnFamily = collections.namedtuple('_SgnFamily', 'prefix what bwd_stats wgrad_stats')
+_SGN = _SgnFamily('sgn', 'SGN', SGN_GRAD_STATS, SGN_WGRAD_STATS)
+
+
+def _sgn_layout(items):
+    """[(name, shape)] -> [(name, offset, shape)]: the sections of an image back to back, offsets in floats."""
+    out, o = [], 0
+    for name, shape in items:
+        out.append((name, o, shape))
+        o += math.prod(shape)
+    return out
+
+
+def _sgn_emb_sections(p):
+    """The two 1x1 layers of an input embedding under the prefix ``p``."""
+    return [(p + '1_w', (3, 64)), (p + '1_b', (64,)), (p + '2_w', (64, 64)), (p + '2_b', (64,))]
+
 
 def sgn_image_sections(V, seg, num_class):
     """The sections of the two folded weight images in their order (csrc/sgn_plan.h: SgnFramesW, SgnClipW) ->
     (frames, clip), each a list of (name, offset, shape)."""
-    def lay(items):
-        out, o = [], 0
-        for name, shape in items:
-            out.append((name, o, shape))
-            o += math.prod(shape)
-        return out
-    emb = lambda p: [(p + '1_w', (3, 64)), (p + '1_b', (64,)), (p + '2_w', (64, 64)), (p + '2_b', (64,))]  # noqa: E731
-    frames = lay([('aff', (4, V, 3))] + emb('je') + emb('de') + [('spa1', (V, 64)), ('g_w', (128, 512)), ('g_b', (512,)),
-                 ('c1_w', (256, 128)), ('c1_b', (128,)), ('c2_w', (256, 256)), ('c2_b', (256,)), ('c3_w', (512, 256)),
-                 ('c3_b', (256,))])
-    clip = lay([('tem1', (seg, 256)), ('t1_w', (768, 256)), ('t1_b', (256,)), ('t2_w', (256, 512)), ('t2_b', (512,)),
-                ('fc_w', (512, num_class)), ('fc_b', (num_class,))])
+    frames = _sgn_layout([('aff', (4, V, 3))] + _sgn_emb_sections('je') + _sgn_emb_sections('de')
+                         + [('spa1', (V, 64)), ('g_w', (128, 512)), ('g_b', (512,)), ('c1_w', (256, 128)), ('c1_b', (128,)),
+                            ('c2_w', (256, 256)), ('c2_b', (256,)), ('c3_w', (512, 256)), ('c3_b', (256,))])
+    clip = _sgn_layout([('tem1', (seg, 256)), ('t1_w', (768, 256)), ('t1_b', (256,)), ('t2_w', (256, 512)),
+                        ('t2_b', (512,)), ('fc_w', (512, num_class)), ('fc_b', (num_class,))])
     return frames, clip
 
 
-def sgn_image_forward_ref(x, wf, wc, V, seg, num_class):
-    """The tensor-code form of the fused SGN forward: x (N, seg, V*3) and the two flat folded images -> (logits, g),
-    differentiable in x, wf and wc.  The CPU route of SGNFineTuneFunction and the comparison of its image gradients."""
+def _sgn_ref_views(name, plan, x, wf, wc, V, seg, sections):
+    """The checks of the two tensor-code references (``name``: the one that was called, ``plan``: the header of its
+    layout) and the two flat images as their ``sections`` -> ({name: view} of the frames image, of the clip image)."""
     if x.dim() != 3 or x.shape[1] != seg or x.shape[2] != 3 * V:
-        raise ValueError(f"agcn_amd: sgn_image_forward_ref takes (N, {seg}, {3 * V}), got {tuple(x.shape)}")
-    fs, cs = sgn_image_sections(V, seg, num_class)
-    if wf.numel() != fs[-1][1] + math.prod(fs[-1][2]) or wc.numel() != cs[-1][1] + math.prod(cs[-1][2]):
-        raise ValueError("agcn_amd: sgn_image_forward_ref: the images do not have the sizes of csrc/sgn_plan.h")
-    f = {n: wf[o:o + math.prod(s)].reshape(s) for n, o, s in fs}
-    c = {n: wc[o:o + math.prod(s)].reshape(s) for n, o, s in cs}
+        raise ValueError(f"agcn_amd: {name} takes (N, {seg}, {3 * V}), got {tuple(x.shape)}")
+    views = []
+    for img, secs in zip((wf, wc), sections):
+        if img.numel() != secs[-1][1] + math.prod(secs[-1][2]):
+            raise ValueError(f"agcn_amd: {name}: the images do not have the sizes of {plan}")
+        views.append({n: img[o:o + math.prod(s)].reshape(s) for n, o, s in secs})
+    return views
+
+
+def _sgn_ref_input(x, f, V, seg, pos, vel):
+    """The input side both models share, from the views ``f`` of a frames image: the affine of the two DataNorms, the
+    embeddings under the prefixes ``pos`` (of x) and ``vel`` (of the frame difference), summed -> (N, seg, V, 64)."""
     relu = torch.relu
     N = x.shape[0]
     xr = x.reshape(N, seg, V, 3)
@@ -1949,8 +1965,17 @@ def sgn_image_forward_ref(x, wf, wc, V, seg, num_class):
     def emb(v, p):
         return relu(relu(v @ f[p + '1_w'] + f[p + '1_b']) @ f[p + '2_w'] + f[p + '2_b'])
 
-    dy = emb(xr * f['aff'][0] + f['aff'][1], 'je') + emb(dif * f['aff'][2] + f['aff'][3], 'de')
-    h = torch.cat([dy, f['spa1'].expand(N, seg, V, 64)], dim=3)
+    return emb(xr * f['aff'][0] + f['aff'][1], pos) + emb(dif * f['aff'][2] + f['aff'][3], vel)
+
+
+def sgn_image_forward_ref(x, wf, wc, V, seg, num_class):
+    """The tensor-code form of the fused SGN forward: x (N, seg, V*3) and the two flat folded images -> (logits, g),
+    differentiable in x, wf and wc.  The CPU route of SGNFineTuneFunction and the comparison of its image gradients."""
+    f, c = _sgn_ref_views("sgn_image_forward_ref", "csrc/sgn_plan.h", x, wf, wc, V, seg,
+                          sgn_image_sections(V, seg, num_class))
+    relu = torch.relu
+    N = x.shape[0]
+    h = torch.cat([_sgn_ref_input(x, f, V, seg, 'je', 'de'), f['spa1'].expand(N, seg, V, 64)], dim=3)
     gg = h @ f['g_w'] + f['g_b']
     g = torch.softmax(gg[..., :256] @ gg[..., 256:].transpose(-1, -2), dim=-1)
     for l in ('c1', 'c2', 'c3'):
@@ -1972,20 +1997,21 @@ def _tape(query, args, like, what):
 def sgn_clip_bwd_tape(feat, wimg, wimg_t, dlogits):
     """``sgn_clip_bwd`` (the same dfeat bits) that also writes the clip tape (csrc/sgn_wgrad_plan.h: SgnClipTape) ->
     (dfeat, tape)."""
-    return _sgn_clip_bwd(feat, wimg, wimg_t, dlogits, tape=True)
+    return _sgn_clip_bwd(_SGN, feat, wimg, wimg_t, dlogits, (), tape=True)
 
 
 def sgn_frames_bwd_tape(x, wimg, wimg_t, dfeat, V):
     """``sgn_frames_bwd`` (the same dx bits) that also writes the frames tape (SgnFramesTape) -> (dx, tape)."""
-    return _sgn_frames_bwd(x, wimg, wimg_t, dfeat, V, tape=True)
+    return _sgn_frames_bwd(_SGN, x, wimg, wimg_t, dfeat, V, (), tape=True)
 
 
-def _sgn_wgrad_ws(N, seg, V, num_class, rows_per_split, like):
+def _sgn_wgrad_ws(fam, args, rows_per_split, like):
+    """The workspace of a reduction of the family ``fam``; ``args``: its size query's, without ``rows_per_split``."""
     if rows_per_split < 0:
         raise ValueError(f"agcn_amd: rows_per_split must be >= 0, got {rows_per_split}")
-    n = _L().agcn_sgn_wgrad_workspace(N, seg, V, num_class, rows_per_split)
+    n = getattr(_L(), f"agcn_{fam.prefix}_wgrad_workspace")(*args, rows_per_split)
     if n == 0:
-        raise ValueError(f"agcn_amd: SGN parameter gradients: {(N, seg, V, num_class)} is outside the kernels' domain")
+        raise ValueError(f"agcn_amd: {fam.what} parameter gradients: {args} is outside the kernels' domain")
     return _empty((n // 4,), like)
 
 
@@ -1994,7 +2020,7 @@ def sgn_frames_wgrad(x, wimg, tape, V, num_class, rows_per_split=0):
     N, seg, _ = x.shape
     if tape.numel() < _L().agcn_sgn_frames_tape_floats(N, seg, V) or x.shape[2] != 3 * V:
         raise ValueError(f"agcn_amd: sgn_frames_wgrad: a tape of {tape.numel()} floats is not the tape of {tuple(x.shape)}")
-    ws = _sgn_wgrad_ws(N, seg, V, num_class, rows_per_split, x)
+    ws = _sgn_wgrad_ws(_SGN, (N, seg, V, num_class), rows_per_split, x)
     d_w = _empty((wimg.numel(),), x)
     _lib.call("agcn_sgn_frames_wgrad", x, wimg, tape, d_w, ws, ws.numel() * 4, N, seg, V, rows_per_split)
     SGN_WGRAD_STATS['frames_wgrad'] += 1
@@ -2007,39 +2033,74 @@ def sgn_clip_wgrad(tape, dfeat, dlogits, wimg, V, rows_per_split=0):
     nc = dlogits.shape[1]
     if tape.numel() < _L().agcn_sgn_clip_tape_floats(N, seg, nc) or tuple(dlogits.shape) != (N, nc):
         raise ValueError(f"agcn_amd: sgn_clip_wgrad: a tape of {tape.numel()} floats is not the tape of {tuple(dfeat.shape)}")
-    ws = _sgn_wgrad_ws(N, seg, V, nc, rows_per_split, dfeat)
+    ws = _sgn_wgrad_ws(_SGN, (N, seg, V, nc), rows_per_split, dfeat)
     d_w = _empty((wimg.numel(),), dfeat)
     _lib.call("agcn_sgn_clip_wgrad", tape, dfeat, dlogits, d_w, ws, ws.numel() * 4, N, seg, nc, rows_per_split)
     SGN_WGRAD_STATS['clip_wgrad'] += 1
     return d_w
 
 
+def _sgn_tape_chunk(fam, args, N, frames_floats, clip_floats, max_tape_bytes, most):
+    """``sgn_tape_chunk`` / ``sgn15_tape_chunk`` from the floats of the two tapes of one clip; at most ``most`` clips."""
+    if frames_floats == 0 or clip_floats == 0:
+        raise ValueError(f"agcn_amd: {fam.what} parameter gradients: {args} is outside the kernels' domain")
+    return max(1, min(N, most, int(max_tape_bytes) // (4 * (frames_floats + clip_floats))))
+
+
 def sgn_tape_chunk(N, seg, V, num_class, max_tape_bytes):
     """Clips per chunk: as many whole clips as fit ``max_tape_bytes`` of tape (both tapes are linear in the clips), at
     least one."""
-    per = 4 * (_L().agcn_sgn_frames_tape_floats(1, seg, V) + _L().agcn_sgn_clip_tape_floats(1, seg, num_class))
-    if per == 0:
-        raise ValueError(f"agcn_amd: SGN parameter gradients: {(seg, V, num_class)} is outside the kernels' domain")
-    return max(1, min(N, int(max_tape_bytes) // per))
+    return _sgn_tape_chunk(_SGN, (seg, V, num_class), N, _L().agcn_sgn_frames_tape_floats(1, seg, V),
+                           _L().agcn_sgn_clip_tape_floats(1, seg, num_class), max_tape_bytes, N)
 
 
-def _sgn_image_backward(x, feat, wf, wc, wf_t, wc_t, dlogits, V, rows_per_split, max_tape_bytes):
-    """-> (dx, d_wf, d_wc): chunks of whole clips, the chunks' image gradients added in chunk order."""
-    N, seg, _ = x.shape
-    nc = dlogits.shape[1]
-    chunk = sgn_tape_chunk(N, seg, V, nc, max_tape_bytes)
+def _sgn_chunked_backward(step, chunk, x, feat, dlogits):
+    """The image backward of both models in chunks of ``chunk`` whole clips -> (dx, d_wf, d_wc).  ``step(x, feat,
+    dlogits)`` of one chunk -> (dx, d_wf, d_wc) is the family's: the taping clip backward, the taping frames backward and
+    the two reductions; its tapes are gone when it returns.  dx is concatenated in clip order and the chunks' image
+    gradients are added in ascending chunk order."""
     dxs, d_wf, d_wc = [], None, None
-    for n0 in range(0, N, chunk):
-        xs, fe, dl = x[n0:n0 + chunk], feat[n0:n0 + chunk], dlogits[n0:n0 + chunk]
-        dfeat, ctape = sgn_clip_bwd_tape(fe, wc, wc_t, dl)
-        dx, ftape = sgn_frames_bwd_tape(xs, wf, wf_t, dfeat, V)
-        gf = sgn_frames_wgrad(xs, wf, ftape, V, nc, rows_per_split)
-        gc = sgn_clip_wgrad(ctape, dfeat, dl, wc, V, rows_per_split)
-        del ftape, ctape
+    for n0 in range(0, x.shape[0], chunk):
+        dx, gf, gc = step(x[n0:n0 + chunk], feat[n0:n0 + chunk], dlogits[n0:n0 + chunk])
         dxs.append(dx)
         d_wf = gf if d_wf is None else d_wf + gf
         d_wc = gc if d_wc is None else d_wc + gc
     return (dxs[0] if len(dxs) == 1 else torch.cat(dxs)), d_wf, d_wc
+
+
+def _sgn_image_backward(x, feat, wf, wc, wf_t, wc_t, dlogits, V, rows_per_split, max_tape_bytes):
+    """-> (dx, d_wf, d_wc) of base SGN, chunked under ``max_tape_bytes`` of tape."""
+    nc = dlogits.shape[1]
+
+    def step(xs, fe, dl):
+        dfeat, ctape = sgn_clip_bwd_tape(fe, wc, wc_t, dl)
+        dx, ftape = sgn_frames_bwd_tape(xs, wf, wf_t, dfeat, V)
+        return (dx, sgn_frames_wgrad(xs, wf, ftape, V, nc, rows_per_split),
+                sgn_clip_wgrad(ctape, dfeat, dl, wc, V, rows_per_split))
+
+    return _sgn_chunked_backward(step, sgn_tape_chunk(x.shape[0], x.shape[1], V, nc, max_tape_bytes), x, feat, dlogits)
+
+
+def _sgn_finetune_ref(ctx, ref, x, wf, wc):
+    """The CPU route of the two fine-tuning Functions: ``ref(x, wf, wc)``, a tensor-code image reference with the logits
+    first, under ``enable_grad`` on fresh leaves, kept for ``_sgn_finetune_backward`` -> its outputs, detached."""
+    with torch.enable_grad():
+        leaves = [t.detach().requires_grad_(True) for t in (x, wf, wc)]
+        out = ref(*leaves)
+    ctx.ref = (leaves, out[0])
+    return tuple(t.detach() for t in out)
+
+
+def _sgn_finetune_backward(ctx, image_backward, dlogits):
+    """The backward of the two fine-tuning Functions -> (dx or None, d_wf, d_wc): autograd of the kept reference on the
+    CPU route, otherwise the family's ``image_backward`` on the saved tensors and ``ctx.geometry``."""
+    if ctx.ref is not None:
+        leaves, logits = ctx.ref
+        with torch.enable_grad():
+            dx, d_wf, d_wc = torch.autograd.grad(logits, leaves, dlogits)
+    else:
+        dx, d_wf, d_wc = image_backward(*ctx.saved_tensors, dlogits.contiguous(), *ctx.geometry, 0, SGN_MAX_TAPE_BYTES)
+    return (dx if ctx.needs_input_grad[0] else None), d_wf, d_wc
 
 
 def sgn_image_gradients(x, wf, wc, wf_t, wc_t, cot, V, num_class, rows_per_split=0, max_tape_bytes=SGN_MAX_TAPE_BYTES):
@@ -2062,35 +2123,73 @@ class SGNFineTuneFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, wf, wc, wf_t, wc_t, V, num_class):
-        ctx.V = V
+        ctx.geometry = (V,)
         if not x.is_cuda:
-            with torch.enable_grad():
-                leaves = [t.detach().requires_grad_(True) for t in (x, wf, wc)]
-                logits, g = sgn_image_forward_ref(*leaves, V, x.shape[1], num_class)
-            ctx.ref = (leaves, logits)
-            g = g.detach()
-            ctx.mark_non_differentiable(g)
-            return logits.detach(), g
-        x = x.contiguous()
-        feat, g = sgn_frames(x, wf.detach(), V)
-        logits = sgn_clip(feat, wc.detach(), num_class)
-        ctx.ref = None
-        ctx.save_for_backward(x, feat, wf, wc, wf_t, wc_t)
+            logits, g = _sgn_finetune_ref(ctx, lambda *leaves: sgn_image_forward_ref(*leaves, V, x.shape[1], num_class),
+                                          x, wf, wc)
+        else:
+            x = x.contiguous()
+            feat, g = sgn_frames(x, wf.detach(), V)
+            logits = sgn_clip(feat, wc.detach(), num_class)
+            ctx.ref = None
+            ctx.save_for_backward(x, feat, wf, wc, wf_t, wc_t)
         ctx.mark_non_differentiable(g)
         return logits, g
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dlogits, _dg):
-        if ctx.ref is not None:
-            leaves, logits = ctx.ref
-            with torch.enable_grad():
-                dx, d_wf, d_wc = torch.autograd.grad(logits, leaves, dlogits)
-        else:
-            x, feat, wf, wc, wf_t, wc_t = ctx.saved_tensors
-            dx, d_wf, d_wc = _sgn_image_backward(x, feat, wf, wc, wf_t, wc_t, dlogits.contiguous(), ctx.V, 0,
-                                                 SGN_MAX_TAPE_BYTES)
-        return (dx if ctx.needs_input_grad[0] else None), d_wf, d_wc, None, None, None, None
+        return _sgn_finetune_backward(ctx, _sgn_image_backward, dlogits) + (None,) * 4
+
+
+# ---- what model/sgn.py and model/sgn_v15.py share around these routes ----
+def _sgn_t(w):
+    """Conv / linear weight (Cout, Cin, ...) -> the (Cin, Cout) row-major image the kernels read."""
+    return w.flatten(1).t()
+
+
+def sgn_input_gradient(x, wf, wc, wf_t, wc_t, cot, V, num_class):
+    """The fused eval forward of base SGN and dx = d sum(logits * cot) / dx as four launches -> (logits, g, dx)."""
+    with torch.no_grad():
+        x = x.detach().contiguous()
+        feat, g = sgn_frames(x, wf, V)
+        logits = sgn_clip(feat, wc, num_class)
+        dfeat = sgn_clip_bwd(feat, wc, wc_t, cot.detach().to(logits).contiguous())
+        return logits, g, sgn_frames_bwd(x, wf, wf_t, dfeat, V)
+
+
+def sgn_composition_gradients(forward_tensor, x, cot, params=()):
+    """The eval-mode gradients of sum(logits * cot) by torch autograd on a model's tensor-code composition
+    ``forward_tensor(x)`` -> (logits, second output) -> (logits, second output, dx, one gradient or None per parameter
+    of ``params``), all detached.  The second output is a tensor (base SGN's g) or SGN v15's dict of tensors, lists of
+    tensors and None."""
+    with torch.enable_grad():
+        xg = x.detach().requires_grad_(True)
+        logits, aux = forward_tensor(xg)
+        grads = torch.autograd.grad((logits * cot.detach().to(logits)).sum(), [xg] + list(params), allow_unused=True)
+    if isinstance(aux, dict):
+        aux = {k: ([a.detach() for a in v] if isinstance(v, list) else None if v is None else v.detach())
+               for k, v in aux.items()}
+    else:
+        aux = aux.detach()
+    return logits.detach(), aux, grads[0], grads[1:]
+
+
+def sgn_named_gradients(named, grads):
+    """[(name, parameter)] and one gradient or None each -> {name: gradient}, zeros where autograd found no path."""
+    return {n: (torch.zeros_like(p) if g is None else g) for (n, p), g in zip(named, grads)}
+
+
+def sgn_fold_gradients(images, image_grads, named):
+    """The gradients of the folded images ``images`` = (wf, wc), built in grad mode by the model's fold, taken through
+    that fold to the trainable parameters ``named`` = [(name, parameter)] -> {name: gradient}.  An image none of whose
+    parameters asks for a gradient (head-only fine-tuning) carries no graph and is skipped; a parameter without a path
+    to the images gets zeros; nothing trainable gives {}."""
+    params = [p for _, p in named]
+    live = [(w, g) for w, g in zip(images, image_grads) if w.requires_grad]
+    grads = (torch.autograd.grad([w for w, _ in live], params, [g for _, g in live], allow_unused=True)
+             if live else (None,) * len(params))
+    return sgn_named_gradients(named, grads)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -2250,21 +2349,15 @@ def sgn15_image_sections(V, seg, num_class, spatial, temporal):
     (din -> dout) is qkv_w (din, 3 inner) = [Wq d_head^-1/2 | Wk | Wv] with the attention BatchNorm folded, qkv_b, o_w
     (inner, din), o_b, f1_w (din, ff) with the feed-forward BatchNorm folded, f1_b, f2_w = [W2 ; Wr] (ff + din, dout),
     f2_b = b2 + br."""
-    def lay(items):
-        out, o = [], 0
-        for name, shape in items:
-            out.append((name, o, shape))
-            o += math.prod(shape)
-        return out
-
     def block(p, din, dout, heads, d_head, ff):
         inner = heads * d_head
         return [(p + 'qkv_w', (din, 3 * inner)), (p + 'qkv_b', (3 * inner,)), (p + 'o_w', (inner, din)), (p + 'o_b', (din,)),
                 (p + 'f1_w', (din, ff)), (p + 'f1_b', (ff,)), (p + 'f2_w', (ff + din, dout)), (p + 'f2_b', (dout,))]
 
-    emb = lambda p: [(p + '1_w', (3, 64)), (p + '1_b', (64,)), (p + '2_w', (64, 64)), (p + '2_b', (64,))]  # noqa: E731
-    frames = lay([('aff', (4, V, 3))] + emb('pe') + emb('ve') + [('spa', (V, 64))] + block('s_', 128, 256, *spatial))
-    clip = lay([('tem', (seg, 256))] + block('t_', 256, 512, *temporal) + [('fc_w', (512, num_class)), ('fc_b', (num_class,))])
+    frames = _sgn_layout([('aff', (4, V, 3))] + _sgn_emb_sections('pe') + _sgn_emb_sections('ve') + [('spa', (V, 64))]
+                         + block('s_', 128, 256, *spatial))
+    clip = _sgn_layout([('tem', (seg, 256))] + block('t_', 256, 512, *temporal)
+                       + [('fc_w', (512, num_class)), ('fc_b', (num_class,))])
     return frames, clip
 
 
@@ -2312,11 +2405,7 @@ def sgn15_bwd_image_sections(spatial, temporal):
     (csrc/sgn_v15_bwd_plan.h: Sgn15FramesWT, Sgn15ClipWT) -> (frames, clip), each a list of (name, offset, shape, source):
     the section is the transpose of section ``source`` of the forward image (``sgn15_image_sections``)."""
     def lay(items):
-        out, o = [], 0
-        for src, shape in items:
-            out.append((src + '_t', o, shape, src))
-            o += math.prod(shape)
-        return out
+        return [(src + '_t', o, shape, src) for src, o, shape in _sgn_layout(items)]
 
     def block(p, din, dout, heads, d_head, ff):
         inner = heads * d_head
@@ -2342,52 +2431,22 @@ def sgn15_clip_bwd(feat, wimg, wimg_t, dlogits, heads, d_head, ff):
     """d logits (N, num_class) -> d feat (N, seg, 256) through fc, the maximum over the frames and the temporal block of
     SGN v15, recomputed from feat (N, seg, 256) as ``sgn15_frames`` returns it.  wimg: the forward clip image, wimg_t: the
     transposed one."""
-    if feat.dim() != 3 or feat.shape[2] != 256:
-        raise ValueError(f"agcn_amd: sgn15_clip_bwd takes (N, seg, 256), got {tuple(feat.shape)}")
-    N, seg, _ = feat.shape
-    if dlogits.dim() != 2 or dlogits.shape[0] != N:
-        raise ValueError(f"agcn_amd: sgn15_clip_bwd takes dlogits ({N}, num_class), got {tuple(dlogits.shape)}")
-    dfeat = _empty((N, seg, 256), feat)
-    _lib.call("agcn_sgn15_clip_bwd", feat, wimg, wimg.numel(), wimg_t, wimg_t.numel(), dlogits, dfeat, N, seg,
-              dlogits.shape[1], heads, d_head, ff)
-    SGN15_BWD_STATS['clip_bwd'] += 1
-    return dfeat
+    return _sgn_clip_bwd(_SGN15, feat, wimg, wimg_t, dlogits, (heads, d_head, ff), tape=False)
 
 
 def sgn15_frames_bwd(x, wimg, wimg_t, dfeat, V, heads, d_head, ff):
     """d feat (N, seg, 256) -> dx (N, seg, V*3) through the maximum over the joints, the spatial block and the input side
     of SGN v15, recomputed from x, and the velocity's coupling between the frames of a clip."""
-    if x.dim() != 3 or x.shape[2] != 3 * V:
-        raise ValueError(f"agcn_amd: sgn15_frames_bwd takes (N, seg, {3 * V}), got {tuple(x.shape)}")
-    N, seg, _ = x.shape
-    if tuple(dfeat.shape) != (N, seg, 256):
-        raise ValueError(f"agcn_amd: sgn15_frames_bwd takes dfeat ({N}, {seg}, 256), got {tuple(dfeat.shape)}")
-    dx = _empty((N, seg, 3 * V), x)
-    ws = _empty((max(1, _L().agcn_sgn15_frames_bwd_workspace(N, seg, V) // 4),), x)
-    _lib.call("agcn_sgn15_frames_bwd", x, wimg, wimg.numel(), wimg_t, wimg_t.numel(), dfeat, dx, ws, ws.numel() * 4, N,
-              seg, V, heads, d_head, ff)
-    SGN15_BWD_STATS['frames_bwd'] += 1
-    return dx
+    return _sgn_frames_bwd(_SGN15, x, wimg, wimg_t, dfeat, V, (heads, d_head, ff), tape=False)
 
 
 def sgn15_forward_ref(x, wf, wc, V, seg, num_class, spatial, temporal):
     """The tensor-code form of the fused SGN v15 forward, reading ONLY the two flat folded images: the CPU-checkable
     specification of the fold and the layout.  x (N, seg, V*3) -> (logits, feat (N, seg, 256) as ``sgn15_frames`` returns
     it, spatial attn (N*seg, heads, V, V), temporal attn (N, heads, seg, seg))."""
-    if x.dim() != 3 or x.shape[1] != seg or x.shape[2] != 3 * V:
-        raise ValueError(f"agcn_amd: sgn15_forward_ref takes (N, {seg}, {3 * V}), got {tuple(x.shape)}")
-    fs, cs = sgn15_image_sections(V, seg, num_class, spatial, temporal)
-    if wf.numel() != fs[-1][1] + math.prod(fs[-1][2]) or wc.numel() != cs[-1][1] + math.prod(cs[-1][2]):
-        raise ValueError("agcn_amd: sgn15_forward_ref: the images do not have the sizes of csrc/sgn_v15_plan.h")
-    f = {n: wf[o:o + math.prod(s)].reshape(s) for n, o, s in fs}
-    c = {n: wc[o:o + math.prod(s)].reshape(s) for n, o, s in cs}
-    relu = torch.relu
+    f, c = _sgn_ref_views("sgn15_forward_ref", "csrc/sgn_v15_plan.h", x, wf, wc, V, seg,
+                          sgn15_image_sections(V, seg, num_class, spatial, temporal))
     N = x.shape[0]
-    xr = x.reshape(N, seg, V, 3)
-    dif = torch.cat([xr.new_zeros(N, 1, V, 3), xr[:, 1:] - xr[:, :-1]], dim=1)
-
-    def emb(v, p):
-        return relu(relu(v @ f[p + '1_w'] + f[p + '1_b']) @ f[p + '2_w'] + f[p + '2_b'])
 
     def block(t, w, p, heads, d_head):
         """t (B, R, din)"""
@@ -2395,11 +2454,10 @@ def sgn15_forward_ref(x, wf, wc, V, seg, num_class, spatial, temporal):
         q, k, v = ((t @ w[p + 'qkv_w'] + w[p + 'qkv_b']).reshape(B, R, 3, heads, d_head).permute(2, 0, 3, 1, 4))
         a = torch.softmax(q @ k.transpose(-1, -2), dim=-1)                       # d_head^-1/2 is folded into q
         t1 = (a @ v).transpose(1, 2).reshape(B, R, heads * d_head) @ w[p + 'o_w'] + w[p + 'o_b'] + t
-        hid = relu(t1 @ w[p + 'f1_w'] + w[p + 'f1_b'])
+        hid = torch.relu(t1 @ w[p + 'f1_w'] + w[p + 'f1_b'])
         return torch.cat([hid, t1], dim=2) @ w[p + 'f2_w'] + w[p + 'f2_b'], a
 
-    h = torch.cat([emb(xr * f['aff'][0] + f['aff'][1], 'pe') + emb(dif * f['aff'][2] + f['aff'][3], 've'),
-                   f['spa'].expand(N, seg, V, 64)], dim=3)
+    h = torch.cat([_sgn_ref_input(x, f, V, seg, 'pe', 've'), f['spa'].expand(N, seg, V, 64)], dim=3)
     y, sa = block(h.reshape(N * seg, V, 128), f, 's_', spatial[0], spatial[1])
     feat = y.reshape(N, seg, V, 256).amax(2)
     z, ta = block(feat + c['tem'], c, 't_', temporal[0], temporal[1])
@@ -2417,48 +2475,18 @@ SGN15_WGRAD_STATS = dict(clip_bwd_tape=0, frames_bwd_tape=0, frames_wgrad=0, cli
 # None, or a callable(label) that tools/sgn_v15_finetune.py sets to record a device event behind the taping launches
 # ('tape') and behind the reductions ('reduce') of every chunk
 SGN15_WGRAD_MARK = None
+_SGN15 = _SgnFamily('sgn15', 'SGN v15', SGN15_BWD_STATS, SGN15_WGRAD_STATS)
 
 
 def sgn15_clip_bwd_tape(feat, wimg, wimg_t, dlogits, heads, d_head, ff):
     """``sgn15_clip_bwd`` (the same dfeat bits) that also writes the clip tape (csrc/sgn_v15_wgrad_plan.h: Sgn15ClipTape)
     -> (dfeat, tape)."""
-    if feat.dim() != 3 or feat.shape[2] != 256:
-        raise ValueError(f"agcn_amd: sgn15_clip_bwd_tape takes (N, seg, 256), got {tuple(feat.shape)}")
-    N, seg, _ = feat.shape
-    if dlogits.dim() != 2 or dlogits.shape[0] != N or dlogits.shape[1] < 1:
-        raise ValueError(f"agcn_amd: sgn15_clip_bwd_tape takes dlogits ({N}, num_class), got {tuple(dlogits.shape)}")
-    nc = dlogits.shape[1]
-    tp = _tape(_L().agcn_sgn15_clip_tape_floats, (N, seg, nc, heads, d_head, ff), feat, "sgn15_clip_bwd_tape")
-    dfeat = _empty((N, seg, 256), feat)
-    _lib.call("agcn_sgn15_clip_bwd_tape", feat, wimg, wimg.numel(), wimg_t, wimg_t.numel(), dlogits, dfeat, N, seg, nc,
-              heads, d_head, ff, tp, tp.numel())
-    SGN15_WGRAD_STATS['clip_bwd_tape'] += 1
-    return dfeat, tp
+    return _sgn_clip_bwd(_SGN15, feat, wimg, wimg_t, dlogits, (heads, d_head, ff), tape=True)
 
 
 def sgn15_frames_bwd_tape(x, wimg, wimg_t, dfeat, V, heads, d_head, ff):
     """``sgn15_frames_bwd`` (the same dx bits) that also writes the frames tape (Sgn15FramesTape) -> (dx, tape)."""
-    if x.dim() != 3 or x.shape[2] != 3 * V:
-        raise ValueError(f"agcn_amd: sgn15_frames_bwd_tape takes (N, seg, {3 * V}), got {tuple(x.shape)}")
-    N, seg, _ = x.shape
-    if tuple(dfeat.shape) != (N, seg, 256):
-        raise ValueError(f"agcn_amd: sgn15_frames_bwd_tape takes dfeat ({N}, {seg}, 256), got {tuple(dfeat.shape)}")
-    tp = _tape(_L().agcn_sgn15_frames_tape_floats, (N, seg, V, heads, d_head, ff), x, "sgn15_frames_bwd_tape")
-    dx = _empty((N, seg, 3 * V), x)
-    ws = _empty((max(1, _L().agcn_sgn15_frames_bwd_workspace(N, seg, V) // 4),), x)
-    _lib.call("agcn_sgn15_frames_bwd_tape", x, wimg, wimg.numel(), wimg_t, wimg_t.numel(), dfeat, dx, ws, ws.numel() * 4, N,
-              seg, V, heads, d_head, ff, tp, tp.numel())
-    SGN15_WGRAD_STATS['frames_bwd_tape'] += 1
-    return dx, tp
-
-
-def _sgn15_wgrad_ws(args, rows_per_split, like):
-    if rows_per_split < 0:
-        raise ValueError(f"agcn_amd: rows_per_split must be >= 0, got {rows_per_split}")
-    n = _L().agcn_sgn15_wgrad_workspace(*args, rows_per_split)
-    if n == 0:
-        raise ValueError(f"agcn_amd: SGN v15 parameter gradients: {args} is outside the kernels' domain")
-    return _empty((n // 4,), like)
+    return _sgn_frames_bwd(_SGN15, x, wimg, wimg_t, dfeat, V, (heads, d_head, ff), tape=True)
 
 
 def sgn15_frames_wgrad(x, wimg, tape, V, heads, d_head, ff, rows_per_split=0):
@@ -2466,7 +2494,7 @@ def sgn15_frames_wgrad(x, wimg, tape, V, heads, d_head, ff, rows_per_split=0):
     N, seg, _ = x.shape
     if x.shape[2] != 3 * V or tape.numel() < _L().agcn_sgn15_frames_tape_floats(N, seg, V, heads, d_head, ff):
         raise ValueError(f"agcn_amd: sgn15_frames_wgrad: a tape of {tape.numel()} floats is not the tape of {tuple(x.shape)}")
-    ws = _sgn15_wgrad_ws((N, seg, V, 0, heads, d_head, ff), rows_per_split, x)
+    ws = _sgn_wgrad_ws(_SGN15, (N, seg, V, 0, heads, d_head, ff), rows_per_split, x)
     d_w = _empty((wimg.numel(),), x)
     _lib.call("agcn_sgn15_frames_wgrad", x, tape, tape.numel(), d_w, d_w.numel(), ws, ws.numel() * 4, N, seg, V, heads,
               d_head, ff, rows_per_split)
@@ -2479,7 +2507,7 @@ def sgn15_clip_wgrad(tape, dlogits, wimg, seg, heads, d_head, ff, rows_per_split
     N, nc = dlogits.shape
     if tape.numel() < _L().agcn_sgn15_clip_tape_floats(N, seg, nc, heads, d_head, ff):
         raise ValueError(f"agcn_amd: sgn15_clip_wgrad: a tape of {tape.numel()} floats is not the tape of {(N, seg, nc)}")
-    ws = _sgn15_wgrad_ws((N, seg, 0, nc, heads, d_head, ff), rows_per_split, dlogits)
+    ws = _sgn_wgrad_ws(_SGN15, (N, seg, 0, nc, heads, d_head, ff), rows_per_split, dlogits)
     d_w = _empty((wimg.numel(),), dlogits)
     _lib.call("agcn_sgn15_clip_wgrad", tape, tape.numel(), dlogits, d_w, d_w.numel(), ws, ws.numel() * 4, N, seg, nc, heads,
               d_head, ff, rows_per_split)
@@ -2490,22 +2518,16 @@ def sgn15_clip_wgrad(tape, dlogits, wimg, seg, heads, d_head, ff, rows_per_split
 def sgn15_tape_chunk(N, seg, V, num_class, spatial, temporal, max_tape_bytes):
     """Clips per chunk: as many whole clips as fit ``max_tape_bytes`` of tape (both tapes are linear in the clips), at
     least one and at most ``SGN15_MAX_CLIPS``."""
-    nf = _L().agcn_sgn15_frames_tape_floats(1, seg, V, *spatial)
-    nc = _L().agcn_sgn15_clip_tape_floats(1, seg, num_class, *temporal)
-    per = 4 * (nf + nc)
-    if nf == 0 or nc == 0:
-        raise ValueError(f"agcn_amd: SGN v15 parameter gradients: {(seg, V, num_class, spatial, temporal)} is outside the "
-                         f"kernels' domain")
-    return max(1, min(N, SGN15_MAX_CLIPS, int(max_tape_bytes) // per))
+    return _sgn_tape_chunk(_SGN15, (seg, V, num_class, spatial, temporal), N,
+                           _L().agcn_sgn15_frames_tape_floats(1, seg, V, *spatial),
+                           _L().agcn_sgn15_clip_tape_floats(1, seg, num_class, *temporal), max_tape_bytes, SGN15_MAX_CLIPS)
 
 
 def _sgn15_image_backward(x, feat, wf, wc, wf_t, wc_t, dlogits, V, spatial, temporal, rows_per_split, max_tape_bytes):
-    """-> (dx, d_wf, d_wc): chunks of whole clips, the chunks' image gradients added in ascending chunk order."""
-    N, seg, _ = x.shape
-    chunk = sgn15_tape_chunk(N, seg, V, dlogits.shape[1], spatial, temporal, max_tape_bytes)
-    dxs, d_wf, d_wc = [], None, None
-    for n0 in range(0, N, chunk):
-        xs, fe, dl = x[n0:n0 + chunk], feat[n0:n0 + chunk], dlogits[n0:n0 + chunk]
+    """-> (dx, d_wf, d_wc) of SGN v15, chunked under ``max_tape_bytes`` of tape and ``SGN15_MAX_CLIPS``."""
+    seg = x.shape[1]
+
+    def step(xs, fe, dl):
         dfeat, ctape = sgn15_clip_bwd_tape(fe, wc, wc_t, dl, *temporal)
         dx, ftape = sgn15_frames_bwd_tape(xs, wf, wf_t, dfeat, V, *spatial)
         if SGN15_WGRAD_MARK:
@@ -2514,21 +2536,36 @@ def _sgn15_image_backward(x, feat, wf, wc, wf_t, wc_t, dlogits, V, spatial, temp
         gc = sgn15_clip_wgrad(ctape, dl, wc, seg, *temporal, rows_per_split=rows_per_split)
         if SGN15_WGRAD_MARK:
             SGN15_WGRAD_MARK('reduce')
-        del ftape, ctape
-        dxs.append(dx)
-        d_wf = gf if d_wf is None else d_wf + gf
-        d_wc = gc if d_wc is None else d_wc + gc
-    return (dxs[0] if len(dxs) == 1 else torch.cat(dxs)), d_wf, d_wc
+        return dx, gf, gc
+
+    chunk = sgn15_tape_chunk(x.shape[0], seg, V, dlogits.shape[1], spatial, temporal, max_tape_bytes)
+    return _sgn_chunked_backward(step, chunk, x, feat, dlogits)
 
 
-def _sgn15_fused_forward(x, wf, wc, V, num_class, spatial, temporal):
-    """The two forward launches per chunk of at most ``SGN15_MAX_CLIPS`` clips -> (logits, feat)."""
-    feats, logits = [], []
-    for lo in range(0, x.shape[0], SGN15_MAX_CLIPS):
-        feat, _ = sgn15_frames(x[lo:lo + SGN15_MAX_CLIPS], wf, V, *spatial)
-        feats.append(feat)
-        logits.append(sgn15_clip(feat, wc, num_class, *temporal)[0])
-    return (logits[0], feats[0]) if len(feats) == 1 else (torch.cat(logits), torch.cat(feats))
+def sgn15_fused_forward(x, wf, wc, V, num_class, spatial, temporal, want_attn=False):
+    """The two forward launches per chunk of at most ``SGN15_MAX_CLIPS`` whole clips (a clip's result does not depend on
+    its batch) -> (logits, feat, spatial attn or None, temporal attn or None)."""
+    parts = []
+    for lo in range(0, x.shape[0], SGN15_MAX_CLIPS):      # one pair of launches unless the batch exceeds their limit
+        feat, sa = sgn15_frames(x[lo:lo + SGN15_MAX_CLIPS], wf, V, *spatial, want_attn=want_attn)
+        logits, ta = sgn15_clip(feat, wc, num_class, *temporal, want_attn=want_attn)
+        parts.append((logits, feat, sa, ta))
+    return parts[0] if len(parts) == 1 else tuple(None if p[0] is None else torch.cat(p) for p in zip(*parts))
+
+
+def sgn15_input_gradient(x, wf, wc, wf_t, wc_t, cot, V, num_class, spatial, temporal, want_attn=False):
+    """The fused eval forward of SGN v15 and dx = d sum(logits * cot) / dx, the two backward launches over the forward's
+    chunks of clips -> (logits, spatial attn or None, temporal attn or None, dx)."""
+    with torch.no_grad():
+        x = x.detach()
+        cot = cot.detach().to(x).contiguous()
+        logits, feat, sa, ta = sgn15_fused_forward(x, wf, wc, V, num_class, spatial, temporal, want_attn)
+        dxs = []
+        for lo in range(0, x.shape[0], SGN15_MAX_CLIPS):
+            hi = lo + SGN15_MAX_CLIPS
+            dfeat = sgn15_clip_bwd(feat[lo:hi], wc, wc_t, cot[lo:hi], *temporal)
+            dxs.append(sgn15_frames_bwd(x[lo:hi], wf, wf_t, dfeat, V, *spatial))
+        return logits, sa, ta, dxs[0] if len(dxs) == 1 else torch.cat(dxs)
 
 
 def sgn15_image_gradients(x, wf, wc, wf_t, wc_t, cot, V, num_class, spatial, temporal, rows_per_split=0,
@@ -2538,7 +2575,7 @@ def sgn15_image_gradients(x, wf, wc, wf_t, wc_t, cot, V, num_class, spatial, tem
     whole clips under both ``max_tape_bytes`` of tape and ``SGN15_MAX_CLIPS``."""
     with torch.no_grad():
         x = x.detach().contiguous()
-        logits, feat = _sgn15_fused_forward(x, wf, wc, V, num_class, spatial, temporal)
+        logits, feat, _, _ = sgn15_fused_forward(x, wf, wc, V, num_class, spatial, temporal)
         cot = cot.detach().to(logits).contiguous()
         if tuple(cot.shape) != tuple(logits.shape):
             raise ValueError(f"agcn_amd: sgn15_image_gradients takes cot {tuple(logits.shape)}, got {tuple(cot.shape)}")
@@ -2555,13 +2592,10 @@ class SGN15FineTuneFunction(torch.autograd.Function):
     def forward(ctx, x, wf, wc, wf_t, wc_t, V, num_class, spatial, temporal):
         ctx.geometry = (V, spatial, temporal)
         if not x.is_cuda:
-            with torch.enable_grad():
-                leaves = [t.detach().requires_grad_(True) for t in (x, wf, wc)]
-                logits = sgn15_forward_ref(*leaves, V, x.shape[1], num_class, spatial, temporal)[0]
-            ctx.ref = (leaves, logits)
-            return logits.detach()
+            return _sgn_finetune_ref(
+                ctx, lambda *leaves: sgn15_forward_ref(*leaves, V, x.shape[1], num_class, spatial, temporal), x, wf, wc)[0]
         x = x.contiguous()
-        logits, feat = _sgn15_fused_forward(x, wf.detach(), wc.detach(), V, num_class, spatial, temporal)
+        logits, feat, _, _ = sgn15_fused_forward(x, wf.detach(), wc.detach(), V, num_class, spatial, temporal)
         ctx.ref = None
         ctx.save_for_backward(x, feat, wf, wc, wf_t, wc_t)
         return logits
@@ -2569,13 +2603,4 @@ class SGN15FineTuneFunction(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dlogits):
-        if ctx.ref is not None:
-            leaves, logits = ctx.ref
-            with torch.enable_grad():
-                dx, d_wf, d_wc = torch.autograd.grad(logits, leaves, dlogits)
-        else:
-            x, feat, wf, wc, wf_t, wc_t = ctx.saved_tensors
-            V, spatial, temporal = ctx.geometry
-            dx, d_wf, d_wc = _sgn15_image_backward(x, feat, wf, wc, wf_t, wc_t, dlogits.contiguous(), V, spatial, temporal,
-                                                   0, SGN_MAX_TAPE_BYTES)
-        return (dx if ctx.needs_input_grad[0] else None), d_wf, d_wc, None, None, None, None, None, None
+        return _sgn_finetune_backward(ctx, _sgn15_image_backward, dlogits) + (None,) * 6

@@ -223,6 +223,31 @@ def test_routing():
     assert 'fused_finetune' not in m.state_dict()
 
 
+def test_parameter_gradients_frames_image_only():
+    """The mirror of the head-only set of ``test_routing``: only ``spatial_mha.*`` trainable, so the CLIP image carries no
+    graph.  On the smallest whole-model fixture."""
+    import agcn_amd  # noqa: F401
+    from agcn_amd import ops
+    case = 'j5_seg3_sliced'
+    m, x, cot, c = wg.build_model(case, DEV)
+    fix = wg.load_paramgrad(case)
+    _, _, want_dx, _ = m.parameter_gradients(x, cot)
+    inside = lambda n: n.startswith('spatial_mha.')      # noqa: E731
+    for n, p in m.named_parameters():
+        p.requires_grad_(inside(n))
+    with torch.enable_grad():
+        wf, wc, _, _ = m._finetune_images()
+    assert wf.requires_grad and not wc.requires_grad
+    fwd, wgs, tensor = _counters(ops)
+    _, _, dx, grads = m.parameter_gradients(x, cot)
+    assert ops.SGN15_STATS == {k: v + 1 for k, v in fwd.items()} and ops.SGN_STATS['forward_tensor'] == tensor
+    assert ops.SGN15_WGRAD_STATS == {k: v + 1 for k, v in wgs.items()}
+    assert sorted(grads) == sorted(n for n, _ in m.named_parameters() if inside(n)) and grads
+    assert torch.equal(dx, want_dx)
+    r = wg.compare(grads, dict(fix, keys=[k for k in fix['keys'] if inside(k)]), f'{case} spatial_mha only')
+    assert all(v <= 1.0 for v in r.values()), r
+
+
 # ---- 5. argument errors of the seven C entries ----
 def test_entries_refuse_bad_arguments():
     """The tape short by one float, the workspace short by 4 bytes, d_head 48, V = 33, num_class 0, rows_per_split -1 and

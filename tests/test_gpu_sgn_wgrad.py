@@ -178,6 +178,20 @@ def test_routing():
     sub = dict(fix, keys=[k for k in fix['keys'] if k.startswith(head)])
     err, name, floor = wu.compare(got, sub, 'head only')
     print(f'head-only fine-tuning: worst {err:.2e} ({name}, reference floor {floor:.1e})')
+    # parameter_gradients with a partial trainable set: the head leaves the frames image without a graph, gcn3 alone the
+    # clip image
+    for tag, pick in (('head only', lambda n: n.startswith(head)), ('gcn3 only', lambda n: n.startswith('gcn3.'))):
+        for n, p in model.named_parameters():
+            p.requires_grad_(pick(n))
+        names = [n for n, _ in model.named_parameters() if pick(n)]
+        assert names
+        before = _stats()
+        _, _, dx, grads = model.parameter_gradients(x, c)
+        fwd, bwd, wg = _delta(before)
+        assert fwd == dict(frames_hip=1, clip_hip=1, sample_hip=0, forward_tensor=0) and wg == ONE
+        assert sorted(grads) == sorted(names) and torch.equal(dx, want_dx)
+        err, name, floor = wu.compare(grads, dict(fix, keys=[k for k in fix['keys'] if pick(k)]), tag)
+        print(f'parameter_gradients, {tag}: worst {err:.2e} ({name}, reference floor {floor:.1e})')
     for p in model.parameters():
         p.requires_grad_(True)
     # the switch and train(): the composition

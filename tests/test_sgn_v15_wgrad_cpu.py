@@ -108,6 +108,37 @@ def test_parameter_gradients_composition_matches_the_reference(case):
         m.parameter_gradients(x, cot)
 
 
+CLIP_SIDE = ('temporal_mha.', 'fc.', 'semantic_embedding.tem_embedding.')      # the parameters folded into the clip image
+TRAINABLE = {'all': lambda n: True, 'clip image side': lambda n: n.startswith(CLIP_SIDE),
+             'frames image side': lambda n: not n.startswith(CLIP_SIDE)}
+
+
+@pytest.mark.parametrize('trainable', sorted(TRAINABLE))
+@pytest.mark.parametrize('case', gu.GRAD_CASES)
+def test_fold_gradients_of_partial_trainable_sets(case, trainable):
+    """``ops.sgn_fold_gradients`` with the image gradients from autograd of ``ops.sgn15_forward_ref``: an image none of
+    whose parameters is trainable carries no graph and is skipped."""
+    import torch
+    from agcn_amd import ops
+    m, x, cot, c = wg.build_model(case)
+    pick = TRAINABLE[trainable]
+    for n, p in m.named_parameters():
+        p.requires_grad_(pick(n))
+    wf, wc, _, _ = m._finetune_images()
+    assert wf.requires_grad == (trainable != 'clip image side') and wc.requires_grad == (trainable != 'frames image side')
+    leaves = [wf.detach().requires_grad_(True), wc.detach().requires_grad_(True)]
+    logits = ops.sgn15_forward_ref(x, *leaves, m.num_point, m.num_segment, m.num_class, *m._geometry())[0]
+    image_grads = torch.autograd.grad((logits * cot).sum(), leaves)
+    named = [(n, p) for n, p in m.named_parameters() if p.requires_grad]
+    got = ops.sgn_fold_gradients((wf, wc), image_grads, named)
+    fix = wg.load_paramgrad(case)
+    r = wg.compare(got, dict(fix, keys=[k for k in fix['keys'] if pick(k)]), f'{case}, {trainable} trainable')
+    assert all(v <= 1.0 for v in r.values()), r
+    for p in m.parameters():
+        p.requires_grad_(False)
+    assert ops.sgn_fold_gradients(m._finetune_images()[:2], image_grads, []) == {}
+
+
 def test_finetune_function_cpu_route_and_flag():
     """``ops.SGN15FineTuneFunction`` on CPU tensors runs ``sgn15_forward_ref`` on the freshly folded images: the
     specification of the fold and of the image gradients' way to the parameters.  The flag is a plain attribute."""

@@ -104,6 +104,62 @@ def test_fold_chain_from_image_gradients_to_parameters(case):
     assert {'.bn.weight', '.bn.bias', 'spa_embed', 'tem_embed'} <= set(groups)
 
 
+CLIP_SIDE = ('cnn.', 'fc.', 'tem_embed.')                  # the parameters folded into the clip image
+TRAINABLE = {'all': lambda n: True, 'clip image side': lambda n: n.startswith(CLIP_SIDE),
+             'frames image side': lambda n: not n.startswith(CLIP_SIDE)}
+
+
+@pytest.mark.parametrize('trainable', sorted(TRAINABLE))
+@pytest.mark.parametrize('case', CASES)
+def test_fold_gradients_of_partial_trainable_sets(case, trainable):
+    """``ops.sgn_fold_gradients``, what ``SGN.parameter_gradients`` does after the kernels: an image none of whose
+    parameters is trainable carries no graph and must be skipped, not handed to autograd."""
+    from agcn_amd import ops
+    model, x, c, d = wu.build_model(case)
+    pick = TRAINABLE[trainable]
+    for n, p in model.named_parameters():
+        p.requires_grad_(pick(n))
+    wf, wc, _, _ = model._finetune_images()
+    assert wf.requires_grad == (trainable != 'clip image side') and wc.requires_grad == (trainable != 'frames image side')
+    leaves = [wf.detach().requires_grad_(True), wc.detach().requires_grad_(True)]
+    logits, _ = ops.sgn_image_forward_ref(x, *leaves, model.num_point, model.seg, model.num_class)
+    image_grads = torch.autograd.grad((logits * c).sum(), leaves)
+    named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+    got = ops.sgn_fold_gradients((wf, wc), image_grads, named)
+    fix = wu.load_paramgrad(case)
+    err, name, floor = wu.compare(got, dict(fix, keys=[k for k in fix['keys'] if pick(k)]), f'{case}, {trainable}')
+    print(f'{case}, {trainable} trainable: worst {err:.2e} ({name}, reference floor {floor:.1e})')
+    for p in model.parameters():
+        p.requires_grad_(False)
+    assert ops.sgn_fold_gradients(model._finetune_images()[:2], image_grads, []) == {}
+
+
+def test_chunked_backward_order():
+    """The chunk loop both models share: dx concatenated in clip order, the chunks' image gradients added in ascending
+    chunk order -- with a triple whose fp32 sum depends on the order, the left-to-right sum bit for bit."""
+    from agcn_amd import ops
+    triple = [torch.tensor([1e8, 1.0]), torch.tensor([-1e8, 0.25]), torch.tensor([1.0, 1e-8])]
+    left = (triple[0] + triple[1]) + triple[2]
+    assert not torch.equal(left, triple[0] + (triple[1] + triple[2])), 'the triple does not tell the orders apart'
+    x = torch.arange(5.0).reshape(5, 1, 1)
+    feat, dlogits = x + 100, x.reshape(5, 1) + 200
+    seen = []
+
+    def step(xs, fe, dl):
+        i = len(seen)
+        assert torch.equal(fe, xs + 100) and torch.equal(dl, xs.reshape(-1, 1) + 200), 'the three slices differ'
+        seen.append(xs.reshape(-1).tolist())
+        return xs * 2, triple[i], triple[i] * 3
+
+    dx, d_wf, d_wc = ops._sgn_chunked_backward(step, 2, x, feat, dlogits)
+    assert seen == [[0.0, 1.0], [2.0, 3.0], [4.0]]
+    assert torch.equal(dx, x * 2) and torch.equal(d_wf, left)
+    assert torch.equal(d_wc, (triple[0] * 3 + triple[1] * 3) + triple[2] * 3)
+    # one chunk: its results as they are
+    one = ops._sgn_chunked_backward(lambda xs, fe, dl: (xs, triple[0], triple[1]), 5, x, feat, dlogits)
+    assert torch.equal(one[0], x) and one[1] is triple[0] and one[2] is triple[1]
+
+
 def test_function_cpu_route_is_the_image_reference():
     from agcn_amd import ops
     model, x, c, d = wu.build_model('v15_seg6')
