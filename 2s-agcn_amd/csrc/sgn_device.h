@@ -134,6 +134,23 @@ __device__ __forceinline__ void colstats(const f32x16 (&acc)[NB], const float* _
   }
 }
 
+// colstats of a tile that sits in LDS (32 rows, odd row stride) instead of in accumulators: the calling thread owns
+// column c and walks its rows < nrows (>= 1) in ascending order, twice, in fp32 -- the sum, then with mean = sum / nrows
+// M2 = the sum of fmaf(d, d, .) about that mean; E[z^2] - mean^2 is formed nowhere.  Consecutive threads on consecutive
+// columns read consecutive banks of one row.  Rows >= nrows are not read; the tile is not written.
+__device__ __forceinline__ void colstats_lds(const float* tile, int stride, int c, int nrows, float& sum, float& m2) {
+  float s = 0.f;
+  for (int i = 0; i < nrows; ++i) s += tile[i * stride + c];
+  const float mean = s / (float)nrows;
+  float q = 0.f;
+  for (int i = 0; i < nrows; ++i) {
+    const float d = tile[i * stride + c] - mean;
+    q = fmaf(d, d, q);
+  }
+  sum = s;
+  m2 = q;
+}
+
 // rowmax with the index: best = the column's maximum of bv + acc over the rows < nrows where that is positive (else 0),
 // arg = its row (else -1), in both lanes of the column.  Rows ascend with j and a strict > keeps the lowest index; the
 // merge of the two half-waves keeps the lower row at a tie.

@@ -9,6 +9,7 @@
 //   sgn_clip_stats_kernel<L>     one workgroup per clip, sgn_clip_kernel's tile loop up to cnn<L>'s product
 //   sgn_stats_clip_merge_kernel  one thread per (clip, channel) merges the clip's groups in ascending order (fp64 state)
 //   sgn_stats_finalize_kernel    one thread per channel merges the clips in ascending order on top of the carry state
+//                                (both in sgn_stats_device.h, shared with sgn_v15_stats.hip)
 // Every group emits (sum, M2 about its own mean); E[z^2] - mean^2 is never formed.  Exact-f32 MFMA in every AGCN_GEMM mode,
 // fixed summation orders, no atomics, no launch reads another launch's LDS: a group's partials are the same bits alone
 // and inside any batch, and a batch merged chunk by chunk through the carry state equals one launch bit for bit.
@@ -17,6 +18,7 @@
 #include "sgn_plan.h"
 #include "sgn_stats_plan.h"
 #include "sgn_device.h"
+#include "sgn_stats_device.h"
 
 __global__ __launch_bounds__(SGN_THREADS) void sgn_input_stats_kernel(const float* __restrict__ x, float* __restrict__ part,
                                                                       int seg, int V) {
@@ -161,69 +163,11 @@ __global__ __launch_bounds__(SGN_THREADS) void sgn_clip_stats_kernel(const float
   }
 }
 
-// (n, mean, M2) <- (n, mean, M2) merged with (nb, meanb, m2b), nb >= 1: the pairwise update of Chan, Golub and LeVeque.
-// From the zero state it returns the second operand itself (nb / tot = 1 and n * nb / tot = 0 exactly).
-__device__ __forceinline__ void chan_merge(double& n, double& mean, double& m2, double nb, double meanb, double m2b) {
-  const double tot = n + nb;
-  const double delta = meanb - mean;
-  mean = mean + delta * (nb / tot);
-  m2 = m2 + m2b + delta * delta * (n * nb / tot);
-  n = tot;
-}
-
-// First level, one thread per (clip, channel): the groups of the clip merged one after the other in ascending index,
-// state in fp64, to the clip's (count, mean, M2) in the workspace.  A group with count 0 is skipped.
-__global__ __launch_bounds__(SGN_STATS_THREADS) void sgn_stats_clip_merge_kernel(const float* __restrict__ part,
-                                                                                 double* __restrict__ ws, int kind, int C,
-                                                                                 int seg, int V) {
-  const int c = blockIdx.y * SGN_STATS_THREADS + threadIdx.x;
-  const long clip = blockIdx.x;
-  if (c >= C) return;
-  const int per = sgn_stats_groups_per_clip(kind, seg);
-  double n = 0., mean = 0., m2 = 0.;
-  for (int i = 0; i < per; ++i) {
-    const long g = clip * per + i;
-    const int cnt = sgn_stats_group_count(kind, g, seg, V);
-    if (cnt < 1) continue;
-    const double nb = (double)cnt;
-    chan_merge(n, mean, m2, nb, (double)part[sgn_stats_part_index(g, 0, c, C)] / nb,
-               (double)part[sgn_stats_part_index(g, 1, c, C)]);
-  }
-  ws[sgn_stats_clip_state_index(clip, 0, c, C)] = n;
-  ws[sgn_stats_clip_state_index(clip, 1, c, C)] = mean;
-  ws[sgn_stats_clip_state_index(clip, 2, c, C)] = m2;
-}
-
-// Second level, one thread per channel: the clips' states merged one after the other in ascending clip index on top of
-// the carry-in state ("no carry-in" and "a carry-in of zeros" are the same bits).
-__global__ __launch_bounds__(SGN_STATS_THREADS) void sgn_stats_finalize_kernel(const double* __restrict__ ws,
-                                                                               const double* __restrict__ carry_in,
-                                                                               double* __restrict__ carry_out,
-                                                                               float* __restrict__ mean_out,
-                                                                               float* __restrict__ var_out, long N, int C) {
-  const int c = blockIdx.x * SGN_STATS_THREADS + threadIdx.x;
-  if (c >= C) return;
-  double n = 0., mean = 0., m2 = 0.;
-  if (carry_in) {
-    n = carry_in[c];
-    mean = carry_in[C + c];
-    m2 = carry_in[2 * C + c];
-  }
-#pragma unroll 4
-  for (long clip = 0; clip < N; ++clip) {
-    const double nb = ws[sgn_stats_clip_state_index(clip, 0, c, C)];
-    const double mb = ws[sgn_stats_clip_state_index(clip, 1, c, C)];
-    const double qb = ws[sgn_stats_clip_state_index(clip, 2, c, C)];
-    if (nb >= 1.) chan_merge(n, mean, m2, nb, mb, qb);
-  }
-  if (carry_out) {
-    carry_out[c] = n;
-    carry_out[C + c] = mean;
-    carry_out[2 * C + c] = m2;
-  }
-  if (mean_out) mean_out[c] = (float)mean;
-  if (var_out) var_out[c] = n > 0. ? (float)(m2 / n) : 0.f;
-}
+// the base model's merge rule (sgn_stats_device.h): groups per clip and samples per group by the pass's kind
+struct SgnStatsRule {
+  int per, kind, seg, V;
+  __device__ int count(long g) const { return sgn_stats_group_count(kind, g, seg, V); }
+};
 
 extern "C" size_t agcn_sgn_stats_part_floats(int kind, int layer, int N, int seg, int V) {
   if (kind == SGN_STATS_CLIP) V = 2;             // a clip pass does not depend on V
@@ -291,10 +235,6 @@ extern "C" int agcn_sgn_stats_finalize(const float* part, size_t part_floats, in
   if (part_floats < (size_t)sgn_stats_part_floats(kind, layer, N, seg, V)) return AGCN_ERR_WORKSPACE;
   if (ws_bytes < (size_t)sgn_stats_workspace_doubles(kind, layer, N, V) * 8) return AGCN_ERR_WORKSPACE;
   const int C = sgn_stats_channels(kind, layer, V);
-  const unsigned blocks = (unsigned)((C + SGN_STATS_THREADS - 1) / SGN_STATS_THREADS);
-  hipLaunchKernelGGL(sgn_stats_clip_merge_kernel, dim3((unsigned)N, blocks), dim3(SGN_STATS_THREADS), 0,
-                     (hipStream_t)stream, part, (double*)ws, kind, C, seg, V);
-  hipLaunchKernelGGL(sgn_stats_finalize_kernel, dim3(blocks), dim3(SGN_STATS_THREADS), 0, (hipStream_t)stream,
-                     (const double*)ws, carry_in, carry_out, mean, var, (long)N, C);
-  return agcn_check_launch();
+  const SgnStatsRule rule{sgn_stats_groups_per_clip(kind, seg), kind, seg, V};
+  return sgn_stats_merge(part, (double*)ws, rule, C, (long)N, carry_in, carry_out, mean, var, (hipStream_t)stream);
 }

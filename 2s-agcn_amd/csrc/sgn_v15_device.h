@@ -80,7 +80,11 @@ __device__ __forceinline__ void sgn15_qkv(const float* X, const float* __restric
 // Barriers inside; the caller puts one in front (X complete) and needs none behind for m.
 // sgn15_block_y is the block up to the accumulators of y (without b2 + br), which the backward takes the arg-max rows
 // from; it leaves x1 in X and a barrier behind the last read of QKV and P.  sgn15_block adds the maximum.
-template <int DIN, int DOUT>
+// X1_ONLY (compile time): stop behind the barrier that follows "x1 = attention + bo + x, in place" -- the attention half,
+// which reads qkv_w, qkv_b, o_w, o_b and nothing else of the block; ff, f1_*, f2_* and accY are then not touched (the
+// batch-statistics pass of n_f, sgn_v15_stats.hip, through sgn15_block_x1 below).  A flag and not a second function: the
+// group walk is written once, and the instantiations without the flag are the code they were.
+template <int DIN, int DOUT, bool X1_ONLY = false>
 __device__ __forceinline__ void sgn15_block_y(float* X, float* QKV, float* P, const float* __restrict__ w,
                                               const Sgn15BlockW& o, int rows, int heads, int d_head, int ff,
                                               float* __restrict__ attn, f32x16 (&accY)[DOUT / SGN15_GROUP]) {
@@ -175,6 +179,7 @@ __device__ __forceinline__ void sgn15_block_y(float* X, float* QKV, float* P, co
     for (int j = 0; j < 16; ++j) X[mfma_row(j, h) * XS + col] += accO[i][j] + bv;
   }
   __syncthreads();
+  if constexpr (X1_ONLY) return;
 
   // y = [relu(x1 W1 + b1) | x1] . [W2 ; Wr] + (b2 + br): the hidden tile in chunks of 128 columns, ascending, then x1
 #pragma unroll
@@ -191,6 +196,14 @@ __device__ __forceinline__ void sgn15_block_y(float* X, float* QKV, float* P, co
     __syncthreads();
   }
   mma_w<NBY>(X + r * XS + h, w + o.f2_w + (long)(ff + h) * DOUT + wave * 32 + r, DOUT, DIN, accY);
+}
+
+// the attention half alone: x -> x1 in place in X, a barrier behind it
+template <int DIN, int DOUT>
+__device__ __forceinline__ void sgn15_block_x1(float* X, float* QKV, float* P, const float* __restrict__ w,
+                                               const Sgn15BlockW& o, int rows, int heads, int d_head) {
+  f32x16 unused[DOUT / SGN15_GROUP];
+  sgn15_block_y<DIN, DOUT, true>(X, QKV, P, w, o, rows, heads, d_head, SGN15_GROUP, nullptr, unused);
 }
 
 template <int DIN, int DOUT>

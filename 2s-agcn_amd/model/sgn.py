@@ -470,13 +470,4 @@ class SGN(nn.Module):
         float: the exponential one.  ``reset=True`` calls ``reset_running_stats()`` first.  -> stats.  The in-place writes
         bump the buffers' versions: the next prediction rebuilds the cached weight images."""
         _, _, stats = self.batch_statistics(x, max_part_bytes)
-        with torch.no_grad():
-            for name, (mean, var, count) in stats.items():
-                bn = self.get_submodule(name)
-                if reset:
-                    bn.reset_running_stats()
-                bn.num_batches_tracked.add_(1)
-                f = 1.0 / float(bn.num_batches_tracked) if momentum is None else float(momentum)
-                bn.running_mean.mul_(1.0 - f).add_(mean.to(bn.running_mean), alpha=f)
-                bn.running_var.mul_(1.0 - f).add_(var.to(bn.running_var) * (count / (count - 1)), alpha=f)
-        return stats
+        return ops.sgn_update_running_stats(self, stats, momentum, reset)

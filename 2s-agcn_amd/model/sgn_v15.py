@@ -30,6 +30,12 @@ csrc/sgn_v15_wgrad.hip, which give the gradients of the two folded images; torch
 (``_finetune_images``, a fresh fold per call) to the parameters.  ``parameter_gradients`` is the same route without
 autograd state.  Nothing of the forward is stored but feat; the tapes are capped by ``ops.SGN_MAX_TAPE_BYTES``.
 
+``batch_statistics(x)`` / ``recalibrate_bn(x)`` in any ``training`` state: the batch statistics of the six BatchNorms of x
+as one batch and the logits under them (the forward half of train-mode BatchNorm, every dropout off), on the fused
+structure as the base SGN's input pass, four truncated passes of the fused forward (csrc/sgn_v15_stats.hip) on freshly
+folded images and the two full-depth launches; otherwise the composition with its BatchNorms in batch mode.  The
+backward of batch-mode BatchNorm is not built in HIP.
+
 One block, with n_a, n_f the two per-channel BatchNorms: a = softmax_j((n_a(x) Wq)(n_a(x) Wk)^T d_head^-1/2) per head,
 x1 = concat_h(a . n_a(x) Wv) Wo + bo + res_a(x), y = relu(n_f(x1) W1 + b1) W2 + b2 + res_f(x1): both residuals take the
 un-normalised input, and a residual is a Linear where the widths differ (crossattention.py:297-304)."""
@@ -412,23 +418,46 @@ class SGN(nn.Module):
         return tuple(out)
 
     @staticmethod
-    def _fold_block(layer):
-        """One block's sections in the order of csrc/sgn_v15_plan.h::Sgn15BlockW."""
+    def _block_base(layer):
+        """The unfolded matrices the two BatchNorms of a block are folded into -> ([Wq d_head^-1/2 | Wk | Wv] (DIN, 3 inner),
+        W1 (DIN, ff), b1)."""
+        att, ffn = layer['attn'].fn, layer['ffn'].fn
+        wqkv = torch.cat([att.to_q.weight.t() * att.scale, att.to_k.weight.t(), att.to_v.weight.t()], dim=1)
+        return wqkv, ffn.net.linear1.weight.t(), ffn.net.linear1.bias
+
+    @staticmethod
+    def _running(bn):
+        return ops._fold((bn.weight, bn.bias, bn.running_mean, bn.running_var))
+
+    @classmethod
+    def _fold_block(cls, layer, fold=None):
+        """One block's sections in the order of csrc/sgn_v15_plan.h::Sgn15BlockW; ``fold(bn)`` -> (scale, shift), by
+        default on the running statistics."""
+        fold = fold or cls._running
         a, f = layer['attn'], layer['ffn']
         att, ffn = a.fn, f.fn
-        sa, sha = ops._fold((a.norm.fn.weight, a.norm.fn.bias, a.norm.fn.running_mean, a.norm.fn.running_var))
-        sf, shf = ops._fold((f.norm.fn.weight, f.norm.fn.bias, f.norm.fn.running_mean, f.norm.fn.running_var))
-        wqkv = torch.cat([att.to_q.weight.t() * att.scale, att.to_k.weight.t(), att.to_v.weight.t()], dim=1)   # (DIN, 3 inner)
-        w1 = ffn.net.linear1.weight.t()                                                                         # (DIN, ff)
+        sa, sha = fold(a.norm.fn)
+        sf, shf = fold(f.norm.fn)
+        wqkv, w1, b1 = cls._block_base(layer)
         return [wqkv * sa[:, None], sha @ wqkv,
                 att.to_out.linear.weight.t(), att.to_out.linear.bias,
-                w1 * sf[:, None], shf @ w1 + ffn.net.linear1.bias,
+                w1 * sf[:, None], shf @ w1 + b1,
                 torch.cat([ffn.net.linear2.weight.t(), ffn.residual.weight.t()]), ffn.net.linear2.bias + ffn.residual.bias]
 
-    def _folded(self):
-        """The folded tensors in the order of the two weight images -> (frames list, clip list)."""
+    def _folded(self, override=None):
+        """The folded tensors in the order of the two weight images -> (frames list, clip list).  ``override``:
+        {BatchNorm module name: (mean, var)} folds that BatchNorm on the given statistics (in the module's own feature
+        order) instead of its running ones: the images of the batch-statistics passes.  Without it every BatchNorm is
+        folded on its running statistics."""
         V, like = self.num_point, self.fc.weight
         fe = self.feature_extractor
+        names = {m: n for n, m in self.named_modules()} if override else {}
+
+        def fold(bn):
+            if override and names[bn] in override:
+                mean, var = override[names[bn]]
+                return ops._fold((bn.weight, bn.bias, mean, var))
+            return self._running(bn)
 
         def emb(e):
             a, b = e.cnn1.block.conv.conv, e.cnn2.block.conv.conv
@@ -437,13 +466,17 @@ class SGN(nn.Module):
 
         aff = []
         for e in (fe.pos_embed, fe.vel_embed):              # BatchNorm feature c*V + v -> [v*3 + c]
-            bn = e.norm.bn
-            aff += [c.reshape(3, V).t() for c in ops._fold((bn.weight, bn.bias, bn.running_mean, bn.running_var))]
+            aff += [c.reshape(3, V).t() for c in fold(e.norm.bn)]
         frames = (aff + emb(fe.pos_embed) + emb(fe.vel_embed) + [self.semantic_embedding.spa()]
-                  + self._fold_block(self.spatial_mha.transformer.layers['l1']))
-        clip = ([self.semantic_embedding.tem()] + self._fold_block(self.temporal_mha.transformer.layers['l1'])
+                  + self._fold_block(self.spatial_mha.transformer.layers['l1'], fold))
+        clip = ([self.semantic_embedding.tem()] + self._fold_block(self.temporal_mha.transformer.layers['l1'], fold)
                 + [self.fc.weight.t(), self.fc.bias])
         return frames, clip
+
+    @staticmethod
+    def _flatten(frames, clip):
+        """The two folded lists -> (frames image, clip image), each one flat tensor."""
+        return torch.cat([t.reshape(-1) for t in frames]), torch.cat([t.reshape(-1) for t in clip])
 
     def _images(self):
         """-> (frames image, clip image, spa table (V, 64), tem table (seg, 256)), cached."""
@@ -577,3 +610,145 @@ class SGN(nn.Module):
                 return logits, self._fused_aux(x.shape[0], sa, ta), dx
         ops.SGN_STATS['forward_tensor'] += 1
         return ops.sgn_composition_gradients(self.forward_tensor, x, cot)[:3]
+
+    # ---- batch statistics: the forward half of train-mode BatchNorm ----
+    def _batch_images(self, known):
+        """Fresh images (never ``_infer_cache``) with the BatchNorms of ``known`` {name: (mean, var)} on those statistics
+        and every other one on its running statistics: the specification of ``_batch_folder``.  A pass never reads a
+        section that depends on a BatchNorm outside ``known`` (csrc/sgn_v15_stats_plan.h)."""
+        return self._flatten(*self._folded(dict(known)))
+
+    def _batch_folder(self):
+        """-> fold(known) for ``ops.sgn15_batch_statistics``: ``_batch_images`` built incrementally.  One fold on the
+        running statistics gives the working images, and the unfolded [Wq d_head^-1/2 | Wk | Wv] and W1, b1 of each block
+        are kept; when a BatchNorm enters ``known`` its sections are written as base * scale and shift @ base (+ b1), the
+        operations ``_fold_block`` applies to the same numbers, so the images hold the bits of ``_batch_images(known)``."""
+        V = self.num_point
+        work = list(self._flatten(*self._folded()))
+        secs = [{n: (o, s) for n, o, s in sec}
+                for sec in ops.sgn15_image_sections(V, self.num_segment, self.num_class, *self._geometry())]
+        where = {}
+        for which, (m, p) in enumerate(((self.spatial_mha, 's_'), (self.temporal_mha, 't_'))):
+            layer = m.transformer.layers['l1']
+            wqkv, w1, b1 = self._block_base(layer)
+            for name, sec, base, bias in zip(ops.SGN15_BN_NAMES[2 + 2 * which:4 + 2 * which], ('qkv', 'f1'), (wqkv, w1),
+                                             (None, b1)):
+                where[name] = (which, p + sec, base, bias)
+        done = set()
+
+        def view(which, name):
+            o, shape = secs[which][name]
+            return work[which][o:o + math.prod(shape)].view(shape)
+
+        def fold(known):
+            for name in known:
+                if name in done:
+                    continue
+                done.add(name)
+                bn = self.get_submodule(name)
+                s, sh = ops._fold((bn.weight, bn.bias, known[name][0], known[name][1]))
+                if name in where:
+                    which, p, base, bias = where[name]
+                    torch.mul(base, s[:, None], out=view(which, p + '_w'))
+                    view(which, p + '_b').copy_(sh @ base if bias is None else sh @ base + bias)
+                else:                                  # DataNorm: BatchNorm feature c*V + v -> aff rows [v*3 + c]
+                    row = 0 if name == ops.SGN15_BN_NAMES[0] else 2
+                    aff = view(0, 'aff')
+                    aff[row].copy_(s.reshape(3, V).t())
+                    aff[row + 1].copy_(sh.reshape(3, V).t())
+            return work[0], work[1]
+
+        return fold
+
+    def _batch_statistics_tensor(self, x):
+        """The composition with every BatchNorm in batch mode and EVERY dropout of the module off -> (logits, aux, stats in
+        the order the BatchNorms run).  Only Python flags are flipped for the duration of the call (a BatchNorm that does
+        not track statistics touches no buffer); hooks read the inputs."""
+        bns = {n: m for n, m in self.named_modules() if isinstance(m, nn.modules.batchnorm._BatchNorm)}
+        mods = list(bns.values()) + [m for m in self.modules() if isinstance(m, nn.modules.dropout._DropoutNd)]
+        flags = [(m.training, getattr(m, 'track_running_stats', None)) for m in mods]
+        seen, hooks = {}, []
+
+        def reader(name):
+            def hook(_m, args):
+                a = args[0]
+                dims = [d for d in range(a.dim()) if d != 1]
+                var, mean = torch.var_mean(a, dim=dims, unbiased=False)
+                seen[name] = (mean, var, a.numel() // a.shape[1])
+            return hook
+
+        try:
+            for n, m in bns.items():
+                m.training, m.track_running_stats = True, False
+                hooks.append(m.register_forward_pre_hook(reader(n)))
+            for m in mods[len(bns):]:
+                m.training = False
+            logits, aux = self.forward_tensor(x)
+        finally:
+            for h in hooks:
+                h.remove()
+            for m, (tr, track) in zip(mods, flags):
+                m.training = tr
+                if track is not None:
+                    m.track_running_stats = track
+        return logits, aux, dict(seen)
+
+    def _stats_fusable(self, x):
+        """What the batch-statistics kernels take, whatever the grad mode and the ``training`` state."""
+        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()):
+            return False
+        if x.shape[1] != self.num_segment or x.shape[2] != 3 * self.num_point or x.shape[0] < 1:
+            return False
+        if not (ops.sgn_hip_enabled() and self._structure_fused()):
+            return False
+        return ops.sgn15_weights_floats(self.num_point, self.num_segment, self.num_class, *self._geometry()) is not None
+
+    def batch_statistics(self, x, max_part_bytes=None):
+        """-> (logits, aux, stats): what ONE train-mode forward of x (N, seg, 3V) as one batch computes with every dropout
+        off (the reference's sgn_v15.py in train() with every dropout probability 0).  ``stats`` = {BatchNorm module name:
+        (mean, biased var, count)} in dependency order (``ops.SGN15_BN_NAMES`` in the fused structure), each in its
+        module's feature order; BatchNorm k sees activations normalised by the batch statistics of the BatchNorms before
+        it.  Mutates nothing, runs under ``no_grad`` and works in any ``training`` state.  On a contiguous fp32 GPU tensor
+        in the fused structure (``_structure_fused``, sizes inside the kernels' domain, AGCN_SGN_HIP != 0):
+        ``ops.sgn15_batch_statistics``, the input pass, four truncated passes of the fused forward
+        (csrc/sgn_v15_stats.hip) chunked under ``max_part_bytes`` and the two full-depth launches, with ``aux`` as the
+        fine-tuning route returns it (the embeddings' tables, no attention maps); otherwise the composition (counted in
+        ``ops.SGN_STATS['forward_tensor']``)."""
+        if x.dim() != 3:
+            raise ValueError(f"agcn_amd: SGN.batch_statistics takes (N, seg, 3 V), got {tuple(x.shape)}")
+        N, seg = x.shape[0], x.shape[1]
+        if N * seg < 2:
+            raise ValueError(f"agcn_amd: SGN.batch_statistics needs more than one value per channel, got {N} x {seg} frames")
+        V = self.num_point
+        with torch.no_grad():
+            if not self._stats_fusable(x):
+                ops.SGN_STATS['forward_tensor'] += 1
+                return self._batch_statistics_tensor(x)
+            cap = ops.SGN_MAX_STATS_BYTES if max_part_bytes is None else max_part_bytes
+            fold = self._batch_folder()
+            logits, raw = ops.sgn15_batch_statistics(x, fold, V, self.num_class, *self._geometry(), cap)
+            counts = [N * seg] * 2 + [N * seg * V] * 2 + [N * seg] * 2
+            stats = {}
+            for i, (name, count) in enumerate(zip(ops.SGN15_BN_NAMES, counts)):
+                mean, var = raw[name]
+                if i < 2:                              # the kernels' [v*3 + c] -> the module's c*V + v
+                    mean, var = (t.view(V, 3).t().reshape(-1) for t in (mean, var))
+                stats[name] = (mean, var, count)
+            wf, wc = fold({})                          # the final images: the embeddings' tables are sections of them
+            o = ops.sgn15_image_sections(V, seg, self.num_class, *self._geometry())[0]
+            spa = next(wf[off:off + math.prod(s)].view(s) for n, off, s in o if n == 'spa')
+            tem = wc[:seg * 256].view(seg, 256)
+            aux = dict(tem_emb=tem.t()[None, :, None, :].expand(N, 256, V, seg),
+                       spa_emb=spa.t()[None, :, :, None].expand(N, 64, V, seg), spatial_attn_list=None,
+                       temporal_attn_list=None)
+            return logits, aux, stats
+
+    def recalibrate_bn(self, x, momentum=None, reset=True, max_part_bytes=None):
+        """Re-estimate the BatchNorms on x (AdaBN, or after frozen-BatchNorm fine-tuning moved the weights under them):
+        ``batch_statistics(x)``, then ``running_mean``, ``running_var`` (unbiased, n / (n - 1)) and
+        ``num_batches_tracked`` are updated in place exactly as one train-mode forward of x would (with every dropout off).
+        ``momentum=None``: the cumulative average (after ``reset`` the running statistics ARE the batch's), a float: the
+        exponential one.  ``reset=True`` calls ``reset_running_stats()`` first.  -> stats.  The in-place writes bump the
+        buffers' versions: the next prediction rebuilds the cached weight images."""
+        _, _, stats = self.batch_statistics(x, max_part_bytes)
+        return ops.sgn_update_running_stats(self, stats, momentum, reset)

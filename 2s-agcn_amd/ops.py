@@ -2192,6 +2192,23 @@ def sgn_fold_gradients(images, image_grads, named):
     return sgn_named_gradients(named, grads)
 
 
+def sgn_update_running_stats(model, stats, momentum=None, reset=True):
+    """``recalibrate_bn`` of both models behind their ``batch_statistics``: ``stats`` {BatchNorm module name: (mean,
+    biased var, count)} -> ``running_mean``, ``running_var`` (unbiased, n / (n - 1)) and ``num_batches_tracked`` updated in
+    place exactly as one train-mode forward of the batch would.  ``momentum=None``: the cumulative average, a float: the
+    exponential one.  ``reset`` calls ``reset_running_stats()`` first."""
+    with torch.no_grad():
+        for name, (mean, var, count) in stats.items():
+            bn = model.get_submodule(name)
+            if reset:
+                bn.reset_running_stats()
+            bn.num_batches_tracked.add_(1)
+            f = 1.0 / float(bn.num_batches_tracked) if momentum is None else float(momentum)
+            bn.running_mean.mul_(1.0 - f).add_(mean.to(bn.running_mean), alpha=f)
+            bn.running_var.mul_(1.0 - f).add_(var.to(bn.running_var) * (count / (count - 1)), alpha=f)
+    return stats
+
+
 # ------------------------------------------------------------------------------------------------
 # base SGN, batch statistics of its seven BatchNorms (csrc/sgn_stats.hip): the forward half of train-mode BatchNorm.
 # BatchNorm k sees activations normalised by the batch statistics of the BatchNorms in front of it, so the statistics come
@@ -2250,22 +2267,27 @@ def sgn_clip_stats(feat, wimg, layer, num_class):
     return part.view(-1, 2, part.numel() // (2 * N * ((seg + 31) // 32)))
 
 
+def _sgn_stats_finalize(entry, counters, C, part, kind, layer, N, seg, V, carry, want_carry):
+    """``agcn_<entry>_finalize`` on ``part`` with its workspace, for both models."""
+    if C == 0 or (carry is not None and (carry.dtype != torch.float64 or tuple(carry.shape) != (3, C)
+                                         or not carry.is_contiguous() or carry.device != part.device)):
+        raise ValueError(f"agcn_amd: {entry}_finalize: pass {(kind, layer)} takes a carry (3, {C}) float64")
+    mean, var = _empty((C,), part), _empty((C,), part)
+    out = torch.empty((3, C), dtype=torch.float64, device=part.device) if want_carry else None
+    nbytes = getattr(_L(), f"agcn_{entry}_finalize_workspace")(kind, layer, N, seg, V)
+    ws = torch.empty((max(1, nbytes // 8),), dtype=torch.float64, device=part.device)
+    _lib.call(f"agcn_{entry}_finalize", part.view(-1), part.numel(), kind, layer, N, seg, V, carry, out, mean, var, ws,
+              nbytes)
+    counters['stats_finalize'] += 1
+    return mean, var, out
+
+
 def sgn_stats_finalize(part, kind, layer, N, seg, V, carry=None, want_carry=False):
     """Merge the groups of ``part`` (pairwise update, fp64 state: the groups of a clip in ascending index, then the clips
     in ascending index) on top of the optional ``carry`` ((3, C) float64: count, mean, M2) -> (mean (C,), biased var
     (C,), carry_out or None)."""
-    C = _L().agcn_sgn_stats_channels(kind, layer, V)
-    if C == 0 or (carry is not None and (carry.dtype != torch.float64 or tuple(carry.shape) != (3, C)
-                                         or not carry.is_contiguous() or carry.device != part.device)):
-        raise ValueError(f"agcn_amd: sgn_stats_finalize: pass {(kind, layer)} takes a carry (3, {C}) float64")
-    mean, var = _empty((C,), part), _empty((C,), part)
-    out = torch.empty((3, C), dtype=torch.float64, device=part.device) if want_carry else None
-    nbytes = _L().agcn_sgn_stats_finalize_workspace(kind, layer, N, seg, V)
-    ws = torch.empty((max(1, nbytes // 8),), dtype=torch.float64, device=part.device)
-    _lib.call("agcn_sgn_stats_finalize", part.view(-1), part.numel(), kind, layer, N, seg, V, carry, out, mean, var, ws,
-              nbytes)
-    SGN_BNSTATS_STATS['stats_finalize'] += 1
-    return mean, var, out
+    return _sgn_stats_finalize('sgn_stats', SGN_BNSTATS_STATS, _L().agcn_sgn_stats_channels(kind, layer, V), part, kind,
+                               layer, N, seg, V, carry, want_carry)
 
 
 def sgn_stats_clip_bytes(seg, V):
@@ -2282,6 +2304,29 @@ def sgn_stats_chunk(N, seg, V, max_part_bytes):
     return max(1, min(N, int(max_part_bytes) // sgn_stats_clip_bytes(seg, V)))
 
 
+def _sgn_stats_runner(N, seg, V, chunk):
+    """-> run(kind, layer, src, launch, finalize): one pass over ``src`` (x or feat) in chunks of ``chunk`` whole clips,
+    the finalize's carry state passing from chunk to chunk -> (mean, var).  Both models' passes."""
+    def run(kind, layer, src, launch, finalize=sgn_stats_finalize):
+        carry = None
+        for n0 in range(0, N, chunk):
+            part = launch(src[n0:n0 + chunk])
+            n = min(chunk, N - n0)
+            mean, var, carry = finalize(part, kind, layer, n, seg, V, carry, want_carry=n0 + chunk < N)
+        return mean, var
+
+    return run
+
+
+def _sgn_stats_input_pass(run, x, V, names, known, out):
+    """The pass of the two input BatchNorms ``names`` (position / joint, velocity / dif), the same in both models:
+    ``out`` takes them in the kernels' feature order [v*3 + c], ``known`` in the module's c*V + v."""
+    mean, var = run(SGN_STATS_INPUT, 0, x, lambda xs: sgn_input_stats(xs, V))
+    for i, name in enumerate(names):
+        out[name] = (mean[i * 3 * V:(i + 1) * 3 * V], var[i * 3 * V:(i + 1) * 3 * V])
+        known[name] = tuple(t.view(V, 3).t().reshape(-1) for t in out[name])
+
+
 def sgn_batch_statistics(x, fold, V, num_class, max_part_bytes=SGN_MAX_STATS_BYTES):
     """The batch statistics of SGN's seven BatchNorms on x (N, seg, V*3) as ONE batch, and the forward under them ->
     (logits, g, {name: (mean, biased var)}) with the names of ``SGN_BN_NAMES``; the two input BatchNorms in the kernels'
@@ -2295,21 +2340,9 @@ def sgn_batch_statistics(x, fold, V, num_class, max_part_bytes=SGN_MAX_STATS_BYT
         raise ValueError(f"agcn_amd: sgn_batch_statistics takes (N, seg, {3 * V}), got {tuple(x.shape)}")
     x = x.detach().contiguous()
     N, seg, _ = x.shape
-    chunk = sgn_stats_chunk(N, seg, V, max_part_bytes)
-
-    def run(kind, layer, src, launch):
-        carry = None
-        for n0 in range(0, N, chunk):
-            part = launch(src[n0:n0 + chunk])
-            n = min(chunk, N - n0)
-            mean, var, carry = sgn_stats_finalize(part, kind, layer, n, seg, V, carry, want_carry=n0 + chunk < N)
-        return mean, var
-
+    run = _sgn_stats_runner(N, seg, V, sgn_stats_chunk(N, seg, V, max_part_bytes))
     known, out = {}, {}
-    mean, var = run(SGN_STATS_INPUT, 0, x, lambda xs: sgn_input_stats(xs, V))
-    for i, name in enumerate(SGN_BN_NAMES[:2]):
-        out[name] = (mean[i * 3 * V:(i + 1) * 3 * V], var[i * 3 * V:(i + 1) * 3 * V])
-        known[name] = tuple(t.view(V, 3).t().reshape(-1) for t in out[name])
+    _sgn_stats_input_pass(run, x, V, SGN_BN_NAMES[:2], known, out)
     for layer in (1, 2, 3):
         name = SGN_BN_NAMES[1 + layer]
         wf, _ = fold(known, name)
@@ -2544,12 +2577,22 @@ def _sgn15_image_backward(x, feat, wf, wc, wf_t, wc_t, dlogits, V, spatial, temp
 
 def sgn15_fused_forward(x, wf, wc, V, num_class, spatial, temporal, want_attn=False):
     """The two forward launches per chunk of at most ``SGN15_MAX_CLIPS`` whole clips (a clip's result does not depend on
-    its batch) -> (logits, feat, spatial attn or None, temporal attn or None)."""
+    its batch) -> (logits, feat, spatial attn or None, temporal attn or None).  ``wc`` may be a callable(feat) -> clip
+    image, for an image that depends on feat of the whole batch (``sgn15_batch_statistics``): then every frames launch
+    runs before the first clip launch."""
     parts = []
-    for lo in range(0, x.shape[0], SGN15_MAX_CLIPS):      # one pair of launches unless the batch exceeds their limit
-        feat, sa = sgn15_frames(x[lo:lo + SGN15_MAX_CLIPS], wf, V, *spatial, want_attn=want_attn)
-        logits, ta = sgn15_clip(feat, wc, num_class, *temporal, want_attn=want_attn)
-        parts.append((logits, feat, sa, ta))
+    if callable(wc):
+        fs = [sgn15_frames(x[lo:lo + SGN15_MAX_CLIPS], wf, V, *spatial, want_attn=want_attn)
+              for lo in range(0, x.shape[0], SGN15_MAX_CLIPS)]
+        wc = wc(fs[0][0] if len(fs) == 1 else torch.cat([f for f, _ in fs]))
+        for feat, sa in fs:
+            logits, ta = sgn15_clip(feat, wc, num_class, *temporal, want_attn=want_attn)
+            parts.append((logits, feat, sa, ta))
+    else:
+        for lo in range(0, x.shape[0], SGN15_MAX_CLIPS):      # one pair of launches unless the batch exceeds their limit
+            feat, sa = sgn15_frames(x[lo:lo + SGN15_MAX_CLIPS], wf, V, *spatial, want_attn=want_attn)
+            logits, ta = sgn15_clip(feat, wc, num_class, *temporal, want_attn=want_attn)
+            parts.append((logits, feat, sa, ta))
     return parts[0] if len(parts) == 1 else tuple(None if p[0] is None else torch.cat(p) for p in zip(*parts))
 
 
@@ -2604,3 +2647,122 @@ class SGN15FineTuneFunction(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, dlogits):
         return _sgn_finetune_backward(ctx, _sgn15_image_backward, dlogits) + (None,) * 6
+
+
+# ------------------------------------------------------------------------------------------------
+# SGN v15, batch statistics of its six BatchNorms (csrc/sgn_v15_stats.hip; the two input ones through the base SGN's input
+# pass): the forward half of train-mode BatchNorm, as sequential passes, each the fused forward cut off at one BatchNorm.
+# A pass never reads a section that depends on the BatchNorm it measures, so its images only need the EARLIER BatchNorms
+# on their batch statistics (csrc/sgn_v15_stats_plan.h).
+# ------------------------------------------------------------------------------------------------
+# the BatchNorm modules of model/sgn_v15.py::SGN in dependency order: the two DataNorms, then n_a and n_f of each block
+SGN15_BN_NAMES = ('feature_extractor.pos_embed.norm.bn', 'feature_extractor.vel_embed.norm.bn',
+                  'spatial_mha.transformer.layers.l1.attn.norm.fn', 'spatial_mha.transformer.layers.l1.ffn.norm.fn',
+                  'temporal_mha.transformer.layers.l1.attn.norm.fn', 'temporal_mha.transformer.layers.l1.ffn.norm.fn')
+SGN15_STATS_FRAMES, SGN15_STATS_CLIP = 1, 2
+
+# diagnostic counters of these launches (a dict of its own; the input pass counts in SGN_BNSTATS_STATS)
+SGN15_BNSTATS_STATS = dict(frames_stats=0, clip_stats=0, stats_finalize=0)
+# None, or a callable(label) that tools/sgn_v15_recalibrate.py sets to record a device event behind every pass and fold
+SGN15_BNSTATS_MARK = None
+
+
+def _sgn15_stats_part(kind, layer, N, seg, V, like):
+    n = _L().agcn_sgn15_stats_part_floats(kind, layer, N, seg, V)
+    if n == 0:
+        raise ValueError(f"agcn_amd: SGN v15 batch statistics: pass {(kind, layer)} of {(N, seg, V)} is outside the kernels' domain")
+    return _empty((n,), like)
+
+
+def sgn15_frames_stats(x, wimg, layer, V, heads, d_head, ff):
+    """``sgn15_frames`` cut off at the token tile [pos + vel | spa] (layer 1: the spatial block's n_a) or behind the
+    attention half of the block (layer 2: n_f, on x1) -> part (N * seg, 2, 128): per frame and channel the sum over the V
+    joints and M2 about the frame's mean."""
+    if x.dim() != 3 or x.shape[2] != 3 * V:
+        raise ValueError(f"agcn_amd: sgn15_frames_stats takes (N, seg, {3 * V}), got {tuple(x.shape)}")
+    N, seg, _ = x.shape
+    part = _sgn15_stats_part(SGN15_STATS_FRAMES, layer, N, seg, V, x)
+    _lib.call("agcn_sgn15_frames_stats", x, wimg, wimg.numel(), part, part.numel(), layer, N, seg, V, heads, d_head, ff)
+    SGN15_BNSTATS_STATS['frames_stats'] += 1
+    return part.view(N * seg, 2, 128)
+
+
+def sgn15_clip_stats(feat, wimg, layer, num_class, heads, d_head, ff):
+    """``sgn15_clip`` cut off behind its load of feat + tem (layer 1: the temporal block's n_a) or behind the attention
+    half of the block (layer 2: n_f) -> part (N, 2, 256): per clip and channel the sum over the seg frames and M2 about
+    the clip's mean."""
+    if feat.dim() != 3 or feat.shape[2] != 256:
+        raise ValueError(f"agcn_amd: sgn15_clip_stats takes feat (N, seg, 256), got {tuple(feat.shape)}")
+    N, seg, _ = feat.shape
+    part = _sgn15_stats_part(SGN15_STATS_CLIP, layer, N, seg, 2, feat)
+    _lib.call("agcn_sgn15_clip_stats", feat, wimg, wimg.numel(), part, part.numel(), layer, N, seg, num_class, heads, d_head,
+              ff)
+    SGN15_BNSTATS_STATS['clip_stats'] += 1
+    return part.view(N, 2, 256)
+
+
+def sgn15_stats_finalize(part, kind, layer, N, seg, V, carry=None, want_carry=False):
+    """``sgn_stats_finalize`` for a pass of SGN v15: the same merge order and carry state."""
+    return _sgn_stats_finalize('sgn15_stats', SGN15_BNSTATS_STATS, _L().agcn_sgn15_stats_channels(kind, layer), part, kind,
+                               layer, N, seg, V, carry, want_carry)
+
+
+def sgn15_stats_clip_bytes(seg, V):
+    """Bytes of the largest partial buffer of a pass per clip (every partial buffer is linear in the clips)."""
+    floats = (_L().agcn_sgn_stats_part_floats(SGN_STATS_INPUT, 0, 1, seg, V),
+              _L().agcn_sgn15_stats_part_floats(SGN15_STATS_FRAMES, 1, 1, seg, V),
+              _L().agcn_sgn15_stats_part_floats(SGN15_STATS_CLIP, 1, 1, seg, V))
+    if min(floats) == 0:
+        raise ValueError(f"agcn_amd: SGN v15 batch statistics: {(seg, V)} is outside the kernels' domain")
+    return 4 * max(floats)
+
+
+def sgn15_stats_chunk(N, seg, V, max_part_bytes):
+    """Clips per chunk: as many whole clips as keep every partial buffer under ``max_part_bytes``, at least one and at
+    most ``SGN15_MAX_CLIPS``."""
+    return max(1, min(N, SGN15_MAX_CLIPS, int(max_part_bytes) // sgn15_stats_clip_bytes(seg, V)))
+
+
+def sgn15_batch_statistics(x, fold, V, num_class, spatial, temporal, max_part_bytes=SGN_MAX_STATS_BYTES):
+    """The batch statistics of SGN v15's six BatchNorms on x (N, seg, V*3) as ONE batch, and the forward under them ->
+    (logits, {name: (mean, biased var)}) with the names of ``SGN15_BN_NAMES``; the two input BatchNorms in the kernels'
+    feature order [v*3 + c].  ``fold(known)`` -> (frames image, clip image): the caller's fold with the BatchNorms in the
+    dict ``known`` {name: (mean, var)} on those statistics (model/sgn_v15.py::SGN._batch_images or the incremental
+    ``_batch_folder``, the same bits in the sections a pass reads); ``known`` only grows between calls and holds the two
+    input BatchNorms in their module's order c*V + v.  The input pass (the base SGN's), the two passes of the spatial
+    block, the full-depth frames launch, the two passes of the temporal block and the full-depth clip launch, each pass
+    chunked by whole clips under ``max_part_bytes`` and ``SGN15_MAX_CLIPS`` with the finalize's carry state, so the
+    chunking does not change a bit."""
+    if x.dim() != 3 or x.shape[2] != 3 * V:
+        raise ValueError(f"agcn_amd: sgn15_batch_statistics takes (N, seg, {3 * V}), got {tuple(x.shape)}")
+    x = x.detach().contiguous()
+    N, seg, _ = x.shape
+    run = _sgn_stats_runner(N, seg, V, sgn15_stats_chunk(N, seg, V, max_part_bytes))
+    mark = SGN15_BNSTATS_MARK or (lambda label: None)
+    known, out = {}, {}
+    mark('start')
+    _sgn_stats_input_pass(run, x, V, SGN15_BN_NAMES[:2], known, out)
+    mark('input')
+
+    def block(kind, names, which, src, launch):
+        for layer, name in zip((1, 2), names):
+            img = fold(known)[which]
+            mark('fold')
+            known[name] = out[name] = run(kind, layer, src, lambda s: launch(s, img, layer), sgn15_stats_finalize)
+            mark(f"{'frames' if which == 0 else 'clip'}{layer}")
+
+    block(SGN15_STATS_FRAMES, SGN15_BN_NAMES[2:4], 0, x, lambda xs, wf, layer: sgn15_frames_stats(xs, wf, layer, V, *spatial))
+
+    def clip_image(feat):
+        mark('frames_full')
+        block(SGN15_STATS_CLIP, SGN15_BN_NAMES[4:6], 1, feat,
+              lambda fs, wc, layer: sgn15_clip_stats(fs, wc, layer, num_class, *temporal))
+        wc = fold(known)[1]
+        mark('fold')
+        return wc
+
+    wf = fold(known)[0]
+    mark('fold')
+    logits = sgn15_fused_forward(x, wf, clip_image, V, num_class, spatial, temporal)[0]
+    mark('clip_full')
+    return logits, out

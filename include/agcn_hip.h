@@ -736,6 +736,43 @@ int agcn_sgn15_clip_wgrad(const float* tape, size_t tape_floats, const float* dl
                           void* ws, size_t ws_bytes, int N, int seg, int num_class, int heads, int d_head, int ff,
                           int rows_per_split, void* stream);
 
+/* ---- SGN v15: batch statistics of its block BatchNorms (csrc/sgn_v15_stats.hip; geometry in
+ * csrc/sgn_v15_stats_plan.h; the merge: csrc/sgn_stats_device.h, shared with the base SGN) ----
+ * The forward half of train-mode BatchNorm for the four BatchNorms of the two attention blocks: PreNorm's BatchNorm1d of
+ * the attention (n_a, on the block's input x) and of the feed-forward (n_f, on x1 = attention + bo + x).  The two
+ * DataNorms in front are measured by sgn_input_stats / sgn_stats_finalize(kind 0) above, unchanged.  The caller runs the
+ * passes in dependency order, each on folded weight images (sgn15_frames_weights / sgn15_clip_weights floats) in which
+ * the EARLIER BatchNorms carry their batch statistics.  A pass never reads a section that depends on the BatchNorm it
+ * measures: layer 1 reads no block section at all, layer 2 reads qkv_w, qkv_b, o_w, o_b and never f1_*, f2_* or fc_*; no
+ * identity fold is needed.  A pass writes per group and channel the sum and M2 = the sum of squares about the group's own
+ * mean to `part` ((groups, 2, C) floats), reduced in fp32 over the real token rows of the LDS tile in ascending order;
+ * sgn15_stats_finalize merges the groups.  Exact-f32 MFMA, fixed orders, no atomics; a group's partials do not depend on
+ * the batch around it.
+ *
+ * kind: 1 = frames (the spatial block, C = 128; one group per frame, V samples each), 2 = clip (the temporal block,
+ *   C = 256; one group per clip, seg samples each; V ignored).  layer: 1 = n_a, 2 = n_f.
+ * sgn15_stats_part_floats: floats of `part` for a launch of N clips (0 outside the domain).  sgn15_stats_channels: C.
+ * sgn15_frames_stats: sgn15_frames cut off at the complete token tile [pos + vel | spa] (layer 1) or behind the attention
+ *   half of the block (layer 2).  Takes the whole frames image (w_floats as for sgn15_frames).
+ * sgn15_clip_stats: sgn15_clip cut off behind its load of feat + tem (layer 1) or behind the attention half (layer 2).
+ * sgn15_stats_finalize: as sgn_stats_finalize -- the groups of a clip in ascending index, then the clips in ascending
+ *   index on top of carry_in, state (count, mean, M2) in fp64 -> mean, biased variance; carry_in / carry_out (3, C)
+ *   doubles, so a batch processed in chunks of whole clips gives the bits of one launch.
+ *   sgn15_stats_finalize_workspace: bytes of ws.
+ * AGCN_ERR_ARG: a null pointer, non-positive sizes, V outside 2..32, kind or layer outside 1..2, w_floats different from
+ *   the size query.  AGCN_ERR_UNSUPPORTED: sizes outside the domain of the forward launch the pass is cut from.
+ *   AGCN_ERR_WORKSPACE: part_floats or ws_bytes below their size queries.  All before any launch. */
+size_t agcn_sgn15_stats_part_floats(int kind, int layer, int N, int seg, int V);
+size_t agcn_sgn15_stats_channels(int kind, int layer);
+int agcn_sgn15_frames_stats(const float* x, const float* w, size_t w_floats, float* part, size_t part_floats, int layer,
+                            int N, int seg, int V, int heads, int d_head, int ff, void* stream);
+int agcn_sgn15_clip_stats(const float* feat, const float* w, size_t w_floats, float* part, size_t part_floats, int layer,
+                          int N, int seg, int num_class, int heads, int d_head, int ff, void* stream);
+size_t agcn_sgn15_stats_finalize_workspace(int kind, int layer, int N, int seg, int V);
+int agcn_sgn15_stats_finalize(const float* part, size_t part_floats, int kind, int layer, int N, int seg, int V,
+                              const double* carry_in, double* carry_out, float* mean, float* var, void* ws, size_t ws_bytes,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif
