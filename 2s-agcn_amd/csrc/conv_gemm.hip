@@ -484,6 +484,7 @@ __global__ void __launch_bounds__(WM* WN * 64, (TAPS == 1 && EPI == 0 && (AGG ==
     const int nmb = (C >= BM) ? (C / BM) : 1;
     const int VV = V * V;
     for (int i = 0; i < 3; ++i) {
+      if (i * C >= a.M) continue;   // block-uniform: a launch over one subset's rows (gcn_dadj_route) has no others
       const int c_lo = max(0, m0 - i * C), c_hi = min(C, m0 + BM - i * C);
       if (c_lo >= c_hi) continue;   // block-uniform
       const int npairs = (c_hi - c_lo + 1) >> 1;
@@ -733,6 +734,21 @@ int gcn_dadj_route(const float* dy, const float* wcat, const float* x, float* da
   a.src_stride = 1; a.f_off = 0; a.out_fs = 1; a.out_fo = 0; a.C = C;
   p.w = wcat; p.sa_m = 1; p.sa_i = 0; p.sa_c = 3L * C; p.tap_flip_from = -1;
   p.ws = workspace; p.ws_bytes = workspace_bytes;
+  constexpr int BM = 64;            // rows of a block of this configuration
+  if (!dry && C < BM && 3 * C > BM) {
+    // the rows of one subset would straddle two row blocks, which share one slot per (sample, subset, tile): one launch
+    // per subset instead (C rows, a single row block), each into its own third of every sample's slots.  The size
+    // query keeps the 3C-row form: the same slots, a workspace that covers the smaller launches.
+    const long per_subset = (long)make_geometry<1, 0, 1, 4, 2, 1, CKD, 1>(V, T, 1, C, Cout).ntiles * V * V;
+    a.M = C;
+    for (int i = 0; i < 3; ++i) {
+      p.w = wcat + (long)i * C;
+      a.dadj = dadj_part + i * per_subset;
+      int rc = launch_cfg<1, 0, 1, 4, 2, 1, CKD, 2, 1>(p, s);
+      if (rc != AGCN_OK) return rc;
+    }
+    return AGCN_OK;
+  }
   return launch_cfg<1, 0, 1, 4, 2, 1, CKD, 2, 1>(p, s);
 }
 

@@ -4,7 +4,10 @@
 //   * tokens: backbone output (N*M, C, T', V) -> (N, [CLS +] M*T', V*C) with the positional table added, and back;
 //   * the attention core of one layer: softmax(q k^T / sqrt(dh) + mask) [dropout] v for all heads from the packed
 //     in_proj output, the head-averaged weights, and its backward;
-//   * LayerNorm of (a + b) over rows of D, and its backward.
+//   * LayerNorm of (a + b) over rows of D, and its backward;
+//   * for the spatial head of aagcn_v24 (reference model/architecture/aagcn/aagcn_v24.py): tokens over joints, one sequence
+//     per frame window, (N*M, C, T', V) -> (N*T', [CLS +] M*V, C); an additive bias (Hb, L, L) on the logits of the
+//     attention core; its gradient, the score gradient summed over the sequences.
 //
 // Arithmetic is fp32 FMA in every AGCN_GEMM mode: the core is ~10 % of the layer's FLOPs and latency-bound at L = 201.
 // No float atomics: every sum over rows / samples / heads is taken by one thread or one workgroup in a fixed order, so
@@ -132,9 +135,19 @@ struct MhaArgs {
   float* avg;
   int N, L, H, dh;
   int heads_per_wg;            // H where avg is written (one workgroup sums the heads in order), else 1
+  const float* bias;           // (Hb, L, L) added to the scaled logits (mha_fwd_kernel<true>), else null
+  int Hb;
 };
 
+// the logit of (i, j): the scaled score, plus the bias where the kernel has one
+template <bool BIAS>
+__device__ __forceinline__ float mha_logit(const MhaArgs& a, float s, float scale, int h, int i, int j) {
+  if (BIAS) return s * scale + a.bias[enc_bias_index(h, i, j, a.L, a.Hb)];
+  return s * scale;
+}
+
 // one workgroup: ENC_ROWS query rows of sample n, head h (or all heads in turn)
+template <bool BIAS>
 __global__ void __launch_bounds__(ENC_THREADS) mha_fwd_kernel(MhaArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const EncMhaPlan p = enc_mha_plan(a.L, a.dh);
@@ -161,13 +174,14 @@ __global__ void __launch_bounds__(ENC_THREADS) mha_fwd_kernel(MhaArgs a) {
       float m = -INFINITY;
       for (int j = lane; j < a.L; j += 64) {
         const bool null_j = a.null_tok != nullptr && a.null_tok[enc_null_index(n, j, a.L)] != 0;
-        if (enc_allowed(i, j, a.causal, null_i, null_j)) m = fmaxf(m, s[j] * scale);
+        if (enc_allowed(i, j, a.causal, null_i, null_j)) m = fmaxf(m, mha_logit<BIAS>(a, s[j], scale, h, i, j));
       }
       m = wave_max(m);
       float sum = 0.f;
       for (int j = lane; j < a.L; j += 64) {
         const bool null_j = a.null_tok != nullptr && a.null_tok[enc_null_index(n, j, a.L)] != 0;
-        const float e = enc_allowed(i, j, a.causal, null_i, null_j) ? expf(s[j] * scale - m) : 0.f;
+        const float e =
+            enc_allowed(i, j, a.causal, null_i, null_j) ? expf(mha_logit<BIAS>(a, s[j], scale, h, i, j) - m) : 0.f;
         s[j] = e;
         sum += e;
       }
@@ -468,6 +482,102 @@ __global__ void __launch_bounds__(ENC_THREADS) tokens_bwd_sums_kernel(const floa
   if (dcls != nullptr && l == 0) dcls[f] = s;
 }
 
+// spatial tokens of aagcn_v24, fwd: tok[n*T' + t, cls + m*V + v, c] = x[n*M + m, c, t, v] + pe[cls + m*V + v, c]; bwd
+// (x = dx written, tok = dtok read).  The tile and its two walks are tokens_kernel's; the outer index differs.
+template <bool BWD>
+__global__ void __launch_bounds__(ENC_THREADS) stokens_kernel(float* __restrict__ x, const float* __restrict__ cls,
+                                                              const float* __restrict__ pe, float* __restrict__ tok,
+                                                              int N, int M, int C, int Tp, int V, int has_cls) {
+  __shared__ float tile[ENC_TOK_LDS];
+  const EncTokPlan p = enc_tok_plan(C, Tp, V);
+  const int tb = blockIdx.x % p.ntb, nm = blockIdx.x / p.ntb;
+  if (nm >= N * M) return;
+  const int n = nm / M, m = nm - n * M;
+  const int D = V * C, L = M * V + has_cls;
+  const int t0 = tb * p.tt, nt = min(p.tt, Tp - t0);
+  const int run = nt * V;                                       // contiguous floats of one channel
+  const int l0 = has_cls + m * V;                               // first token of person m
+  if (!BWD) {
+    for (int e = threadIdx.x; e < C * run; e += ENC_THREADS) {
+      const int c = e / run, q = e - c * run;
+      tile[c * p.w + q] = x[enc_x_index(nm, c, t0, 0, C, Tp, V) + q];
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < nt * D; e += ENC_THREADS) {
+      const int tt = e / D, f = e - tt * D;                     // f = v*C + c: token l0 + v, feature c
+      const int v = f / C, c = f - v * C;
+      float val = tile[c * p.w + tt * V + v];
+      if (pe != nullptr) val += pe[(long)l0 * C + f];
+      tok[enc_stok_index(n, t0 + tt, l0, 0, Tp, L, C) + f] = val;
+    }
+    if (has_cls && m == 0) {
+      for (int e = threadIdx.x; e < nt * C; e += ENC_THREADS) {
+        const int tt = e / C, c = e - tt * C;
+        tok[enc_stok_index(n, t0 + tt, 0, c, Tp, L, C)] = pe != nullptr ? cls[c] + pe[c] : cls[c];
+      }
+    }
+  } else {
+    for (int e = threadIdx.x; e < nt * D; e += ENC_THREADS) {
+      const int tt = e / D, f = e - tt * D;
+      const int v = f / C, c = f - v * C;
+      tile[c * p.w + tt * V + v] = tok[enc_stok_index(n, t0 + tt, l0, 0, Tp, L, C) + f];
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < C * run; e += ENC_THREADS) {
+      const int c = e / run, q = e - c * run;
+      x[enc_x_index(nm, c, t0, 0, C, Tp, V) + q] = tile[c * p.w + q];
+    }
+  }
+}
+
+// stage 1 of a sum over sequences: part[slot, col] = sum of src[s, col] over the slot's sequences s (ascending), col < W;
+// a sequence of src is `stride` floats long (W <= stride: the first W columns are summed)
+__global__ void __launch_bounds__(ENC_THREADS) seq_partial_kernel(const float* __restrict__ src, float* __restrict__ part,
+                                                                  long S, long stride, long W) {
+  const long col = (long)blockIdx.x * ENC_THREADS + threadIdx.x;
+  const long slot = blockIdx.y;
+  if (col >= W) return;
+  const long s0 = slot * ENC_SEQ_CHUNK, s1 = s0 + ENC_SEQ_CHUNK < S ? s0 + ENC_SEQ_CHUNK : S;
+  float acc = 0.f;
+  for (long s = s0; s < s1; ++s) acc += src[s * stride + col];
+  part[enc_seq_slab_index(slot, col, W)] = acc;
+}
+
+// stage 1 of the bias gradient: part[slot, (hb, i, j)] = sum over the slot's sequences n (ascending) and, when Hb = 1,
+// over the heads h (ascending inside n) of dS[n, h, i, j]
+__global__ void __launch_bounds__(ENC_THREADS) bias_partial_kernel(const float* __restrict__ ds, float* __restrict__ part,
+                                                                   int N, int L, int H, int Hb) {
+  const long LL = (long)L * L, W = (long)Hb * LL;
+  const long col = (long)blockIdx.x * ENC_THREADS + threadIdx.x;
+  const long slot = blockIdx.y;
+  if (col >= W) return;
+  const int hb = (int)(col / LL);
+  const long ij = col - (long)hb * LL;
+  const int h0 = Hb == 1 ? 0 : hb, h1 = Hb == 1 ? H : hb + 1;
+  const long n0 = slot * ENC_SEQ_CHUNK, n1 = n0 + ENC_SEQ_CHUNK < N ? n0 + ENC_SEQ_CHUNK : N;
+  float acc = 0.f;
+  for (long n = n0; n < n1; ++n)
+    for (int h = h0; h < h1; ++h) acc += ds[enc_prob_index((int)n, h, 0, 0, L, H) + ij];
+  part[enc_seq_slab_index(slot, col, W)] = acc;
+}
+
+__global__ void __launch_bounds__(ENC_THREADS) enc_zero_kernel(float* __restrict__ out, long count) {
+  const long e = (long)blockIdx.x * ENC_THREADS + threadIdx.x;
+  if (e < count) out[e] = 0.f;
+}
+
+// out[col] = sum over the S sequences of src[s, col], col < W, through the slab `part` (enc_seq_slots(S) x W floats)
+int seq_sum(const float* src, float* part, float* out, long S, long stride, long W, hipStream_t stream) {
+  const long slots = enc_seq_slots(S);          // <= ENC_SEQ_MAX_SLOTS: the y dimension of the grid
+  hipLaunchKernelGGL(seq_partial_kernel, dim3((unsigned)((W + ENC_THREADS - 1) / ENC_THREADS), (unsigned)slots),
+                     dim3(ENC_THREADS), 0, stream, src, part, S, stride, W);
+  int rc = agcn_check_launch();
+  if (rc != AGCN_OK) return rc;
+  hipLaunchKernelGGL(enc_slab_sum_kernel, dim3((unsigned)((W + 15) / 16)), dim3(ENC_THREADS), 0, stream,
+                     (const float*)part, (int)slots, (int)W, out, out, (int)W);
+  return agcn_check_launch();
+}
+
 int mha_grid(int N, int L, int H, int dh, int groups_per_sample, long* grid) {
   const EncMhaPlan p = enc_mha_plan(L, dh);
   if (enc_mha_lds_bytes(p) > ENC_LDS_LIMIT) return AGCN_ERR_UNSUPPORTED;
@@ -476,23 +586,63 @@ int mha_grid(int N, int L, int H, int dh, int groups_per_sample, long* grid) {
   return AGCN_OK;
 }
 
-}  // namespace
-
-extern "C" int agcn_mha_fwd(const float* qkv, const unsigned char* null_tok, int causal, const unsigned char* keep,
-                            float keep_scale, float* ctx, float* prob, float* avg, int N, int L, int H, int dh,
-                            void* stream) {
-  if (!qkv || !ctx || N < 1 || L < 1 || H < 1 || dh < 1 || causal < 0 || causal > 2) return AGCN_ERR_ARG;
+// agcn_mha_fwd (bias null) and agcn_mha_bias_fwd: one launcher, the bias in the instantiation of its own
+int mha_fwd_launch(const float* qkv, const float* bias, int Hb, const unsigned char* null_tok, int causal,
+                   const unsigned char* keep, float keep_scale, float* ctx, float* prob, float* avg, int N, int L, int H,
+                   int dh, hipStream_t stream) {
   if (!enc_mha_domain(N, L, H, dh)) return AGCN_ERR_UNSUPPORTED;
   long grid;
   const int per_wg = avg != nullptr ? H : 1;
   int rc = mha_grid(N, L, H, dh, H / per_wg, &grid);
   if (rc != AGCN_OK) return rc;
   const EncMhaPlan p = enc_mha_plan(L, dh);
-  MhaArgs a = {qkv, null_tok, keep, keep_scale, causal, ctx, prob, avg, N, L, H, dh, per_wg};
-  AGCN_NOTE_KERNEL("mha_fwd_kernel L=%d dh=%d rows=%d kb=%d lds=%ld heads/wg=%d", L, dh, ENC_ROWS, ENC_KB,
-                   enc_mha_lds_bytes(p), per_wg);
-  return agcn_launch_big<mha_fwd_kernel>(dim3((unsigned)grid), dim3(ENC_THREADS), (size_t)enc_mha_lds_bytes(p),
-                                         (hipStream_t)stream, a);
+  MhaArgs a = {qkv, null_tok, keep, keep_scale, causal, ctx, prob, avg, N, L, H, dh, per_wg, bias, Hb};
+  AGCN_NOTE_KERNEL("mha_fwd_kernel L=%d dh=%d rows=%d kb=%d lds=%ld heads/wg=%d%s", L, dh, ENC_ROWS, ENC_KB,
+                   enc_mha_lds_bytes(p), per_wg, bias != nullptr ? (Hb == 1 ? " bias=1" : " bias=H") : "");
+  if (bias != nullptr)
+    return agcn_launch_big<mha_fwd_kernel<true>>(dim3((unsigned)grid), dim3(ENC_THREADS), (size_t)enc_mha_lds_bytes(p),
+                                                 stream, a);
+  return agcn_launch_big<mha_fwd_kernel<false>>(dim3((unsigned)grid), dim3(ENC_THREADS), (size_t)enc_mha_lds_bytes(p),
+                                                stream, a);
+}
+
+}  // namespace
+
+extern "C" int agcn_mha_fwd(const float* qkv, const unsigned char* null_tok, int causal, const unsigned char* keep,
+                            float keep_scale, float* ctx, float* prob, float* avg, int N, int L, int H, int dh,
+                            void* stream) {
+  if (!qkv || !ctx || N < 1 || L < 1 || H < 1 || dh < 1 || causal < 0 || causal > 2) return AGCN_ERR_ARG;
+  return mha_fwd_launch(qkv, nullptr, 1, null_tok, causal, keep, keep_scale, ctx, prob, avg, N, L, H, dh,
+                        (hipStream_t)stream);
+}
+
+extern "C" int agcn_mha_bias_fwd(const float* qkv, const float* bias, int Hb, const unsigned char* null_tok, int causal,
+                                 const unsigned char* keep, float keep_scale, float* ctx, float* prob, float* avg, int N,
+                                 int L, int H, int dh, void* stream) {
+  if (!qkv || !bias || !ctx || N < 1 || L < 1 || H < 1 || dh < 1 || causal < 0 || causal > 2) return AGCN_ERR_ARG;
+  if (!enc_bias_heads_ok(Hb, H)) return AGCN_ERR_ARG;
+  return mha_fwd_launch(qkv, bias, Hb, null_tok, causal, keep, keep_scale, ctx, prob, avg, N, L, H, dh,
+                        (hipStream_t)stream);
+}
+
+extern "C" size_t agcn_mha_bias_grad_workspace(int N, int L, int H, int Hb) {
+  return enc_bias_grad_domain(N, L, H, Hb) ? (size_t)enc_bias_grad_ws_bytes(N, L, H, Hb) : 0;
+}
+
+extern "C" int agcn_mha_bias_grad(const float* ds, float* dbias, void* ws, size_t ws_bytes, int N, int L, int H, int Hb,
+                                  void* stream) {
+  if (!ds || !dbias || !ws || N < 1 || L < 1 || H < 1 || !enc_bias_heads_ok(Hb, H)) return AGCN_ERR_ARG;
+  if (!enc_bias_grad_domain(N, L, H, Hb)) return AGCN_ERR_UNSUPPORTED;
+  if ((long)ws_bytes < enc_bias_grad_ws_bytes(N, L, H, Hb)) return AGCN_ERR_WORKSPACE;
+  const long W = (long)Hb * L * L, slots = enc_seq_slots(N);
+  AGCN_NOTE_KERNEL("bias_partial_kernel+enc_slab_sum_kernel N=%d L=%d H=%d Hb=%d slots=%ld", N, L, H, Hb, slots);
+  hipLaunchKernelGGL(bias_partial_kernel, dim3((unsigned)((W + ENC_THREADS - 1) / ENC_THREADS), (unsigned)slots),
+                     dim3(ENC_THREADS), 0, (hipStream_t)stream, ds, (float*)ws, N, L, H, Hb);
+  int rc = agcn_check_launch();
+  if (rc != AGCN_OK) return rc;
+  hipLaunchKernelGGL(enc_slab_sum_kernel, dim3((unsigned)((W + 15) / 16)), dim3(ENC_THREADS), 0, (hipStream_t)stream,
+                     (const float*)ws, (int)slots, (int)W, dbias, dbias, (int)W);
+  return agcn_check_launch();
 }
 
 extern "C" int agcn_mha_bwd(const float* dctx, const float* qkv, const float* prob, const unsigned char* keep,
@@ -580,5 +730,61 @@ extern "C" int agcn_tokens_bwd(const float* dtok, float* dx, float* dcls, float*
                        0, (hipStream_t)stream, dtok, dcls, dpe, N, L, D, rows);
     return agcn_check_launch();
   }
+  return AGCN_OK;
+}
+
+extern "C" int agcn_tokens_spatial_fwd(const float* x, const float* cls, const float* pe, int pe_rows, float* tok, int N,
+                                       int M, int C, int Tp, int V, void* stream) {
+  if (!x || !tok || N < 1 || M < 1 || C < 1 || Tp < 1 || V < 1) return AGCN_ERR_ARG;
+  const int has_cls = cls != nullptr;
+  if (!enc_stok_domain(N, M, C, Tp, V, has_cls)) return AGCN_ERR_UNSUPPORTED;
+  if (pe != nullptr && pe_rows < M * V + has_cls) return AGCN_ERR_ARG;
+  const EncTokPlan p = enc_tok_plan(C, Tp, V);
+  if (p.lds_floats > ENC_TOK_LDS) return AGCN_ERR_UNSUPPORTED;
+  AGCN_NOTE_KERNEL("stokens_kernel<fwd> C=%d T'=%d V=%d tt=%d", C, Tp, V, p.tt);
+  hipLaunchKernelGGL(stokens_kernel<false>, dim3((unsigned)((long)p.ntb * N * M)), dim3(ENC_THREADS), 0,
+                     (hipStream_t)stream, const_cast<float*>(x), cls, pe, tok, N, M, C, Tp, V, has_cls);
+  return agcn_check_launch();
+}
+
+extern "C" size_t agcn_tokens_spatial_bwd_workspace(int N, int M, int C, int Tp, int V, int has_cls) {
+  return enc_stok_domain(N, M, C, Tp, V, has_cls) ? (size_t)enc_stok_bwd_ws_bytes(N, M, C, Tp, V, has_cls) : 0;
+}
+
+extern "C" int agcn_tokens_spatial_bwd(const float* dtok, float* dx, float* dcls, float* dpe, int has_cls, int pe_rows,
+                                       void* ws, size_t ws_bytes, int N, int M, int C, int Tp, int V, void* stream) {
+  if (!dtok || N < 1 || M < 1 || C < 1 || Tp < 1 || V < 1 || (has_cls != 0 && has_cls != 1)) return AGCN_ERR_ARG;
+  if (dcls != nullptr && !has_cls) return AGCN_ERR_ARG;
+  if ((dcls != nullptr || dpe != nullptr) && !ws) return AGCN_ERR_ARG;
+  if (!enc_stok_domain(N, M, C, Tp, V, has_cls)) return AGCN_ERR_UNSUPPORTED;
+  const int L = M * V + has_cls;
+  if (dpe != nullptr && (pe_rows < L || pe_rows > 65536)) return AGCN_ERR_ARG;
+  if ((dcls != nullptr || dpe != nullptr) && (long)ws_bytes < enc_stok_bwd_ws_bytes(N, M, C, Tp, V, has_cls))
+    return AGCN_ERR_WORKSPACE;
+  const EncTokPlan p = enc_tok_plan(C, Tp, V);
+  if (p.lds_floats > ENC_TOK_LDS) return AGCN_ERR_UNSUPPORTED;
+  AGCN_NOTE_KERNEL("stokens_kernel<bwd> C=%d T'=%d V=%d tt=%d", C, Tp, V, p.tt);
+  hipStream_t st = (hipStream_t)stream;
+  if (dx != nullptr) {
+    hipLaunchKernelGGL(stokens_kernel<true>, dim3((unsigned)((long)p.ntb * N * M)), dim3(ENC_THREADS), 0, st, dx,
+                       (const float*)nullptr, (const float*)nullptr, const_cast<float*>(dtok), N, M, C, Tp, V, has_cls);
+    int rc = agcn_check_launch();
+    if (rc != AGCN_OK) return rc;
+  }
+  const long S = (long)N * Tp, LC = (long)L * C;
+  if (dpe != nullptr) {
+    // rows < L: the sum over the sequences; the table rows behind them: zeros; dcls is row 0 summed once more, the
+    // same additions in the same order
+    int rc = seq_sum(dtok, (float*)ws, dpe, S, LC, LC, st);
+    if (rc != AGCN_OK) return rc;
+    const long tail = ((long)pe_rows - L) * C;
+    if (tail > 0) {
+      hipLaunchKernelGGL(enc_zero_kernel, dim3((unsigned)((tail + ENC_THREADS - 1) / ENC_THREADS)), dim3(ENC_THREADS), 0,
+                         st, dpe + LC, tail);
+      rc = agcn_check_launch();
+      if (rc != AGCN_OK) return rc;
+    }
+  }
+  if (dcls != nullptr) return seq_sum(dtok, (float*)ws, dcls, S, LC, C, st);
   return AGCN_OK;
 }

@@ -147,3 +147,42 @@ ENC_HD EncTokPlan enc_tok_plan(int C, int Tp, int V) {
 }
 ENC_HD long enc_x_index(int nm, int c, int t, int v, int C, int Tp, int V) { return (((long)nm * C + c) * Tp + t) * V + v; }
 ENC_HD long enc_tok_index(int n, int l, int f, int L, int D) { return ((long)n * L + l) * D + f; }
+
+// ---- additive attention bias (aagcn_v24): bias (Hb, L, L), Hb = 1 (shared by the heads) or H (one slice per head) ----
+ENC_HD bool enc_bias_heads_ok(int Hb, int H) { return Hb == 1 || Hb == H; }
+ENC_HD long enc_bias_index(int h, int i, int j, int L, int Hb) { return (((long)(Hb == 1 ? 0 : h)) * L + i) * L + j; }
+
+// ---- sums over sequences (the bias gradient, dcls / dpe of the spatial tokens), two stages ----
+// Stage 1: slot b holds the sum over the sequences [b*ENC_SEQ_CHUNK, min(S, (b+1)*ENC_SEQ_CHUNK)), ascending, of every
+// column; stage 2 (enc_slab_sum_kernel) adds the slots in its fixed order.  ENC_SEQ_CHUNK = 32 sequences per slot.
+#define ENC_SEQ_CHUNK 32
+#define ENC_SEQ_MAX_W (1L << 28)        // most columns of a slab (an int column index, W + 16 without overflow)
+#define ENC_SEQ_MAX_SLOTS 65535         // the slots are the y dimension of stage 1's grid: at most 2 097 120 sequences
+ENC_HD long enc_seq_slots(long S) { return (S + ENC_SEQ_CHUNK - 1) / ENC_SEQ_CHUNK; }
+ENC_HD long enc_seq_slab_index(long slot, long col, long W) { return slot * W + col; }
+
+// dbias[hb, i, j] = sum_n (sum_h when Hb = 1) dS[n, h, i, j]: n ascending, h ascending inside n; slab [slots][Hb*L*L]
+ENC_HD bool enc_bias_grad_domain(int N, int L, int H, int Hb) {
+  return N >= 1 && L >= 1 && L <= ENC_MAX_L && H >= 1 && H <= ENC_MAX_D && enc_bias_heads_ok(Hb, H) &&
+         (long)Hb * L * L <= ENC_SEQ_MAX_W && enc_seq_slots(N) <= ENC_SEQ_MAX_SLOTS;
+}
+ENC_HD long enc_bias_grad_ws_bytes(int N, int L, int H, int Hb) { return enc_seq_slots(N) * ((long)Hb * L * L) * 4; }
+
+// ---- spatial tokens (aagcn_v24): x (N*M, C, T', V) <-> tok (N*T', L, C), L = cls + M*V: sequence n*T' + t, token
+// cls + m*V + v, feature c.  For a fixed (n, m, t) the V*C floats of tok are contiguous, as in the temporal tokens: the
+// same tile (enc_tok_plan), another outer index.  The positional row of token l is pe[l, :]. ----
+ENC_HD bool enc_stok_domain(int N, int M, int C, int Tp, int V, int has_cls) {
+  if (N < 1 || M < 1 || C < 1 || Tp < 1 || V < 1) return false;
+  if (C > ENC_MAX_D || (long)C * (V | 1) > ENC_TOK_LDS) return false;       // one frame of the tile fits the LDS
+  const long L = (long)M * V + (has_cls ? 1 : 0);
+  if (L > ENC_MAX_L || L * C > ENC_SEQ_MAX_W) return false;
+  return (long)N * M * Tp <= (1L << 30) && (long)N * Tp * L * C <= (1L << 40) &&
+         enc_seq_slots((long)N * Tp) <= ENC_SEQ_MAX_SLOTS;
+}
+ENC_HD long enc_stok_index(int n, int t, int l, int c, int Tp, int L, int C) {
+  return ((((long)n * Tp + t) * L) + l) * C + c;
+}
+// slab [slots][L*C] of the sums over the N*T' sequences
+ENC_HD long enc_stok_bwd_ws_bytes(int N, int M, int C, int Tp, int V, int has_cls) {
+  return enc_seq_slots((long)N * Tp) * (((long)M * V + (has_cls ? 1 : 0)) * C) * 4;
+}

@@ -1473,7 +1473,8 @@ for _f in (UnitGCNFunction, UnitTCNFunction, TCNResidualFunction, TCNGCNUnitFunc
 
 
 # ------------------------------------------------------------------------------------------------
-# transformer-encoder head of aagcn_v17 (csrc/encoder.hip): tokens, attention core, add + LayerNorm
+# transformer-encoder head of aagcn_v17 (csrc/encoder.hip): tokens, attention core, add + LayerNorm; for the spatial head
+# of aagcn_v24: tokens over joints (one sequence per frame window) and the attention core with an additive bias
 # ------------------------------------------------------------------------------------------------
 def encoder_hip_enabled():
     """AGCN_ENCODER_HIP=0 runs the encoder head as the tensor-code composition of the same maths (``tokens_ref``,
@@ -1527,6 +1528,62 @@ def tokens_ref(x, cls, pe, M):
     return tok
 
 
+def _spatial_dims(x, cls, pe, M, what):
+    if x.dim() != 4 or M < 1 or x.shape[0] % M != 0:
+        raise ValueError(f"agcn_amd.ops.{what}: x must be (N*M, C, T', V) with M = {M}, got {tuple(x.shape)}")
+    NM, C, Tp, V = x.shape
+    L = M * V + (cls is not None)
+    if cls is not None and tuple(cls.shape) != (1, 1, C):
+        raise ValueError(f"agcn_amd.ops.{what}: cls must be (1, 1, {C}), got {tuple(cls.shape)}")
+    if pe is not None and (pe.dim() != 3 or pe.shape[0] != 1 or pe.shape[2] != C or pe.shape[1] < L):
+        raise ValueError(f"agcn_amd.ops.{what}: pe must be (1, rows >= {L}, {C}), got {tuple(pe.shape)}")
+    return NM // M, C, Tp, V, L
+
+
+class SpatialTokensFunction(torch.autograd.Function):
+    """x (N*M, C, T', V), cls (1, 1, C) or None, pe (1, rows >= L, C) or None -> tok (N*T', L, C), L = cls + M*V: one
+    sequence per frame window, token cls + m*V + v, feature c, plus the positional rows (reference aagcn_v24.py:287-292).
+    args: x, cls, pe, M"""
+
+    @staticmethod
+    def forward(ctx, x, cls, pe, M):
+        N, C, Tp, V, L = _spatial_dims(x, cls, pe, M, 'SpatialTokensFunction')
+        x = x.contiguous()
+        cls_ = None if cls is None else cls.contiguous()
+        pe_ = None if pe is None else pe.contiguous()
+        tok = _empty((N * Tp, L, C), x)
+        _lib.call("agcn_tokens_spatial_fwd", x, cls_, pe_, 0 if pe is None else pe.shape[-2], tok, N, M, C, Tp, V)
+        ctx.dims = (N, M, C, Tp, V, cls is not None, None if pe is None else tuple(pe.shape))
+        return tok
+
+    @staticmethod
+    def backward(ctx, dtok):
+        N, M, C, Tp, V, has_cls, pe_shape = ctx.dims
+        dtok = dtok.contiguous()
+        ng = ctx.needs_input_grad
+        dx = _empty((N * M, C, Tp, V), dtok) if ng[0] else None
+        dcls = _empty((1, 1, C), dtok) if (has_cls and ng[1]) else None
+        dpe = _empty(pe_shape, dtok) if (pe_shape is not None and ng[2]) else None
+        ws, nbytes = None, 0
+        if dcls is not None or dpe is not None:
+            nbytes = _L().agcn_tokens_spatial_bwd_workspace(N, M, C, Tp, V, int(has_cls))
+            ws = _ws(nbytes, dtok)
+        _lib.call("agcn_tokens_spatial_bwd", dtok, dx, dcls, dpe, int(has_cls), 0 if dpe is None else pe_shape[-2], ws,
+                  nbytes, N, M, C, Tp, V)
+        return dx, dcls, dpe, None
+
+
+def tokens_spatial_ref(x, cls, pe, M):
+    """The tensor-code form of SpatialTokensFunction (any device, any dtype)."""
+    N, C, Tp, V, L = _spatial_dims(x, cls, pe, M, 'tokens_spatial_ref')
+    tok = x.reshape(N, M, C, Tp, V).permute(0, 3, 1, 4, 2).reshape(N * Tp, M * V, C)
+    if cls is not None:
+        tok = torch.cat((cls.expand(N * Tp, 1, C), tok), dim=1)
+    if pe is not None:
+        tok = tok + pe[:, :tok.size(1), :]
+    return tok
+
+
 class MHAFunction(torch.autograd.Function):
     """The attention core of one encoder layer on the packed in_proj output.
     args: qkv (N, L, 3D), H, null_tok (N, L) uint8 or None, causal (0 none, 1 j <= i, 2 j >= i), keep (N, H, L, L) uint8
@@ -1561,13 +1618,84 @@ class MHAFunction(torch.autograd.Function):
         return dqkv, None, None, None, None, None, None
 
 
-def mha_ref(qkv, H, null_tok=None, causal=0, keep=None, keep_scale=1.0, need_avg=False, want_prob=False):
-    """The tensor-code form of MHAFunction (any device, any dtype); want_prob also returns the softmax before dropout."""
+def _check_bias(bias, L, H, what):
+    """bias (Hb, L, L), Hb in {1, H}: the additive attention bias of aagcn_v24, checked before any foreign call."""
+    if bias.dim() != 3 or tuple(bias.shape[1:]) != (L, L) or bias.shape[0] not in (1, H):
+        raise ValueError(f"agcn_amd.ops.{what}: bias must be (Hb, L, L) with Hb in (1, {H}) and L = {L}, got "
+                         f"{tuple(bias.shape)}")
+
+
+class MHABiasFunction(torch.autograd.Function):
+    """MHAFunction with an additive bias on the logits (aagcn_v24's ``alpha * PA``): softmax(q k^T / sqrt(dh) + bias),
+    the bias added before the masks and the row maximum.
+    args: qkv (N, L, 3D), H, bias (Hb, L, L) with Hb in {1, H} or None, null_tok, causal, keep, keep_scale, need_avg ->
+    ctx, avg.  dbias is the score gradient summed over the N sequences (and over the heads when Hb = 1), in a fixed
+    order (agcn_mha_bias_grad).  bias None: MHAFunction's launches, bit for bit."""
+
+    @staticmethod
+    def forward(ctx, qkv, H, bias, null_tok, causal, keep, keep_scale, need_avg):
+        if qkv.dim() != 3 or qkv.shape[-1] % (3 * H) != 0:
+            raise ValueError(f"agcn_amd.ops.MHABiasFunction: qkv must be (N, L, 3*H*dh) with H = {H}, got "
+                             f"{tuple(qkv.shape)}")
+        qkv = qkv.contiguous()
+        N, L, D3 = qkv.shape
+        D = D3 // 3
+        dh = D // H
+        Hb = 0
+        if bias is not None:
+            _check_bias(bias, L, H, 'MHABiasFunction')
+            bias = bias.contiguous()
+            Hb = bias.shape[0]
+        if null_tok is not None and tuple(null_tok.shape) != (N, L):
+            raise ValueError(f"agcn_amd.ops.MHABiasFunction: null_tok must be {(N, L)}, got {tuple(null_tok.shape)}")
+        if keep is not None and tuple(keep.shape) != (N, H, L, L):
+            raise ValueError(f"agcn_amd.ops.MHABiasFunction: keep must be {(N, H, L, L)}, got {tuple(keep.shape)}")
+        out = _empty((N, L, D), qkv)
+        need_bwd = ctx.needs_input_grad[0] or ctx.needs_input_grad[2]
+        prob = _empty((N, H, L, L), qkv) if need_bwd else None
+        avg = _empty((N, L, L), qkv) if need_avg else None
+        if bias is None:
+            _lib.call("agcn_mha_fwd", qkv, null_tok, int(causal), keep, float(keep_scale), out, prob, avg, N, L, H, dh)
+        else:
+            _lib.call("agcn_mha_bias_fwd", qkv, bias, Hb, null_tok, int(causal), keep, float(keep_scale), out, prob, avg,
+                      N, L, H, dh)
+        if need_bwd:
+            ctx.save_for_backward(qkv, prob, keep)
+        ctx.dims, ctx.keep_scale, ctx.Hb = (N, L, H, dh), float(keep_scale), Hb
+        if avg is not None:
+            ctx.mark_non_differentiable(avg)
+        return out, avg
+
+    @staticmethod
+    def backward(ctx, dout, _davg):
+        qkv, prob, keep = ctx.saved_tensors
+        N, L, H, dh = ctx.dims
+        dout = dout.contiguous()
+        dqkv = torch.empty_like(qkv)
+        ds = _empty((N, H, L, L), qkv)
+        _lib.call("agcn_mha_bwd", dout, qkv, prob, keep, ctx.keep_scale, dqkv, ds, ds.numel() * 4, N, L, H, dh)
+        dbias = None
+        if ctx.Hb and ctx.needs_input_grad[2]:
+            dbias = _empty((ctx.Hb, L, L), qkv)
+            nbytes = _L().agcn_mha_bias_grad_workspace(N, L, H, ctx.Hb)
+            if nbytes == 0:
+                raise RuntimeError(f"agcn_amd.ops.MHABiasFunction: no bias gradient for N={N} L={L} H={H} Hb={ctx.Hb}")
+            ws = _ws(nbytes, qkv)
+            _lib.call("agcn_mha_bias_grad", ds, dbias, ws, nbytes, N, L, H, ctx.Hb)
+        return (dqkv if ctx.needs_input_grad[0] else None), None, dbias, None, None, None, None, None
+
+
+def mha_ref(qkv, H, null_tok=None, causal=0, keep=None, keep_scale=1.0, need_avg=False, want_prob=False, bias=None):
+    """The tensor-code form of MHAFunction / MHABiasFunction (any device, any dtype); want_prob also returns the softmax
+    before dropout; bias (Hb, L, L), Hb in {1, H}, is added to the scaled logits."""
     N, L, D3 = qkv.shape
     D = D3 // 3
     dh = D // H
     q, k, v = (t.reshape(N, L, H, dh).transpose(1, 2) for t in qkv.split(D, dim=-1))
     s = (q @ k.transpose(-1, -2)) / (dh ** 0.5)
+    if bias is not None:
+        _check_bias(bias, L, H, 'mha_ref')
+        s = s + bias[None]
     masked = torch.zeros(N, 1, L, L, dtype=torch.bool, device=qkv.device)
     if null_tok is not None:
         nt = null_tok.bool()

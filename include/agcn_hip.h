@@ -476,6 +476,36 @@ int agcn_ln_fwd(const float* a, const float* b, const float* gamma, const float*
 int agcn_ln_bwd(const float* dy, const float* a, const float* b, const float* gamma, const float* mean, const float* rstd,
                 float* dx, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, long R, int D, void* stream);
 
+/* ---- spatial transformer head of aagcn_v24 (csrc/encoder.hip; geometry in csrc/encoder_plan.h) ----
+ * The same rules as the entries above: fp32 FMA, no float atomics, fixed summation orders, bitwise reproducible outputs,
+ * AGCN_ERR_ARG / AGCN_ERR_UNSUPPORTED before any HIP call.  Sums over sequences take two stages: slot b of a slab holds
+ * the sum over the sequences [32 b, 32 b + 32) in ascending order, the slots are then added in the fixed order of the
+ * LayerNorm slab (16 interleaved chains, then the 16 chain sums in order).
+ *
+ * tokens_spatial_fwd: x (N*M, C, T', V), cls (C) or NULL, pe (pe_rows >= L, C) or NULL -> tok (N*T', L, C),
+ *   L = (cls ? 1 : 0) + M*V: tok[n*T' + t, cls + m*V + v, c] = x[n*M + m, c, t, v] + pe[cls + m*V + v, c],
+ *   tok[n*T' + t, 0] = cls + pe[0].  Domain: L <= 640, C <= 2048, C * (V | 1) <= 8192, N*T' <= 2 097 120.
+ * tokens_spatial_bwd: dtok -> dx (or NULL), dcls (C) = sum over the N*T' sequences of dtok[s, 0] (or NULL; needs has_cls),
+ *   dpe (pe_rows, C) = the same sum of dtok[s, l] for l < L and 0 for the rows behind (or NULL).  ws: the slab,
+ *   tokens_spatial_bwd_workspace bytes (0 outside the domain), needed when dcls or dpe is asked for.
+ *
+ * mha_bias_fwd: mha_fwd with bias (Hb, L, L), Hb = 1 (one slice for all heads) or H (slice h for head h; anything else is
+ *   AGCN_ERR_ARG): logits q.k / sqrt(dh) + bias, added before the masks and before the row maximum is taken.  mha_bwd
+ *   serves both forwards: the bias changes prob, not the formulas.
+ * mha_bias_grad: ds (N, H, L, L), the scratch mha_bwd has filled -> dbias (Hb, L, L) = sum_n (sum_h when Hb = 1) of
+ *   ds[n, h], n ascending, h ascending inside n.  ws: mha_bias_grad_workspace bytes (0 outside the domain). */
+int agcn_tokens_spatial_fwd(const float* x, const float* cls, const float* pe, int pe_rows, float* tok, int N, int M,
+                            int C, int Tp, int V, void* stream);
+size_t agcn_tokens_spatial_bwd_workspace(int N, int M, int C, int Tp, int V, int has_cls);
+int agcn_tokens_spatial_bwd(const float* dtok, float* dx, float* dcls, float* dpe, int has_cls, int pe_rows, void* ws,
+                            size_t ws_bytes, int N, int M, int C, int Tp, int V, void* stream);
+int agcn_mha_bias_fwd(const float* qkv, const float* bias, int Hb, const unsigned char* null_tok, int causal,
+                      const unsigned char* keep, float keep_scale, float* ctx, float* prob, float* avg, int N, int L,
+                      int H, int dh, void* stream);
+size_t agcn_mha_bias_grad_workspace(int N, int L, int H, int Hb);
+int agcn_mha_bias_grad(const float* ds, float* dbias, void* ws, size_t ws_bytes, int N, int L, int H, int Hb,
+                       void* stream);
+
 /* ---- base SGN, eval-mode inference (csrc/sgn.hip; geometry and weight-image layouts in csrc/sgn_plan.h) ----
  * The model the reference's online recogniser deploys (model/architecture/sgn/archiv/sgn.py, infer/inference.py:129-150)
  * as three launches.  Exact-f32 MFMA in every AGCN_GEMM mode, fixed summation orders, no atomics: outputs are bitwise

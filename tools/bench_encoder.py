@@ -2,6 +2,7 @@
 3 layers, dropout 0.2), and the whole aagcn_v17 training step at batch 64, T = 300.
 
     python tools/bench_encoder.py [--iters 30] [--warmup 5] [--reps 5] [--no-step]
+    python tools/bench_encoder.py --v24        # the aagcn_v24 head instead: 6400 sequences x 51 tokens x 144, H = 3
 
 One JSON line per part: tokens, attention core, add + LayerNorm (HIP kernels against the tensor-code composition that
 AGCN_ENCODER_HIP=0 selects), the four projections + activation of a layer (F.linear / ATen on either path), one whole
@@ -73,18 +74,67 @@ def report(name, variants, args, extra=None):
     return line
 
 
+def v24_case(args, dev):
+    """The spatial head of aagcn_v24 at the shape of its yaml (batch 64, T' = 100: 6400 sequences of 51 tokens, width 144,
+    3 heads, 3 layers, add_A single, cossin, CLS_MASK, dropout 0.2): the spatial tokens, the attention core with the
+    bias (forward, backward and the bias gradient), and the whole head as the model runs it (forward_postprocess: tokens,
+    3 layers, the masked mean), HIP kernels against AGCN_ENCODER_HIP=0."""
+    from agcn_amd import ops
+    from agcn_amd.model import aagcn_v24
+    n, m_, c, tp, v, h = 64, 2, 144, 100, 25, 3
+    seqs, ltok = n * tp, 1 + m_ * v
+    g = torch.Generator(device=dev).manual_seed(24)
+    rnd = lambda *s: torch.randn(*s, device=dev, generator=g)      # noqa: E731
+    leaf = lambda *s: rnd(*s).requires_grad_(True)                 # noqa: E731
+    x, cls, pe = leaf(n * m_, c, tp, v), leaf(1, 1, c), leaf(1, 100, c)
+    report('v24_spatial_tokens', {
+        'hip': fwd_bwd(lambda: ops.SpatialTokensFunction.apply(x, cls, pe, m_), [x, cls, pe]),
+        'tensor': fwd_bwd(lambda: ops.tokens_spatial_ref(x, cls, pe, m_), [x, cls, pe])}, args,
+        {'bytes_fwd': 4 * (x.numel() + seqs * ltok * c)})
+    qkv, bias = leaf(seqs, ltok, 3 * c), leaf(1, ltok, ltok)
+    keep = (torch.rand(seqs, h, ltok, ltok, device=dev, generator=g) >= P_DROP).to(torch.uint8)
+    ks = 1.0 / (1.0 - P_DROP)
+    flops = 4.0 * seqs * h * ltok * ltok * (c // h)
+    report('v24_attention_core_bias', {
+        'hip': fwd_bwd(lambda: ops.MHABiasFunction.apply(qkv, h, bias, None, 0, keep, ks, False)[0], [qkv, bias]),
+        'tensor': fwd_bwd(lambda: ops.mha_ref(qkv, h, None, 0, keep, ks, False, bias=bias)[0], [qkv, bias])}, args,
+        {'flop_fwd': flops, 'flop_bwd': 2.5 * flops, 'workgroups_fwd': seqs * h * ((ltok + 15) // 16)})
+    model = aagcn_v24.Model(graph='graph.ntu_rgb_d.Graph', graph_args=dict(labeling_mode='spatial'), kernel_size=3,
+                            pad=False, s_trans_cfg=dict(num_heads=h, model_dim=c, ffn_dim=4 * c, dropout=P_DROP,
+                                                        activation='gelu', prenorm=False, num_layers=LAYERS),
+                            add_A='single', pos_enc='cossin', classifier_type='CLS_MASK', model_layers=101).to(dev).train()
+    with torch.no_grad():
+        model.alpha.fill_(0.8)
+    model.attn_mask = (torch.rand(n, tp, 1, device=dev, generator=g) < 0.3)
+    size = torch.Size((n, 3, 3 * tp, v, m_))
+    feat = leaf(n * m_, c, tp, v)
+    leaves = [feat] + [p for k, p in model.named_parameters() if k.startswith(('s_', 'alpha'))]
+
+    def head(flag):
+        def f():
+            os.environ['AGCN_ENCODER_HIP'] = flag
+            return model.forward_postprocess(feat, size)[0]
+        return f
+    report('v24_head_3_layers', {'hip': fwd_bwd(head('1'), leaves), 'tensor': fwd_bwd(head('0'), leaves)}, args,
+           {'sequences': seqs, 'tokens': ltok, 'width': c, 'heads': h, 'layers': LAYERS})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=30)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--no-step', action='store_true', help='skip the whole-model training step')
+    ap.add_argument('--v24', action='store_true', help='the aagcn_v24 spatial head instead of the aagcn_v17 parts')
     args = ap.parse_args()
     import agcn_amd  # noqa: F401
     from agcn_amd import ops
     from agcn_amd.model import aagcn_v17
     assert torch.cuda.is_available(), "bench_encoder.py measures on the GPU"
     dev = torch.device('cuda:0')
+    if args.v24:
+        v24_case(args, dev)
+        return
     g = torch.Generator(device=dev).manual_seed(1)
     rnd = lambda *s: torch.randn(*s, device=dev, generator=g)      # noqa: E731
     leaf = lambda *s: rnd(*s).requires_grad_(True)                 # noqa: E731
