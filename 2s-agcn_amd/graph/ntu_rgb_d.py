@@ -10,6 +10,9 @@ _bones_1based = [(1, 2), (2, 21), (3, 21), (4, 3), (5, 21), (6, 5), (7, 6), (8, 
 inward = [(i - 1, j - 1) for (i, j) in _bones_1based]
 outward = [(j, i) for (i, j) in inward]
 neighbor = inward + outward
+# parent of every joint for the bone stream (ops.skeleton_streams): the 1-based pairs of the reference's
+# data_gen/gen_bone_data.py:6-13 minus 1.  Stated as data: joint 20 (the spine) is its own parent, which no edge says.
+bone_parents = [1, 20, 20, 2, 20, 4, 5, 6, 20, 8, 9, 10, 0, 12, 13, 14, 0, 16, 17, 18, 20, 22, 7, 24, 11]
 
 
 class Graph:
@@ -19,6 +22,7 @@ class Graph:
         self.inward = inward
         self.outward = outward
         self.neighbor = neighbor
+        self.bone_parents = list(bone_parents)
         self.A = self.get_adjacency_matrix(labeling_mode)
 
     def get_adjacency_matrix(self, labeling_mode=None):

@@ -13,6 +13,10 @@ _chains = [(0, 1),                    # nose -> neck
 inward = [(a, b) for chain in _chains for a, b in zip(chain[:-1], chain[1:])]
 outward = [(j, i) for (i, j) in inward]
 neighbor = inward + outward
+# parent of every joint for the bone stream (ops.skeleton_streams).  The reference's data_gen/gen_bone_data.py has no
+# table for this skeleton, so this one has no reference counterpart: the parents are this graph's own (child, parent)
+# edges, and the neck (joint 1), which every bone points towards, is its own parent.
+bone_parents = [dict(inward).get(v, v) for v in range(num_node)]
 
 
 class Graph:
@@ -22,6 +26,7 @@ class Graph:
         self.inward = inward
         self.outward = outward
         self.neighbor = neighbor
+        self.bone_parents = list(bone_parents)
         self.A = self.get_adjacency_matrix(labeling_mode)
 
     def get_adjacency_matrix(self, labeling_mode=None):

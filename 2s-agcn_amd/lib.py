@@ -6,9 +6,9 @@ definition that drifts is a compile error) and this module parses its text at im
 library.
 
 ``call(name, *args)`` / ``status(name, *args)`` are the checked way in: tensors are passed as they are and converted by
-the DECLARED parameter types (a wrong device, layout or element type raises before the foreign call), the trailing
-``void* stream`` is the current stream, and ``call`` turns a non-zero status into a ``RuntimeError`` that names the entry
-point.  ``load()`` returns the bare handle for size queries and for callers that pass addresses themselves (``ptr``,
+the DECLARED parameter types (a wrong device, layout or element type raises before the foreign call), a
+``const int* host_<name>`` parameter takes a host sequence of ints, the trailing ``void* stream`` is the current stream,
+and ``call`` turns a non-zero status into a ``RuntimeError`` that names the entry point.  ``load()`` returns the bare handle for size queries and for callers that pass addresses themselves (``ptr``,
 ``ptr_bits``, ``stream``, ``check``).
 
 The library is built in-tree by ``__graft_entry__.build()`` (``hipcc --offload-arch=gfx950``).  There is NO
@@ -101,6 +101,32 @@ def _pointer_converter(ctype, where):
     return convert
 
 
+def _host_ints_converter(where):
+    """A HOST array for one ``const int* host_<name>`` parameter, the only pointers of the header that are not device
+    pointers: a sequence of Python ints (or a numpy / CPU int array) becomes a C int array that lives for the call; None
+    is NULL.  The entry point validates the values; a device tensor, a float or a bool is refused here."""
+    def convert(values):
+        if values is None:
+            return None
+        if torch.is_tensor(values):
+            if values.is_cuda or values.dtype.is_floating_point or values.dtype == torch.bool:
+                raise RuntimeError(f"agcn_amd: {where}: expected a host sequence of ints, got {values.dtype} on "
+                                   f"{values.device}")
+            values = values.tolist()
+        values = list(values)
+        if any(isinstance(v, bool) or int(v) != v for v in values):
+            raise RuntimeError(f"agcn_amd: {where}: expected a host sequence of ints, got {values!r}")
+        return (ctypes.c_int * len(values))(*[int(v) for v in values])
+    return convert
+
+
+def _converter(ctype, pname, name):
+    if pname.startswith("host_"):
+        assert ctype == "const int*", f"{name}({pname}): host arrays are `const int*`"
+        return _host_ints_converter(f"{name}({pname})")
+    return _pointer_converter(ctype, f"{name}({pname})")
+
+
 DECLARATIONS, _CODES = parse_header(_read_header())
 ERR_ARG, ERR_WORKSPACE, ERR_UNSUPPORTED = (_CODES[k] for k in ("AGCN_ERR_ARG", "AGCN_ERR_WORKSPACE",
                                                                 "AGCN_ERR_UNSUPPORTED"))
@@ -113,8 +139,7 @@ _CONVERTERS = {}
 for _name, (_ret, _params) in DECLARATIONS.items():
     if any(t in _POINTERS for t, _ in _params):
         assert _ret == "int" and _params[-1] == ("void*", "stream"), f"{_name}: not `int {_name}(..., void* stream)`"
-        _CONVERTERS[_name] = tuple(_pointer_converter(t, f"{_name}({p})") if t in _POINTERS else None
-                                   for t, p in _params[:-1])
+        _CONVERTERS[_name] = tuple(_converter(t, p, _name) if t in _POINTERS else None for t, p in _params[:-1])
 
 _lib = None
 

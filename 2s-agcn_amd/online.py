@@ -15,6 +15,14 @@ With ``sgn_preprocess=True`` the recognisers run the reference's deployed SGN (`
 ``inference.py:102-107, 148-150`` does: the normalised window goes through ``ops.sgn_sample`` (``NTUDataLoaders.to_fix_length``:
 ``multi_test`` random subsamples of ``model.seg`` rows), the model runs on the subsamples and their logits are averaged.
 
+With ``streams=[(stream, model, model_args, weights), ...]`` (streams out of joint, bone, joint_motion, bone_motion) and
+``alpha=[...]`` (one weight per stream, default ones) a recogniser serves the reference's multi-stream result
+(``ensemble.py``: joint + alpha * bone) from the one joint window: the derived streams come out of one
+``ops.skeleton_streams`` launch, each model runs on its stream, ``logits = sum_i alpha_i * logits_i`` (the per-stream logits
+stay in ``stream_logits``), and ``explain`` folds the models' input gradients into one gradient with respect to the joint
+window with one ``ops.streams_bwd`` launch.  Still one synchronising copy per prediction.  The parent table is
+``stream_parents``, by default ``bone_parents`` of the first model's graph.
+
 The frame handed to ``append_data`` always carries exactly ``max_num_skeleton`` bodies (absent ones as zeros), as the
 reference's main loop does; its ``M < max_person`` case, which leaves stale rows in the window, is not reproduced."""
 import numpy as np
@@ -62,9 +70,9 @@ class _Recogniser:
     """What the recognisers share: the model in eval mode on the device, the window geometry and the normalisation
     options."""
 
-    def __init__(self, model, model_args=None, weights=None, max_frame=300, max_num_skeleton=4,
+    def __init__(self, model=None, model_args=None, weights=None, max_frame=300, max_num_skeleton=4,
                  max_num_skeleton_true=2, num_joint=25, moving_avg=1, zaxis=(0, 1), xaxis=(8, 4), zaxis2=None,
-                 device='cuda:0', sgn_preprocess=False, multi_test=5):
+                 device='cuda:0', sgn_preprocess=False, multi_test=5, streams=None, alpha=None, stream_parents=None):
         if not 1 <= max_num_skeleton_true <= max_num_skeleton:
             raise ValueError("agcn_amd: need 1 <= max_num_skeleton_true <= max_num_skeleton")
         if sgn_preprocess and (max_num_skeleton_true != 2 or multi_test < 1):
@@ -72,6 +80,16 @@ class _Recogniser:
         if not 1 <= moving_avg <= max_frame:
             raise ValueError("agcn_amd: need 1 <= moving_avg <= max_frame")
         self.device = torch.device(device)
+        # several input streams served from one normalised window (the reference's two-stream result, ensemble.py:
+        # joint + alpha * bone): one model per stream, the streams derived on the device, the logits fused
+        self.stream_names = self.models = self.alpha = self.stream_parents = None
+        self.stream_logits = None          # the per-stream logits of the last forward, in the order of `streams`
+        if streams is not None:
+            model = self._load_streams(model, sgn_preprocess, streams, alpha, stream_parents, num_joint)
+        elif model is None:
+            raise ValueError("agcn_amd: a recogniser needs `model` or `streams`")
+        elif alpha is not None or stream_parents is not None:
+            raise ValueError("agcn_amd: alpha and stream_parents belong to `streams`")
         if isinstance(model, str):
             model = load_model(model, model_args, weights)
             from .model.sgn_v15 import SGN as SGN15
@@ -90,6 +108,44 @@ class _Recogniser:
         self.sgn_preprocess, self.multi_test = bool(sgn_preprocess), int(multi_test)
         self.seg = int(self.model.seg) if self.sgn_preprocess else None
         self.draws = self.rows = None          # the last draws (N, multi_test, seg) int32 bit patterns, and row counts
+
+    def _load_streams(self, model, sgn_preprocess, streams, alpha, stream_parents, num_joint):
+        """``streams`` = [(stream, model, model_args, weights), ...] (model a dotted class path or a module; the two
+        trailing fields may be left out) -> the first model; fills stream_names, models, alpha, stream_parents."""
+        if sgn_preprocess:
+            raise ValueError("agcn_amd: sgn_preprocess with streams is not built: the SGN sampler reads joint windows")
+        if model is not None:
+            raise ValueError("agcn_amd: with `streams` the models are given per stream; leave `model` out")
+        entries = [tuple(e) + (None,) * (4 - len(tuple(e))) for e in streams]
+        names = [e[0] for e in entries]
+        if not entries or any(len(e) != 4 for e in entries) or any(n not in ops.STREAMS for n in names) or \
+                len(set(names)) != len(names):
+            raise ValueError(f"agcn_amd: streams is a non-empty list of (stream, model[, model_args[, weights]]) with "
+                             f"distinct streams out of {ops.STREAMS}, got {names}")
+        alpha = [1.0] * len(entries) if alpha is None else [float(a) for a in alpha]
+        if len(alpha) != len(entries):
+            raise ValueError(f"agcn_amd: alpha has one weight per stream: {len(entries)}, got {len(alpha)}")
+        nets = [load_model(m, a, w) if isinstance(m, str) else m for _, m, a, w in entries]
+        nets = [net.to(self.device).eval() for net in nets]
+        if any(n != 'joint' for n in names):
+            if stream_parents is None:
+                stream_parents = next((net.graph.bone_parents for net in nets
+                                       if getattr(getattr(net, 'graph', None), 'bone_parents', None) is not None), None)
+            if stream_parents is None:
+                raise ValueError("agcn_amd: the streams need stream_parents: no model carries a graph with bone_parents")
+            stream_parents = tuple(int(p) for p in stream_parents)
+            if len(stream_parents) != int(num_joint) or any(not 0 <= p < int(num_joint) for p in stream_parents):
+                raise ValueError(f"agcn_amd: stream_parents holds one joint index in [0, {num_joint}) per joint, got "
+                                 f"{list(stream_parents)}")
+        self.stream_names, self.models, self.alpha, self.stream_parents = names, nets, alpha, stream_parents
+        return nets[0]
+
+    def _stream_inputs(self, window):
+        """The inputs of the stream models from the normalised window: every derived stream out of ONE launch."""
+        want = tuple(n for n in self.stream_names if n != 'joint')
+        inputs = ops.skeleton_streams(window, self.stream_parents, want) if want else {}
+        inputs['joint'] = window
+        return inputs
 
     def _draws(self, draws, N):
         """None -> fresh draws on the device; else (N, S, seg) (or (S, seg) for one window) uint32 / int32 patterns."""
@@ -112,6 +168,16 @@ class _Recogniser:
                 rows, self.rows = ops.sgn_sample(window, self.draws, self.seg)
                 out = self.model(rows.view(N * self.multi_test, self.seg, -1))
                 self.logits = out[0].view(N, self.multi_test, -1).mean(1)
+            elif self.models is not None:
+                # logits = sum_i alpha_i * logits_i (reference ensemble.py:26-28: joint + alpha * bone)
+                inputs = self._stream_inputs(window.contiguous())
+                self.stream_logits, fused = [], None
+                for name, net, a in zip(self.stream_names, self.models, self.alpha):
+                    out = net(inputs[name])
+                    out = out[0] if isinstance(out, tuple) else out
+                    self.stream_logits.append(out)
+                    fused = a * out if fused is None else fused + a * out
+                self.logits = fused
             else:
                 out = self.model(window)
                 self.logits = out[0] if isinstance(out, tuple) else out
@@ -144,25 +210,40 @@ class _Recogniser:
                     cot = (onehot / S).repeat_interleave(S, 0)               # the mean logit of the draws
                     _, _, dx = self.model.input_gradient(rows.view(N * S, self.seg, -1), cot)
                     dwin = ops.sgn_sample_bwd(window, self.draws, dx.view(N, S, self.seg, -1), self.seg)
+            elif self.models is not None:
+                # each model's gradient with respect to ITS input, then one launch that carries them back to the joint
+                # window through the transposes of the streams, weighted by the alphas
+                with torch.no_grad():
+                    inputs = self._stream_inputs(window.contiguous())
+                cot = {name: self._input_gradient(net, inputs[name], onehot).contiguous()
+                       for name, net in zip(self.stream_names, self.models)}
+                weights = dict(zip(self.stream_names, self.alpha))
+                dwin = ops.streams_bwd(cot, self.stream_parents if self.stream_parents is not None else
+                                       tuple(range(window.shape[3])), [weights.get(n, 0.0) for n in ops.STREAMS])
             else:
-                # AGCN / AAGCN: the eval-mode backward with respect to the window alone (tools/saliency.py::saliency).
-                # The parameters' requires_grad is switched off for the call on purpose: the units' autograd Functions
-                # decide at forward time, from it, whether their backward computes weight gradients and the BatchNorm
-                # parameter sums (agcn_bn_bwd_eval with want_sums = 1); autograd.grad(inputs=x) alone would still run
-                # all of that and throw it away.  It is put back in the finally clause.
-                params = [p for p in self.model.parameters() if p.requires_grad]
-                for p in params:
-                    p.requires_grad_(False)
-                try:
-                    with torch.enable_grad():
-                        x = window.detach().clone().requires_grad_(True)
-                        out = self.model(x)
-                        out = out[0] if isinstance(out, tuple) else out
-                        dwin, = torch.autograd.grad((out * onehot).sum(), x)
-                finally:
-                    for p in params:
-                        p.requires_grad_(True)
+                dwin = self._input_gradient(self.model, window, onehot)
         return dwin, classes
+
+    @staticmethod
+    def _input_gradient(net, window, onehot):
+        """AGCN / AAGCN: the eval-mode backward with respect to the window alone (tools/saliency.py::saliency).
+        The parameters' requires_grad is switched off for the call on purpose: the units' autograd Functions
+        decide at forward time, from it, whether their backward computes weight gradients and the BatchNorm
+        parameter sums (agcn_bn_bwd_eval with want_sums = 1); autograd.grad(inputs=x) alone would still run
+        all of that and throw it away.  It is put back in the finally clause."""
+        params = [p for p in net.parameters() if p.requires_grad]
+        for p in params:
+            p.requires_grad_(False)
+        try:
+            with torch.enable_grad():
+                x = window.detach().clone().requires_grad_(True)
+                out = net(x)
+                out = out[0] if isinstance(out, tuple) else out
+                dwin, = torch.autograd.grad((out * onehot).sum(), x)
+        finally:
+            for p in params:
+                p.requires_grad_(True)
+        return dwin
 
     def explain(self, k=None):
         """Which joints and frames drove the last prediction: -> (saliency (N, T, K, V) float32 numpy, classes (N,) int64

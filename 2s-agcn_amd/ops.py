@@ -1304,6 +1304,190 @@ def skel_append_many(rings, frames, slot, count, moving_avg=1):
     _lib.call("agcn_skel_append_many", frames, rings, slot, count, S, Mmax, Tmax, V, int(moving_avg))
 
 
+# ---- bone and motion input streams from joint data (csrc/streams.hip) -----------------------------------------------------
+STREAMS = ('joint', 'bone', 'joint_motion', 'bone_motion')
+STREAM_MAX_V = 32
+
+
+def stream_hip_enabled():
+    """AGCN_STREAM_HIP=0 runs the streams as tensor code (``streams_ref`` / ``streams_bwd_ref``): for A/B."""
+    return os.environ.get('AGCN_STREAM_HIP', '1') != '0'
+
+
+def _stream_parents(parent, V):
+    """The parent table as a tuple of V Python ints in [0, V), checked on the host (the C entry checks it again)."""
+    if torch.is_tensor(parent) or isinstance(parent, np.ndarray):
+        parent = parent.tolist()
+    parent = tuple(parent)
+    if len(parent) != V:
+        raise ValueError(f"agcn_amd: the parent table has {len(parent)} entries for {V} joints")
+    if any(isinstance(p, bool) or int(p) != p or not 0 <= int(p) < V for p in parent):
+        raise ValueError(f"agcn_amd: every parent must be a joint index in [0, {V}), got {list(parent)}")
+    return tuple(int(p) for p in parent)
+
+
+def _stream_tensor(t, shape, like, what):
+    """One (N, C, T, V, M) tensor of a streams call: shape, dtype, layout and device, before any launch."""
+    if not torch.is_tensor(t) or t.dim() != 5 or (shape is not None and tuple(t.shape) != tuple(shape)):
+        want = "a 5-D (N, C, T, V, M) tensor" if shape is None else f"a tensor of shape {tuple(shape)}"
+        raise ValueError(f"agcn_amd: {what} must be {want}, got {tuple(t.shape) if torch.is_tensor(t) else type(t)}")
+    if not t.is_contiguous():
+        raise ValueError(f"agcn_amd: {what} must be contiguous (N, C, T, V, M), got strides {t.stride()}")
+    if like is not None and (t.device != like.device or t.dtype != like.dtype):
+        raise ValueError(f"agcn_amd: {what} must be {like.dtype} on {like.device}, got {t.dtype} on {t.device}")
+    if t.is_cuda and stream_hip_enabled() and t.dtype != torch.float32:
+        raise ValueError(f"agcn_amd: {what} must be float32 for the HIP route, got {t.dtype}")
+    if not t.dtype.is_floating_point:
+        raise ValueError(f"agcn_amd: {what} must be a floating-point tensor, got {t.dtype}")
+    if t.numel() == 0:
+        raise ValueError(f"agcn_amd: {what} is empty: {tuple(t.shape)}")
+    return t
+
+
+def _stream_want(want):
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or len(set(want)) != len(want) or any(w not in STREAMS[1:] for w in want):
+        raise ValueError(f"agcn_amd: want is a non-empty selection of {STREAMS[1:]} without repeats, got {want}")
+    return want
+
+
+def _motion_ref(x):
+    return torch.cat((x[:, :, 1:] - x[:, :, :-1], torch.zeros_like(x[:, :, :1])), 2)
+
+
+def streams_ref(x, parent, want=('bone',)):
+    """The tensor-code form of ``skeleton_streams`` (any device, any floating dtype): the same subtractions in the same
+    order, so the same bits in fp32.  -> dict."""
+    want = _stream_want(want)
+    parent = _stream_parents(parent, x.shape[3])
+    out = {}
+    if 'bone' in want or 'bone_motion' in want:
+        bone = x - x.index_select(3, torch.tensor(parent, dtype=torch.long, device=x.device))
+        if 'bone' in want:
+            out['bone'] = bone
+        if 'bone_motion' in want:
+            out['bone_motion'] = _motion_ref(bone)
+    if 'joint_motion' in want:
+        out['joint_motion'] = _motion_ref(x)
+    return {w: out[w] for w in want}
+
+
+def _motion_t_ref(d):
+    """motion^T: (t > 0 ? d[t-1] : 0) - (t < T-1 ? d[t] : 0)"""
+    z = torch.zeros_like(d[:, :, :1])
+    return torch.cat((z, d[:, :, :-1]), 2) - torch.cat((d[:, :, :-1], z), 2)
+
+
+def _bone_t_ref(d, parent):
+    """bone^T: d[v] - sum over the children c of v (ascending) of d[c]"""
+    out = d.clone()
+    for c, p in enumerate(parent):
+        out[:, :, :, p] -= d[:, :, :, c]
+    return out
+
+
+def streams_bwd_ref(cot, parent, weights=(1.0, 1.0, 1.0, 1.0)):
+    """The tensor-code form of ``streams_bwd``.  cot: dict stream name -> cotangent (absent or None: nothing)."""
+    dx = None
+    for name, w in zip(STREAMS, weights):
+        d = cot.get(name)
+        if d is None:
+            continue
+        if name.endswith('motion'):
+            d = _motion_t_ref(d)
+        if name.startswith('bone'):
+            d = _bone_t_ref(d, parent)
+        dx = w * d if dx is None else dx + w * d
+    if dx is None:
+        raise ValueError("agcn_amd: streams_bwd needs at least one cotangent")
+    return dx
+
+
+def streams_bwd(cot, parent, weights=(1.0, 1.0, 1.0, 1.0)):
+    """The transpose of the streams in one launch (agcn_streams_bwd): cot maps 'joint' / 'bone' / 'joint_motion' /
+    'bone_motion' to cotangents (N, C, T, V, M) (absent or None: nothing), ``weights`` the four factors in that order ->
+        dx = w_j d_joint + w_b bone^T(d_bone) + w_jm motion^T(d_jm) + w_bm bone^T(motion^T(d_bm)),
+    added in that order, a joint's children ascending.  CPU tensors and AGCN_STREAM_HIP=0 run ``streams_bwd_ref``."""
+    if any(k not in STREAMS for k in cot):
+        raise ValueError(f"agcn_amd: streams_bwd takes cotangents named {STREAMS}, got {sorted(cot)}")
+    given = [cot.get(k) for k in STREAMS]
+    first = next((d for d in given if d is not None), None)
+    if first is None:
+        raise ValueError("agcn_amd: streams_bwd needs at least one cotangent")
+    _stream_tensor(first, None, None, 'cotangent')
+    for k, d in zip(STREAMS, given):
+        if d is not None:
+            _stream_tensor(d, first.shape, first, f'd_{k}')
+    N, C, T, V, M = first.shape
+    parent = _stream_parents(parent, V)
+    weights = tuple(float(w) for w in weights)
+    if len(weights) != 4:
+        raise ValueError("agcn_amd: streams_bwd takes four weights (joint, bone, joint_motion, bone_motion)")
+    if not (first.is_cuda and stream_hip_enabled()):
+        return streams_bwd_ref(dict(zip(STREAMS, given)), parent, weights)
+    if V > STREAM_MAX_V:
+        raise ValueError(f"agcn_amd: the stream kernels take at most {STREAM_MAX_V} joints, got {V}")
+    dx = torch.empty_like(first)
+    _lib.call("agcn_streams_bwd", *given, dx, parent, *weights, N, C, T, V, M)
+    return dx
+
+
+class StreamsFunction(torch.autograd.Function):
+    """x (N, C, T, V, M) -> the streams named in ``want`` (a tuple of tensors in that order), one agcn_streams_fwd launch;
+    the backward is one agcn_streams_bwd launch over whichever cotangents arrive.  CPU tensors and AGCN_STREAM_HIP=0 run
+    the tensor-code forms.  args: x, parent (tuple of ints), want (tuple of names), out (dict name -> tensor, or None)"""
+
+    @staticmethod
+    def forward(ctx, x, parent, want, out):
+        ctx.parent, ctx.want = parent, want
+        ctx.set_materialize_grads(False)
+        if not (x.is_cuda and stream_hip_enabled()):
+            res = streams_ref(x, parent, want)
+            if out is not None:
+                for w in want:
+                    out[w].copy_(res[w])
+                res = out
+            return tuple(res[w] for w in want)
+        N, C, T, V, M = x.shape
+        res = {w: (out[w] if out is not None else torch.empty_like(x)) for w in want}
+        _lib.call("agcn_streams_fwd", x, res.get('bone'), res.get('joint_motion'), res.get('bone_motion'), parent,
+                  N, C, T, V, M)
+        return tuple(res[w] for w in want)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        cot = {w: g.contiguous() for w, g in zip(ctx.want, grads) if g is not None}
+        if not cot:
+            return None, None, None, None
+        return streams_bwd(cot, ctx.parent), None, None, None
+
+
+def skeleton_streams(x, parent, want=('bone',), out=None):
+    """Bone and motion streams of joint data x (N, C, T, V, M), contiguous (reference data_gen/gen_bone_data.py,
+    gen_motion_data.py): bone = x - x[parent], joint_motion[t] = x[t+1] - x[t] (0 in the last frame), bone_motion = the
+    motion of the bone tensor.  ``parent``: V joint indices in [0, V) (``Graph().bone_parents``), host data.  ``want``: a
+    non-empty selection of 'bone', 'joint_motion', 'bone_motion'; all of them come out of ONE launch that reads x once
+    -> dict name -> tensor.  ``out``: optional dict of preallocated tensors to write into (no autograd then).
+    Differentiable in x.  Everything is checked here, before any launch."""
+    want = _stream_want(want)
+    _stream_tensor(x, None, None, 'x')
+    V = x.shape[3]
+    parent = _stream_parents(parent, V)
+    if x.is_cuda and stream_hip_enabled() and V > STREAM_MAX_V:
+        raise ValueError(f"agcn_amd: the stream kernels take at most {STREAM_MAX_V} joints, got {V}")
+    if out is not None:
+        if x.requires_grad and torch.is_grad_enabled():
+            raise ValueError("agcn_amd: skeleton_streams writes into `out` only where no gradient is recorded")
+        if set(out) != set(want):
+            raise ValueError(f"agcn_amd: out must hold exactly the wanted streams {want}, got {sorted(out)}")
+        for w in want:
+            _stream_tensor(out[w], x.shape, x, f'out[{w!r}]')
+        ptrs = [x.data_ptr()] + [out[w].data_ptr() for w in want]
+        if len(set(ptrs)) != len(ptrs):
+            raise ValueError("agcn_amd: the outputs of skeleton_streams must not alias x or each other")
+    return dict(zip(want, StreamsFunction.apply(x, parent, want, out)))
+
+
 # ---- the autograd nodes ---------------------------------------------------------------------------------------------------
 class _Args:
     """The argument names of one autograd Function's forward, declared once next to it: the positions looked up in

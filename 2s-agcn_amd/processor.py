@@ -9,7 +9,9 @@ paths resolved by ``import_class``, state_dict checkpoints named ``<work_dir>/we
 per-epoch LR rule, mean-CE loss, clip 1.0, SGD.  What differs (MI355X-first): one process per GPU, flat
 parameter/gradient buffers, one RCCL all-reduce and one fused clip+SGD launch chain per step (trainer.py), tensor
 or tuple model outputs both accepted, unknown config keys warn instead of assert, and a
-built-in synthetic feeder so the loop runs without a dataset.  Out of scope here: SAM/LLRD optimizers and TensorBoard.
+built-in synthetic feeder so the loop runs without a dataset.  ``--stream bone | joint_motion | bone_motion`` derives that
+input from the joint data on the GPU, before the feeder's transforms (``ops.skeleton_streams``; the reference trains on
+files written by data_gen/gen_bone_data.py / gen_motion_data.py).  Out of scope here: SAM/LLRD optimizers and TensorBoard.
 ``Processor`` itself stays SGD-only; with ``use_sgn_dataloader`` ``main.py`` runs ``sgn_processor.SGNProcessor`` instead:
 ``model.sgn.SGN`` on the SGN collate (``feeders.sgn.SGNBatches``) with Adam or SGD and the label-smoothing loss.
 """
@@ -24,6 +26,8 @@ import torch
 import yaml
 
 from . import dp as _dp
+from . import ops
+from .ops import STREAMS
 from .trainer import TrainEngine, learning_rate
 
 
@@ -83,6 +87,12 @@ def get_parser():
     p.add_argument('--device-augment', type=str2bool, default=True,
                    help='apply the feeder\'s random transforms to whole batches on the GPU (feeders.DeviceAugment) '
                         'instead of per sample on the host; only feeders that support it (feeders.feeder.Feeder)')
+    p.add_argument('--stream', default='joint', choices=list(STREAMS),
+                   help='the input stream of the two-/four-stream recipe, computed on the GPU from the JOINT data the '
+                        'feeder loads (ops.skeleton_streams; reference data_gen/gen_bone_data.py, gen_motion_data.py), '
+                        'before the feeder\'s transforms')
+    p.add_argument('--stream-parents', type=int, default=None, nargs='+',
+                   help='parent joint of every joint for the bone streams (default: bone_parents of the model\'s graph)')
     p.add_argument('--prefetch-depth', type=int, default=2, help='batches staged ahead through pinned host buffers')
     p.add_argument('--use-sgn-dataloader', type=str2bool, default=False,
                    help='train / evaluate model.sgn.SGN on the SGN collate (sgn_processor.SGNProcessor, feeders.sgn.SGNBatches)')
@@ -154,11 +164,45 @@ def use_device_augment(Feeder, feeder_kwargs, flag):
     return not (feeder_kwargs.get('stretch') or feeder_kwargs.get('random_subsample') is not None)
 
 
-def prepare_batch(data, aug):
-    """What BOTH phases feed the model: the batch as float32 with the feeder's (device-side) transforms applied.  The
-    reference applies normalization / window padding / ... in ``__getitem__`` whatever the phase (feeder.py:182-221);
-    with device_augment the feeder returns raw clips and the same transforms live in ``aug``."""
+RANDOM_TRANSFORMS = ('random_choose', 'random_shift', 'random_move', 'random_zaxis_flip', 'random_xaxis_scale',
+                     'random_yaxis_scale', 'random_subsample', 'random_rotation')
+
+
+def check_stream(stream, Feeder, feeder_kwargs, device_augment, which='train_feeder_args'):
+    """A stream other than ``joint`` is derived from the raw joint clip BEFORE the feeder's transforms, as the reference
+    derives its bone / motion files from the raw data and augments afterwards (``random_move`` translates, and a
+    translation does not commute with the bone difference).  Two configurations cannot keep that order and are refused
+    with a ValueError that names the argument:
+      * the feeder's random transforms run on the host, inside ``__getitem__``, ahead of everything here: ``device_augment``
+        off (or forced off by ``stretch`` / ``random_subsample``) while a random transform is on;
+      * the feeder's ``normalization``: its mean / std maps are those of the joint file."""
+    if stream not in STREAMS:
+        raise ValueError(f"agcn_amd.Processor: --stream must be one of {STREAMS}, got {stream!r}")
+    if stream == 'joint':
+        return
+    kw = dict(feeder_kwargs or {})
+    if kw.get('normalization'):
+        raise ValueError(f"agcn_amd.Processor: --stream {stream} with {which}.normalization: the feeder's mean / std maps "
+                         f"are statistics of the joint data; switch normalization off")
+    on = [k for k in RANDOM_TRANSFORMS if (kw.get(k) is not None if k == 'random_subsample' else kw.get(k))]
+    if on and not use_device_augment(Feeder, kw, device_augment):
+        raise ValueError(f"agcn_amd.Processor: --stream {stream} needs the random transforms {on} of {which} to run "
+                         f"after the stream is derived, that is on the device: --device-augment is off, or forced off by "
+                         f"stretch / random_subsample, or the feeder cannot defer its transforms")
+
+
+def prepare_batch(data, aug, stream='joint', parents=None):
+    """What BOTH phases feed the model: the batch as float32, turned into the wanted input stream (``ops.skeleton_streams``,
+    one launch) and then put through the feeder's (device-side) transforms.  The reference applies normalization / window
+    padding / ... in ``__getitem__`` whatever the phase (feeder.py:182-221); with device_augment the feeder returns raw
+    clips and the same transforms live in ``aug``."""
     data = data.float()
+    if stream != 'joint':
+        if stream not in STREAMS:
+            raise ValueError(f"agcn_amd: stream must be one of {STREAMS}, got {stream!r}")
+        if parents is None:
+            raise ValueError(f"agcn_amd: stream {stream!r} needs the parent table (stream_parents / Graph().bone_parents)")
+        data = ops.skeleton_streams(data.contiguous(), parents, (stream,))[stream]
     return aug(data) if aug is not None else data
 
 
@@ -176,8 +220,14 @@ class _IndexSampler(torch.utils.data.Sampler):
 
 
 class Processor:
+    stream, stream_parents = 'joint', None      # the input stream (--stream) and its parent table
+
     def __init__(self, arg):
         self.arg = arg
+        # the input stream: refused configurations raise here, before a device or a dataset is touched
+        self.stream = getattr(arg, 'stream', 'joint') or 'joint'
+        self.stream_parents = None
+        self._check_stream()
         self.rank, self.world = _dp.init_distributed()
         dev = arg.device if isinstance(arg.device, int) else arg.device[0]
         local = int(os.environ.get('LOCAL_RANK', dev))
@@ -210,10 +260,34 @@ class Processor:
                 with open(os.path.join(self.arg.work_dir, 'log.txt'), 'a') as f:
                     print(line, file=f)
 
+    # ---- input stream ---------------------------------------------------------------------------------------------
+    def _check_stream(self):
+        arg = self.arg
+        if self.stream == 'joint':
+            return check_stream(self.stream, None, None, None)
+        Feeder = import_class(arg.feeder)
+        flag = getattr(arg, 'device_augment', True)
+        if arg.phase == 'train':
+            check_stream(self.stream, Feeder, arg.train_feeder_args, flag, 'train_feeder_args')
+        check_stream(self.stream, Feeder, arg.test_feeder_args or arg.train_feeder_args, flag,
+                     'test_feeder_args' if arg.test_feeder_args else 'train_feeder_args')
+
+    def _stream_parents(self):
+        """--stream-parents, else bone_parents of the model's graph."""
+        parents = getattr(self.arg, 'stream_parents', None)
+        if parents is None:
+            parents = getattr(getattr(self.model, 'graph', None), 'bone_parents', None)
+        if parents is None:
+            raise ValueError(f"agcn_amd.Processor: --stream {self.stream} needs --stream-parents: the model's graph "
+                             f"has no bone_parents table")
+        return tuple(int(p) for p in parents)
+
     # ---- model / weights -----------------------------------------------------------------------------------------
     def load_model(self):
         Model = import_class(self.arg.model)
         self.model = Model(**self.arg.model_args).to(self.device)
+        if self.stream != 'joint':
+            self.stream_parents = self._stream_parents()
         if self.arg.weights:
             self.load_weights(self.arg.weights)
 
@@ -319,7 +393,7 @@ class Processor:
             return dt
         for step, (data, label, _) in enumerate(loader):
             timer['dataloader'] += split()
-            data = prepare_batch(data, aug)
+            data = prepare_batch(data, aug, self.stream, self.stream_parents)
             if freeze_pa:
                 loss = self._train_step_frozen_pa(data, label)
             else:
@@ -375,7 +449,7 @@ class Processor:
         scores, loss_sum, seen = [], 0.0, 0
         with torch.no_grad():
             for data, label, _ in loader:
-                out = self.model(prepare_batch(data, aug))
+                out = self.model(prepare_batch(data, aug, self.stream, self.stream_parents))
                 out = out[0] if isinstance(out, tuple) else out
                 loss_sum += float(torch.nn.functional.cross_entropy(out, label, reduction='sum'))
                 seen += label.numel()

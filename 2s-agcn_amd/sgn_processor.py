@@ -39,6 +39,9 @@ class SGNProcessor(Processor):
         self.arg = arg
         if int(getattr(arg, 'world_size', 1)) > 1 or int(os.environ.get('WORLD_SIZE', '1')) > 1:
             raise ValueError("agcn_amd.SGNProcessor: more than one process is not built for the SGN route (world_size > 1)")
+        if (getattr(arg, 'stream', 'joint') or 'joint') != 'joint':
+            raise ValueError(f"agcn_amd.SGNProcessor: --stream {arg.stream} is not built for the SGN route (its collate "
+                             f"reads joint data)")
         self.rank, self.world = 0, 1
         dev = arg.device if isinstance(arg.device, int) else arg.device[0]
         torch.cuda.set_device(dev)

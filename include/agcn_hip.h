@@ -8,7 +8,8 @@
  *
  * Conventions
  *  - every pointer is a DEVICE pointer to contiguous fp32 owned by the caller (PyTorch's caching allocator in our
- *    host code); the library never allocates, frees or keeps device memory; scratch/workspace is passed in and its
+ *    host code), with one exception by name: a `const int* host_<name>` parameter is a HOST array (the parent table of
+ *    agcn_streams_*); the library never allocates, frees or keeps device memory; scratch/workspace is passed in and its
  *    size is given by the matching *_workspace / *_scratch_bytes / *_num_* query;
  *  - activations are (N, C, T, V) row-major ("NCHW"), N = batch*persons, V <= 32 joints, P = T*V;
  *  - `stream` is a hipStream_t passed as void*; all work is enqueued on it, nothing synchronises the device, the
@@ -802,6 +803,32 @@ size_t agcn_sgn15_stats_finalize_workspace(int kind, int layer, int N, int seg, 
 int agcn_sgn15_stats_finalize(const float* part, size_t part_floats, int kind, int layer, int N, int seg, int V,
                               const double* carry_in, double* carry_out, float* mean, float* var, void* ws, size_t ws_bytes,
                               void* stream);
+
+/* ---- bone and motion input streams from joint data (csrc/streams.hip; index arithmetic in csrc/streams_plan.h) ----
+ * replaces the reference's offline passes over the dataset files: data_gen/gen_bone_data.py:40-55 (bone),
+ * data_gen/gen_motion_data.py:18-31 (joint_motion, bone_motion), and their autograd transpose.  Tensors are contiguous
+ * (N, C, T, V, M) fp32 on the device.
+ *   bone[.., v, m] = x[.., v, m] - x[.., parent[v], m]                 (a joint that is its own parent gives exactly 0)
+ *   joint_motion[t] = x[t+1] - x[t] for t < T-1, 0 at t = T-1          (padded zero frames are frames like any other)
+ *   bone_motion[t]  = bone[t+1] - bone[t] for t < T-1, 0 at t = T-1
+ * streams_fwd reads x once and writes every output whose pointer is not NULL in one launch; each value is one or two
+ * correctly rounded fp32 subtractions in a fixed order: the result is bit-exact.
+ * streams_bwd: dx = w_joint d_joint + w_bone bone^T(d_bone) + w_joint_motion motion^T(d_joint_motion)
+ *                 + w_bone_motion bone^T(motion^T(d_bone_motion)),  a NULL cotangent contributes nothing;
+ *   motion^T(d)[t] = (t > 0 ? d[t-1] : 0) - (t < T-1 ? d[t] : 0),  bone^T(d)[v] = d[v] - sum_{c : parent[c] == v} d[c].
+ *   One launch, gather form, no atomics: the streams are added in the order written, the children c ascending.
+ * host_parent is a HOST array of V ints, the only pointer of this header that is not a device pointer.  It is validated
+ * on the host at every call and copied into the kernel's arguments by value: no index is ever read from device memory,
+ * and an index outside [0, V) cannot reach a kernel.
+ * AGCN_ERR_ARG: x (dx) NULL, no output (no cotangent) given, host_parent NULL, a non-positive size, a table entry outside
+ *   [0, V).  AGCN_ERR_UNSUPPORTED: V > 32, or N*C*T*V*M > 2^31 - 1 (the kernels index with 32 bits).  All before any
+ *   launch.  M of 2 or 4 with every pointer aligned to 4 M bytes moves one joint per lane as a vector; anything else runs
+ *   element by element, with the same bits. */
+int agcn_streams_fwd(const float* x, float* bone, float* joint_motion, float* bone_motion, const int* host_parent, int N,
+                     int C, int T, int V, int M, void* stream);
+int agcn_streams_bwd(const float* d_joint, const float* d_bone, const float* d_joint_motion, const float* d_bone_motion,
+                     float* dx, const int* host_parent, float w_joint, float w_bone, float w_joint_motion,
+                     float w_bone_motion, int N, int C, int T, int V, int M, void* stream);
 
 #ifdef __cplusplus
 }
