@@ -735,18 +735,22 @@ int gcn_dadj_route(const float* dy, const float* wcat, const float* x, float* da
   p.w = wcat; p.sa_m = 1; p.sa_i = 0; p.sa_c = 3L * C; p.tap_flip_from = -1;
   p.ws = workspace; p.ws_bytes = workspace_bytes;
   constexpr int BM = 64;            // rows of a block of this configuration
-  if (!dry && C < BM && 3 * C > BM) {
+  if (C < BM && 3 * C > BM) {
     // the rows of one subset would straddle two row blocks, which share one slot per (sample, subset, tile): one launch
     // per subset instead (C rows, a single row block), each into its own third of every sample's slots.  The size
-    // query keeps the 3C-row form: the same slots, a workspace that covers the smaller launches.
-    const long per_subset = (long)make_geometry<1, 0, 1, 4, 2, 1, CKD, 1>(V, T, 1, C, Cout).ntiles * V * V;
+    // query dry-runs one of the three (they are alike): the same slots as the 3C-row form, the C-row launch's workspace.
     a.M = C;
+    if (dry) return launch_cfg<1, 0, 1, 4, 2, 1, CKD, 2, 1>(p, s);
+    const long per_subset = (long)make_geometry<1, 0, 1, 4, 2, 1, CKD, 1>(V, T, 1, C, Cout).ntiles * V * V;
     for (int i = 0; i < 3; ++i) {
       p.w = wcat + (long)i * C;
       a.dadj = dadj_part + i * per_subset;
       int rc = launch_cfg<1, 0, 1, 4, 2, 1, CKD, 2, 1>(p, s);
       if (rc != AGCN_OK) return rc;
     }
+    char name[128];
+    snprintf(name, sizeof(name), "%s", agcn_last_kernel_buf);
+    AGCN_NOTE_KERNEL("%s [one launch per subset]", name);
     return AGCN_OK;
   }
   return launch_cfg<1, 0, 1, 4, 2, 1, CKD, 2, 1>(p, s);

@@ -426,6 +426,7 @@ int gcn_wgrad_route(const float* dy, const float* x, const float* adj, float* dw
   a.so_m = 3L * C; a.so_t = C; a.so_c = 1; a.wsize = 3L * Cout * C;
   if (chain_wgrad_enabled() && agcn_wgrad_chain_supported(Cout, C, V))
     return chain_wgrad_and_reduce(1, a, dwcat, workspace, workspace_bytes, s, dy_absmax, x_absmax, dry);
+  if (!dry) AGCN_NOTE_KERNEL("conv_wgrad_kernel<1, 1, %d>", Cout % 128 == 0 ? 4 : 2);
   if (Cout % 128 == 0) return launch_wgrad<1, 1, 4, 2, 1, false, 2>(a, dwcat, workspace, workspace_bytes, s, dry);
   return launch_wgrad<1, 1, 2, 2, 2, true, 2>(a, dwcat, workspace, workspace_bytes, s, dry);
 }

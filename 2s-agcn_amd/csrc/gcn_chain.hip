@@ -14,6 +14,7 @@
 // Pipeline: weight images are double-buffered in LDS; the global loads of stage s+2 (and of the next x chunk) are
 // issued into registers before the matrix-core work of stage s and committed before stage s+1: one barrier per stage.
 #include "agcn_common.h"
+#include "dadj_plan.h"
 #include "split_f16.h"
 
 namespace {
@@ -1284,7 +1285,7 @@ struct DadjPackArgs {
   int C3, Cout, nkc;
 };
 
-constexpr int KC = 32;         // dy channels per stage (two 16-deep MFMA steps)
+constexpr int KC = DADJ_KC;    // dy channels per stage (two 16-deep MFMA steps): the channel arithmetic is dadj_plan.h
 
 // one block per (mblock, kchunk) image: [plane][ks][tm][lane][8]; slot e of lane (row m, h) = channel kc*32 + ks*16 + h*8 + e
 template <int TM, bool F16>
@@ -1304,8 +1305,8 @@ __global__ void __launch_bounds__(256) dadj_pack_kernel(const DadjPackArgs p) {
     float v[2];
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-      const int o = kc * KC + ks * 16 + h * 8 + 2 * e2 + q;
-      v[q] = (m < p.C3 && o < p.Cout) ? p.w[(long)o * p.C3 + m] : 0.f;
+      const int o = dadj_pack_channel(kc, ks, h, 2 * e2 + q);
+      v[q] = (m < p.C3 && dadj_pack_live(o, p.Cout)) ? p.w[(long)o * p.C3 + m] : 0.f;
     }
     unsigned ph, pm, pl = 0;
     if constexpr (F16) split_pair_f16(v[0] * F16_W_SCALE, v[1] * F16_W_SCALE, ph, pm);
@@ -1375,7 +1376,8 @@ __global__ void __launch_bounds__(NW * 64, 2) gcn_dadj_chain_kernel(const DadjAr
   // dy staging: lane task = (8-channel group og = ks*2 + h, 4 consecutive positions): eight 16-byte loads (one per
   // channel) instead of 32 scalar ones -- the per-CU address path, not HBM, bounded the scalar version.  Positions
   // beyond the tile's valid frames are never used (their waves skip), so nothing is masked; only the last positions of
-  // the whole tensor take the clamped scalar path.
+  // the whole tensor, and a group that holds the tensor's last channel without being full (Cout no multiple of 8: its
+  // missing channels are staged as zeros, never read from a shifted address), take the checked scalar path.
   u32x4 ra[EA];
   f32x4 rb[8];
   const u32x4* wp4 = reinterpret_cast<const u32x4*>(a.wp) + (long)mbk * S * A16;
@@ -1389,19 +1391,20 @@ __global__ void __launch_bounds__(NW * 64, 2) gcn_dadj_chain_kernel(const DadjAr
     asm volatile("" : "+v"(tk));                       // (keeps the task indices out of loop-invariant registers)
     if (tk < ntask) {
       const int og = tk / npiece, pos = (tk - og * npiece) * 4;
-      const int o0 = s * KC + og * 8;
-      const float* src2 = a.dy + ((long)n * a.Cout + min(o0, a.Cout - 8)) * P + (long)t0 * V + pos;
-      if (src2 + 7 * P + 4 <= dy_end) {
+      const int o0 = dadj_stage_first(s, og);
+      const long at = (long)t0 * V + pos;
+      const float* src2 = a.dy + ((long)n * a.Cout + dadj_stage_channel(o0, 0, a.Cout)) * P + at;
+      if (dadj_stage_count(o0, a.Cout) == 8 && src2 + 7 * P + 4 <= dy_end) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) rb[e] = *reinterpret_cast<const f32x4_u*>(src2 + (long)e * P);
       } else {
 #pragma unroll
-        for (int e = 0; e < 8; ++e)
+        for (int e = 0; e < 8; ++e) {
+          const float* pe = a.dy + ((long)n * a.Cout + dadj_stage_channel(o0, e, a.Cout)) * P + at;
+          const bool live = dadj_stage_live(o0, e, a.Cout);
 #pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const float* pq = src2 + (long)e * P + q;
-            rb[e][q] = (pq < dy_end) ? *pq : 0.f;
-          }
+          for (int q = 0; q < 4; ++q) rb[e][q] = (live && pe + q < dy_end) ? pe[q] : 0.f;
+        }
       }
     }
   };
@@ -1576,6 +1579,7 @@ int dadj_chain_launch(DadjArgs a, const float* wcat, void* ws, size_t ws_bytes, 
       if (int rc = agcn_operand_max(a.x_absmax, a.x, (long)a.N * a.C * a.T * a.V, amax + 1, stream, &a.x_absmax)) return rc;
     }
   }
+  AGCN_NOTE_KERNEL("gcn_dadj_chain_kernel<%d, %d, %s>", TM, NW, F16 ? "true" : "false");
   DadjPackArgs pk;
   pk.w = wcat; pk.wp = (unsigned short*)ws; pk.C3 = 3 * a.C; pk.Cout = a.Cout; pk.nkc = a.nkc;
   hipLaunchKernelGGL((dadj_pack_kernel<TM, F16>), dim3(a.nmb * a.nkc), dim3(256), 0, stream, pk);

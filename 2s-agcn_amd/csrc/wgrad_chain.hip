@@ -706,6 +706,7 @@ int wc_launch(WcArgs a, void* ws, size_t ws_bytes, int* nslabs_out, hipStream_t 
   a.part = (float*)ws;
   a.ntiles = g.ntiles; a.pairs_per_split = g.pairs_per_split; a.ncg = g.ncg; a.XP = g.XP;
   *nslabs_out = g.nslabs;
+  AGCN_NOTE_KERNEL("wgrad_chain_kernel<%d, %d, %d, %d, %d>", AGG, TM, NCB, VS, NW);
   return agcn_launch_big<wgrad_chain_kernel<AGG, TM, NCB, VS, NW>>(dim3(g.grid_x, g.nsplit), dim3(NW * 64), g.smem_bytes,
                                                                    stream, a);
 }

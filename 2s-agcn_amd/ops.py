@@ -299,6 +299,9 @@ def adjacency_bwd(dy, wcat, x, tp, P, alpha=None, wab=None, bab=None, dy_amax=No
     Cout = wcat.shape[0]
     Ci = (tp.shape[1] if tp is not None else wab.shape[0]) // 6
     nslots = _L().agcn_dadj_num_slots(C, V, T)
+    if nslots <= 0:
+        raise ValueError(f"agcn_amd: the adjacency gradient does not support {C} input channels (V = {V}): supported are "
+                         "widths below 64 and multiples of 64, with V <= 32")
     dpart = _empty((N, 3, nslots, V, V), x)
     ws, nb = _gcn_ws(C, Cout, T, V, x)
     _lib.call("agcn_gcn_dadj_ex", dy, wcat, x, dpart, ws, nb, N, C, Cout, T, V, dy_amax, x_amax)
